@@ -1,6 +1,6 @@
 """bench.py — headline benchmark: audio-seconds/s of the wavlm-large-s80 pipeline (segmentation + embedding + AHC).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f32h|f32s|f32|f16] [--minutes 30]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f32h|f32s|f32|f16] [--minutes 30] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher in the environment (WORLD_SIZE unset) makes bench.py launch its own N ranks
@@ -42,7 +42,6 @@ ROOT = Path(__file__).resolve().parent
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # before the first HIP call: see diarizen_amd/__init__.py (stream -> hardware-queue mapping)
 import torch  # noqa: E402
 
 # MI355X dense MFMA peaks (MI355X_MICROARCH.md).  "f32s" contractions run fp32 arithmetic as 6 bf16 MFMA
@@ -367,6 +366,37 @@ def shard_slice(num_samples: int, window: int, step: int, rank: int, world: int)
     if c1 <= c0:
         return c0, c1, 0, 0
     return c0, c1, c0 * step, (c1 - c0 - 1) * step + window
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, seg, emb, tracks) -> dict:
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy — `segmentations` (the u8 hard decisions
+    [windows, frames, speakers] as float32), `embeddings` (float32 [windows, speakers, dim]; full stage only) and `diarization`
+    (float64 [segments, 3]: start s, end s, speaker index into the sorted labels, in RTTM order; full stage only).  Past 64 MB
+    in all, a seeded sample of the windows (the same rows of both arrays) is written, with their indices in `window_index`."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {"segmentations": seg.numpy().astype(np.float32)}
+    if emb is not None:
+        arrays["embeddings"] = emb.numpy().astype(np.float32)
+    if tracks is not None:
+        arrays["diarization"] = np.asarray(tracks, dtype=np.float64).reshape(-1, 3)
+    per_window = sum(a[0].nbytes for k, a in arrays.items() if k != "diarization" and len(a))
+    fixed = arrays["diarization"].nbytes if "diarization" in arrays else 0
+    n = len(arrays["segmentations"])
+    if per_window * n + fixed > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - fixed - 8 * n) // per_window)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, keep), replace=False))
+        for k in ("segmentations", "embeddings"):
+            if k in arrays:
+                arrays[k] = arrays[k][idx]
+        arrays["window_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(out_dir / f"{k}.npy", np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def batches_note(n_windows: int, batch: int) -> str:
@@ -771,10 +801,15 @@ def main():
     ap.add_argument("--strong-minutes", type=float, default=None,
                     help="length of the ONE recording of the strong-scaling end-to-end leg (BASELINE configs[3]: 240); "
                          "default: 240 when --gpus > 1, off at 1 GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (decisions, embeddings, diarization) as "
+                         "DIR/<name>.npy on rank 0, for output-for-output comparison of two builds (bench.py:dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     one_device = bool(os.environ.get("DZN_BENCH_ONE_DEVICE"))    # rehearsal only: N ranks on device 0 (gloo staging)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args, sys.argv[1:], one_device))
@@ -864,12 +899,16 @@ def main():
     clustering.device = dev.index if dev.index is not None else 0
     chunks_sw = SlidingWindow(start=0.0, duration=args.window, step=0.1 * args.window)
     acc = {"on": False, "device_s": 0.0, "host_s": 0.0, "host_wait_s": 0.0, "speakers": 0, "rttm_lines": 0}
+    last = {"seg": None, "emb": None, "tracks": None}       # the last timed step's results (--dump-outputs)
 
     def host(seg_t, emb_t):
         ann = run_host_stage(seg_t.numpy(), emb_t.numpy(), chunks=chunks_sw, clustering=clustering,
                              min_speakers=clu["min_speakers"], max_speakers=clu["max_speakers"], sess_name="bench", device=dev)
         rttm = ann.to_rttm()
         acc["speakers"], acc["rttm_lines"] = len(ann.labels()), len(rttm.splitlines())
+        if acc["on"] and args.dump_outputs:      # host stages finish in step order: the last write is the last timed step's
+            spk = {lab: i for i, lab in enumerate(ann.labels())}
+            last["tracks"] = [(s.start, s.end, spk[lab]) for s, _, lab in ann.itertracks(yield_label=True)]
         return rttm
 
     def device_part():
@@ -924,6 +963,7 @@ def main():
         if acc["on"]:
             acc["device_s"] += t_b - t_a
             acc["host_wait_s"] += time.perf_counter() - t_b
+            last["seg"], last["emb"] = seg_t, emb_t
 
     for _ in range(args.warmup):
         step()
@@ -982,6 +1022,9 @@ def main():
     unprofiled_ms = (time.perf_counter() - t1) * 1e3 / 2
     if pool is not None:
         pool.shutdown(wait=True)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last["seg"], last["emb"], last["tracks"] if full else None)
 
     strong_min = args.strong_minutes if args.strong_minutes is not None else (240.0 if world > 1 else 0.0)
     strong_res = None
@@ -1130,6 +1173,8 @@ def main():
             "parity": PARITY_NOTE,
             "kernels": kernels,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": str(args.dump_outputs), "shapes": dumped}
         if world == 1 and not args.no_alt and args.precision in ("f32h", "f32s"):
             # the same workload in the other fp32 modes (strict parity tests run in all three)
             alt = {}

@@ -12,4 +12,3 @@ run headline_only --no-alt --no-e2e --no-profile
 run headline_profiled --no-alt --no-e2e
 run with_alt --no-e2e
 run with_e2e --no-alt
-GPU_MAX_HW_QUEUES=8 run all_hwq8

@@ -180,3 +180,40 @@ def test_other_roof_names_the_binding_roof():
     h2 = bench.other_roof({"flops": 404.677e9, "bytes": 2.393908e9, "ms": 1.3288}, "f32h")
     assert h2["binding_roof"] == "mfma" and h2["ridge_flop_per_byte"] == 104.2
     assert bench.other_roof({"flops": 1e9, "bytes": 0.0, "ms": 1.0}, "f32h") == {}
+
+
+def test_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """--dump-outputs: decisions / embeddings / diarization of the last timed step as float32 / float64 .npy, unchanged."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    seg = (torch.rand(7, 399, 4, generator=g) > 0.5).to(torch.uint8)
+    emb = torch.randn(7, 4, 256, generator=g)
+    tracks = [(0.031, 2.5, 1), (1.2, 3.0, 0)]
+    shapes = bench.dump_outputs(tmp_path / "d", seg, emb, tracks)
+    assert shapes == {"segmentations": [7, 399, 4], "embeddings": [7, 4, 256], "diarization": [2, 3]}
+    s, e, d = (np.load(tmp_path / "d" / f"{k}.npy") for k in ("segmentations", "embeddings", "diarization"))
+    assert s.dtype == np.float32 and e.dtype == np.float32 and d.dtype == np.float64
+    assert np.array_equal(s, seg.numpy()) and np.array_equal(e, emb.numpy()) and np.array_equal(d, np.array(tracks, float))
+    assert not (tmp_path / "d" / "window_index.npy").exists()
+    assert bench.dump_outputs(tmp_path / "s", seg, None, None) == {"segmentations": [7, 399, 4]}      # --stage seg
+
+
+def test_dump_outputs_samples_the_same_windows_past_the_cap(tmp_path, monkeypatch):
+    """past the size cap a seeded sample of the windows (the same rows of decisions and embeddings) is written, with its
+    indices, and two runs pick the same rows"""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10_000)      # the full set is 20 824 bytes
+    seg = torch.arange(50 * 10 * 4).reshape(50, 10, 4).remainder(2).to(torch.uint8)
+    emb = torch.arange(50 * 4 * 16, dtype=torch.float32).reshape(50, 4, 16)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, seg, emb, [(0.0, 1.0, 0)])
+    files = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("segmentations", "embeddings", "diarization", "window_index")}
+    assert sum(a.nbytes for a in files.values()) <= 10_000
+    idx = files["window_index"].astype(np.int64)
+    assert 1 <= len(idx) < 50 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(files["segmentations"], seg.numpy()[idx]) and np.array_equal(files["embeddings"], emb.numpy()[idx])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "window_index.npy").astype(np.int64))
