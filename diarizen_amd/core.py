@@ -93,6 +93,35 @@ except Exception:  # ImportError and friends
         def __bool__(self) -> bool:
             return len(self._tracks) > 0
 
+        def __delitem__(self, key) -> None:
+            segment, track = key
+            del self._tracks[segment][track]
+            if not self._tracks[segment]:
+                del self._tracks[segment]
+
+        def support(self, collar: float = 0.0) -> "Annotation":
+            """pyannote.core's Annotation.support: per label (in label order), its segments in time order are merged while
+            the gap to the current merged segment is empty (<= 1e-6 s, pyannote.core's SEGMENT_PRECISION) or shorter than
+            `collar` (Timeline.support_iter); every merged segment gets a new string track "A", "B", ... (string_generator)
+            shared across labels."""
+            import itertools
+            import string
+            names = ("".join(p) for n in itertools.count(1) for p in itertools.product(string.ascii_uppercase, repeat=n))
+            out = Annotation(uri=self.uri, modality=self.modality)
+            for label in self.labels():
+                segs = sorted({seg for seg, tracks in self._tracks.items() if label in tracks.values()})
+                cur = None
+                for seg in segs + [None]:
+                    if cur is not None and seg is not None:
+                        gap = max(seg.start, cur.start) - min(seg.end, cur.end)     # Segment ^ Segment
+                        if gap <= 1e-6 or gap < collar:
+                            cur = Segment(min(cur.start, seg.start), max(cur.end, seg.end))
+                            continue
+                    if cur is not None:
+                        out[cur, next(names)] = label
+                    cur = seg
+            return out
+
         def itertracks(self, yield_label: bool = False):
             for segment in sorted(self._tracks):
                 tracks = self._tracks[segment]

@@ -1955,6 +1955,7 @@ int dzn_checked_collect_resblock_ws(unsigned int*, int);
 int dzn_checked_collect_attention_split(unsigned int*, int);
 int dzn_checked_collect_attention_planes(unsigned int*, int);
 int dzn_checked_collect_frontend_fused(unsigned int*, int);
+int dzn_checked_collect_post(unsigned int*, int);
 }
 #endif
 int dzn_checked_status(uint32_t* out4, int32_t reset) {
@@ -1963,7 +1964,7 @@ int dzn_checked_status(uint32_t* out4, int32_t reset) {
   const collect_fn fns[] = {dzn_checked_collect_gemm_split, dzn_checked_collect_gemm_mx, dzn_checked_collect_gemm_split_pre,
                             dzn_checked_collect_resblock_fused, dzn_checked_collect_resblock_ws,
                             dzn_checked_collect_attention_split, dzn_checked_collect_attention_planes,
-                            dzn_checked_collect_frontend_fused};
+                            dzn_checked_collect_frontend_fused, dzn_checked_collect_post};
   unsigned int tot[4] = {0u, 0u, 0u, 0u};
   for (collect_fn f : fns) {
     unsigned int w[4] = {0u, 0u, 0u, 0u};

@@ -7,7 +7,11 @@
 //     speakers are zeroed ("clean" mask); a speaker falls back to its full mask when its clean
 //     mask has <= min_num_frames frames.
 // Integer/byte work, one workgroup per window, everything staged in LDS.
+// Also the two detection pipelines' aggregation and hysteresis (dzn_detect, below).
 #include "common.h"
+#include "checked.h"
+
+DZN_CHECKED_TU(post)
 
 namespace {
 
@@ -121,6 +125,97 @@ __global__ __launch_bounds__(256) void cluster_accum_kernel(const uint8_t* __res
   }
 }
 
+
+// ---- voice activity / overlapped speech detection (dzn_detect) --------------------------------------------------------
+// Inference.aggregate(hamming=True, missing=0.0, warm_up) (PA/core/inference.py:389-397, 544-666) of the pre-aggregation
+// hooks max_s (voice_activity_detection.py:125) and second-largest_s (overlapped_speech_detection.py:132) over hard 0/1
+// decisions.  The reference adds window after window into float32 arrays with float64 operands:
+//     acc[t] = f32(f64(acc[t]) + score * mask * hamming[l] * warm_up[l]),   cnt[t] likewise without the score,
+// so the rounding sequence is the window order.  One thread per output frame walks ITS covering windows in ascending order
+// (start[] is non-decreasing: closest_frame of increasing times) and reproduces that sequence; the file is compiled with
+// -ffp-contract=off, and the float64 adds are spelled __dadd_rn so no contraction can creep in.  score * mask is 0 or 1, so the
+// float64 product is the host's weight table w[l] = hamming[l] * warm_up[l] (the same two factors, the same product) or 0.
+__global__ __launch_bounds__(256) void detect_scores_kernel(const uint8_t* __restrict__ seg, int C, int L, int S,
+                                                            const int32_t* __restrict__ start, const double* __restrict__ w,
+                                                            int T, int tasks, int K, float* __restrict__ scores) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= T) return;
+  // covering windows: start[c] <= t < start[c] + L  ->  c in [c0, c1)
+  int lo = 0, hi = C;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (start[mid] > t - L) hi = mid; else lo = mid + 1;
+  }
+  const int c0 = lo;
+  hi = C;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (start[mid] > t) hi = mid; else lo = mid + 1;
+  }
+  const int c1 = lo;
+  float sp = 0.f, ov = 0.f, cnt = 0.f;
+  for (int c = c0; c < c1; ++c) {
+    const int l = t - start[c];
+    DZN_CHECK(l >= 0 && l < L, 0x800, c);
+    DZN_CHECK(c == 0 || start[c - 1] <= start[c], 0x801, c);
+    if (l < 0 || l >= L) continue;          // only reachable with a start[] that is not non-decreasing
+    const uint8_t* row = seg + ((int64_t)c * L + l) * S;
+    int act = 0;
+    for (int s = 0; s < S; ++s) act += row[s] != 0;
+    const double wl = w[l];
+    sp = (float)__dadd_rn((double)sp, act >= 1 ? wl : 0.0);
+    ov = (float)__dadd_rn((double)ov, act >= 2 ? wl : 0.0);
+    cnt = (float)__dadd_rn((double)cnt, wl);
+  }
+  // average = acc / max(cnt, epsilon) in float32 (count_finalize_kernel); frames no window covers are `missing` = 0
+  const float den = fmaxf(cnt, 1e-12f);
+  float* out = scores + (int64_t)t * K;
+  int k = 0;
+  if (tasks & 1) out[k++] = c1 > c0 ? __fdiv_rn(sp, den) : 0.f;
+  if (tasks & 2) out[k++] = c1 > c0 ? __fdiv_rn(ov, den) : 0.f;
+  DZN_CHECK(k == K, 0x802, k);
+}
+
+// Binarize's hysteresis (PA/utils/signal.py:270-296) as a scan.  Frame t >= 1 is DECISIVE when y > onset (-> active) or
+// y < offset (-> inactive); with onset >= offset the two cannot both hold and the reference's state machine is "the verdict
+// of the last decisive frame", frame 0 always deciding (y[0] > onset).  Comparisons in float32 against float32 thresholds:
+// the reference compares numpy float32 scalars with Python floats, which numpy >= 2 (NEP 50) evaluates in float32.
+// One workgroup per task column; each thread owns a contiguous chunk, chunk summaries (-1 = no decisive frame) are combined
+// by a Hillis-Steele scan in LDS (right-most defined value wins), then every thread re-walks its chunk from its entry state.
+constexpr int kHystThreads = 1024;
+
+__global__ __launch_bounds__(kHystThreads) void hysteresis_kernel(const float* __restrict__ scores, int T, int K,
+                                                                  float onset, float offset, uint8_t* __restrict__ active) {
+  __shared__ int8_t sv[kHystThreads];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  const int per = (T + kHystThreads - 1) / kHystThreads;
+  const int t0 = min(tid * per, T), t1 = min(t0 + per, T);
+  int v = -1;
+  for (int t = t0; t < t1; ++t) {
+    const float y = scores[(int64_t)t * K + k];
+    if (t == 0) v = y > onset;
+    else if (y > onset) v = 1;
+    else if (y < offset) v = 0;
+  }
+  sv[tid] = (int8_t)v;
+  __syncthreads();
+  for (int off = 1; off < kHystThreads; off <<= 1) {
+    const int8_t mine = sv[tid], left = tid >= off ? sv[tid - off] : (int8_t)-1;
+    __syncthreads();
+    sv[tid] = mine >= 0 ? mine : left;
+    __syncthreads();
+  }
+  int state = tid > 0 ? sv[tid - 1] : -1;       // entry state of this chunk: defined whenever the chunk is not empty
+  DZN_CHECK(t0 == t1 || tid == 0 || state >= 0, 0x803, tid);
+  for (int t = t0; t < t1; ++t) {
+    const float y = scores[(int64_t)t * K + k];
+    if (t == 0) state = y > onset;
+    else if (y > onset) state = 1;
+    else if (y < offset) state = 0;
+    active[(int64_t)t * K + k] = (uint8_t)state;
+  }
+}
+
 }  // namespace
 
 extern "C" int dzn_speaker_count(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame,
@@ -152,6 +247,21 @@ extern "C" int dzn_cluster_activations(const uint8_t* d_seg, const int8_t* d_har
     hipLaunchKernelGGL(cluster_accum_kernel, dim3((unsigned)g), dim3(256), 0, st, d_seg, d_hard, CL, L, S, d_start_frame,
                        T, K, d_act);
   }
+  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+extern "C" int dzn_detect(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame,
+                          const double* d_weight, int32_t T, int32_t tasks, float onset, float offset, float* d_scores,
+                          uint8_t* d_active, void* stream) {
+  if (!d_seg || !d_start_frame || !d_weight || !d_scores || C < 0 || L < 1 || S < 1 || S > 8 || T < 1 ||
+      (tasks & 3) == 0 || (tasks & ~3) != 0 || !(offset <= onset))
+    return DZN_E_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int K = (tasks & 1) + ((tasks >> 1) & 1);
+  hipLaunchKernelGGL(detect_scores_kernel, dim3((T + 255) / 256), dim3(256), 0, st, d_seg, C, L, S, d_start_frame, d_weight, T,
+                     tasks, K, d_scores);
+  if (d_active)
+    hipLaunchKernelGGL(hysteresis_kernel, dim3(K), dim3(kHystThreads), 0, st, d_scores, T, K, onset, offset, d_active);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 

@@ -82,6 +82,7 @@ class Engine:
         self._h = C.c_void_p()
         cfg = make_dzn_config(seg, emb if emb_state is not None else None, max_batch, max_samples,
                               precision)
+        self._cfg_has_embedding = cfg.has_embedding
         with torch.cuda.device(self.device):
             check(self.lib.dzn_create(C.byref(cfg), C.byref(self._h)), None, "dzn_create")
             self._load(seg_state, "")
@@ -109,6 +110,11 @@ class Engine:
     # ------------------------------------------------------------------ info
     def num_frames(self, num_samples: int) -> int:
         return self.lib.dzn_num_frames(self._h, num_samples)
+
+    @property
+    def has_embedding(self) -> int:
+        """1 when the handle carries the ResNet34 embedding model (weights + workspace), 0 for a segmentation-only engine"""
+        return int(self._cfg_has_embedding)
 
     @property
     def workspace_bytes(self) -> int:

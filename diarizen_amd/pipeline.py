@@ -110,6 +110,39 @@ def run_host_stage(seg: np.ndarray, emb: np.ndarray, *, chunks: SlidingWindow, c
     return binarize(discrete, onset=0.5, offset=0.5, uri=sess_name)
 
 
+def load_hub_config(hub: Path) -> Dict[str, Any]:
+    """`<hub>/config.toml` of a DiariZen hub directory ([model], [inference.args], [clustering.args])"""
+    with open(Path(hub) / "config.toml", "rb") as f:
+        return _toml.load(f)
+
+
+def resolve_hub(repo_id: str, cache_dir: Optional[str] = None) -> Path:
+    """a local hub directory as is, else the HF hub snapshot of `repo_id` (needs network or, with cache_dir, the cache)"""
+    if os.path.isdir(repo_id):
+        return Path(repo_id).expanduser().absolute()
+    from huggingface_hub import snapshot_download
+    return Path(snapshot_download(repo_id=repo_id, cache_dir=cache_dir,
+                                  local_files_only=cache_dir is not None)).expanduser().absolute()
+
+
+def open_recording(in_wav, sample_rate: int, lazy: bool = False):
+    """what `DiariZenPipeline.__call__` accepts (path, BytesIO, bytes or a ProtocolFile mapping with "audio") -> first channel
+    at `sample_rate`, float32.  lazy=True (sharded runs): a WAV file at that rate is opened as an audio.WavSource, so that
+    every rank decodes only the byte range of its windows (other files need the resampler's context and are decoded whole)."""
+    if isinstance(in_wav, Mapping):                    # pyannote ProtocolFile (a Mapping, not a dict)
+        in_wav = in_wav["audio"]
+    assert isinstance(in_wav, (str, os.PathLike, BytesIO, bytes)), \
+        f"input must be either a str, BytesIO or a ProtocolFile; there was {type(in_wav)}"
+    if lazy and isinstance(in_wav, (str, os.PathLike)):
+        try:
+            src = audio_io.WavSource(in_wav)
+            if src.sample_rate == sample_rate:
+                return src
+        except ValueError:
+            pass
+    return audio_io.first_channel_16k(in_wav, sample_rate)
+
+
 class DiariZenPipeline:
     def __init__(self, diarizen_hub, embedding_model, config_parse: Optional[Dict[str, Any]] = None,
                  rttm_out_dir: Optional[str] = None, *, device: Optional[torch.device] = None,
@@ -127,8 +160,7 @@ class DiariZenPipeline:
         them); `close()` releases them.  1 = the single-stream engine of r1-r3."""
         hub = Path(diarizen_hub) if diarizen_hub is not None else None
         if config is None:
-            with open(hub / "config.toml", "rb") as f:
-                config = _toml.load(f)
+            config = load_hub_config(hub)
         if config_parse is not None:
             config["inference"]["args"] = config_parse["inference"]["args"]
             config["clustering"]["args"] = config_parse["clustering"]["args"]
@@ -208,15 +240,9 @@ class DiariZenPipeline:
                         **kwargs) -> "DiariZenPipeline":
         """repo_id: HF hub id (needs network/cache, as in the reference) or a local hub directory.
         The embedding checkpoint is `<dir>/wespeaker/pytorch_model.bin` when present locally."""
-        if os.path.isdir(repo_id):
-            hub = Path(repo_id).expanduser().absolute()
-            local = hub / "wespeaker" / "pytorch_model.bin"
-            embedding_model = str(local) if local.exists() else None
-        else:
-            from huggingface_hub import snapshot_download
-            hub = Path(snapshot_download(repo_id=repo_id, cache_dir=cache_dir,
-                                         local_files_only=cache_dir is not None)).expanduser().absolute()
-            embedding_model = None
+        hub = resolve_hub(repo_id, cache_dir)
+        local = hub / "wespeaker" / "pytorch_model.bin"
+        embedding_model = str(local) if os.path.isdir(repo_id) and local.exists() else None
         if embedding_model is None:
             from huggingface_hub import hf_hub_download
             embedding_model = hf_hub_download(repo_id=EMBEDDING_REPO, filename="pytorch_model.bin",
@@ -355,20 +381,7 @@ class DiariZenPipeline:
     def _open(self, in_wav):
         """decode (or, in a sharded run, lazily open) one recording: the first lines of `__call__`"""
         from . import dist as dz_dist
-        if isinstance(in_wav, Mapping):                    # pyannote ProtocolFile (a Mapping, not a dict)
-            in_wav = in_wav["audio"]
-        assert isinstance(in_wav, (str, os.PathLike, BytesIO, bytes)), \
-            f"input must be either a str, BytesIO or a ProtocolFile; there was {type(in_wav)}"
-        if dz_dist.world_size() > 1 and isinstance(in_wav, (str, os.PathLike)):
-            # sharded run: every rank decodes only the byte range of its windows (files at the model's rate; others need
-            # the resampler's context and are decoded whole)
-            try:
-                src = audio_io.WavSource(in_wav)
-                if src.sample_rate == self.segmentation_model.sample_rate:
-                    return src
-            except ValueError:
-                pass
-        return audio_io.first_channel_16k(in_wav, self.segmentation_model.sample_rate)
+        return open_recording(in_wav, self.segmentation_model.sample_rate, lazy=dz_dist.world_size() > 1)
 
     # ------------------------------------------------------------------ __call__
     def __call__(self, in_wav, sess_name: Optional[str] = None, hook=None) -> Annotation:

@@ -182,6 +182,83 @@ class DevicePost:
         return _select_top_count(SlidingWindowFeature(a, count.sliding_window), count)
 
 
+# ----------------------------------------------------------------------------- detection (VAD / OSD) scores
+DETECT_SPEECH, DETECT_OVERLAP = 1, 2       # dzn_detect task bits (include/dzn.h)
+
+
+def detection_hook(task: int, scores: np.ndarray) -> np.ndarray:
+    """the pre-aggregation hooks of the two detection pipelines on [C, L, S] scores: max over speakers
+    (PA/pipelines/voice_activity_detection.py:125) / second largest (PA/pipelines/overlapped_speech_detection.py:132)"""
+    if task == DETECT_SPEECH:
+        return np.max(scores, axis=-1, keepdims=True)
+    return np.partition(scores, -2, axis=-1)[:, :, -2, np.newaxis]
+
+
+def detection_weights(L: int, duration: float, warm_up=(0.0, 0.0), epsilon: float = 1e-12) -> np.ndarray:
+    """float64 [L]: the Hamming window times the warm-up window of Inference.aggregate (PA/core/inference.py:590-611, warm_up in
+    seconds), the factors a decision of 1 is multiplied with (a 0 contributes 0)"""
+    ham = np.hamming(L).reshape(-1, 1)
+    wu = np.ones((L, 1))
+    left = round(warm_up[0] / duration * L)
+    wu[:left] = epsilon
+    right = round(warm_up[1] / duration * L)
+    wu[L - right:] = epsilon
+    return np.ascontiguousarray((ham * wu).reshape(-1), dtype=np.float64)
+
+
+def crop_end(n: int, frames: SlidingWindow, end: float) -> int:
+    """number of leading frames kept by SlidingWindowFeature.crop(Segment(0, end), mode="loose") on a grid starting at 0
+    (PA/core/inference.py:400-403; pyannote.core SlidingWindow.crop: j = floor((end - start) / step), frames 0 .. j kept,
+    clipped to the data)"""
+    j = int(np.floor((end - frames.start) / frames.step))
+    return max(0, min(j + 1, n))
+
+
+def detection_scores_host(seg: np.ndarray, chunks: SlidingWindow, frames: SlidingWindow, task: int,
+                          num_samples: Optional[int] = None, sample_rate: int = 16000) -> SlidingWindowFeature:
+    """the numpy composition of the detection scores (Inference.__call__ with a pre-aggregation hook,
+    PA/core/inference.py:389-403): hook -> aggregate(hamming=True, missing=0.0) -> crop when the last window was zero-padded
+    (num_samples given and not on the step grid).  The device path (dzn_detect) is checked against it."""
+    agg = aggregate(detection_hook(task, seg.astype(np.float32)), chunks, frames, hamming=True, missing=0.0)
+    if num_samples is not None:
+        window, step = int(np.floor(chunks.duration * sample_rate)), int(round(chunks.step * sample_rate))
+        if num_samples < window or (num_samples - window) % step > 0:
+            agg.data = agg.data[:crop_end(len(agg.data), agg.sliding_window, num_samples / sample_rate)]
+    return agg
+
+
+def detect_device(seg, chunks: SlidingWindow, frames: SlidingWindow, tasks: int, num_frames: Optional[int] = None,
+                  onset: float = 0.5, offset: Optional[float] = None, want_scores: bool = False, warm_up=(0.0, 0.0)):
+    """dzn_detect on the current stream: seg u8 [C, L, S] (device tensor or host array) -> (activity u8 [T, K] host,
+    scores f32 [T, K] host or None, frame grid).  T = num_frames (the cropped length) or the full aggregate length; the
+    window start frames and the weight table are computed on the host with the reference's float64 arithmetic."""
+    import ctypes as C_
+    import torch
+    from . import _lib
+    offset = onset if offset is None else offset
+    seg_t = seg if isinstance(seg, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(seg, dtype=np.uint8)).cuda()
+    assert seg_t.is_cuda and seg_t.dtype == torch.uint8 and seg_t.is_contiguous()
+    dev = seg_t.device
+    Cn, L, S = seg_t.shape
+    grid, starts, T = _frame_grid(Cn, L, chunks, frames)
+    T = T if num_frames is None else int(num_frames)
+    K = bin(tasks & 3).count("1")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev)
+        d_start = torch.from_numpy(starts).to(dev, non_blocking=False)
+        d_w = torch.from_numpy(detection_weights(L, chunks.duration, warm_up)).to(dev)
+        scores = torch.empty((T, K), device=dev, dtype=torch.float32)
+        active = torch.empty((T, K), device=dev, dtype=torch.uint8)
+        p = lambda t: C_.c_void_p(t.data_ptr())      # noqa: E731
+        _lib.check(lib.dzn_detect(p(seg_t), Cn, L, S, p(d_start), p(d_w), T, tasks, float(np.float32(onset)),
+                                  float(np.float32(offset)), p(scores), p(active), C_.c_void_p(st.cuda_stream)),
+                   None, "dzn_detect")
+        act = active.cpu().numpy()
+        sc = scores.cpu().numpy() if want_scores else None
+    return act, sc, grid
+
+
 def _select_top_count(act: SlidingWindowFeature, count: SlidingWindowFeature):
     """tail of to_diarization (PA/pipelines/utils/diarization.py:222-239) on aggregated activations"""
     K = act.data.shape[1]
@@ -235,7 +312,26 @@ def binarize(diar: SlidingWindowFeature, onset: float = 0.5, offset: Optional[fl
     offset = onset if offset is None else offset
     data = diar.data
     n, K = data.shape
-    fr = diar.sliding_window
+    act = np.zeros((n, K), dtype=bool)
+    if n >= 2:
+        for k in range(K):
+            y = data[:, k]
+            # hysteresis state machine; with onset == offset on {0,1} data it is a plain threshold
+            if onset == offset:
+                act[:, k] = y > onset
+                # frames exactly equal to the threshold keep the previous state
+                if (y == onset).any():
+                    act[:, k] = _hysteresis(y, onset, offset)
+            else:
+                act[:, k] = _hysteresis(y, onset, offset)
+    return activity_regions(act, diar.sliding_window, uri=uri)
+
+
+def activity_regions(active: np.ndarray, fr: SlidingWindow, uri: Optional[str] = None, labels=None) -> Annotation:
+    """the region half of Binarize (PA/utils/signal.py:270-300) on precomputed per-frame activity [n, K]: a region runs
+    from the middle of the frame that switched on to the middle of the frame that switched off (or of the last frame).
+    Column k becomes track k with label `labels[k]` (default k)."""
+    n, K = active.shape
     # frames[i].middle with pyannote.core's exact float64 op order (the .3f RTTM rounding of the
     # x.xxx5 timestamps depends on it): s = start + i*step ; e = s + duration ; middle = .5*(s + e)
     s_ = fr.start + np.arange(n) * fr.step
@@ -245,17 +341,8 @@ def binarize(diar: SlidingWindowFeature, onset: float = 0.5, offset: Optional[fl
         return ann
     fast = not HAVE_PYANNOTE_CORE and type(ann).__setitem__ is Annotation.__setitem__ and hasattr(ann, "_tracks")
     for k in range(K):
-        y = data[:, k]
-        # hysteresis state machine; with onset == offset on {0,1} data it is a plain threshold
-        if onset == offset:
-            on = y > onset
-            act = on.copy()
-            # frames exactly equal to the threshold keep the previous state
-            eq = y == onset
-            if eq.any():
-                act = _hysteresis(y, onset, offset)
-        else:
-            act = _hysteresis(y, onset, offset)
+        act = active[:, k]
+        label = k if labels is None else labels[k]
         d = np.diff(act.astype(np.int8))
         starts = np.nonzero(d == 1)[0] + 1
         ends = np.nonzero(d == -1)[0] + 1
@@ -270,10 +357,10 @@ def binarize(diar: SlidingWindowFeature, onset: float = 0.5, offset: Optional[fl
             tracks = ann._tracks
             for a, b in zip(t0, t1):
                 if b > a:                     # pyannote ignores empty segments
-                    tracks.setdefault(Segment(a, b), {})[k] = k
+                    tracks.setdefault(Segment(a, b), {})[k] = label
         else:
             for a, b in zip(t0, t1):
-                ann[Segment(a, b), k] = k
+                ann[Segment(a, b), k] = label
     return ann
 
 

@@ -208,6 +208,24 @@ int dzn_speaker_count(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, con
 int dzn_cluster_activations(const uint8_t* d_seg, const int8_t* d_hard, int32_t C, int32_t L, int32_t S,
                             const int32_t* d_start_frame, int32_t T, int32_t K, int32_t* d_act, void* hip_stream);
 
+/*
+ * Voice activity / overlapped speech detection from the per-window decisions (stateless, no handle; the detection pipelines
+ * of diarizen_amd/detection.py):
+ *   scores  <- Inference.aggregate(hamming=True, missing=0.0, warm_up) of the pre-aggregation hook
+ *              PA/core/inference.py:389-403, 544-666 with
+ *              bit 0 (speech)  np.max(scores, axis=-1)                     PA/pipelines/voice_activity_detection.py:125
+ *              bit 1 (overlap) np.partition(scores, -2, axis=-1)[..., -2]   PA/pipelines/overlapped_speech_detection.py:132
+ *   active  <- Binarize's hysteresis (onset, offset; strict > / <, frames at a threshold keep the state)
+ *              PA/utils/signal.py:254-296
+ * d_seg u8 [C,L,S] hard decisions (S <= 8), d_start_frame int32 [C] non-decreasing (closest_frame, host float64, as for
+ * dzn_speaker_count), d_weight f64 [L] = np.hamming(L) * warm-up window (host), T = output frames (the cropped length:
+ * frames >= T are not computed).  `tasks` selects the columns of d_scores f32 [T,K] / d_active u8 [T,K] in bit order
+ * (K = number of bits set).  d_active may be NULL (scores only).  The float64 accumulation order is the reference's window
+ * order, so the scores are the reference's bits.  Thresholds are float32; offset <= onset.
+ */
+int dzn_detect(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame, const double* d_weight,
+               int32_t T, int32_t tasks, float onset, float offset, float* d_scores, uint8_t* d_active, void* hip_stream);
+
 /* Copy a named intermediate activation of the LAST forward to host (debug / parity
  * tests).  *n_elems receives the element count; host_out may be NULL to query. */
 int dzn_debug_fetch(dzn_handle* h, const char* name, float* host_out, int64_t cap,
