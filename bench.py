@@ -1,7 +1,13 @@
 """bench.py — headline benchmark: audio-seconds/s of the wavlm-large-s80 pipeline (segmentation + embedding + AHC).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f32h|f32s|f32|f16] [--minutes 30] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f32h|f32s|f32|f16] [--minutes 30] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line: `value`, `ms_per_step`,
+`device_value`, `step_breakdown`, the per-kernel `roofline` / `kernels` that the in-situ profiler records inside those steps and
+the board `power` sampled while they run.  `--full` adds every leg that takes runs of its own (`extra_legs`): the serial steps,
+the other arithmetic modes, two streams, `e2e`, the strong-scaling leg, `config1` and `cpu_baseline`; their `--no-*` flags trim
+a `--full` run.
 
 `--gpus N` with N > 1 and no launcher in the environment (WORLD_SIZE unset) makes bench.py launch its own N ranks
 (`torch.distributed.run --standalone`-style rendezvous on 127.0.0.1, one GPU each, RCCL); it refuses to run — non-zero
@@ -24,10 +30,10 @@ path of the same steps alone (what r1-r4 called `value`); `e2e` = the same pipel
 the host -> HBM upload of the recording.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (in-situ HIP-event
-timing of the dominant kernel class over the timed steps), `cpu_baseline` (the oracle — a CPU
-port of the reference arithmetic — on a bounded sample of the same workload), `parity` (what holds the path to the
-reference), the same workload in the other arithmetic modes, `e2e` (the whole pipeline incl. host clustering) and, with
-N > 1 ranks (or --strong-minutes), `strong_scaling_e2e`: ONE 4 h recording sharded over the ranks, end to end.
+timing of the dominant kernel class over the timed steps), `parity` (what holds the path to the reference) and, with --full,
+`cpu_baseline` (the oracle — a CPU port of the reference arithmetic — on a bounded sample of the same workload), the same
+workload in the other arithmetic modes, `e2e` (the whole pipeline incl. host clustering) and, with N > 1 ranks (or
+--strong-minutes), `strong_scaling_e2e`: ONE 4 h recording sharded over the ranks, end to end.
 """
 from __future__ import annotations
 
@@ -750,7 +756,36 @@ def rendezvous_check(args, rank: int, world: int):
         raise SystemExit("bench.py --rendezvous-check: " + "; ".join(problems))
 
 
-def main():
+def strong_minutes(args, world: int) -> float:
+    """length of the ONE recording of the strong-scaling leg: --strong-minutes, else 240 at N > 1 ranks and none at one"""
+    return args.strong_minutes if args.strong_minutes is not None else (240.0 if world > 1 else 0.0)
+
+
+def extra_legs(args, world: int) -> set:
+    """the legs a run measures besides its timed steps.  A plain run has none: it sets up, warms up, times the steps, dumps and
+    prints the line (`roofline` / `kernels` / `power` are recorded while the timed steps run, so they stay with them).  --full
+    adds the legs that take runs of their own, as they ran before the option existed, each trimmed by its --no-* flag."""
+    if not args.full:
+        return set()
+    seg_emb = args.stage == "full"
+    legs = {"serial"}
+    if world == 1 and not args.no_alt:
+        if args.precision in ("f32h", "f32s"):
+            legs.add("other_modes")
+        if args.streams == 1:
+            legs.add("two_streams")
+    if world == 1 and seg_emb and not args.no_e2e and args.minutes <= 60:
+        legs.add("e2e")
+    if strong_minutes(args, world) > 0 and seg_emb and not args.no_e2e:
+        legs.add("strong")
+    if world == 1 and not args.no_config1:
+        legs.add("config1")
+    if world == 1 and seg_emb and not args.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    return legs
+
+
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -800,11 +835,19 @@ def main():
                          "{n_gpus, ranks} and exit")
     ap.add_argument("--strong-minutes", type=float, default=None,
                     help="length of the ONE recording of the strong-scaling end-to-end leg (BASELINE configs[3]: 240); "
-                         "default: 240 when --gpus > 1, off at 1 GPU")
+                         "default: 240 when --gpus > 1, off at 1 GPU; runs with --full")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (decisions, embeddings, diarization) as "
                          "DIR/<name>.npy on rank 0, for output-for-output comparison of two builds (bench.py:dump_outputs)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg that takes runs of its own (extra_legs): the serial steps, the other arithmetic "
+                         "modes, two streams, e2e, the strong-scaling leg, config1 and cpu_baseline; without it a run only sets "
+                         "up, warms up, times the steps, dumps and prints the line")
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -885,6 +928,7 @@ def main():
     wave = wave_host.to(dev)
 
     full = args.stage == "full"
+    legs = extra_legs(args, world)
     # (r5) a step is the WHOLE pipeline of BASELINE configs[2] — "segmentation + embedding + AHC" — on a recording resident in
     # HBM: device hot path, results to the host, then the host stage (speaker counting, centroid-linkage AHC, constrained
     # assignment, reconstruction, Binarize, RTTM text: diarizen/pipelines/inference.py:137-185) through the product's
@@ -1014,21 +1058,23 @@ def main():
         dt, dev_max_s = tt[0].item(), tt[1].item()
     else:
         dev_max_s = acc["device_s"]
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(2):
-        step(serial=True)                       # device stage, THEN host stage: the step of the first r5 runs, unprofiled
-    torch.cuda.synchronize()
-    unprofiled_ms = (time.perf_counter() - t1) * 1e3 / 2
+    unprofiled_ms = None
+    if "serial" in legs:
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(2):
+            step(serial=True)                   # device stage, THEN host stage: the step of the first r5 runs, unprofiled
+        torch.cuda.synchronize()
+        unprofiled_ms = (time.perf_counter() - t1) * 1e3 / 2
     if pool is not None:
         pool.shutdown(wait=True)
     dumped = None
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(args.dump_outputs, last["seg"], last["emb"], last["tracks"] if full else None)
 
-    strong_min = args.strong_minutes if args.strong_minutes is not None else (240.0 if world > 1 else 0.0)
+    strong_min = strong_minutes(args, world)
     strong_res = None
-    if strong_min > 0 and full and not args.no_e2e and world > 1:     # collective: every rank takes part
+    if "strong" in legs and world > 1:          # collective: every rank takes part
         del eng, runner, wave
         torch.cuda.empty_cache()
         strong_res = strong_leg(args, dev, rank, world, strong_min)
@@ -1039,6 +1085,8 @@ def main():
         total_audio = audio_s if strong else world * audio_s
         value = total_audio * args.steps / dt
         device_value = total_audio * args.steps / dev_max_s if dev_max_s > 0 else None
+        serial_ms = round(unprofiled_ms, 2) if unprofiled_ms else None
+        serial_value = round(total_audio * 1e3 / unprofiled_ms, 2) if unprofiled_ms else None
         roofline = None
         kernels = []
         extra = {}
@@ -1143,7 +1191,7 @@ def main():
                        "cpu_baseline_kind": None,
                        # audit keys, inside `config` because the driver keeps this object whole:
                        "device_value": round(device_value, 2) if device_value else None,
-                       "serial_value": round(total_audio * 1e3 / unprofiled_ms, 2),
+                       "serial_value": serial_value,
                        "emb_windows_per_step": (skip1[0] - skip0[0]) // max(args.steps, 1) if full else None,
                        "emb_trunk_skipped_per_step": (skip1[1] - skip0[1]) // max(args.steps, 1) if full else None,
                        "emb_note": "windows handed to dzn_embed_forward per step / windows whose ResNet34 trunk was skipped because no "
@@ -1164,9 +1212,9 @@ def main():
                                        "thresholds up) + RTTM text, as busy time of the worker thread; host_exposed = what the stepping "
                                        "thread waited for it (step i's host stage runs beside step i+1's device stage; the last one of "
                                        "the K is drained inside the timed region)"},
-            "unprofiled_ms_per_step": round(unprofiled_ms, 2),
-            "serial_ms_per_step": round(unprofiled_ms, 2),
-            "serial_value": round(total_audio * 1e3 / unprofiled_ms, 2),
+            "unprofiled_ms_per_step": serial_ms,
+            "serial_ms_per_step": serial_ms,
+            "serial_value": serial_value,
             "roofline": roofline,
             "power": power.result() if power else None,
             "roofline_extra": extra,
@@ -1175,7 +1223,7 @@ def main():
         }
         if dumped is not None:
             out["dumped_outputs"] = {"dir": str(args.dump_outputs), "shapes": dumped}
-        if world == 1 and not args.no_alt and args.precision in ("f32h", "f32s"):
+        if "other_modes" in legs:
             # the same workload in the other fp32 modes (strict parity tests run in all three)
             alt = {}
             for prec in ("f32s", "f32h", "f32"):
@@ -1210,7 +1258,7 @@ def main():
                                    **({"tflops": round(p["flops"] / (p["ms"] * 1e-3) / 1e12, 1)} if p["flops"] > 0 and p["ms"] > 0 else {})}
                                   for p in sorted(prof16, key=lambda p: -p["ms"])[:8]]
             out["reduced_precision_mode"] = {"f16": red}
-        if world == 1 and not args.no_alt and args.streams == 1:
+        if "two_streams" in legs:
             # the same steps with consecutive batches alternating over TWO engine handles / HIP streams (what DiariZenPipeline
             # does by default, num_streams = 2): reported beside the headline, whose steps stay on one stream because the
             # per-kernel event timing behind `roofline` is only meaningful there
@@ -1232,23 +1280,23 @@ def main():
                                   "steps": ALT_STEPS, "note": "consecutive batches alternate over two engine handles on two HIP "
                                   "streams (inference.WindowRunner extra_engines; the pipeline's default): same results bit "
                                   "for bit, independent batches overlap on the device; unprofiled"}
-        if world == 1 and full and not args.no_e2e and args.minutes <= 60:
+        if "e2e" in legs:
             eng = None
             torch.cuda.empty_cache()
             out["e2e"] = e2e_leg(args, dev, wave_host, sd, esd)
-        if strong_min > 0 and full and not args.no_e2e and world == 1:     # one GPU: the same leg as the N > 1 runs, for the curve
+        if "strong" in legs and world == 1:     # one GPU: the same leg as the N > 1 runs, for the curve
             eng = None
             torch.cuda.empty_cache()
             strong_res = strong_leg(args, dev, rank, world, strong_min)
         if strong_res is not None:
             out["strong_scaling_e2e"] = strong_res
-        if world == 1 and not args.no_config1:
+        if "config1" in legs:
             eng = runner = None
             import gc
             gc.collect()
             torch.cuda.empty_cache()
             out["config1"] = config1_leg(args, dev)
-        if not args.no_cpu_baseline and world == 1 and full:
+        if "cpu_baseline" in legs:
             out["cpu_baseline"] = cpu_baseline(cfg, sd, esd, window, 0.1 * args.window, clustering_args=clu)
             out["config"]["cpu_baseline_kind"] = out["cpu_baseline"]["kind"]
         # first-class companions of `value`, right behind it: the end-to-end rate (configs[2] as worded: upload + device

@@ -17,5 +17,5 @@ timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- pyt
 cd $R
 cp $(find $O/kt -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 find $O -name '*kernel_trace.csv' -delete; find $O -name '*counter_collection.csv' -delete; find $O -name '*agent_info.csv' -delete
-( time timeout 400 python bench.py ) > $O/bench_f32h.json 2> $O/bench.err
+( time timeout 400 python bench.py --full ) > $O/bench_f32h.json 2> $O/bench.err
 tail -c 600 $O/bench_f32h.json; head -6 $O/kernel_stats.csv | cut -c1-200

@@ -12,14 +12,14 @@ cd $R
 tail -4 $O/all_gpu_tests.log
 timeout 600 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -5 $O/smoke.log
 timeout 900 bash scripts/run_checked.sh > /dev/null 2>&1; cp gpurun_out/r5_checked_build.log $O/checked_build.log; tail -3 $O/checked_build.log
-timeout 900 python bench.py > $O/bench_f32h.json 2> $O/bench.err
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver_style.json 2> $O/bench_driver_style.err
+timeout 900 python bench.py --full > $O/bench_f32h.json 2> $O/bench.err
+( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $O/bench_driver_style.json 2> $O/bench_driver_style.err
 cd /tmp
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt --no-e2e --no-config1 > $O/bench_under_rocprof.json 2> $O/kt.err
 cd $R
 cp $(find $O/kt -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 find $O -name '*kernel_trace.csv' -delete; find $O -name '*agent_info.csv' -delete
-( time DZN_BENCH_ONE_DEVICE=1 timeout 500 python bench.py --gpus 2 --steps 2 --warmup 1 --strong-minutes 30 --batch 192 --no-config1 ) > $O/bench_gpus2_one_device.json 2> $O/bench_gpus2.err
+( time DZN_BENCH_ONE_DEVICE=1 timeout 500 python bench.py --gpus 2 --steps 2 --warmup 1 --strong-minutes 30 --full --batch 192 --no-config1 ) > $O/bench_gpus2_one_device.json 2> $O/bench_gpus2.err
 DZN_LINKAGE_DEBUG=1 timeout 600 python scripts/e2e_timing.py 240 576 > $O/e2e_4h.log 2>&1; grep -m1 "^timings" $O/e2e_4h.log; grep -m1 "^E2E_JSON" $O/e2e_4h.log | cut -c10- > $O/e2e_4h_1gpu.json
 python - <<PY
 import json

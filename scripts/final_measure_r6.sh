@@ -27,14 +27,14 @@ cd $R
 cp $(find $O/kt -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 cp $O/kernel_stats.csv $R/profiles/r6_kernel_stats_f32h_30min_b576.csv
 find $O -name '*kernel_trace.csv' -delete; find $O -name '*agent_info.csv' -delete
-timeout 900 python bench.py > $O/bench_f32h.json 2> $O/bench.err
-( time timeout 700 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver_style.json 2> $O/bench_driver_style.err
+timeout 900 python bench.py --full > $O/bench_f32h.json 2> $O/bench.err
+( time timeout 700 python bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $O/bench_driver_style.json 2> $O/bench_driver_style.err
 head -12 $O/kernel_stats.csv | cut -c1-160
 cut -c1-1500 $O/bench_f32h.json
 tail -3 $O/bench_driver_style.err; cut -c1-300 $O/bench_driver_style.json
 else
 DZN_LINKAGE_DEBUG=1 timeout 600 python scripts/e2e_timing.py 240 576 > $O/e2e_4h.log 2>&1; grep -m1 "^timings" $O/e2e_4h.log; grep -m1 "^E2E_JSON" $O/e2e_4h.log | cut -c10- > $O/e2e_4h_1gpu.json
-timeout 600 python bench.py --steps 1 --warmup 1 --no-alt --no-cpu-baseline --no-config1 --strong-minutes 240 > $O/bench_with_strong_4h_leg.json 2> $O/bench_strong.err; python - <<PY
+timeout 600 python bench.py --full --steps 1 --warmup 1 --no-alt --no-cpu-baseline --no-config1 --strong-minutes 240 > $O/bench_with_strong_4h_leg.json 2> $O/bench_strong.err; python - <<PY
 import json
 d=json.loads(open("$O/bench_with_strong_4h_leg.json").read().strip().splitlines()[-1]); print(d.get("strong_scaling_e2e"))
 PY

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-probe}; mkdir -p $O
 T=${2:-"tests/test_ops_gpu.py tests/test_seg_gpu.py tests/test_properties_gpu.py"}
 timeout 1200 python -m pytest $T -x -q -m gpu > $O/tests.txt 2>&1; tail -5 $O/tests.txt
-timeout 600 python bench.py --no-cpu-baseline --no-alt ${3:-} > $O/bench_default.json 2> $O/bench_default.err; python - <<PY
+timeout 600 python bench.py --full --no-cpu-baseline --no-alt ${3:-} > $O/bench_default.json 2> $O/bench_default.err; python - <<PY
 import json
 d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1])
 print(d["value"], d["ms_per_step"], d["roofline"]["achieved"], d["roofline"]["launches"], d.get("e2e"))

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_pipeline_gpu.py -q -x -k "diarize_many o
 tail -5 gpurun_out/r5_overlap_tests.log
 timeout 600 python -m pytest tests/test_ops_gpu.py -q -k "linkage or cdist" >> gpurun_out/r5_overlap_tests.log 2>&1
 tail -3 gpurun_out/r5_overlap_tests.log
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-alt --no-e2e --no-config1"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --no-alt --no-e2e --no-config1"
 timeout 400 python bench.py $B > gpurun_out/r5_bench_overlap.json 2> gpurun_out/r5_bench_overlap.err
 timeout 400 python bench.py $B --no-overlap > gpurun_out/r5_bench_no_overlap.json 2> gpurun_out/r5_bench_no_overlap.err
 timeout 400 python bench.py $B > gpurun_out/r5_bench_overlap2.json 2>> gpurun_out/r5_bench_overlap.err

@@ -108,6 +108,23 @@ def test_no_gpu_is_a_loud_failure():
         assert r.returncode != 0 and "HIP device" in r.stderr
 
 
+def test_plain_run_has_no_extra_legs_and_full_keeps_them():
+    """a plain `bench.py --gpus 1 --steps N --warmup W` runs no leg besides its timed steps; --full runs every leg the line carried
+    before the option existed, and the --no-* flags trim it as they did"""
+    b = _bench()
+    plain = b.arg_parser().parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full
+    assert b.extra_legs(plain, 1) == set() and b.extra_legs(plain, 8) == set()
+    full = b.arg_parser().parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert b.extra_legs(full, 1) == {"serial", "other_modes", "two_streams", "e2e", "config1", "cpu_baseline"}
+    assert b.extra_legs(full, 8) == {"serial", "strong"}
+    one_gpu_strong = b.arg_parser().parse_args(["--full", "--strong-minutes", "240", "--no-alt", "--no-config1", "--no-cpu-baseline"])
+    assert b.extra_legs(one_gpu_strong, 1) == {"serial", "e2e", "strong"}
+    assert b.extra_legs(b.arg_parser().parse_args(["--full", "--stage", "seg", "--precision", "f32"]), 1) == {"serial", "two_streams", "config1"}
+    trimmed = b.arg_parser().parse_args(["--full", "--no-alt", "--no-e2e", "--no-config1", "--no-cpu-baseline"])
+    assert b.extra_legs(trimmed, 1) == {"serial"}
+
+
 def test_power_sampler_reads_the_rocm_smi_csv(monkeypatch):
     """bench.py's `power` object: package power / cap / sclk parsed from `rocm-smi --showpower --showclocks --showmaxpower --csv`
     (the layout recorded on the MI355X box in profiles/r4_power_cap.txt); a missing or silent rocm-smi yields None, never an error."""
