@@ -94,7 +94,7 @@ class DznGemmDesc(C.Structure):
         ("W2h", C.c_void_p), ("col_scale", C.c_void_p), ("a_amax", C.c_void_p), ("c_amax", C.c_void_p),
         ("amax_unit", C.c_int32),
         ("stat_partial", C.c_void_p), ("stat_final", C.c_void_p), ("stat_C", C.c_int32), ("stat_eps", C.c_float),
-        ("z_count", C.c_void_p), ("z_list", C.c_void_p), ("ln_centered", C.c_int32),
+        ("z_count", C.c_void_p), ("z_list", C.c_void_p),
         ("Wmx", C.c_void_p), ("col_scale_mx", C.c_void_p),
         ("amax_count", C.c_int32),
         ("kv_planes", C.c_void_p), ("kv_plane_stride", C.c_int64), ("kv_scale", C.c_void_p), ("kv_ld", C.c_int32),

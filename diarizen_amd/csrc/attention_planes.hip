@@ -52,12 +52,12 @@ __device__ __forceinline__ uint2 lds_tr16(const unsigned char* p) {
 // serves twice the matrix work (per tile a wavefront reads the WHOLE K and V images: 32 KB for 48 MFMAs at QB = 1; twelve
 // wavefronts per CU keep the LDS pipe ~50 % busy for a matrix pipe at 25 %).
 // PF: the NEXT tile's K / V pieces are requested as soon as this tile's are in LDS and travel while this tile is computed (32
-// more live registers: two workgroups per CU instead of three).
+// more live registers; both QB = 1 forms still fit three workgroups per CU, and the launch bounds hold them there).
 template <bool BIAS, int QB, bool PF>
-__global__ __launch_bounds__(256, (QB == 1 && !PF) ? AP_OCC : 2) void attn_planes_kernel(
+__global__ __launch_bounds__(256, QB == 1 ? AP_OCC : 2) void attn_planes_kernel(
     const float* __restrict__ qkv, const uint16_t* __restrict__ planes, const float* __restrict__ kvs, float* __restrict__ out,
     const float* __restrict__ gate, const float* __restrict__ table, const int32_t* __restrict__ head_idx, int B, int L, int h,
-    int Htot, int ldqkv, int ldo, int kv_ld, int64_t plane_stride, float scale, const float* __restrict__ amax, const int abl) {
+    int Htot, int ldqkv, int ldo, int kv_ld, int64_t plane_stride, float scale, const float* __restrict__ amax) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sK = smem;                          // 2 planes
   unsigned char* sV = smem + 2 * AP_PLANE;           // 2 planes
@@ -165,13 +165,10 @@ __global__ __launch_bounds__(256, (QB == 1 && !PF) ? AP_OCC : 2) void attn_plane
   const bool wave_on = __builtin_amdgcn_readfirstlane(q_base) < L;
   if constexpr (PF) fetch(0);
   for (int kt = 0; kt < nkt; ++kt) {
-    if constexpr (!PF) {
-      if (!(abl & 1) || kt == 0) fetch(kt);         // abl bit 0 (measurement only, wrong results): one tile fetched, re-used
-    }
+    if constexpr (!PF) fetch(kt);
     __syncthreads();  // previous tile fully consumed
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      if ((abl & 1) && kt > 0) break;
       const int key = skey + 32 * i;
       const int offk = dblk_s * 2048 + key * 32 + ((half_s ^ ((key >> 3) & 1)) << 4);
       const int offv = dblk_s * 2048 + key * 32 + (half_s << 4);
@@ -229,7 +226,6 @@ __global__ __launch_bounds__(256, (QB == 1 && !PF) ? AP_OCC : 2) void attn_plane
     const float rA = sA[0];
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
-      if (abl & 2) break;                            // abl bit 1: no un-scaling / bias / softmax (the scores go on as probabilities)
 #pragma unroll
       for (int kb = 0; kb < 4; ++kb) {
         const float4 ik = *reinterpret_cast<const float4*>(sIK + kb * 16 + lq * 4);
@@ -285,7 +281,6 @@ __global__ __launch_bounds__(256, (QB == 1 && !PF) ? AP_OCC : 2) void attn_plane
     //      a V fragment (two transpose reads) serves QB query blocks ----
 #pragma unroll
     for (int mm = 0; mm < 2; ++mm) {
-      if (abl & 4) break;                            // abl bit 2: no P split / V fragments / P.V products
       u32x4 pf[QB][2];
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) split_np<2>(s[qb][2 * mm], s[qb][2 * mm + 1], 1.0f, pf[qb]);
@@ -335,13 +330,6 @@ __global__ __launch_bounds__(256, (QB == 1 && !PF) ? AP_OCC : 2) void attn_plane
 // two query blocks per wavefront 149 (slower: its softmax section runs at two wavefronts per SIMD).
 int g_ap_qb = getenv("DZN_ATT_QB") ? atoi(getenv("DZN_ATT_QB")) : 1;
 int g_ap_pf = getenv("DZN_ATT_PF") ? atoi(getenv("DZN_ATT_PF")) : 1;     // 1 = the next tile travels while this one is computed
-#ifdef DZN_TUNING
-// DZN_ATT_ABL (DZN_TUNING builds, measurement only - WRONG results): bit 0 = one K / V tile fetched and re-used (PF = 0 form),
-// bit 1 = no un-scaling / bias / softmax, bit 2 = no P.V.  Record: profiles/r6_attention_ablation.txt
-const int g_ap_abl = getenv("DZN_ATT_ABL") ? atoi(getenv("DZN_ATT_ABL")) : 0;
-#else
-constexpr int g_ap_abl = 0;
-#endif
 
 // test helper: what the contraction's epilogue writes for the K / V slots, from a plain fp32 [rows][3 h 64] tensor
 __global__ __launch_bounds__(64) void kv_pack_kernel(const float* __restrict__ qkv, int ldqkv, int col0, uint16_t* __restrict__ planes,
@@ -392,7 +380,7 @@ int launch_attention_planes(const float* qkv, const void* planes, int64_t plane_
   const uint16_t* pl = reinterpret_cast<const uint16_t*>(planes);
 #define DZN_AP(BV, QV, PV)                                                                                                      \
   hipLaunchKernelGGL((attn_planes_kernel<BV, QV, PV>), grid, dim3(256), lds, s, qkv, pl, kvs, out, gate, table, head_idx, B, L, h, Htot, \
-                     ldqkv, ldo, kv_ld, plane_stride, scale, amax, g_ap_abl)
+                     ldqkv, ldo, kv_ld, plane_stride, scale, amax)
   if (bias && qb == 2) DZN_AP(true, 2, false);
   else if (bias && g_ap_pf) DZN_AP(true, 1, true);
   else if (bias) DZN_AP(true, 1, false);

@@ -225,7 +225,6 @@ struct dzn_handle {
   // mode's RTTM against the fp32 RTTM on the 30 s fixture 0.05 % (one 20 ms frame) instead of 0.17 % (three), inside SURVEY 8d's
   // 0.1 abs; device step 1872 -> 1856 audio-s/s on one box (profiles/r5_reduced_mode_keep2_probe.txt)
   unsigned f16_keep2 = 0x3f01;
-  bool f16_center = false;
   // (r5) DZN_PREC_F16: the classes whose bit is set run fp16 hi*hi + the two cross terms in fp8 (gemm_mx.hip) — every linear
   // contraction of the segmentation model: the class sweep of profiles/r4_reduced_mode_emulation.txt shows that any one of them
   // at a single fp16 term costs 0.04-0.21 of max |dlogp| against SURVEY 8d's 5e-2, only the positional conv (bit 2) can stay at
@@ -484,19 +483,6 @@ void finalize_seg(H* h) {
       for (int e = 0; e < 10; ++e) {
         const double lam = std::max(Aj[e * 10 + e], 0.0);
         for (int j = 0; j < 10; ++j) lq[10 + e * 10 + j] = (float)(std::sqrt(lam) * V[j * 10 + e]);
-      }
-      if (k0 == 10 && C0 % 2 == 0) {
-        // behind the coefficients (from float 112 on): conv0's taps + LayerNorm affine, two channels per 24-float record
-        // [w c[10], w c+1[10], gamma c, gamma c+1, beta c, beta c+1] — what a producer wavefront of frontend_fused.hip's
-        // conv01_ws_kernel needs per channel pair, as ONE contiguous scalar load
-        const std::vector<float>& g0 = need(h, pre + ".layer_norm.weight").v;
-        const std::vector<float>& b0 = need(h, pre + ".layer_norm.bias").v;
-        lq.resize(112 + (size_t)(C0 / 2) * 24, 0.f);
-        for (int cp = 0; cp < C0 / 2; ++cp) {
-          float* r = lq.data() + 112 + (size_t)cp * 24;
-          for (int t = 0; t < 10; ++t) { r[t] = w.v[(size_t)(2 * cp) * 10 + t]; r[10 + t] = w.v[(size_t)(2 * cp + 1) * 10 + t]; }
-          r[20] = g0[2 * cp]; r[21] = g0[2 * cp + 1]; r[22] = b0[2 * cp]; r[23] = b0[2 * cp + 1];
-        }
       }
       h->conv0_lnq = upload(h, lq);
     }
@@ -1130,7 +1116,6 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
       const bool mx = cls >= 0 && ((h->f16_mx >> cls) & 1) && d.Wmx;
       if (!mx) d.Wmx = nullptr;     // single-term fp16 (or two terms, next line)
       if (cls >= 0 && ((h->f16_keep2 >> cls) & 1)) d.precision = DZN_PREC_F32_H2;
-      else if (!mx && d.ln_stats && h->f16_center) d.ln_centered = 1;
     }
     // |max| trackers are per window: rows of a [B*L, .] tensor belong to window m / L; z-batched launches
     // (conv stack: z = window) use the z index
@@ -1759,7 +1744,6 @@ int dzn_create(const dzn_config* cfg, dzn_handle** out) {
   h->fuse_resblock = getenv("DZN_NO_RESBLOCK_FUSION") == nullptr;
   if (const char* e = getenv("DZN_RESBLOCK_WS")) h->resblock_ws = atoi(e);
   if (const char* e = getenv("DZN_F16_KEEP2")) h->f16_keep2 = (unsigned)strtoul(e, nullptr, 0);
-  if (const char* e = getenv("DZN_F16_CENTER")) h->f16_center = e[0] != '0';
   if (const char* e = getenv("DZN_F16_MX")) h->f16_mx = (unsigned)strtoul(e, nullptr, 0);
   const char* dbg = getenv("DZN_DEBUG_TAPS");
   h->debug = dbg && dbg[0] == '1';

@@ -52,23 +52,18 @@ struct FusedArgs {
   const float* beta1;
   float* amax1;                // [B] |max| tracker of that output (scale of conv2's fp16 split) or null
   int C1;                      // real conv1 channels (<= N1p)
-  int abl;                     // timing probe only (DZN_CONV01_ABL): 1 = skip the VALU phase, 2 = skip the MFMA phase (wrong results)
 };
 
-// PP = true (round 3, "ping-pong"): ONE 512-thread workgroup per CU carries TWO tiles.  Wavefronts 0-3 (group 0) own
-// tile 2 x, wavefronts 4-7 (group 1) tile 2 x + 1, each with its private planes / strip in LDS, and group 1 runs one
-// barrier interval behind: while one group is in its VALU phase (conv0 + LayerNorm + GELU + split -> LDS) the other is in
-// its MFMA phase (conv1 from LDS), on every SIMD, by construction.  Measured with the phases switched off one at a time
-// (DZN_CONV01_ABL, scripts/probe_kernel_class.py, 374 windows): VALU alone 7.8 ms, MFMA alone 8.9 ms, both 13.9 ms with
-// two independent 256-thread workgroups per CU (PP = false: their phases overlap only by chance).
-// UF (r5): conv0 frames a wavefront carries through the VALU phase at once (independent 10-FMA -> LayerNorm -> erf chains that
-// interleave); 4 = r2-r4.
-template <bool PP, int UF = 4>
-__global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const FusedArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-  constexpr int GROUP_LDS = (2 * FF_PLANE + (int)sizeof(float) * (5 * (FF_FR - 1) + 10 + 6 + 112) + (int)sizeof(float2) * FF_FR + 15) / 16 * 16;
-  const int grp = PP ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) : 0;
-  unsigned char* smem = smem_all + grp * GROUP_LDS;
+// Two independent 256-thread workgroups per CU: their phases overlap only by chance.  The form that forced the overlap (one
+// 512-thread workgroup carrying two tiles in anti-phase) measured slower and was removed: DESIGN.md §4.9,
+// profiles/r3_conv01_phase_probe.txt, profiles/r5_conv01_probe.txt.
+// UF: conv0 frames a wavefront carries through the VALU phase at once (independent 10-FMA -> LayerNorm -> erf chains that
+// interleave; 8 against 4: 22.03 -> 21.65 ms per 561-window launch, profiles/r5_conv01_probe.txt).
+constexpr int FF_UF = 8;
+constexpr int FF_LDS = (2 * FF_PLANE + (int)sizeof(float) * (5 * (FF_FR - 1) + 10 + 6 + 112) + (int)sizeof(float2) * FF_FR + 15) / 16 * 16;
+
+__global__ __launch_bounds__(256, 2) void conv01_fused_kernel(const FusedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* pl0 = smem;                                   // hi plane  [FF_FR][64 ch] fp16, slots swizzled
   unsigned char* pl1 = smem + FF_PLANE;                        // lo plane
   float* sx = reinterpret_cast<float*>(smem + 2 * FF_PLANE);   // normalised samples of the strip
@@ -78,15 +73,11 @@ __global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const F
   // profiles/r5_conv01_resources.txt)
   float* slnq = reinterpret_cast<float*>(sst + FF_FR);
 
-  const int tid = threadIdx.x & 255, lane = tid & 63;  // thread / wavefront index inside the group
+  const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, lq = lane >> 4;
   const int b = blockIdx.y;
-  const int ntile = (a.T1 + FF_BM - 1) / FF_BM;
-  int tile = PP ? 2 * (int)blockIdx.x + grp : (int)blockIdx.x;
-  const bool live = tile < ntile;                      // PP, odd tile count: the last group 1 re-does the last tile, stores nothing
-  tile = live ? tile : ntile - 1;
-  const int t1_0 = tile * FF_BM;                       // first conv1 frame of the tile
+  const int t1_0 = (int)blockIdx.x * FF_BM;            // first conv1 frame of the tile
   const int f0 = 2 * t1_0;                             // first conv0 frame
   const int nfr = min(FF_FR, a.T0 - f0);               // conv0 frames that exist
   const int nsamp = 5 * (nfr - 1) + 10;
@@ -123,11 +114,10 @@ __global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const F
   const int KB = 3 * a.C0 / 32;            // 32-blocks of conv1's K
   const int nslab = a.C0 / 64;
 
-  if (PP && grp) __syncthreads();     // group 1 runs one interval behind (both groups execute the same number of barriers)
   for (int slab = 0; slab < nslab; ++slab) {
     __syncthreads();   // statistics written (first slab) / previous slab's planes fully consumed
     // ---- VALU phase: conv0 + LayerNorm + GELU + two-term split of channel (slab * 64 + lane).  A wavefront takes
-    // frames wave, wave + 4, ...; FOUR of them per iteration so that the long dependent chains (10 FMAs -> LayerNorm ->
+    // frames wave, wave + 4, ...; FF_UF of them per iteration so that the long dependent chains (10 FMAs -> LayerNorm ->
     // erf) of different frames interleave — with one frame at a time the chain latency, not the VALU rate, set the pace.
     {
       const int ch = slab * 64 + lane;
@@ -136,10 +126,10 @@ __global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const F
       for (int t = 0; t < 10; ++t) w0[t] = a.w0[ch * 10 + t];
       const float g0 = a.gamma0[ch], b0 = a.beta0[ch];
       const int cslot = lane >> 3, cbyte = (lane & 7) * 2;
-      for (int fb = wave; fb < (a.abl == 1 ? 0 : FF_FR); fb += 4 * UF) {
-        float o[UF];
+      for (int fb = wave; fb < FF_FR; fb += 4 * FF_UF) {
+        float o[FF_UF];
 #pragma unroll
-        for (int u = 0; u < UF; ++u) {
+        for (int u = 0; u < FF_UF; ++u) {
           const int f = fb + 4 * u;
           const int fc = f < nfr ? f : nfr - 1;            // clamped: results of frames past the strip are zeroed below
           float acc0 = 0.f;
@@ -149,9 +139,9 @@ __global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const F
           o[u] = (acc0 - st.x) * st.y * g0 + b0;
         }
 #pragma unroll
-        for (int u = 0; u < UF; ++u) o[u] = gelu_erf(o[u]);
+        for (int u = 0; u < FF_UF; ++u) o[u] = gelu_erf(o[u]);
 #pragma unroll
-        for (int u = 0; u < UF; ++u) {
+        for (int u = 0; u < FF_UF; ++u) {
           const int f = fb + 4 * u;
           if (f < FF_FR) {                                  // wave-uniform
             const float xs = (f < nfr ? o[u] : 0.f) * a.a_scale;
@@ -198,7 +188,6 @@ __global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const F
       }
     };
     u32x4 wfa[NI][2], wfb[NI][2];
-    if (a.abl == 2) continue;
     load_w(0, wfa);
 #pragma unroll
     for (int ks = 0; ks < 6; ks += 2) {
@@ -209,7 +198,6 @@ __global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const F
     }
   }
 
-  if (PP && !grp) __syncthreads();    // matches group 1's offset barrier
   // ---- epilogue: lane (lr, lq) of block (i, jn) holds frame t1_0 + wm*64 + i*16 + lr, channels n0 .. n0 + 3 ----
   float* ob = a.out + (int64_t)b * a.T1 * a.N1p;
   // undo the exact power-of-two operand scales first
@@ -270,7 +258,7 @@ __global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const F
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
         const int t1 = t1_0 + wm * 64 + i * 16 + lr;
-        if (!live || t1 >= a.T1) continue;
+        if (t1 >= a.T1) continue;
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -283,7 +271,6 @@ __global__ __launch_bounds__(PP ? 512 : 256, 2) void conv01_fused_kernel(const F
     if (a.amax1) track_amax(a.amax1 + b, mx);
     return;
   }
-  if (!live) return;
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
     const int t1 = t1_0 + wm * 64 + i * 16 + lr;
@@ -409,7 +396,7 @@ __global__ __launch_bounds__(512, 1) void conv01_ws_kernel(const FusedArgs a, co
         unsigned char* pl1 = pl0 + WS_PLANE;
         const v2f xp[5] = {{x[0], x[1]}, {x[2], x[3]}, {x[4], x[5]}, {x[6], x[7]}, {x[8], x[9]}};
         const v2f mup = {mu, mu}, rsp = {rstd, rstd}, scp = {sc, sc};
-        for (int cg = ((a.abl & 3) == 1 ? 8 : 0); cg < 8; ++cg) {        // 8 channels -> one 16-byte slot of the row, per plane
+        for (int cg = 0; cg < 8; ++cg) {        // 8 channels -> one 16-byte slot of the row, per plane
           u32x4 hw, lw;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
@@ -549,33 +536,29 @@ __global__ __launch_bounds__(512, 1) void conv01_ws_kernel(const FusedArgs a, co
           __builtin_amdgcn_sched_barrier(0);
         }
       };
-      if ((a.abl & 3) != 2) {
-        u32x4 afa[2], afb[2];
-        if (gc == 0) load_w(slab, 0, wfa);          // (later steps: requested before the previous barrier)
-        load_a(0, 0, afa);
+      u32x4 afa[2], afb[2];
+      if (gc == 0) load_w(slab, 0, wfa);          // (later steps: requested before the previous barrier)
+      load_a(0, 0, afa);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int ks = 0; ks < 6; ++ks) {
+        u32x4 (&wc)[NI][2] = (ks & 1) ? wfb : wfa;
+        u32x4 (&wx)[NI][2] = (ks & 1) ? wfa : wfb;
+        if (ks + 1 < 6) load_w(slab, ks + 1, wx);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int ks = 0; ks < 6; ++ks) {
-          u32x4 (&wc)[NI][2] = (ks & 1) ? wfb : wfa;
-          u32x4 (&wx)[NI][2] = (ks & 1) ? wfa : wfb;
-          if (ks + 1 < 6 && !(a.abl & 4)) load_w(slab, ks + 1, wx);      // (abl 4 / 8: timing probes without the W / A traffic)
+        for (int i = 0; i < MI; ++i) {
+          u32x4 (&ac)[2] = (i & 1) ? afb : afa;
+          u32x4 (&ax)[2] = (i & 1) ? afa : afb;
+          if (i + 1 < MI) load_a(ks, i + 1, ax);
+          else if (ks + 1 < 6) load_a(ks + 1, 0, ax);
           __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < MI; ++i) {
-            u32x4 (&ac)[2] = (i & 1) ? afb : afa;
-            u32x4 (&ax)[2] = (i & 1) ? afa : afb;
-            if (!(a.abl & 8)) {
-              if (i + 1 < MI) load_a(ks, i + 1, ax);
-              else if (ks + 1 < 6) load_a(ks + 1, 0, ax);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            mma_block(i, wc, ac);
-          }
+          mma_block(i, wc, ac);
         }
-        // 6 steps, MI = 4 blocks each: the buffers alternate evenly, so the next slab starts on wfa / afa again
-        if (g < nstep && !(a.abl & 4)) load_w(slab + 1 < nslab ? slab + 1 : 0, 0, wfa);
-        __builtin_amdgcn_sched_barrier(0);
       }
+      // 6 steps, MI = 4 blocks each: the buffers alternate evenly, so the next slab starts on wfa / afa again
+      if (g < nstep) load_w(slab + 1 < nslab ? slab + 1 : 0, 0, wfa);
+      __builtin_amdgcn_sched_barrier(0);
       if (slab == nslab - 1) {
         // ---- the tile is complete: undo the exact power-of-two operand scales ----
 #pragma unroll
@@ -712,30 +695,15 @@ int launch_conv01_fused(const float* wave, int B, int N, const float* wstats, co
   a.W2h = static_cast<const u16*>(W2h); a.col_scale = col_scale; a.out = out;
   a.N = N; a.T0 = T0; a.T1 = T1; a.C0 = C0; a.N1p = N1p; a.eps = eps;
   a.gamma1 = gamma1; a.beta1 = beta1; a.C1 = C1; a.amax1 = amax1;
-  static const int abl = getenv("DZN_CONV01_ABL") ? atoi(getenv("DZN_CONV01_ABL")) : 0;
-  a.abl = abl;
   {   // exact power-of-two scale that puts the bound into [2^14, 2^15)
     int e;
     (void)frexpf(act_bound, &e);          // act_bound = m * 2^e, m in [0.5, 1)
     a.a_scale = ldexpf(1.0f, 15 - e);
     a.a_inv = ldexpf(1.0f, e - 15);
   }
-  const size_t group_lds = (2 * FF_PLANE + sizeof(float) * (5 * (FF_FR - 1) + 10 + 6 + 112) + sizeof(float2) * FF_FR + 15) / 16 * 16;
-  // two tiles per 512-thread workgroup with the phases in anti-phase: measured SLOWER (15.7 vs 13.7 ms per 374 windows,
-  // profiles/r3_conv01_phase_probe.txt) — a phase that runs on ONE wavefront per SIMD is bound by its dependent chains
-  // (VALU alone: 13.4 ms in this form, 7.8 ms when two workgroups share the SIMDs), so forcing the overlap costs more
-  // than it hides.  Kept behind DZN_CONV01_PP=1 for the record; the default is two independent workgroups per CU.
-  static const bool pp = getenv("DZN_CONV01_PP") != nullptr;
-  // frames per wavefront iteration of the VALU phase: 8 since r5 (22.03 -> 21.65 ms per 561-window launch; 4 = r2-r4's kernel;
-  // profiles/r5_conv01_probe.txt, which also re-measures the anti-phase form: 23.8 / 22.7 ms at 4 / 8 — still slower)
-  static const int uf = getenv("DZN_CONV01_UF") ? atoi(getenv("DZN_CONV01_UF")) : 8;
   static unsigned long long attr_mask = 0;
-  if (first_use_on_device(attr_mask)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv01_fused_kernel<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv01_fused_kernel<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv01_fused_kernel<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv01_fused_kernel<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
+  if (first_use_on_device(attr_mask))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv01_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   const int ntile = (T1 + FF_BM - 1) / FF_BM;
   // algorithmic work: conv0 + conv1 flops; algorithmic HBM bytes: waveform in, conv1's raw output out
   const int pid = prof_begin(st, "conv01_fused", 2.0 * B * ((double)T0 * C0 * 10 + (double)T1 * 153.0 * 3 * C0),
@@ -743,7 +711,7 @@ int launch_conv01_fused(const float* wave, int B, int N, const float* wstats, co
   // (r6) producer / consumer wavefronts in persistent workgroups (conv01_ws_kernel); DZN_CONV01_WS=0: the phase-alternating kernel
   const char* ws_env = getenv("DZN_CONV01_WS");      // read per call (tests compare the two kernels in one process)
   const bool ws = !(ws_env && atoi(ws_env) == 0);
-  if (ws && !pp && (!gamma1 || (C1 > 80 && C1 <= 160))) {
+  if (ws && (!gamma1 || (C1 > 80 && C1 <= 160))) {
     static unsigned long long ws_mask = 0;
     static int cus[64];
     int dev = 0;
@@ -758,10 +726,9 @@ int launch_conv01_fused(const float* wave, int B, int N, const float* wstats, co
     const int64_t items = (int64_t)B * wtile;
     const int grid = (int)(items < cus[dev & 63] ? items : cus[dev & 63]);
     hipLaunchKernelGGL(conv01_ws_kernel, dim3(grid), dim3(512), WS_LDS, st, a, B, wtile);
-  } else if (pp && uf == 8) hipLaunchKernelGGL((conv01_fused_kernel<true, 8>), dim3((ntile + 1) / 2, B), dim3(512), 2 * group_lds, st, a);
-  else if (pp) hipLaunchKernelGGL((conv01_fused_kernel<true, 4>), dim3((ntile + 1) / 2, B), dim3(512), 2 * group_lds, st, a);
-  else if (uf == 8) hipLaunchKernelGGL((conv01_fused_kernel<false, 8>), dim3(ntile, B), dim3(256), group_lds, st, a);
-  else hipLaunchKernelGGL((conv01_fused_kernel<false, 4>), dim3(ntile, B), dim3(256), group_lds, st, a);
+  } else {
+    hipLaunchKernelGGL(conv01_fused_kernel, dim3(ntile, B), dim3(256), FF_LDS, st, a);
+  }
   prof_end(pid, st);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }

@@ -361,8 +361,7 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const dzn_gemm_desc d) {
 template <int BM, int BN, int WGM, int WGN, bool LOWP>
 int launch_cfg(const dzn_gemm_desc& d, hipStream_t s) {
   const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
-  static const int lds_pad = getenv("DZN_GEMM_LDS_PAD") ? atoi(getenv("DZN_GEMM_LDS_PAD")) : 0;
-  const size_t lds = 2 * (BM + BN) * 128 + lds_pad;
+  const size_t lds = 2 * (BM + BN) * 128;
   auto kern = gemm_kernel<BM, BN, WGM, WGN, LOWP>;
   static unsigned long long attr_mask = 0;  // one bit per HIP device: function attributes are per device
   if (first_use_on_device(attr_mask)) {
@@ -465,8 +464,6 @@ int launch_gemm(const dzn_gemm_desc& din, hipStream_t s) {
                     !(d.kv_plane_stride & 3) && d.N > 32 && !getenv("DZN_GEMM_CFG") && !getenv("DZN_NO_H2");
     if (!ok) return DZN_E_INVALID;
   }
-  if (d.ln_centered && !(d.precision == DZN_PREC_F16 && d.W3 && !(d.K & 31) && !(d.kc & 31) && d.ldw == d.K && !d.a_split3))
-    return DZN_E_INVALID;    // only gemm_split.hip's single-term kernel subtracts the row mean (see launch_gemm_split)
   if (d.a_split3) return prec_is_split(d.precision) ? launch_gemm_split_pre(d, s) : DZN_E_INVALID;
   if (prec_is_split(d.precision) && d.W3 && !(d.K & 31) && !(d.kc & 31) && d.ldw == d.K)
     return launch_gemm_split(d, s);

@@ -98,8 +98,7 @@ __device__ __forceinline__ void split8_mx(const f32x4& u, const f32x4& v, float 
 // BM x BN tile per workgroup of WGM x WGN wavefronts, S LDS stages of one 32-k tile each; wavefront tiles of 32 x 32 blocks.
 // sc_one / sc_lo arrive as kernel arguments so that the scale operands of the MX instruction are registers (a literal there is
 // taken as an f32 constant by the compiler).
-// RPF: residual prefetch at kernel start (gemm_epilogue.h), for the short-K launches whose time is their epilogue.
-template <int BM, int BN, int WGM, int WGN, int S, int OCC = 1, bool RPF = false>
+template <int BM, int BN, int WGM, int WGN, int S, int OCC = 1>
 __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_mx_kernel(const dzn_gemm_desc d, const int sc_one, const int sc_lo) {
   constexpr int NW = WGM * WGN;
   constexpr int BK = 32;
@@ -149,12 +148,6 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_mx_kernel(const dzn_
   const int64_t cz = z0 * d.c_z0 + z1 * d.c_z1;
   const int64_t bz = z0 * d.b_z0 + z1 * d.b_z1;
 
-  f32x4 rpre[RPF ? MI : 1][RPF ? 4 * NJ : 1];
-  bool use_rpre = false;
-  if constexpr (RPF) {
-    use_rpre = d.R != nullptr && gemm_epilogue_vec(d, cz, bz);
-    if (use_rpre) gemm_prefetch_residual<BM, BN, TM, TN, MI, 4 * NJ, 32, 8>(d, rpre, tm, tn, wm, wn, l31, lh, cz);
-  }
   // ---- LDS-DMA sources: identical to gemm_split_kernel ----
   const int r0 = tid >> 3;
   const int csw = (tid & 7) ^ ((r0 >> 1) & 7);
@@ -389,22 +382,15 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_mx_kernel(const dzn_
       for (int g = 0; g < 4; ++g)
 #pragma unroll
         for (int e = 0; e < 4; ++e) accv[i][4 * j + g][e] = acc[i][j][4 * g + e];
-  if constexpr (RPF) {
-    if (use_rpre) {
-      gemm_epilogue<BM, BN, TM, TN, MI, 4 * NJ, true, 32, 8>(d, accv, tm, tn, wm, wn, l31, lh, cz, bz, z0, row_inv, d.col_scale_mx,
-                                                           reinterpret_cast<float*>(smem) + wave * 3 * TN, rpre);
-      return;
-    }
-  }
   gemm_epilogue<BM, BN, TM, TN, MI, 4 * NJ, true, 32, 8>(d, accv, tm, tn, wm, wn, l31, lh, cz, bz, z0, row_inv, d.col_scale_mx,
                                                        reinterpret_cast<float*>(smem) + wave * 3 * TN);
 }
 
-template <int BM, int BN, int WGM, int WGN, int S, int OCC, bool RPF = false>
+template <int BM, int BN, int WGM, int WGN, int S, int OCC>
 int launch_mx_cfg(const dzn_gemm_desc& d, hipStream_t s) {
   const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
   const size_t lds = (size_t)S * (BM * 128 + 2 * BN * 64);
-  auto kern = gemm_mx_kernel<BM, BN, WGM, WGN, S, OCC, RPF>;
+  auto kern = gemm_mx_kernel<BM, BN, WGM, WGN, S, OCC>;
   static unsigned long long attr_mask = 0;
   if (first_use_on_device(attr_mask))
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -414,7 +400,7 @@ int launch_mx_cfg(const dzn_gemm_desc& d, hipStream_t s) {
     char cls[64];
     static const bool by_shape = getenv("DZN_PROFILE_SHAPES") != nullptr;
     if (by_shape) snprintf(cls, sizeof(cls), "gemm_mx_%dx%d M%d N%d K%d z%d", BM, BN, d.M, d.N, d.K, d.nz);
-    else snprintf(cls, sizeof(cls), "gemm_mx_%dx%d%s", BM, BN, RPF ? "_rpf" : "");
+    else snprintf(cls, sizeof(cls), "gemm_mx_%dx%d", BM, BN);
     const double fl = d.alg_flops > 0 ? d.alg_flops * d.nz : 2.0 * d.M * d.N * d.K * d.nz;
     pid = prof_begin(s, cls, fl, gemm_alg_bytes(d, 4));
   }
@@ -486,7 +472,6 @@ int launch_gemm_mx(const dzn_gemm_desc& d, hipStream_t s) {
   const char* force = g_mx_force();
   if (force && !strcmp(force, "128x64")) return launch_mx_cfg<128, 64, 4, 1, 2, 3>(d, s);
   if (force && !strcmp(force, "128x128")) return launch_mx_cfg<128, 128, 4, 1, 2, 2>(d, s);
-  if (force && !strcmp(force, "128x64rpf")) return launch_mx_cfg<128, 64, 4, 1, 2, 2, true>(d, s);
   if (force && !strcmp(force, "256x128")) return launch_mx_cfg<256, 128, 8, 1, 2, 2>(d, s);     // probe: 8 wavefronts, one workgroup per CU
   if (narrow) return launch_mx_cfg<128, 64, 4, 1, 2, 3>(d, s);
   return launch_mx_cfg<128, 128, 4, 1, 2, 2>(d, s);

@@ -68,13 +68,8 @@ __device__ __forceinline__ void wait_vm_lgkm0() {
 //     rows is multiplied, then [wait tile kt+1, barrier, refill the stage of tile kt], then the
 //     fragments of tile kt+1 are read into the second register set while the second half of
 //     tile kt is multiplied — the matrix pipe has work queued across the barrier.
-// ABL != 0: ABLATION probes for scripts/bench_gemm_cfgs.py (wrong results on purpose; never launched by the engines):
-//   1 = no operand split (raw bits as fragments), 2 = no MFMAs, 3 = no steady-state LDS-DMA refills, 4 = no barrier,
-//   5 = no fragment reads after the first tile
-// RPF (r5): the residual of the whole wavefront tile is requested before the first operand tile (gemm_prefetch_residual): the
-// short-K launches' epilogue is then stores only.
-template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1, int ABL = 0, bool RPF = false>
-__global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const dzn_gemm_desc d, const int ngroups) {
+template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1>
+__global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const dzn_gemm_desc d) {
   constexpr int NW = WGM * WGN;           // wavefronts per workgroup
   constexpr int BK = 32;
   constexpr int TM = BM / WGM, TN = BN / WGN;
@@ -103,31 +98,12 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
     t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
-  // (r4) COLUMN GROUPS.  t walks the tiles XCD by XCD (contiguous ranges).  With ngroups == 1 that order is row-block-major:
-  // an XCD works on a few row blocks with ALL their column tiles, so it streams the whole weight-plane set (N x K x 2 NP bytes)
-  // once per row block — and from ~4 MB on that set no longer survives in the XCD's 4 MB L2 between two row blocks
-  // (profiles/r4_gemm_refetch_probe.txt: fabric reads 1.02 x the algorithmic bytes at N = 128, 2.1 x at N = K = 1024, 4.7 x at
-  // N = 2048; the excess is 0.27 / 0.69 of the plane set PER ROW BLOCK).  With ngroups = G the column tiles are cut into G
-  // contiguous groups and the order is group-major, so an XCD meets only 1 / G of the planes (they stay in its L2) while a row
-  // block of A is fetched by G XCDs instead of one; the launcher picks G from that trade (choose_column_groups).  A
-  // permutation of the tile index: every tile is computed exactly once, by the same code — results do not change.
-  int tm, tn;
-  if (ngroups <= 1) {
-    tm = t / tilesN;
-    tn = t % tilesN;
-  } else {
-    const int tilesM_ = (int)gridDim.x / tilesN;
-    const int base = tilesN / ngroups, rem = tilesN % ngroups;
-    int g = 0, cg = base + (rem > 0), cs = 0, r = t;
-    while (r >= tilesM_ * cg) {     // ngroups <= 8 iterations, scalar
-      r -= tilesM_ * cg;
-      cs += cg;
-      ++g;
-      cg = base + (g < rem);
-    }
-    tm = r / cg;
-    tn = cs + r - tm * cg;
-  }
+  // t walks the tiles XCD by XCD (contiguous ranges) in row-block-major order: an XCD works on a few row blocks with ALL their
+  // column tiles, so it streams the whole weight-plane set (N x K x 2 NP bytes) once per row block.  From ~4 MB on that set no
+  // longer survives in the XCD's 4 MB L2 between two row blocks, but the re-fetched planes come from the Infinity Cache at no
+  // measurable cost in time: a group-major order that cut the fabric reads as modelled left the step unchanged and was removed
+  // (DESIGN.md §5 "Switch retirement", profiles/r4_gemm_refetch_probe.txt).
+  const int tm = t / tilesN, tn = t % tilesN;
   const int z = blockIdx.y;
   int z0 = z / d.zdiv;
   const int z1 = z - z0 * d.zdiv;
@@ -152,23 +128,6 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
       const int unit = d.amax_unit > 0 ? m / d.amax_unit : z0;
       DZN_CHECK(d.amax_count <= 0 || (unit >= 0 && unit < d.amax_count), 0x101, unit);   // tracker index inside its array
       h2_scale(d.a_amax[unit], a_scale[i], row_inv[i]);
-    }
-  }
-  // NP = 1 with a folded LayerNorm (d.ln_centered): the row mean is subtracted before the fp16 rounding; |x - mean| <=
-  // 2 amax, so the scale gives up one bit of headroom
-  float a_mean[MI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i) a_mean[i] = 0.f;
-  if constexpr (NP == 1) {
-    if (d.ln_centered && d.ln_stats) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        int m = tm * BM + wm * TM + i * 16 + (lane & 15);
-        m = m < d.M ? m : d.M - 1;
-        a_mean[i] = d.ln_stats[2 * (int64_t)m];
-        a_scale[i] *= 0.5f;
-        row_inv[i] *= 2.f;
-      }
     }
   }
   const int64_t cz = z0 * d.c_z0 + z1 * d.c_z1;
@@ -231,12 +190,6 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
 #pragma unroll
     for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int lr = lane & 15, lq = lane >> 4;
-  f32x4 rpre[RPF ? MI : 1][RPF ? NI : 1];
-  bool use_rpre = false;
-  if constexpr (RPF) {
-    use_rpre = d.R != nullptr && gemm_epilogue_vec(d, cz, bz);
-    if (use_rpre) gemm_prefetch_residual<BM, BN, TM, TN, MI, NI>(d, rpre, tm, tn, wm, wn, lr, lq, cz);
-  }
 
   // per-lane LDS byte offsets of the fragments inside a stage
   int woff[NI], aoff0[MI], aoff1[MI];
@@ -275,10 +228,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
   // the products of one 16-row block against all NI column blocks: smallest terms first, NI independent
   // accumulators between dependent MFMAs.  af[] = A terms (hi, [mid,] lo), wf[j][] = W planes (hi, [mid,] lo).
   auto mma = [&](int i, const u32x4 (&wf)[NI][NP], const u32x4 (&af)[NP]) {
-    if constexpr (ABL == 2) {
-#pragma unroll
-      for (int j = 0; j < NI; ++j) acc[i][j][0] += __uint_as_float(wf[j][0][0] ^ af[0][0]);   // keep the operands live
-    } else if constexpr (NP == 3) {
+    if constexpr (NP == 3) {
       constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PA[6] = {0, 2, 1, 0, 1, 0};   // lo*hi hi*lo mid*mid mid*hi hi*mid hi*hi
 #pragma unroll
       for (int t = 0; t < 6; ++t)
@@ -295,11 +245,8 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
       for (int j = 0; j < NI; ++j) acc[i][j] = mfma_np<NP>(wf[j][0], af[0], acc[i][j]);
     }
   };
-  auto split = [&](const f32x4 (&a)[2], u32x4 (&af)[NP], float sc, float mu = 0.f) {
-    if constexpr (ABL == 1) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p) af[p] = __builtin_bit_cast(u32x4, a[p & 1]);
-    } else if constexpr (NP == 3) {
+  auto split = [&](const f32x4 (&a)[2], u32x4 (&af)[NP], float sc) {
+    if constexpr (NP == 3) {
       bf16x8 h_, m_, l_;
       split8(a[0], a[1], h_, m_, l_);
       af[0] = __builtin_bit_cast(u32x4, h_);
@@ -308,7 +255,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
     } else if constexpr (NP == 2) {
       split8_h2(a[0], a[1], sc, af[0], af[1]);
     } else {
-      cvt8_h1(a[0] - mu, a[1] - mu, sc, af[0]);      // mu = 0 unless d.ln_centered (x - 0 is exact)
+      cvt8_h1(a[0], a[1], sc, af[0]);
     }
   };
 
@@ -329,7 +276,6 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
   f32x4 ar[MI][2];
   read_w(0, wfa);
   read_a(0, ar);
-  if constexpr (ABL == 5) read_w(0, wfb);
   int stage = 0;
 
   // one K tile: `wc` holds its W fragments, `ar` its raw A fragments; leaves tile kt+1 in (wn_, ar)
@@ -338,25 +284,22 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
 #pragma unroll
     for (int i = 0; i < MH; ++i) {
       u32x4 af[NP];
-      split(ar[i], af, a_scale[i], a_mean[i]);
+      split(ar[i], af, a_scale[i]);
       mma(i, wc, af);
     }
     u32x4 af2[MI - MH][NP];
 #pragma unroll
-    for (int i = MH; i < MI; ++i) split(ar[i], af2[i - MH], a_scale[i], a_mean[i]);
+    for (int i = MH; i < MI; ++i) split(ar[i], af2[i - MH], a_scale[i]);
     const int nstage = stage + 1 == S ? 0 : stage + 1;
     __builtin_amdgcn_sched_barrier(0);  // keep the second half of the MFMAs BEHIND the barrier block
     if (more) {
       // tile kt+1 landed (tiles kt+2 .. kt+S-1 may stay in flight); all my reads of tile kt retired
       if (kt + S <= nk) wait_tiles(std::integral_constant<int, S - 2>{});
       else wait_vm_lgkm0<0>();
-      if constexpr (ABL != 4) __builtin_amdgcn_s_barrier();
-      if constexpr (ABL != 3)
-        if (kt + S < nk) issue(stage);  // every wave is past its reads of tile kt
-      if constexpr (ABL != 5) {
-        read_w(nstage, wn_);
-        read_a(nstage, ar);
-      }
+      __builtin_amdgcn_s_barrier();
+      if (kt + S < nk) issue(stage);  // every wave is past its reads of tile kt
+      read_w(nstage, wn_);
+      read_a(nstage, ar);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -367,349 +310,21 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
     step(kt, wfa, wfb);
     if (kt + 1 < nk) step(kt + 1, wfb, wfa);
   }
-  if constexpr (true) {
-    // the epilogue's column vectors live in LDS (48 registers less than holding them): the stages are dead once every
-    // wavefront left the loop
-    __syncthreads();
-    if constexpr (RPF) {
-      if (use_rpre) {
-        gemm_epilogue<BM, BN, TM, TN, MI, NI, true>(d, acc, tm, tn, wm, wn, lr, lq, cz, bz, z0, row_inv, NP <= 2 ? d.col_scale : nullptr,
-                                                    reinterpret_cast<float*>(smem) + wave * 3 * TN, rpre);
-        return;
-      }
-    }
-    gemm_epilogue<BM, BN, TM, TN, MI, NI, true>(d, acc, tm, tn, wm, wn, lr, lq, cz, bz, z0, row_inv, NP <= 2 ? d.col_scale : nullptr,
-                                                reinterpret_cast<float*>(smem) + wave * 3 * TN);
-  } else {
-    gemm_epilogue<BM, BN, TM, TN, MI, NI>(d, acc, tm, tn, wm, wn, lr, lq, cz, bz, z0, row_inv, NP <= 2 ? d.col_scale : nullptr);
-  }
-}
-
-#ifdef DZN_TUNING
-// ---- (r4) the same contraction on 32x32x16 MFMA blocks: a MEASURED NEGATIVE, kept as a DZN_TUNING probe ------------------
-// VERDICT r3 item 4 asked for it.  Result (profiles/r4_gemm_m32_probe.txt, M = 149 226): 253-272 TFLOP/s where the
-// 16x16x32 tile below has 285-305 on the same shapes (N = K = 1024: 270 vs 305; N 1920: 272 vs 304; K = 256: 149 vs 170),
-// s_setprio around the MFMA cluster changes nothing, 2 x 2 / 256 x 128 wavefront layouts are slower still, and in the
-// pipeline the step loses 4 % (1160 vs 1116 ms).  Same LDS bytes, same DMA schedule, half the MFMA instructions: the
-// contraction is evidently not bound by MFMA issue or operand-register reads.  (Not isolated further: the form has 4
-// independent accumulator blocks per wavefront where the 16x16 form has 16, against a 16-pass dependent latency.)
-// v_mfma_f32_32x32x16_f16 does twice the flops of v_mfma_f32_16x16x32_f16 from the same 4 + 4 operand registers: half
-// the operand-register reads per flop, and the instruction retires 2 x 16 passes where two 16x16x32 need 2 x 8 + issue gaps
-// (guide: 2178 vs 1955 TFLOP/s fp16 micro-benchmark ceilings).  Same tile, same LDS images, same LDS-DMA schedule and the
-// same weight planes as gemm_split_kernel — only the lane -> element map changes:
-//   * lane (l31 = lane & 31, lh = lane >> 5) owns row / column l31 of a 32-wide block and the k subset of chunk
-//     c = 2 kh + lh of the 32-k tile, kh = 0, 1 being the two 16-k MFMAs of the tile.  The weight planes keep their k
-//     order (chunk c = k in {4c..4c+3} u {16+4c..16+4c+3}); the A fragment of chunk c is the fp32 slots c and 4 + c of the
-//     row — exactly what the 16x16 form reads for lq = c — so both operands of an MFMA cover the same 16 k.
-//   * ds_read_b128 stays conflict free: a 16-lane group of the instruction now holds 16 different rows of ONE chunk; the
-//     A swizzle (slot ^ (row >> 1) & 7) and the W swizzle (slot ^ g((row >> 2) & 3)) spread those over all 16 slots.
-//   * accumulators: lane holds row l31, columns 32 j + 8 g + 4 lh + (0..3) for g = 0..3: four float4 per block; the
-//     epilogue sees them as 8-column blocks (gemm_epilogue<..., RS = 32, CS = 8>).
-// The K tile is multiplied in its two 16-k halves with the barrier block between them (the 16x16 form splits by rows).
-// NP = 2 (f32h) and NP = 1 (f16) only.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1, int PRIO = 0>
-__global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split32_kernel(const dzn_gemm_desc d) {
-  static_assert(NP == 1 || NP == 2, "fp16 forms only");
-  constexpr int NW = WGM * WGN;
-  constexpr int BK = 32;
-  constexpr int TM = BM / WGM, TN = BN / WGN;
-  constexpr int MI = TM / 32, NJ = TN / 32;
-  constexpr int RB = NW * 1024;
-  constexpr int ACH = BM * 128 / RB;
-  constexpr int WROWS = NW * 16;
-  constexpr int WR = (BN + WROWS - 1) / WROWS;
-  constexpr int ABYTES = BM * 128, WPLANE = BN * 64, BUF = ABYTES + NP * WPLANE;
-  constexpr int LPT = ACH + NP * WR;
-  constexpr bool WPART = BN % WROWS != 0;
-  static_assert(BM * 128 % RB == 0 && TM % 32 == 0 && TN % 32 == 0, "tile geometry");
-  static_assert(S >= 2 && (S - 1) * LPT < 64, "vmcnt range");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WGN, wn = wave % WGN;
-  const int tilesN = (d.N + BN - 1) / BN;
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int tm = t / tilesN, tn = t % tilesN;
-  const int z = blockIdx.y;
-  int z0 = z / d.zdiv;
-  const int z1 = z - z0 * d.zdiv;
-  if (d.z_list) {
-    if (z0 >= d.z_count[0]) return;
-    z0 = d.z_list[z0];
-  }
-  const float* __restrict__ A = d.A + z0 * d.a_z0 + z1 * d.a_z1;
-  const u16* __restrict__ W2 = reinterpret_cast<const u16*>(d.W2h) + 2 * (z0 * d.w_z0 + z1 * d.w_z1);
-  const int l31 = lane & 31, lh = lane >> 5;
-  float a_scale[MI], row_inv[MI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    int m = tm * BM + wm * TM + i * 32 + l31;
-    m = m < d.M ? m : d.M - 1;
-    h2_scale(d.a_amax[d.amax_unit > 0 ? m / d.amax_unit : z0], a_scale[i], row_inv[i]);
-  }
-  const int64_t cz = z0 * d.c_z0 + z1 * d.c_z1;
-  const int64_t bz = z0 * d.b_z0 + z1 * d.b_z1;
-
-  // ---- LDS-DMA sources: identical to gemm_split_kernel ----
-  const int r0 = tid >> 3;
-  const int csw = (tid & 7) ^ ((r0 >> 1) & 7);
-  const float* aptr[ACH];
-#pragma unroll
-  for (int i = 0; i < ACH; ++i) {
-    int m = tm * BM + r0 + 8 * NW * i;
-    m = m < d.M ? m : d.M - 1;
-    aptr[i] = A + (d.a_rowoff ? (int64_t)d.a_rowoff[m] : (int64_t)m * d.lda) + csw * 4;
-  }
-  const bool wfull = !WPART || (WR - 1) * WROWS + wave * 16 < BN;
-  const int wr0 = wave * 16 + (lane >> 2);
-  const int wsw = (lane & 3) ^ wswz(wr0);
-  const u16* wptr[WR];
-#pragma unroll
-  for (int i = 0; i < WR; ++i) {
-    int n = tn * BN + wr0 + WROWS * i;
-    n = n < d.N ? n : d.N - 1;
-    wptr[i] = W2 + (int64_t)n * 2 * d.ldw + wsw * 8;
-  }
-  int ik = 0, irem = 0;
-  int64_t ikoff = 0;
-  auto issue = [&](int stage) {
-    unsigned char* sA = smem + stage * BUF + wave * 1024;
-    unsigned char* sW = smem + stage * BUF + ABYTES + wave * 1024;
-#pragma unroll
-    for (int i = 0; i < ACH; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(aptr[i] + ikoff),
-                                       (__attribute__((address_space(3))) void*)(sA + i * RB), 16, 0, 0);
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int i = 0; i < WR; ++i)
-        if (i + 1 < WR || wfull)
-          __builtin_amdgcn_global_load_lds(
-              (const __attribute__((address_space(1))) void*)(wptr[i] + 2 * ik + p * 32),
-              (__attribute__((address_space(3))) void*)(sW + p * WPLANE + i * RB), 16, 0, 0);
-    ik += BK;
-    irem += BK;
-    ikoff += BK;
-    if (irem == d.kc) { irem = 0; ikoff += d.ldk - d.kc; }
-  };
-
-  f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  // per-lane LDS byte offsets: [block][k half]
-  int woff[NJ][2], aoff0[MI][2], aoff1[MI][2];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int row = wn * TN + j * 32 + l31;
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) woff[j][kh] = ABYTES + row * 64 + (((2 * kh + lh) ^ wswz(row)) << 4);
-  }
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int row = wm * TM + i * 32 + l31;
-    const int sw = (row >> 1) & 7;
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-      const int c = 2 * kh + lh;
-      aoff0[i][kh] = row * 128 + ((c ^ sw) << 4);
-      aoff1[i][kh] = row * 128 + (((4 + c) ^ sw) << 4);
-    }
-  }
-  auto read_w = [&](int stage, u32x4 (&wf)[NJ][2][NP]) {
-    const unsigned char* base = smem + stage * BUF;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-        for (int p = 0; p < NP; ++p) wf[j][kh][p] = *reinterpret_cast<const u32x4*>(base + p * WPLANE + woff[j][kh]);
-  };
-  auto read_a = [&](int stage, f32x4 (&ar)[MI][2][2]) {
-    const unsigned char* base = smem + stage * BUF;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        ar[i][kh][0] = *reinterpret_cast<const f32x4*>(base + aoff0[i][kh]);
-        ar[i][kh][1] = *reinterpret_cast<const f32x4*>(base + aoff1[i][kh]);
-      }
-  };
-  auto mfma32 = [&](const u32x4& a, const u32x4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  };
-  // the products of row block i against all NJ column blocks for one 16-k half: smallest terms first, NJ independent
-  // accumulators between dependent MFMAs (32x32x16: 16 passes, the next MFMA on the same block is 4 instructions away)
-  auto mma = [&](int i, int kh, const u32x4 (&wf)[NJ][2][NP], const u32x4 (&af)[NP]) {
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
-    if constexpr (NP == 2) {
-      constexpr int PW[3] = {1, 0, 0}, PA[3] = {0, 1, 0};                     // lo*hi hi*lo hi*hi
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = mfma32(wf[j][kh][PW[t]], af[PA[t]], acc[i][j]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[i][j] = mfma32(wf[j][kh][0], af[0], acc[i][j]);
-    }
-    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-  };
-  auto split = [&](const f32x4 (&a)[2], u32x4 (&af)[NP], float sc) {
-    if constexpr (NP == 2) split8_h2(a[0], a[1], sc, af[0], af[1]);
-    else cvt8_h1(a[0], a[1], sc, af[0]);
-  };
-
-  const int nk = d.K / BK;
-#pragma unroll
-  for (int s = 0; s < S; ++s)
-    if (s < nk) issue(s);
-  auto wait_tiles = [&](auto tiles) {
-    constexpr int T = decltype(tiles)::value;
-    if (wfull) wait_vm_lgkm0<T * LPT>();
-    else wait_vm_lgkm0<T * (LPT - NP)>();
-  };
-  if (nk >= S) wait_tiles(std::integral_constant<int, S - 1>{});
-  else wait_vm_lgkm0<0>();
-  __builtin_amdgcn_s_barrier();
-  u32x4 wfa[NJ][2][NP], wfb[NJ][2][NP];
-  f32x4 ar[MI][2][2];
-  read_w(0, wfa);
-  read_a(0, ar);
-  int stage = 0;
-
-  auto step = [&](int kt, const u32x4 (&wc)[NJ][2][NP], u32x4 (&wn_)[NJ][2][NP]) {
-    const bool more = kt + 1 < nk;
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      u32x4 af[NP];
-      split(ar[i][0], af, a_scale[i]);
-      mma(i, 0, wc, af);
-    }
-    u32x4 af2[MI][NP];
-#pragma unroll
-    for (int i = 0; i < MI; ++i) split(ar[i][1], af2[i], a_scale[i]);
-    const int nstage = stage + 1 == S ? 0 : stage + 1;
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) {
-      if (kt + S <= nk) wait_tiles(std::integral_constant<int, S - 2>{});
-      else wait_vm_lgkm0<0>();
-      __builtin_amdgcn_s_barrier();
-      if (kt + S < nk) issue(stage);
-      read_w(nstage, wn_);
-      read_a(nstage, ar);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < MI; ++i) mma(i, 1, wc, af2[i]);
-    stage = nstage;
-  };
-  for (int kt = 0; kt < nk; kt += 2) {
-    step(kt, wfa, wfb);
-    if (kt + 1 < nk) step(kt + 1, wfb, wfa);
-  }
+  // the epilogue's column vectors live in LDS (48 registers less than holding them): the stages are dead once every
+  // wavefront left the loop
   __syncthreads();
-  // accumulators as 8-column blocks: block 4 j + g of lane (l31, lh) = columns 32 j + 8 g + 4 lh .. + 3 of row 32 i + l31
-  f32x4 accv[MI][4 * NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) accv[i][4 * j + g][e] = acc[i][j][4 * g + e];
-  gemm_epilogue<BM, BN, TM, TN, MI, 4 * NJ, true, 32, 8>(d, accv, tm, tn, wm, wn, l31, lh, cz, bz, z0, row_inv, d.col_scale,
-                                                       reinterpret_cast<float*>(smem) + wave * 3 * TN);
+  gemm_epilogue<BM, BN, TM, TN, MI, NI, true>(d, acc, tm, tn, wm, wn, lr, lq, cz, bz, z0, row_inv, NP <= 2 ? d.col_scale : nullptr,
+                                              reinterpret_cast<float*>(smem) + wave * 3 * TN);
 }
 
-template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1, int PRIO = 0>
-int launch_split32_cfg(const dzn_gemm_desc& d, hipStream_t s) {
-  const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
-  const size_t lds = (size_t)S * (BM * 128 + NP * BN * 64);
-  auto kern = gemm_split32_kernel<BM, BN, WGM, WGN, S, NP, OCC, PRIO>;
-  static unsigned long long attr_mask = 0;
-  if (first_use_on_device(attr_mask))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  dim3 grid(tilesM * tilesN, d.nz > 0 ? d.nz : 1, 1);
-  int pid = -1;
-  if (prof_enabled()) {
-    char cls[64];
-    static const bool by_shape = getenv("DZN_PROFILE_SHAPES") != nullptr;
-    if (by_shape)
-      snprintf(cls, sizeof(cls), "gemm_%s_%dx%d M%d N%d K%d z%d", NP == 2 ? "f32h" : "f16", BM, BN, d.M, d.N, d.K, d.nz);
-    else
-      snprintf(cls, sizeof(cls), "gemm_%s_%dx%d", NP == 2 ? "f32h" : "f16", BM, BN);
-    const double fl = d.alg_flops > 0 ? d.alg_flops * d.nz : 2.0 * d.M * d.N * d.K * d.nz;
-    pid = prof_begin(s, cls, fl, gemm_alg_bytes(d, NP * 2));
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, d);
-  prof_end(pid, s);
-  if (hipGetLastError() != hipSuccess) return DZN_E_HIP;
-  if (d.stat_partial && d.stat_final)
-    return launch_stats_finalize(d.stat_partial, d.M, tilesN * WGN, d.stat_C, d.stat_eps, d.stat_final, s);
-  return DZN_OK;
-}
+// (r4) The same contraction on 32x32x16 MFMA blocks measured 253-272 TFLOP/s against 285-305 for the 16x16x32
+// tile above and lost 4 % on the step; it was removed (profiles/r4_gemm_m32_probe.txt).
 
-#endif  // DZN_TUNING (32x32x16 probe)
-
-// Column groups of a launch (gemm_split_kernel, "COLUMN GROUPS").  Fabric reads of a launch as a function of G, from the
-// measured miss fractions of the weight-plane set per row block (profiles/r4_gemm_refetch_probe.txt; M = 149226, K = 1024,
-// one XCD = 4 MB of L2 shared with the streaming A / C / residual traffic):
-//     plane set seen by an XCD   0.5 MB   1 MB    2 MB    4 MB    8 MB
-//     fraction re-fetched        0.02     0.055   0.12    0.27    0.69        (log-linear between, 1.0 from 12 MB on)
-//     reads(G) = G x A  +  row_blocks x W x miss(W / G)
-// G in {1, 2, 4, 8}, G <= column tiles, the smallest reads(G) wins and G = 1 unless the saving is worth 5 % of the launch's reads.
-// STATE (end of r4): built, correct (kernel tests + the turn-taking goldens pass under forced G = 3 / 4), and NEUTRAL in time — the
-// step is 1040.8 ms with the model's choice against 1039.2 ms with G = 1 — although the fabric reads DO drop as modelled (N = 2048:
-// 8.59 -> 4.82 GB per launch, model 4.9; profiles/r4_gemm_refetch_probe.txt): the re-fetched planes come from the 256 MB
-// Infinity Cache, which costs neither time nor measurable power.  So the default stays G = 1, the r1-r3 order;
-// DZN_GEMM_NGROUPS (read once) = "auto" takes the model's choice, a number forces it.
-int choose_column_groups(const dzn_gemm_desc& d, int tilesM, int tilesN, int BM, int NP) {
-  static const char* env = getenv("DZN_GEMM_NGROUPS");
-  static const bool automatic = env && !strcmp(env, "auto");
-  static const int forced = env && !automatic ? atoi(env) : 0;
-  if (tilesN < 2 || d.w_z0 || d.w_z1 || (!automatic && forced <= 1)) return 1;
-  if (forced > 0) return forced < tilesN ? (forced > 8 ? 8 : forced) : tilesN > 8 ? 8 : tilesN;
-  if ((d.nz > 1) || (int64_t)tilesM * tilesN < 1024) return 1;   // z-batched / small launches: the planes are small or the chip is not full
-  const double W = (double)d.N * d.K * 2.0 * NP;
-  const double a_cols = d.a_rowoff ? (double)d.kc : (d.lda > 0 && d.lda < d.K ? (double)d.lda : (double)d.K);
-  const double A = (double)d.M * a_cols * 4.0;
-  auto miss = [](double bytes) {
-    static const double mb[] = {0.5, 1.0, 2.0, 4.0, 8.0, 12.0}, f[] = {0.02, 0.055, 0.12, 0.27, 0.69, 1.0};
-    const double x = bytes / (1024.0 * 1024.0);
-    if (x <= mb[0]) return f[0] * x / mb[0];
-    for (int i = 1; i < 6; ++i)
-      if (x <= mb[i]) return f[i - 1] + (f[i] - f[i - 1]) * (log2(x) - log2(mb[i - 1])) / (log2(mb[i]) - log2(mb[i - 1]));
-    return 1.0;
-  };
-  int best = 1;
-  const double r1 = A + tilesM * W * miss(W);
-  double rbest = r1;
-  for (int G = 2; G <= 8 && G <= tilesN; G *= 2) {
-    const double r = G * A + tilesM * W * miss(W / G);
-    if (r < rbest) { rbest = r; best = G; }
-  }
-  (void)BM;
-  return rbest < 0.95 * r1 ? best : 1;
-}
-
-template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1, int ABL = 0, bool RPF = false>
+template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1>
 int launch_split_cfg(const dzn_gemm_desc& d, hipStream_t s) {
   const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
   const size_t lds = (size_t)S * (BM * 128 + NP * BN * 64);
-  auto kern = gemm_split_kernel<BM, BN, WGM, WGN, S, NP, OCC, ABL, RPF>;
+  auto kern = gemm_split_kernel<BM, BN, WGM, WGN, S, NP, OCC>;
   static unsigned long long attr_mask = 0;  // one bit per HIP device: function attributes are per device
   if (first_use_on_device(attr_mask)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -724,11 +339,11 @@ int launch_split_cfg(const dzn_gemm_desc& d, hipStream_t s) {
       snprintf(cls, sizeof(cls), "gemm_%s_%dx%d M%d N%d K%d z%d", NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", BM, BN, d.M,
                d.N, d.K, d.nz);
     else
-      snprintf(cls, sizeof(cls), "gemm_%s_%dx%d%s", NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", BM, BN, RPF ? "_rpf" : "");
+      snprintf(cls, sizeof(cls), "gemm_%s_%dx%d", NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", BM, BN);
     const double fl = d.alg_flops > 0 ? d.alg_flops * d.nz : 2.0 * d.M * d.N * d.K * d.nz;
     pid = prof_begin(s, cls, fl, gemm_alg_bytes(d, NP * 2));
   }
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, d, choose_column_groups(d, tilesM, tilesN, BM, NP));
+  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, d);
   prof_end(pid, s);
   if (hipGetLastError() != hipSuccess) return DZN_E_HIP;
   if (d.stat_partial && d.stat_final)
@@ -788,35 +403,6 @@ int launch_gemm_split_np(const dzn_gemm_desc& d, hipStream_t s) {
     if constexpr (NP == 1) {
       if (!strcmp(force, "256x128w8s3")) return launch_split_cfg<256, 128, 8, 1, 3, NP, 2>(d, s);
     }
-#ifdef DZN_TUNING
-    if constexpr (NP <= 2) {    // (r4) 32x32x16 MFMA forms
-      if (!strcmp(force, "m32_128x128")) return launch_split32_cfg<128, 128, 4, 1, 2, NP, 2>(d, s);
-      if (!strcmp(force, "m32_128x64")) return launch_split32_cfg<128, 64, 4, 1, 2, NP, 3>(d, s);
-    }   // probe / ablation instantiations (profiles/r2_gemm_cfg_probe.txt, r2_gemm_ablation.txt): build with
-                    // DZN_TUNING=1 (diarizen_amd/build.py); they triple the compile time of this file
-    if (!strcmp(force, "256x128")) return launch_split_cfg<256, 128, 4, 2, 2, NP>(d, s);
-    if constexpr (NP != 3) {
-      if (!strcmp(force, "128x128")) return launch_split_cfg<128, 128, 2, 2, 2, NP>(d, s);
-    }
-    if constexpr (NP <= 2) {
-      if (!strcmp(force, "m32_128x128p")) return launch_split32_cfg<128, 128, 4, 1, 2, NP, 2, 1>(d, s);   // + s_setprio around the MFMAs
-      if (!strcmp(force, "m32_128x128w22")) return launch_split32_cfg<128, 128, 2, 2, 2, NP, 2>(d, s);    // 2 x 2 wavefronts of 64 x 64
-      if (!strcmp(force, "m32_256x128")) return launch_split32_cfg<256, 128, 4, 2, 2, NP, 1>(d, s);       // 8 wavefronts of 64 x 64
-      if (!strcmp(force, "m32_256x128w8")) return launch_split32_cfg<256, 128, 8, 1, 2, NP, 1>(d, s);     // 8 wavefronts of 32 x 128
-      if (!strcmp(force, "m32_128x64p")) return launch_split32_cfg<128, 64, 4, 1, 2, NP, 3, 1>(d, s);
-      // deeper LDS-DMA pipelines (more K tiles in flight per CU): probes of the load-latency bound.  (128x128 with
-      // S = 3 / 4 were probed too — one wavefront per SIMD in the two-term kernel, 30 % slower)
-      if (!strcmp(force, "256x128s3")) return launch_split_cfg<256, 128, 4, 2, 3, NP>(d, s);
-      if (!strcmp(force, "256x128w8s3")) return launch_split_cfg<256, 128, 8, 1, 3, NP, 2>(d, s);
-      if (!strcmp(force, "128x64s3")) return launch_split_cfg<128, 64, 4, 1, 3, NP>(d, s);
-      if (!strcmp(force, "256x64s3")) return launch_split_cfg<256, 64, 8, 1, 3, NP>(d, s);
-      if (!strcmp(force, "abl1")) return launch_split_cfg<128, 128, 4, 1, 2, NP, 2, 1>(d, s);
-      if (!strcmp(force, "abl2")) return launch_split_cfg<128, 128, 4, 1, 2, NP, 2, 2>(d, s);
-      if (!strcmp(force, "abl3")) return launch_split_cfg<128, 128, 4, 1, 2, NP, 2, 3>(d, s);
-      if (!strcmp(force, "abl4")) return launch_split_cfg<128, 128, 4, 1, 2, NP, 2, 4>(d, s);
-      if (!strcmp(force, "abl5")) return launch_split_cfg<128, 128, 4, 1, 2, NP, 2, 5>(d, s);
-    }
-#endif
   }
   // (r3's 8-wavefront ping-pong forms — gemm_pp.hip, 256 x 192 tiles — measured +0.5 % on the step and were removed in r4;
   // the A/B record is profiles/r3_gemm_pq_probe.txt, the source is in the history at 7bb9ad7)
@@ -824,12 +410,6 @@ int launch_gemm_split_np(const dzn_gemm_desc& d, hipStream_t s) {
   // profiles/r4_gemm_a3_probe.txt; persistent workgroups with the next tile's prologue fill under the epilogue — 6ff2eda,
   // profiles/r4_gemm_persist_probe.txt; 256 x 256 tiles at one wavefront per SIMD — e863011, profiles/r4_gemm_wide_probe.txt,
   // whose PMC pass shows clock x matrix-pipe-busy constant across both forms: the K loop sits on a power-limited MFMA rate)
-#ifdef DZN_TUNING
-  // (r4) DZN_GEMM_M32 (read once): bit 0 = the 128 x 128 class, bit 1 = the 128 x 64 class run on 32x32x16 MFMA blocks
-  static const int m32 = getenv("DZN_GEMM_M32") ? atoi(getenv("DZN_GEMM_M32")) : 0;
-#else
-  constexpr int m32 = 0;
-#endif
   // launch bounds pin the occupancy the tile was tuned at (r3: the pipelined epilogue gives the register allocator
   // room to trade occupancy for more loads in flight; 128x64 tiles want 3 workgroups per CU, 128x128 two)
   constexpr int OCC64 = NP <= 2 ? 3 : 2;
@@ -840,21 +420,8 @@ int launch_gemm_split_np(const dzn_gemm_desc& d, hipStream_t s) {
   // shapes now that the epilogue is pipelined — 424 vs 444 us at 149226 x 1024 x 256; in the pipeline the step time did
   // not move (1139 vs 1124-1142 ms), so the short-K launches stay on the narrow tile and the 128x128 symbol stays a
   // homogeneous K >= 768 class for the roofline line)
-#ifdef DZN_TUNING
-  if constexpr (NP <= 2) {
-    if ((m32 & 2) && d.N > 32 && (d.N <= 64 || d.K <= 512)) return launch_split32_cfg<128, 64, 4, 1, 2, NP, 3>(d, s);
-  }
-#endif
-  if constexpr (NP == 2) {
-    // (r5) short-K launches with a residual (out_proj / FFN-output) with the residual requested at kernel START: a MEASURED
-    // NEGATIVE, kept as a switch (DZN_GEMM_RPF=1, read once).  The 32 residual registers cost the third workgroup per CU: class
-    // 168 -> 134 TFLOP/s, device step 1743 -> 1705 audio-s/s on one box (profiles/r5_rpf_probe.txt); at three workgroups per CU
-    // the form spills (probed as DZN_GEMM_RPF=2, instantiation removed).  The epilogue's load latency is not what these launches wait for.
-    static const int rpf = getenv("DZN_GEMM_RPF") ? atoi(getenv("DZN_GEMM_RPF")) : 0;
-    if (rpf && d.R && d.N > 64 && d.K <= 512) {
-      return launch_split_cfg<128, 64, 4, 1, 2, NP, 2, 0, true>(d, s);   // (at 3 workgroups per CU the form spills 24 registers: probed, removed)
-    }
-  }
+  // (r5) requesting the residual of short-K launches at kernel start cost the third workgroup per CU (class 168 -> 134 TFLOP/s) and
+  // was removed: DESIGN.md §4.9, profiles/r5_rpf_probe.txt
   if (d.N <= 64 || d.K <= 512) return launch_split_cfg<128, 64, 4, 1, 2, NP, OCC64>(d, s);
   // 128-wide column tiles unless 64-wide ones save more than ~1/8 of the (padded) columns; widths that
   // are multiples of 80 but not of 64 (conv1 of the extractor: 153 -> 160) get exact 80-wide tiles
@@ -870,12 +437,7 @@ int launch_gemm_split_np(const dzn_gemm_desc& d, hipStream_t s) {
   // NP = 1 (DZN_PREC_F16) is bound by the global -> LDS fill, not by MFMA / VALU (ablation: profiles/r2_gemm_ablation.txt):
   // 256 x 128 tiles halve the W bytes per flop and a third stage keeps two K tiles in flight: +7..13 % (r2_gemm_cfg_probe.txt)
   if constexpr (NP == 1) return launch_split_cfg<256, 128, 8, 1, 3, NP, 2>(d, s);
-  if constexpr (NP == 2) {
-#ifdef DZN_TUNING
-    if (m32 & 1) return launch_split32_cfg<128, 128, 4, 1, 2, NP, 2>(d, s);
-#endif
-    return launch_split_cfg<128, 128, 4, 1, 2, NP, 2>(d, s);   // held to 2 wavefronts per SIMD
-  }
+  if constexpr (NP == 2) return launch_split_cfg<128, 128, 4, 1, 2, NP, 2>(d, s);   // held to 2 wavefronts per SIMD
   return launch_split_cfg<128, 128, 2, 2, 2, NP, 2>(d, s);
 }
 
@@ -912,15 +474,13 @@ int launch_gemm_split(const dzn_gemm_desc& d, hipStream_t s) {
   // that do not move with z (col_scale is indexed by the output column alone)
   static const bool no_h2 = getenv("DZN_NO_H2") != nullptr;
   // DZN_PREC_F16 with the MX planes: fp16 hi*hi + fp8 cross terms (gemm_mx.hip); without them the single-term fp16 kernel
-  // (ln_centered — the row mean subtracted before the fp16 rounding — is implemented by the single-term kernel alone: any
-  // other dispatch with it set would silently drop the mean term of the folded LayerNorm, so it is refused)
   if (d.precision == DZN_PREC_F16 && d.Wmx && d.col_scale_mx && d.a_amax && !d.w_z0 && !d.w_z1 && !no_h2)
-    return d.ln_centered ? DZN_E_INVALID : launch_gemm_mx(d, s);
+    return launch_gemm_mx(d, s);
   if (prec_is_h2(d.precision) && d.W2h && d.col_scale && d.a_amax && !d.w_z0 && !d.w_z1 && !no_h2) {
     if (d.precision == DZN_PREC_F16) return launch_gemm_split_np<1>(d, s);
-    return d.ln_centered ? DZN_E_INVALID : launch_gemm_split_np<2>(d, s);
+    return launch_gemm_split_np<2>(d, s);
   }
-  if (!d.W3 || d.ln_centered) return DZN_E_INVALID;
+  if (!d.W3) return DZN_E_INVALID;
   return launch_gemm_split_np<3>(d, s);
 }
 

@@ -108,10 +108,6 @@ typedef struct dzn_gemm_desc {
    * z0 = z_list[y / zdiv] when y / zdiv < z_count[0] and exits otherwise.  NULL = every z0. */
   const int32_t* z_count;
   const int32_t* z_list;
-  /* DZN_PREC_F16 with ln_stats: the single-term kernel subtracts the row mean BEFORE it rounds A to fp16 and the epilogue
-   * only multiplies by rstd — C = rstd * ((x - mean) W'^T) + bias, LayerNorm as defined, instead of the folded form
-   * rstd * (x W'^T - mean colsum), whose two terms cancel to the size of the rounding error when |mean| >> std(x). */
-  int32_t ln_centered;
   /* DZN_PREC_F16 (r5): the reduced-precision contraction of csrc/gemm_mx.hip — fp16 hi*hi plus the two cross terms in fp8 on the
    * block-scaled matrix instruction.  Wmx = planes from dzn_op_split_weights_mx ([rows][K/32][128 B]: fp16 hi | fp8 hi, fp8 lo of
    * w * 2^e_row), col_scale_mx[n] = 2^-e_row; needs a_amax like the fp16 two-term form.  Either NULL -> the single-term fp16
@@ -181,9 +177,9 @@ int dzn_checked_status(uint32_t* out4, int32_t reset);
 /* tests / tuning: force one tile shape of csrc/gemm_mx.hip ("128x128", "128x64"; "auto" / NULL = the shape rule) */
 int dzn_op_set_gemm_mx_cfg(const char* cfg);
 
-/* tuning knob (scripts/bench_gemm_h2.py): force one tile configuration of csrc/gemm_split.hip for the calls that
- * follow ("128x128", "256x128s3", ...; "auto" / NULL = the shape heuristic).  Same effect as the DZN_GEMM_CFG
- * environment variable, which is read once per process. */
+/* tuning knob (scripts/bench_gemm_h2.py): force one of the production tiles of csrc/gemm_split.hip for the calls that
+ * follow ("128x64", "128x80", "128x32", "128x128" (f32s) / "128x128w4" (f32h, f16), "256x128w8s3" (f16); "auto" / NULL =
+ * the shape heuristic).  Same effect as the DZN_GEMM_CFG environment variable, which is read once per process. */
 int dzn_op_set_gemm_cfg(const char* cfg);
 
 /* amax[0] = max(amax[0], max |x[0..n)|) — the |max| tracker of a tensor whose producer has no fused tracker */

@@ -1,5 +1,4 @@
-"""Time the kernel classes of one batch of windows in situ (HIP-event profiler):  python scripts/probe_kernel_class.py [B] [class-substring ...]
-Used with ablation environment switches (e.g. DZN_CONV01_ABL=1/2: the fused frontend without its VALU / MFMA phase)."""
+"""Time the kernel classes of one batch of windows in situ (HIP-event profiler):  python scripts/probe_kernel_class.py [B] [class-substring ...]"""
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))

@@ -68,3 +68,29 @@ def test_cited_test_names_are_defined(doc):
             continue
         unknown.add(name)
     assert not unknown, f"{doc} quotes tests that do not exist: {sorted(unknown)}"
+
+
+def test_script_switches_are_read_somewhere():
+    """Switch rot guard: every `DZN_*` environment variable that a file under scripts/ assigns (`DZN_X=` in a shell script,
+    `os.environ["DZN_X"] =` in Python) is read (`getenv` / `os.environ`) somewhere under diarizen_amd/, tests/, bench.py or
+    scripts/*.py — a script that drives a switch no source reads measures nothing."""
+    assigned = {}
+    for f in sorted((ROOT / "scripts").iterdir()):
+        if f.suffix == ".sh":
+            found = re.findall(r"\b(DZN_[A-Z0-9_]+)=", f.read_text())
+        elif f.suffix == ".py":
+            found = re.findall(r"os\.environ\[[\"'](DZN_[A-Z0-9_]+)[\"']\]\s*=(?!=)", f.read_text())
+        else:
+            continue
+        for name in found:
+            assigned.setdefault(name, set()).add(f.name)
+    readers = [p for d in ("diarizen_amd", "tests") for p in (ROOT / d).rglob("*") if p.suffix in (".py", ".hip", ".cpp", ".h", ".c")]
+    readers += [ROOT / "bench.py", *(ROOT / "scripts").glob("*.py")]
+    read = set()
+    for p in readers:
+        text = p.read_text()
+        read.update(re.findall(r"getenv\(\s*\"(DZN_[A-Z0-9_]+)\"", text))
+        read.update(re.findall(r"os\.environ(?:\.get\(|\.pop\(|\[)\s*[\"'](DZN_[A-Z0-9_]+)[\"']\]?(?!\s*=[^=])", text))
+        read.update(re.findall(r"[\"'](DZN_[A-Z0-9_]+)[\"']\s+(?:not\s+)?in\s+os\.environ", text))
+    unread = {name: sorted(files) for name, files in assigned.items() if name not in read}
+    assert not unread, f"scripts/ assign switches that nothing reads: {unread}"
