@@ -28,8 +28,6 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-re
          # the fused epilogue (4 x 6 accumulator blocks x erf-GELU ...) is fully unrolled by pragma; past the
          # default cost cap clang silently keeps the loop and the accumulators go to scratch (tests/test_host.py)
          "-mllvm", "-pragma-unroll-threshold=65536"]
-if os.environ.get("DZN_TUNING"):     # builds the quarantined bf16 engine mode (csrc/gemm_lowp.hip) and nothing else
-    FLAGS.append("-DDZN_TUNING")
 
 
 def _headers_mtime() -> float:

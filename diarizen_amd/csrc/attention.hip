@@ -19,9 +19,9 @@
 
 namespace {
 
-template <bool BIAS, typename TO>
+template <bool BIAS>
 __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv,
-                                                   TO* __restrict__ out,
+                                                   float* __restrict__ out,
                                                    const float* __restrict__ gate,
                                                    const float* __restrict__ table,
                                                    const int32_t* __restrict__ head_idx, int B,
@@ -181,9 +181,9 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv
     const int q = qt * 64 + wave * 16 + lq * 4 + rg;
     if (q < L) {
       const float inv = 1.0f / lt;
-      TO* op = out + (rowbase + q) * ldo + j * 64 + lr * 4;
+      float* op = out + (rowbase + q) * ldo + j * 64 + lr * 4;
 #pragma unroll
-      for (int dblk = 0; dblk < 4; ++dblk) st_act(op, dblk, O[dblk][rg] * inv);
+      for (int dblk = 0; dblk < 4; ++dblk) op[dblk] = O[dblk][rg] * inv;
     }
   }
 }
@@ -192,8 +192,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv
 //   t = Linear(64->8)(y[row, H*64:(H+1)*64]) ; (a, b) = sigmoid(sum t[0:4]), sigmoid(sum t[4:8])
 //   gate = a * (b * const[H] - 1) + 2
 // One wavefront per row; lane (H = lane/4, sub = lane%4) computes outputs 2*sub, 2*sub+1.
-template <typename TI>
-__global__ __launch_bounds__(256) void gate_kernel(const TI* __restrict__ y, int64_t ldy,
+__global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ y, int64_t ldy,
                                                    const float* __restrict__ Wg,  // [8,64]
                                                    const float* __restrict__ bg,  // [8]
                                                    const float* __restrict__ cst,  // [Htot]
@@ -211,12 +210,12 @@ __global__ __launch_bounds__(256) void gate_kernel(const TI* __restrict__ y, int
     const int H = H0 + (lane >> 2);
     float t0 = 0.f, t1 = 0.f;
     if (H < Htot) {
-      const TI* yp = y + row * ldy + H * 64;
+      const float* yp = y + row * ldy + H * 64;
       const float* w0 = sW + (2 * sub) * 64;
       const float* w1 = w0 + 64;
 #pragma unroll 8
       for (int d = 0; d < 64; ++d) {
-        const float v = ld_act(yp, d);
+        const float v = yp[d];
         t0 = fmaf(v, w0[d], t0);
         t1 = fmaf(v, w1[d], t1);
       }
@@ -357,7 +356,7 @@ extern "C" int dzn_op_gate_stats(const float* x, int64_t ldx, const float* gamma
                            reinterpret_cast<hipStream_t>(stream));
 }
 
-int launch_attention_t(const float* qkv, void* out, int out_bf16, const float* gate, const float* table,
+int launch_attention_t(const float* qkv, float* out, const float* gate, const float* table,
                        const int32_t* head_idx, int B, int L, int h, int Htot, int ldqkv, int ldo,
                        float scale, hipStream_t s) {
   if (h <= 0 || B <= 0 || L <= 0) return DZN_OK;
@@ -369,14 +368,11 @@ int launch_attention_t(const float* qkv, void* out, int out_bf16, const float* g
   const int pid = prof_begin(s, bias ? "attention_relpos_f32" : "attention_f32",
                              4.0 * B * h * (double)L * L * 64.0,
                              (double)B * L * h * 64.0 * 4.0 * 4.0 + (gate ? (double)B * L * Htot * 4.0 : 0.0));
-#define DZN_ATT(BIASV, T)                                                                          \
-  hipLaunchKernelGGL((attn_kernel<BIASV, T>), grid, dim3(256), lds, s, qkv, static_cast<T*>(out), gate, \
-                     table, head_idx, B, L, h, Htot, ldqkv, ldo, scale)
-  if (bias) {
-    if (out_bf16) DZN_ATT(true, u16); else DZN_ATT(true, float);
-  } else {
-    if (out_bf16) DZN_ATT(false, u16); else DZN_ATT(false, float);
-  }
+#define DZN_ATT(BIASV)                                                                                    \
+  hipLaunchKernelGGL((attn_kernel<BIASV>), grid, dim3(256), lds, s, qkv, out, gate, table, head_idx, B, L, \
+                     h, Htot, ldqkv, ldo, scale)
+  if (bias) DZN_ATT(true);
+  else DZN_ATT(false);
 #undef DZN_ATT
   prof_end(pid, s);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
@@ -387,25 +383,15 @@ int launch_attention(const float* qkv, float* out, const float* gate, const floa
                      float scale, int precision, hipStream_t s) {
   if (prec_is_split(precision))
     return launch_attention_split(qkv, out, gate, table, head_idx, B, L, h, Htot, ldqkv, ldo, scale, s);
-  return launch_attention_t(qkv, out, 0, gate, table, head_idx, B, L, h, Htot, ldqkv, ldo, scale, s);
-}
-
-int launch_gate_t(const void* y, int y_bf16, int64_t ldy, const float* Wg, const float* bg,
-                  const float* cst, float* gate, int64_t rows, int Htot, hipStream_t s) {
-  ProfScope prof_scope_(s, "gate", 0.0, (double)rows * Htot * (64.0 + 1.0) * 4.0);
-  if (rows <= 0) return DZN_OK;
-  if (y_bf16)
-    hipLaunchKernelGGL(gate_kernel<u16>, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, s,
-                       static_cast<const u16*>(y), ldy, Wg, bg, cst, gate, rows, Htot);
-  else
-    hipLaunchKernelGGL(gate_kernel<float>, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, s,
-                       static_cast<const float*>(y), ldy, Wg, bg, cst, gate, rows, Htot);
-  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+  return launch_attention_t(qkv, out, gate, table, head_idx, B, L, h, Htot, ldqkv, ldo, scale, s);
 }
 
 int launch_gate(const float* y, int64_t ldy, const float* Wg, const float* bg, const float* cst,
                 float* gate, int64_t rows, int Htot, hipStream_t s) {
-  return launch_gate_t(y, 0, ldy, Wg, bg, cst, gate, rows, Htot, s);
+  ProfScope prof_scope_(s, "gate", 0.0, (double)rows * Htot * (64.0 + 1.0) * 4.0);
+  if (rows <= 0) return DZN_OK;
+  hipLaunchKernelGGL(gate_kernel, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, s, y, ldy, Wg, bg, cst, gate, rows, Htot);
+  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
 extern "C" int dzn_op_attention(const float* qkv, float* out, const float* gate,

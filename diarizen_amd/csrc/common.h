@@ -89,26 +89,6 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   }
 }
 
-// ---- activation element access: fp32 buffers, or bf16 buffers in the bf16 engine mode ----
-__device__ __forceinline__ float ld_act(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float ld_act(const u16* p, int64_t i) {
-  return __uint_as_float(((unsigned int)p[i]) << 16);
-}
-__device__ __forceinline__ void st_act(float* p, int64_t i, float v) { p[i] = v; }
-__device__ __forceinline__ void st_act(u16* p, int64_t i, float v) {
-  __bf16 h = (__bf16)v;  // round to nearest even
-  p[i] = *reinterpret_cast<u16*>(&h);
-}
-
-// host-side float -> bf16 (round to nearest even), used when packing weights
-static inline u16 f32_to_bf16_host(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u16)((u >> 16) | 0x40);  // NaN
-  uint32_t r = 0x7fffu + ((u >> 16) & 1u);
-  return (u16)((u + r) >> 16);
-}
-
 // DZN_PREC_F32_H2 is DZN_PREC_F32_SPLIT for every kernel that has no two-term fp16 variant
 // (DZN_PREC_F16 is the DZN_PREC_F32_H2 engine whose plain contractions keep one fp16 term: gemm_split*.hip NP = 1)
 static inline bool prec_is_h2(int p) { return p == DZN_PREC_F32_H2 || p == DZN_PREC_F16; }
@@ -116,9 +96,6 @@ static inline bool prec_is_split(int p) { return p == DZN_PREC_F32_SPLIT || prec
 
 // ---- kernel launchers (implemented in the .hip files) ----
 int launch_gemm(const dzn_gemm_desc& d, hipStream_t s);
-#ifdef DZN_TUNING
-int launch_gemm_lowp(const dzn_gemm_desc& d, hipStream_t s);  // gemm_lowp.hip: A and W both bf16 (bf16 engine mode: DZN_TUNING builds only)
-#endif
 int launch_gemm_split(const dzn_gemm_desc& d, hipStream_t s); // gemm_split.hip: fp32 via 3-way bf16 split
 int launch_gemm_split_pre(const dzn_gemm_desc& d, hipStream_t s);  // gemm_split_pre.hip: A pre-split planes
 int launch_pad_rows_split3(const float* x, void* planes, int64_t plane_stride, int B, int L, int Lp, int pad, int D,
@@ -141,10 +118,9 @@ int launch_stats_finalize(const float* partial, int64_t rows, int P, int C, floa
 int launch_layernorm(const float* x, int64_t ldx, float* y, int64_t ldy, const float* g,
                      const float* b, int64_t rows, int C, int Cpad, float eps, int gelu,
                      hipStream_t s);
-int launch_layernorm_t(const void* x, int x_bf16, int64_t ldx, void* y, int y_bf16, int64_t ldy,
-                       const float* g, const float* b, const float* post, int64_t rows, int C, int Cpad,
-                       float eps, int gelu, hipStream_t s, float* amax = nullptr, int64_t amax_unit = 0);
-int launch_cast_bf16(const float* x, void* y, int64_t n, hipStream_t s);
+int launch_layernorm_t(const float* x, int64_t ldx, float* y, int64_t ldy, const float* g, const float* b,
+                       const float* post, int64_t rows, int C, int Cpad, float eps, int gelu, hipStream_t s,
+                       float* amax = nullptr, int64_t amax_unit = 0);
 int launch_row_stats(const float* x, int64_t ldx, int64_t rows, int C, float eps, float* stats, hipStream_t s);
 int launch_gate_stats(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wg,
                       const float* bg, const float* cst, float* gate, float* stats, int64_t rows, int Htot, float eps,
@@ -152,9 +128,7 @@ int launch_gate_stats(const float* x, int64_t ldx, const float* gamma, const flo
 int launch_wave_stats(const float* w, int B, int N, float eps, float* stats, hipStream_t s);
 int launch_gate(const float* y, int64_t ldy, const float* Wg, const float* bg, const float* cst,
                 float* gate, int64_t rows, int Htot, hipStream_t s);
-int launch_gate_t(const void* y, int y_bf16, int64_t ldy, const float* Wg, const float* bg,
-                  const float* cst, float* gate, int64_t rows, int Htot, hipStream_t s);
-int launch_attention_t(const float* qkv, void* out, int out_bf16, const float* gate, const float* table,
+int launch_attention_t(const float* qkv, float* out, const float* gate, const float* table,
                        const int32_t* head_idx, int B, int L, int h, int Htot, int ldqkv, int ldo,
                        float scale, hipStream_t s);
 int launch_attention_split(const float* qkv, float* out, const float* gate, const float* table,
@@ -172,12 +146,11 @@ int launch_attention_planes(const float* qkv, const void* planes, int64_t plane_
 // frontend.hip
 int launch_conv0(const float* wave, int B, int N, const float* stats, const float* w,
                  const float* gamma, const float* beta, int C0, int Cp, int k, int s, int T0,
-                 int layer_norm, float eps, void* out, int out_bf16, hipStream_t st, const float* lnq = nullptr);
-int launch_groupnorm_gelu(const float* x, void* y, int y_bf16, int B, int T, int C, int Cp, int64_t ld,
+                 int layer_norm, float eps, float* out, hipStream_t st, const float* lnq = nullptr);
+int launch_groupnorm_gelu(const float* x, float* y, int B, int T, int C, int Cp, int64_t ld,
                           const float* gamma, const float* beta, float eps, float* stats, hipStream_t st, float* amax = nullptr);
 int64_t gn_stats_floats(int B, int T, int C, int Cp);   // size of launch_groupnorm_gelu's `stats` (statistics + chunk partials)
-int launch_pad_rows(const float* x, void* xpad, int out_bf16, int B, int L, int Lp, int pad, int D,
-                    hipStream_t st);
+int launch_pad_rows(const float* x, float* xpad, int B, int L, int Lp, int pad, int D, hipStream_t st);
 int launch_ws_accum(const float* x, float* ws, float w, int init, int64_t n, hipStream_t st);
 // ws = ((0 + w[0] x[0]) + w[1] x[1]) + ... in that order, element-wise over n floats: the layer-weighted sum in ONE pass over
 // the per-layer buffers (the same additions, in the same order, as n ws_accum / epilogue read-modify-writes)
@@ -188,8 +161,7 @@ struct WsSumArgs {
   int n;
 };
 int launch_ws_sum(const WsSumArgs& a, float* ws, int64_t n, hipStream_t st);
-int launch_col_scale(void* x, int x_bf16, int64_t rows, int C, int64_t ld, const float* scale,
-                     hipStream_t st);
+int launch_col_scale(float* x, int64_t rows, int C, int64_t ld, const float* scale, hipStream_t st);
 // frontend_fused.hip (DZN_PREC_F32_H2): conv0 + LN + GELU + conv1 in one kernel
 int launch_split_weights_h2_natural(const float* W, int64_t rows, int K, void* W2, float* col_scale, hipStream_t s);
 int launch_fragment_major(const void* W2, int rows, int K, void* out, hipStream_t s);   // frontend_fused.hip: conv1 planes for the producer / consumer kernel
@@ -198,8 +170,8 @@ int launch_conv01_fused(const float* wave, int B, int N, const float* wstats, co
                         const float* col_scale, int N1p, float act_bound, float eps, float* out, hipStream_t st,
                         const float* gamma1 = nullptr, const float* beta1 = nullptr, int C1 = 0, float* amax1 = nullptr);
 // conformer.hip
-int launch_glu_dwconv(const float* u, int64_t ldu, const float* w, const float* bias, void* out,
-                      int out_bf16, int64_t ldo, int B, int L, int A, int ks, hipStream_t st);
+int launch_glu_dwconv(const float* u, int64_t ldu, const float* w, const float* bias, float* out,
+                      int64_t ldo, int B, int L, int A, int ks, hipStream_t st);
 int launch_classify(const float* z, int64_t ldz, const float* W, const float* bias,
                     const uint8_t* mapping, int64_t rows, int A, int NC, int S, float* logp,
                     uint8_t* multilabel, hipStream_t st);
@@ -211,9 +183,9 @@ int launch_window_active(const float* masks, int B, int per_window, int* flag, h
 int launch_compact_active(const int* flag, int B, int* count, int* list, long long* totals, hipStream_t st);
 int launch_log_cmn(float* mel, int B, int T, int NB, float eps, hipStream_t st);
 int launch_stem_conv(const float* fb, int B, int T, int NB, int C, const float* w, const float* bias,
-                     void* img, int out_bf16, hipStream_t st, float* amax = nullptr, const int* z_count = nullptr,
+                     float* img, hipStream_t st, float* amax = nullptr, const int* z_count = nullptr,
                      const int* z_list = nullptr);   // (z_count, z_list): device-chosen subset of the B images
-int launch_stats_pool(const void* img, int in_bf16, int B, int H, int W, int C, const float* masks, int S,
+int launch_stats_pool(const float* img, int B, int H, int W, int C, const float* masks, int S,
                       int L, float* stats, hipStream_t st, const int* active = nullptr);   // active[b] == 0 -> zeros
 
 // conv_split.hip: 3x3 stride-1 conv 32 -> 32 over zero-bordered NHWC images (DZN_PREC_F32_SPLIT)
@@ -261,10 +233,10 @@ static inline bool first_use_on_device(unsigned long long& mask) {
 static inline double gemm_alg_bytes(const dzn_gemm_desc& d, int w_bytes_per_elem) {
   const double nz = d.nz > 0 ? d.nz : 1;
   const double a_cols = d.a_rowoff ? (double)d.kc : (d.lda > 0 && d.lda < d.K ? (double)d.lda : (double)d.K);
-  double b = (double)d.M * a_cols * (d.a_bf16 ? 2.0 : 4.0) * nz;
+  double b = (double)d.M * a_cols * 4.0 * nz;
   b += (double)d.N * d.K * w_bytes_per_elem * ((d.w_z0 || d.w_z1) ? nz : 1.0);
-  b += (double)d.M * d.N * (d.c_bf16 ? 2.0 : 4.0) * nz;
-  if (d.R) b += (double)d.M * d.N * (d.r_bf16 ? 2.0 : 4.0) * nz;
+  b += (double)d.M * d.N * 4.0 * nz;
+  if (d.R) b += (double)d.M * d.N * 4.0 * nz;
   if (d.WS) b += 2.0 * (double)d.M * d.N * 4.0 * nz;
   return b;
 }

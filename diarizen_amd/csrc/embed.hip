@@ -11,7 +11,6 @@
 //      zero-bordered NHWC image the 3x3 contractions read.
 //  stats_pool_kernel : TSTP / StatsPool weighted mean + std for ALL speaker masks of a window
 //      from one trunk pass (resnet.py:49-66, PA/models/blocks/pooling.py:44-75,107-131).
-#include <type_traits>
 
 #include "common.h"
 
@@ -100,12 +99,11 @@ __global__ __launch_bounds__(256) void log_cmn_kernel(float* __restrict__ mel, i
 // 128-byte line written by 8 neighbouring lanes) and the |max| tracker is updated once per workgroup.  r2's form
 // (flat index over everything: three 64-bit div/mods, 36 tap loads, four 4-byte stores and a tracker probe PER ELEMENT)
 // wrote its 3 GB per launch at 1.27 TB/s.
-template <typename TO>
 __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict__ fb, int B, int T,
                                                         int NB, int C,
                                                         const float* __restrict__ w,  // [C, 9] folded
                                                         const float* __restrict__ bias,
-                                                        TO* __restrict__ img, float* __restrict__ amax,
+                                                        float* __restrict__ img, float* __restrict__ amax,
                                                         const int* __restrict__ z_count, const int* __restrict__ z_list) {
   const int cq = C >> 2;                       // channel quads per pixel (8 for the 32-channel stem)
   int b = blockIdx.y;
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
   const int per = (npix + gridDim.x - 1) / gridDim.x;
   const int p0 = blockIdx.x * per, p1 = min(npix, p0 + per);
   const float* fbb = fb + (int64_t)b * T * NB;
-  TO* ib = img + (int64_t)b * (NB + 2) * (T + 2) * C;
+  float* ib = img + (int64_t)b * (NB + 2) * (T + 2) * C;
   float mx = 0.f;
   for (int p = p0 + pl; p < p1; p += ppb) {
     const int h = p / T, wv = p - h * T;       // pixel (mel bin h, frame wv): consecutive pixels walk along time
@@ -145,13 +143,8 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
       for (int k = 0; k < 9; ++k) acc = fmaf(in[k], wr[c][k], acc);
       o[c] = fmaxf(acc + br[c], 0.f);
     }
-    TO* op = ib + ((int64_t)(h + 1) * (T + 2) + wv + 1) * C + q * 4;
-    if constexpr (std::is_same<TO, float>::value) {
-      *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) st_act(op, c, o[c]);
-    }
+    float* op = ib + ((int64_t)(h + 1) * (T + 2) + wv + 1) * C + q * 4;
+    *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
     mx = fmaxf(mx, fmaxf(fmaxf(o[0], o[1]), fmaxf(o[2], o[3])));     // post-ReLU: non-negative
   }
   if (amax) {   // per-image |max| tracker (DZN_PREC_F32_H2: scale of the stage-1 convolutions' fp16 split)
@@ -165,8 +158,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
 
 // img [B, H+2, W+2, C] (padded NHWC), masks [B, S, L]  ->  stats [B, S, 2*C*H]
 // feature index f = c*H + h (rearrange "b d c f -> b (d c) f" of resnet.py:49-66)
-template <typename TI>
-__global__ __launch_bounds__(256) void stats_pool_kernel(const TI* __restrict__ img, int H, int W,
+__global__ __launch_bounds__(256) void stats_pool_kernel(const float* __restrict__ img, int H, int W,
                                                          int C, const float* __restrict__ masks,
                                                          int S, int L, float* __restrict__ stats,
                                                          const int* __restrict__ active) {
@@ -193,7 +185,7 @@ __global__ __launch_bounds__(256) void stats_pool_kernel(const TI* __restrict__ 
     sw[i] = (W == L) ? masks[((int64_t)b * S + s) * L + t] : masks[((int64_t)b * S + s) * L + src];
   }
   __syncthreads();
-  const TI* base = img + (((int64_t)b * (H + 2) + h + 1) * (W + 2) + 1) * C;
+  const float* base = img + (((int64_t)b * (H + 2) + h + 1) * (W + 2) + 1) * C;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     for (int s = 0; s < S; ++s) {
       const float* wt = sw + s * W;
@@ -202,13 +194,13 @@ __global__ __launch_bounds__(256) void stats_pool_kernel(const TI* __restrict__ 
         const float wv = wt[t];
         v1 += wv;
         v2 += wv * wv;
-        sx += ld_act(base, (int64_t)t * C + c) * wv;
+        sx += base[(int64_t)t * C + c] * wv;
       }
       v1 += 1e-8f;
       const float mean = sx / v1;
       float sq = 0.f;
       for (int t = 0; t < W; ++t) {
-        const float d = ld_act(base, (int64_t)t * C + c) - mean;
+        const float d = base[(int64_t)t * C + c] - mean;
         sq += d * d * wt[t];
       }
       const float var = sq / (v1 - v2 / v1 + 1e-8f);
@@ -304,33 +296,23 @@ int launch_log_cmn(float* mel, int B, int T, int NB, float eps, hipStream_t st) 
 }
 
 int launch_stem_conv(const float* fb, int B, int T, int NB, int C, const float* w, const float* bias,
-                     void* img, int out_bf16, hipStream_t st, float* amax, const int* z_count, const int* z_list) {
+                     float* img, hipStream_t st, float* amax, const int* z_count, const int* z_list) {
   ProfScope prof_scope_(st, "stem_conv", 2.0 * B * NB * (double)T * C * 9.0,
-                        (double)B * NB * T * 4.0 + (double)B * NB * T * C * (out_bf16 ? 2.0 : 4.0));   // fbank in, C-channel image out
+                        (double)B * NB * T * 4.0 + (double)B * NB * T * C * 4.0);   // fbank in, C-channel image out
   if (C % 4 || 256 % (C / 4)) return DZN_E_INVALID;
   // ~8 sweeps of 256 / (C / 4) pixels per workgroup
   const int npix = NB * T, ppb = 256 / (C / 4);
   int gx = (npix + 8 * ppb - 1) / (8 * ppb);
   gx = gx < 1 ? 1 : gx;
   const dim3 grid(gx, B);
-  if (out_bf16)
-    hipLaunchKernelGGL(stem_conv_kernel<u16>, grid, dim3(256), 0, st, fb, B, T, NB, C, w, bias,
-                       static_cast<u16*>(img), amax, z_count, z_list);
-  else
-    hipLaunchKernelGGL(stem_conv_kernel<float>, grid, dim3(256), 0, st, fb, B, T, NB, C, w, bias,
-                       static_cast<float*>(img), amax, z_count, z_list);
+  hipLaunchKernelGGL(stem_conv_kernel, grid, dim3(256), 0, st, fb, B, T, NB, C, w, bias, img, amax, z_count, z_list);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
-int launch_stats_pool(const void* img, int in_bf16, int B, int H, int W, int C, const float* masks, int S,
+int launch_stats_pool(const float* img, int B, int H, int W, int C, const float* masks, int S,
                       int L, float* stats, hipStream_t st, const int* active) {
-  ProfScope prof_scope_(st, "stats_pool", 0.0, (double)B * H * W * C * (in_bf16 ? 2.0 : 4.0) + (double)B * S * L * 4.0);
+  ProfScope prof_scope_(st, "stats_pool", 0.0, (double)B * H * W * C * 4.0 + (double)B * S * L * 4.0);
   const size_t lds = (size_t)S * W * sizeof(float);
-  if (in_bf16)
-    hipLaunchKernelGGL(stats_pool_kernel<u16>, dim3(H, B), dim3(256), lds, st, static_cast<const u16*>(img),
-                       H, W, C, masks, S, L, stats, active);
-  else
-    hipLaunchKernelGGL(stats_pool_kernel<float>, dim3(H, B), dim3(256), lds, st,
-                       static_cast<const float*>(img), H, W, C, masks, S, L, stats, active);
+  hipLaunchKernelGGL(stats_pool_kernel, dim3(H, B), dim3(256), lds, st, img, H, W, C, masks, S, L, stats, active);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }

@@ -41,10 +41,6 @@ struct EngineError : std::runtime_error {
   EngineError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 
-// Makes the handle's device current for the duration of a C-ABI call and restores the caller's
-// (lazy allocations, table uploads and kernel launches must not land on whatever device the calling
-// thread happens to have current — e.g. DiariZenPipeline(device="cuda:1") in a process at device 0).
-
 struct HostT {
   std::vector<float> v;
   std::vector<int64_t> shape;
@@ -52,7 +48,6 @@ struct HostT {
 
 struct Lin {       // y = x W^T + b with W [N, K] (rows zero-padded to Np, cols to Kp)
   float* W = nullptr;
-  u16* W16 = nullptr;
   u16* W3 = nullptr;   // exact 3-way bf16 split planes (DZN_PREC_F32_SPLIT), gemm_split.hip layout
   float* b = nullptr;
   u16* W2h = nullptr;  // two-term fp16 planes of W * 2^e_row (DZN_PREC_F32_H2) ...
@@ -156,7 +151,7 @@ struct dzn_handle {
   // ---- segmentation: workspace ----
   int maxT[DZN_MAX_CONV]{};
   int maxL = 0;
-  float *stats = nullptr, *gn_stats = nullptr, *bufA = nullptr, *bufB = nullptr, *craw = nullptr;
+  float *stats = nullptr, *gn_stats = nullptr, *bufA = nullptr, *bufB = nullptr;
   float *x = nullptr, *xpad = nullptr, *y = nullptr, *ws = nullptr, *qkv = nullptr, *ao = nullptr,
         *gate = nullptr, *mid = nullptr;
   float *hz = nullptr, *ht = nullptr, *hmid = nullptr, *hv = nullptr;
@@ -255,14 +250,6 @@ float* upload(H* h, const std::vector<float>& v) {
   return p;
 }
 
-u16* upload_bf16(H* h, const std::vector<float>& v) {
-  std::vector<u16> t(v.size());
-  for (size_t i = 0; i < v.size(); ++i) t[i] = f32_to_bf16_host(v[i]);
-  u16* p = dalloc<u16>(h, (int64_t)t.size(), false);
-  if (!t.empty()) HIPCHK(hipMemcpy(p, t.data(), t.size() * sizeof(u16), hipMemcpyHostToDevice));
-  return p;
-}
-
 int pad32(int v) { return round_up(v, 32); }
 
 const HostT& need(H* h, const std::string& key) {
@@ -290,7 +277,6 @@ Lin make_lin(H* h, const std::vector<float>& W, const float* bias, int N, int K,
   l.Nt = N;
   l.Kt = K;
   l.W = upload(h, wp);
-  if (h->cfg.precision == DZN_PREC_BF16) l.W16 = upload_bf16(h, wp);
   if (prec_is_split(h->cfg.precision) && Kp % 32 == 0) {
     l.W3 = dalloc<u16>(h, (int64_t)3 * Np * Kp, false);
     if (launch_split_weights(l.W, Np, Kp, Kp, l.W3, nullptr) != DZN_OK)
@@ -394,22 +380,11 @@ int relpos_bucket(int rel, int num_buckets, int max_distance) {
   return ret + (int)large;
 }
 
-int64_t lnx_raw_elems(H* h, int64_t B) {
-  const dzn_config& c = h->cfg;
-  int64_t need = 1;
-  if (c.extractor_layer_norm) {
-    for (int i = 1; i < c.n_conv; ++i) need = std::max(need, B * h->maxT[i] * h->Cp[i]);
-  } else {
-    need = B * h->maxT[0] * h->Cp[0];
-  }
-  return need;
-}
-
 // ------------------------------------------------------------------ segmentation: finalize
 void finalize_seg(H* h) {
   const dzn_config& c = h->cfg;
   const std::string P = "wavlm_model.";
-  h->fold_ln = c.precision != DZN_PREC_BF16 && !getenv("DZN_NO_LN_FOLD");
+  h->fold_ln = !getenv("DZN_NO_LN_FOLD");
   h->nconv = c.n_conv;
   h->D = c.embed_dim;
   h->H = c.total_heads;
@@ -745,11 +720,6 @@ void finalize_seg(H* h) {
     for (int i = 1; i < c.n_conv; i += 2) need_b = std::max(need_b, B * h->maxT[i] * h->Cp[i]);
     h->bufB = dalloc<float>(h, need_b);
   }
-  if (c.precision == DZN_PREC_BF16) {
-    // fp32 scratch for raw conv outputs in front of their LayerNorm / GroupNorm (bf16 mode only)
-    int64_t need_r = lnx_raw_elems(h, B);
-    h->craw = dalloc<float>(h, need_r);
-  }
   h->x = dalloc<float>(h, ML * D);
   h->xpad = dalloc<float>(h, B * (n + c.pos_conv_kernel) * D);
   if (prec_is_split(c.precision)) {
@@ -993,39 +963,19 @@ void chk(int rc, const char* what) {
   if (rc != DZN_OK) throw EngineError(rc, std::string("kernel launch failed: ") + what);
 }
 
-// byte-level offset into an activation buffer whose element type depends on the engine mode
-inline float* eoff(float* p, int64_t elems, bool bf16) {
-  return reinterpret_cast<float*>(reinterpret_cast<char*>(p) + elems * (bf16 ? 2 : 4));
-}
-inline const float* eoff(const float* p, int64_t elems, bool bf16) {
-  return reinterpret_cast<const float*>(reinterpret_cast<const char*>(p) + elems * (bf16 ? 2 : 4));
-}
-
-void tap(H* h, const char* name, const float* p, int64_t rows, int cols, int64_t ld, hipStream_t st,
-         bool bf16 = false) {
+void tap(H* h, const char* name, const float* p, int64_t rows, int cols, int64_t ld, hipStream_t st) {
   if (!h->debug) return;
   HIPCHK(hipStreamSynchronize(st));
   std::vector<float>& v = h->taps[name];
   v.resize((size_t)rows * cols);
-  if (!bf16) {
-    HIPCHK(hipMemcpy2D(v.data(), (size_t)cols * 4, p, (size_t)ld * 4, (size_t)cols * 4, (size_t)rows,
-                       hipMemcpyDeviceToHost));
-    return;
-  }
-  std::vector<u16> t((size_t)rows * cols);
-  HIPCHK(hipMemcpy2D(t.data(), (size_t)cols * 2, p, (size_t)ld * 2, (size_t)cols * 2, (size_t)rows,
+  HIPCHK(hipMemcpy2D(v.data(), (size_t)cols * 4, p, (size_t)ld * 4, (size_t)cols * 4, (size_t)rows,
                      hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < t.size(); ++i) {
-    const uint32_t u = (uint32_t)t[i] << 16;
-    memcpy(&v[i], &u, 4);
-  }
 }
 
 dzn_gemm_desc gd(H* h, const float* A, const Lin& l, float* C, int64_t M, int64_t lda, int64_t ldc) {
   dzn_gemm_desc d{};
   d.A = A;
   d.W = l.W;
-  d.W16 = l.W16;
   d.W3 = l.W3;
   d.W2h = l.W2h;
   d.col_scale = l.wsc;
@@ -1050,11 +1000,10 @@ dzn_gemm_desc gd(H* h, const float* A, const Lin& l, float* C, int64_t M, int64_
   return d;
 }
 
-// LayerNorm with typed input / output (fp32, or bf16 in the bf16 engine mode)
-void ln_t(const float* x, bool x16, int64_t ldx, float* y, bool y16, int64_t ldy, const LNp& p, int64_t rows,
+void ln_t(const float* x, int64_t ldx, float* y, int64_t ldy, const LNp& p, int64_t rows,
           int Cpad, int gelu, hipStream_t st, const float* post = nullptr, float* amax = nullptr,
           int64_t amax_unit = 0) {
-  chk(launch_layernorm_t(x, x16, ldx, y, y16, ldy, p.g, p.b, post, rows, p.C, Cpad, 1e-5f, gelu, st, amax, amax_unit),
+  chk(launch_layernorm_t(x, ldx, y, ldy, p.g, p.b, post, rows, p.C, Cpad, 1e-5f, gelu, st, amax, amax_unit),
       "layernorm");
 }
 
@@ -1087,12 +1036,8 @@ void ensure_table(H* h, int L, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ segmentation forward
-// `lp` (bf16 engine mode): every contraction input is a bf16 buffer written by its producer
-// (conv0, LayerNorm, GELU / Swish epilogues, attention, depthwise conv); the residual stream x, the
-// layer-weighted sum, q/k/v, softmax and all norm statistics stay fp32.
 void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* d_ml, hipStream_t st) {
   const dzn_config& c = h->cfg;
-  const bool lp = c.precision == DZN_PREC_BF16;
   const bool lnx = c.extractor_layer_norm != 0;
   int T[DZN_MAX_CONV];
   {
@@ -1108,9 +1053,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
   const int64_t ML = (int64_t)B * L;
   // DZN_PREC_F16: contraction classes that keep BOTH fp16 terms (three products) — f16_keep2 is a bit mask over
   // F16_CLASSES below (dzn_handle::f16_keep2, default chosen from the measured sensitivity: profiles/r4_f16_sensitivity*)
-  auto gemm = [&](dzn_gemm_desc& d, bool a16, bool c16, const char* what) {
-    d.a_bf16 = a16;
-    d.c_bf16 = c16;
+  auto gemm = [&](dzn_gemm_desc& d, const char* what) {
     if (c.precision == DZN_PREC_F16) {
       const int cls = f16_class(what);
       const bool mx = cls >= 0 && ((h->f16_mx >> cls) & 1) && d.Wmx;
@@ -1151,25 +1094,23 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
   if (lnx && fuse01) {
   } else if (lnx) {
     chk(launch_conv0(wave, B, N, stats, h->conv0_w, h->conv_ln[0].g, h->conv_ln[0].b, h->C[0], h->Cp[0],
-                     c.conv_k[0], c.conv_s[0], T[0], 1, 1e-5f, h->bufA, lp, st, h->conv0_lnq),
+                     c.conv_k[0], c.conv_s[0], T[0], 1, 1e-5f, h->bufA, st, h->conv0_lnq),
         "conv0");
   } else {
-    float* raw = lp ? h->craw : h->bufA;
     chk(launch_conv0(wave, B, N, stats, h->conv0_w, nullptr, nullptr, h->C[0], h->Cp[0], c.conv_k[0],
-                     c.conv_s[0], T[0], 0, 1e-5f, raw, 0, st),
+                     c.conv_s[0], T[0], 0, 1e-5f, h->bufA, st),
         "conv0");
-    chk(launch_groupnorm_gelu(raw, h->bufA, lp, B, T[0], h->C[0], h->Cp[0], h->Cp[0], h->conv_ln[0].g,
+    chk(launch_groupnorm_gelu(h->bufA, h->bufA, B, T[0], h->C[0], h->Cp[0], h->Cp[0], h->conv_ln[0].g,
                               h->conv_ln[0].b, 1e-5f, h->gn_stats, st, am(conv_slot(h->bufA))),
         "groupnorm");
   }
-  tap(h, "conv0", h->bufA, (int64_t)B * T[0], h->C[0], h->Cp[0], st, lp);
+  tap(h, "conv0", h->bufA, (int64_t)B * T[0], h->C[0], h->Cp[0], st);
   float* cur = h->bufA;
   float* nxt = h->bufB;
   const int last = c.n_conv - 1;
   for (int i = 1; i < c.n_conv; ++i) {
     // conv1d(k, s) over channels-last rows: row t of the contraction starts at (t*s)*Cp_in
-    float* dst = (lnx && lp) ? h->craw : nxt;
-    dzn_gemm_desc d = gd(h, cur, h->conv[i], dst, T[i], (int64_t)c.conv_s[i] * h->Cp[i - 1], h->Cp[i]);
+    dzn_gemm_desc d = gd(h, cur, h->conv[i], nxt, T[i], (int64_t)c.conv_s[i] * h->Cp[i - 1], h->Cp[i]);
     d.nz = B;
     d.a_z0 = (int64_t)T[i - 1] * h->Cp[i - 1];
     d.c_z0 = (int64_t)T[i] * h->Cp[i];
@@ -1177,23 +1118,23 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
     d.a_amax = am(conv_slot(cur));   // (r3: the group-norm element pass tracks its |max| too, so conv1 takes the fp16 split)
     if (!lnx) d.c_amax = am(conv_slot(nxt));
     // (r3) the fused front end also finishes conv1's own LayerNorm + GELU in its epilogue (its tile holds whole rows)
-    const bool ln_in_01 = i == 1 && fuse01 && lnx && !lp && i != last && !getenv("DZN_CONV01_NO_LN");
+    const bool ln_in_01 = i == 1 && fuse01 && lnx && i != last && !getenv("DZN_CONV01_NO_LN");
     if (i == 1 && fuse01)
       chk(launch_conv01_fused(wave, B, N, stats, h->conv0_w, h->conv_ln[0].g, h->conv_ln[0].b, h->conv0_lnq, h->C[0],
-                              T[0], T[1], h->conv1_W2n, h->conv1_wscn, h->Cp[1], h->conv0_bound, 1e-5f, ln_in_01 ? nxt : dst,
+                              T[0], T[1], h->conv1_W2n, h->conv1_wscn, h->Cp[1], h->conv0_bound, 1e-5f, nxt,
                               st, ln_in_01 ? h->conv_ln[1].g : nullptr, ln_in_01 ? h->conv_ln[1].b : nullptr, h->C[1],
                               ln_in_01 ? am(conv_slot(nxt)) : nullptr),
           "conv01 fused");
     else
-      gemm(d, lp, lp && !lnx, "conv gemm");
+      gemm(d, "conv gemm");
     if (lnx && !ln_in_01)  // channel LayerNorm + GELU (+ dummy_weight after the last conv, components.py:208)
-      ln_t(dst, false, h->Cp[i], nxt, lp, h->Cp[i], h->conv_ln[i], (int64_t)B * T[i], h->Cp[i], 1, st,
+      ln_t(nxt, h->Cp[i], nxt, h->Cp[i], h->conv_ln[i], (int64_t)B * T[i], h->Cp[i], 1, st,
            i == last ? h->dummy_w : nullptr, am(conv_slot(nxt)), T[i]);
     std::swap(cur, nxt);
   }
   if (!lnx || c.n_conv == 1)
-    chk(launch_col_scale(cur, lp, ML, h->C[last], h->Cp[last], h->dummy_w, st), "dummy_weight");
-  tap(h, "features", cur, ML, h->C[last], h->Cp[last], st, lp);
+    chk(launch_col_scale(cur, ML, h->C[last], h->Cp[last], h->dummy_w, st), "dummy_weight");
+  tap(h, "features", cur, ML, h->C[last], h->Cp[last], st);
 
   // ---- feature projection (components.py:305-306) ----
   const bool fold = h->fold_ln;   // LayerNorms feeding only linears are folded into those contractions
@@ -1209,21 +1150,18 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
     // tracker only needs to bound the magnitude within the 2^15 / 65504 headroom -> skip the fp16 path there)
     if (lnx && c.n_conv > 1) d.a_amax = am(conv_slot(cur));
     d.c_amax = am(dzn_handle::AM_X);
-    gemm(d, false, false, "feature projection");
+    gemm(d, "feature projection");
   } else {
-    ln_t(cur, lp, h->Cp[last], nxt, lp, h->Cp[last], h->fp_ln, ML, h->Cp[last], 0, st);
+    ln_t(cur, h->Cp[last], nxt, h->Cp[last], h->fp_ln, ML, h->Cp[last], 0, st);
     dzn_gemm_desc d = gd(h, nxt, h->fp, h->x, ML, h->Cp[last], D);
     d.c_amax = am(dzn_handle::AM_X);
-    gemm(d, lp, false, "feature projection");
+    gemm(d, "feature projection");
   }
   tap(h, "featproj", h->x, ML, D, D, st);
 
   // ---- positional conv: x = x + gelu(conv_pos(x))  (components.py:980-987, 366-380) ----
   {
     const int Kc = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G, Lp = L + Kc;
-    // the LDS-DMA bf16 kernel needs kc % 32 == 0; otherwise (base: 768/16 = 48 channels per group)
-    // keep this one contraction on fp32 activations (register-staged kernel converts on the fly)
-    const bool pc16 = lp && (cg % 32 == 0);
     // f32s: every element of the padded copy feeds 128 taps — split it ONCE here (three bf16 planes) and
     // let the contraction read the planes (gemm_split_pre.hip) instead of re-splitting it per K tile
     const int cgp = h->pos_cgp > 0 ? h->pos_cgp : cg, Dp = G * cgp;     // plane rows: G groups of cgp channels
@@ -1236,8 +1174,8 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
     else if (pre3)
       chk(launch_pad_rows_split3(h->x, h->xpad3, h->xpad3_plane, B, L, Lp, Kc / 2, Dp, st, cg, cgp), "pad_rows_split3");
     else
-      chk(launch_pad_rows(h->x, h->xpad, pc16, B, L, Lp, Kc / 2, D, st), "pad_rows");
-    // the un-split copy (fp32 / bf16 modes) keeps cg channels per group; the planes have cgp
+      chk(launch_pad_rows(h->x, h->xpad, B, L, Lp, Kc / 2, D, st), "pad_rows");
+    // the un-split copy (fp32 mode) keeps cg channels per group; the planes have cgp
     const int ca = pre3 ? cgp : cg, Da = pre3 ? Dp : D;
     if (!pre3 && cgp != cg) throw EngineError(DZN_E_INVALID, "padded positional-conv groups need the pre-split planes");
     // one contraction per channel group over ALL B*L rows (row-offset table into the padded copy), so
@@ -1273,9 +1211,9 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
       if (pre2) d.a_amax = am(dzn_handle::AM_XPAD);
     }
     d.c_amax = am(dzn_handle::AM_X);
-    gemm(d, pc16, false, "pos conv");
+    gemm(d, "pos conv");
   }
-  if (!c.layer_norm_first) ln_t(h->x, false, D, h->x, false, D, h->enc_ln, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
+  if (!c.layer_norm_first) ln_t(h->x, D, h->x, D, h->enc_ln, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
   // the residual stream: `xr` = rows of the representation the next operation reads.  With the deferred layer-weighted sum
   // every layer moves it into its own buffer (the first residual update of layer i reads xr and writes xl[i], the second
   // one works in place there) and (xr, weight) is noted per layer; else xr == h->x throughout.
@@ -1300,7 +1238,6 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
     bool have_stats = false;   // LN2's statistics already left in rstat by the out_proj epilogue
     if (Ly.attn) {
       const float* yin = xr;
-      bool y16 = false;
       const bool fold1 = fold && c.layer_norm_first;
       if (fold1) {
         // one pass over x: LN statistics for the folded q/k/v contraction + the gate on LN(x) (never written)
@@ -1308,21 +1245,16 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
                               st),
             "gate_stats");
       } else if (c.layer_norm_first) {
-        ln_t(xr, false, D, h->y, lp, D, Ly.ln1, ML, D, 0, st, nullptr, am(dzn_handle::AM_Y), L);
+        ln_t(xr, D, h->y, D, Ly.ln1, ML, D, 0, st, nullptr, am(dzn_handle::AM_Y), L);
         yin = h->y;
-        y16 = lp;
-      } else if (lp) {
-        chk(launch_cast_bf16(xr, h->y, ML * D, st), "cast");
-        yin = h->y;
-        y16 = true;
       }
-      if (!fold1) chk(launch_gate_t(yin, y16, D, Ly.Wg, Ly.bg, Ly.cst, h->gate, ML, h->H, st), "gate");
+      if (!fold1) chk(launch_gate(yin, D, Ly.Wg, Ly.bg, Ly.cst, h->gate, ML, h->H, st), "gate");
       const int hd = Ly.h * 64;
       dzn_gemm_desc d = gd(h, yin, Ly.qkv, h->qkv, ML, D, 3 * hd);
       if (fold1) folded(d, Ly.qkv);
       d.a_amax = am(yin == xr ? dzn_handle::AM_X : dzn_handle::AM_Y);
       d.c_amax = am(dzn_handle::AM_QKV);
-      const bool planes = h->kvp != nullptr && !y16 && d.W2h && d.col_scale && d.a_amax;     // the f32h contraction writes them
+      const bool planes = h->kvp != nullptr && d.W2h && d.col_scale && d.a_amax;     // the f32h contraction writes them
       const int64_t pstride = (ML + 64) * (int64_t)(2 * hd);
       if (planes) {
         d.kv_planes = h->kvp;
@@ -1331,7 +1263,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
         d.kv_ld = 2 * hd;
         d.kv_col0 = hd;
       }
-      gemm(d, y16, false, "qkv");
+      gemm(d, "qkv");
       if (planes)
         chk(launch_attention_planes(h->qkv, h->kvp, pstride, h->kvs, 2 * hd, h->ao, h->gate, h->table, Ly.head_idx, B, L, Ly.h, h->H,
                                     3 * hd, hd, 0.125f, st, am(dzn_handle::AM_QKV)),
@@ -1341,7 +1273,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
                                    0.125f, st, am(dzn_handle::AM_QKV)),
             "attention");
       else
-        chk(launch_attention_t(h->qkv, h->ao, lp, h->gate, h->table, Ly.head_idx, B, L, Ly.h, h->H, 3 * hd,
+        chk(launch_attention_t(h->qkv, h->ao, h->gate, h->table, Ly.head_idx, B, L, Ly.h, h->H, 3 * hd,
                                hd, 0.125f, st),
             "attention");
       dzn_gemm_desc o = gd(h, h->ao, Ly.out, own, ML, hd, D);
@@ -1356,7 +1288,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
         o.stat_eps = 1e-5f;
         have_stats = true;
       }
-      gemm(o, lp, false, "out_proj");
+      gemm(o, "out_proj");
       xr = own;
     }
     if (c.layer_norm_first) {
@@ -1366,14 +1298,14 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
           if (!have_stats) chk(launch_row_stats(xr, D, ML, D, 1e-5f, h->rstat, st), "row_stats");
           fin = xr;
         } else {
-          ln_t(xr, false, D, h->y, lp, D, Ly.ln2, ML, D, 0, st, nullptr, am(dzn_handle::AM_Y), L);
+          ln_t(xr, D, h->y, D, Ly.ln2, ML, D, 0, st, nullptr, am(dzn_handle::AM_Y), L);
         }
         dzn_gemm_desc f1 = gd(h, fin, Ly.f1, h->mid, ML, D, Ly.Fp);
         if (fold) folded(f1, Ly.f1);
         f1.act = DZN_ACT_GELU;
         f1.a_amax = am(fin == xr ? dzn_handle::AM_X : dzn_handle::AM_Y);
         f1.c_amax = am(dzn_handle::AM_MID);
-        gemm(f1, lp, lp, "ffn1");
+        gemm(f1, "ffn1");
         dzn_gemm_desc f2 = gd(h, h->mid, Ly.f2, own, ML, Ly.Fp, D);
         f2.R = xr;
         if (!defer) {
@@ -1383,7 +1315,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
         }
         f2.a_amax = am(dzn_handle::AM_MID);
         f2.c_amax = am(dzn_handle::AM_X);
-        gemm(f2, lp, false, "ffn2");
+        gemm(f2, "ffn2");
         xr = own;
       } else if (!defer) {
         chk(launch_ws_accum(xr, h->ws, wl, 0, ML * D, st), "ws_accum");
@@ -1393,25 +1325,20 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
         wsum.w[wsum.n++] = wl;
       }
     } else {
-      ln_t(xr, false, D, xr, false, D, Ly.ln1, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
+      ln_t(xr, D, xr, D, Ly.ln1, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
       if (Ly.ffn) {
-        const float* fin = xr;
-        if (lp) {
-          chk(launch_cast_bf16(xr, h->y, ML * D, st), "cast");
-          fin = h->y;
-        }
-        dzn_gemm_desc f1 = gd(h, fin, Ly.f1, h->mid, ML, D, Ly.Fp);
+        dzn_gemm_desc f1 = gd(h, xr, Ly.f1, h->mid, ML, D, Ly.Fp);
         f1.act = DZN_ACT_GELU;
         f1.a_amax = am(dzn_handle::AM_X);
         f1.c_amax = am(dzn_handle::AM_MID);
-        gemm(f1, lp, lp, "ffn1");
+        gemm(f1, "ffn1");
         dzn_gemm_desc f2 = gd(h, h->mid, Ly.f2, xr, ML, Ly.Fp, D);
         f2.R = xr;
         f2.a_amax = am(dzn_handle::AM_MID);
         f2.c_amax = am(dzn_handle::AM_X);
-        gemm(f2, lp, false, "ffn2");
+        gemm(f2, "ffn2");
       }
-      ln_t(xr, false, D, xr, false, D, Ly.ln2, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
+      ln_t(xr, D, xr, D, Ly.ln2, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
       chk(launch_ws_accum(xr, h->ws, wl, 0, ML * D, st), "ws_accum");
     }
     if (h->debug) {
@@ -1424,14 +1351,9 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
 
   // ---- head: proj + LN, Conformer x conf_layers, classifier (model_wavlm_conformer.py:256-262) ----
   {
-    const float* pin = h->ws;
-    if (lp) {
-      chk(launch_cast_bf16(h->ws, h->y, ML * D, st), "cast");
-      pin = h->y;
-    }
-    dzn_gemm_desc d = gd(h, pin, h->proj, h->hz, ML, D, A);
-    gemm(d, lp, false, "proj");   // (ws has no tracker: bf16 split)
-    ln_t(h->hz, false, A, h->hz, false, A, h->lnorm, ML, A, 0, st, nullptr, am(dzn_handle::AM_HZ), L);
+    dzn_gemm_desc d = gd(h, h->ws, h->proj, h->hz, ML, D, A);
+    gemm(d, "proj");   // (ws has no tracker: bf16 split)
+    ln_t(h->hz, A, h->hz, A, h->lnorm, ML, A, 0, st, nullptr, am(dzn_handle::AM_HZ), L);
   }
   tap(h, "head_in", h->hz, ML, A, A, st);
   for (int i = 0; i < c.conf_layers; ++i) {
@@ -1442,25 +1364,25 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
         chk(launch_row_stats(h->hz, A, ML, A, 1e-5f, h->rstat, st), "row_stats");
         in = h->hz;
       } else {
-        ln_t(h->hz, false, A, h->ht, lp, A, ln, ML, A, 0, st);
+        ln_t(h->hz, A, h->ht, A, ln, ML, A, 0, st);
       }
       dzn_gemm_desc a = gd(h, in, w1, h->hmid, ML, A, Fh);
       if (fold) folded(a, w1);
       a.act = DZN_ACT_SWISH;
       if (in == h->hz) a.a_amax = am(dzn_handle::AM_HZ);
       a.c_amax = am(dzn_handle::AM_HMID);
-      gemm(a, lp, lp, "conf ffn w1");
+      gemm(a, "conf ffn w1");
       dzn_gemm_desc b = gd(h, h->hmid, w2, h->hz, ML, Fh, A);
       b.alpha = 0.5f;
       b.R = h->hz;
       b.a_amax = am(dzn_handle::AM_HMID);
       b.c_amax = am(dzn_handle::AM_HZ);
-      gemm(b, lp, false, "conf ffn w2");
+      gemm(b, "conf ffn w2");
     };
     half_ffn(Cl.ffn1_ln, Cl.ffn1_w1, Cl.ffn1_w2);
     // MHSA
     if (fold) chk(launch_row_stats(h->hz, A, ML, A, 1e-5f, h->rstat, st), "row_stats");
-    else ln_t(h->hz, false, A, h->ht, lp, A, Cl.mha_ln, ML, A, 0, st);
+    else ln_t(h->hz, A, h->ht, A, Cl.mha_ln, ML, A, 0, st);
     {
       dzn_gemm_desc q = gd(h, fold ? h->hz : h->ht, Cl.qkv, h->hmid, ML, A, 3 * A);
       if (fold) {
@@ -1468,24 +1390,24 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
         q.a_amax = am(dzn_handle::AM_HZ);
       }
       q.c_amax = am(dzn_handle::AM_HMID);
-      gemm(q, lp, false, "conf qkv");
+      gemm(q, "conf qkv");
       if (prec_is_split(c.precision))
         chk(launch_attention_split(h->hmid, h->hv, nullptr, nullptr, nullptr, B, L, c.conf_heads, 0, 3 * A, A,
                                    0.125f, st, am(dzn_handle::AM_HMID)),
             "conf attention");
       else
-        chk(launch_attention_t(h->hmid, h->hv, lp, nullptr, nullptr, nullptr, B, L, c.conf_heads, 0, 3 * A, A,
+        chk(launch_attention_t(h->hmid, h->hv, nullptr, nullptr, nullptr, B, L, c.conf_heads, 0, 3 * A, A,
                                0.125f, st),
             "conf attention");
       dzn_gemm_desc o = gd(h, h->hv, Cl.o, h->hz, ML, A, A);
       o.R = h->hz;
       o.a_amax = am(dzn_handle::AM_HMID);   // attention output <= max |q/k/v| (convex combinations of v)
       o.c_amax = am(dzn_handle::AM_HZ);
-      gemm(o, lp, false, "conf out");
+      gemm(o, "conf out");
     }
     // conv module
     if (fold) chk(launch_row_stats(h->hz, A, ML, A, 1e-5f, h->rstat, st), "row_stats");
-    else ln_t(h->hz, false, A, h->ht, lp, A, Cl.conv_ln, ML, A, 0, st);
+    else ln_t(h->hz, A, h->ht, A, Cl.conv_ln, ML, A, 0, st);
     {
       dzn_gemm_desc p1 = gd(h, fold ? h->hz : h->ht, Cl.pw1, h->hmid, ML, A, 2 * A);
       if (fold) {
@@ -1493,16 +1415,16 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
         p1.a_amax = am(dzn_handle::AM_HZ);
       }
       p1.c_amax = am(dzn_handle::AM_HMID);
-      gemm(p1, lp, false, "conf pw1");
-      chk(launch_glu_dwconv(h->hmid, 2 * A, Cl.dw, Cl.dwb, h->hv, lp, A, B, L, A, c.conf_kernel, st),
+      gemm(p1, "conf pw1");
+      chk(launch_glu_dwconv(h->hmid, 2 * A, Cl.dw, Cl.dwb, h->hv, A, B, L, A, c.conf_kernel, st),
           "glu_dwconv");
       dzn_gemm_desc p2 = gd(h, h->hv, Cl.pw2, h->hz, ML, A, A);
       p2.R = h->hz;
       p2.c_amax = am(dzn_handle::AM_HZ);    // (glu_dwconv output has no tracker: bf16 split)
-      gemm(p2, lp, false, "conf pw2");
+      gemm(p2, "conf pw2");
     }
     half_ffn(Cl.ffn2_ln, Cl.ffn2_w1, Cl.ffn2_w2);
-    ln_t(h->hz, false, A, h->hz, false, A, Cl.out_ln, ML, A, 0, st, nullptr, am(dzn_handle::AM_HZ), L);
+    ln_t(h->hz, A, h->hz, A, Cl.out_ln, ML, A, 0, st, nullptr, am(dzn_handle::AM_HZ), L);
     if (h->debug) {
       const std::string nm = "conf" + std::to_string(i);
       tap(h, nm.c_str(), h->hz, ML, A, A, st);
@@ -1514,8 +1436,6 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
 }
 
 // ------------------------------------------------------------------ embedding forward
-// bf16 engine mode: the ResNet images are bf16 (operands, residuals and outputs of every conv);
-// fbank (DFT / mel), pooling statistics and seg_1 stay fp32.
 // `subset`: windows in which no speaker is active skip the trunk.  Zero weights pool to zero
 // (PA/models/blocks/pooling.py:44-131 with its 1e-8 guards), so every one of their embeddings is seg_1's bias (SURVEY a18;
 // tests/test_emb_gpu.py holds the device to that bit for bit).  The masks decide it and they only exist on the device, so
@@ -1524,14 +1444,13 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
 // (include/dzn.h), and it can be captured in a HIP graph.  The fbank (1 % of the stage) stays dense.
 void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int N, int L, float* d_emb, hipStream_t st) {
   const dzn_config& c = h->cfg;
-  const bool lp = c.precision == DZN_PREC_BF16;
   const int flen = 400, fshift = 160, Kp = 416, NB = c.num_mel_bins;
   if (N < flen) throw EngineError(DZN_E_INVALID, "waveform shorter than one fbank frame (400 samples)");
   const int T = 1 + (N - flen) / fshift;
   if (T > h->maxTf) throw EngineError(DZN_E_INVALID, "N exceeds max_samples");
   if (S < 1 || S > 8) throw EngineError(DZN_E_INVALID, "S must be in [1, 8]");
   emb_set_geometry(h, T, st);
-  const bool subset = h->emb_skip && !h->debug && !lp && h->seg1.b != nullptr;
+  const bool subset = h->emb_skip && !h->debug && h->seg1.b != nullptr;
   const int *zc = nullptr, *zl = nullptr, *zflag = nullptr;
   if (subset) {
     chk(launch_window_active(masks, B, S * L, h->win_flag, st), "window_active");
@@ -1571,7 +1490,7 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
         if (buf == h->sbuf[s2][k]) return h->amax + (dzn_handle::AM_IMG0 + 3 * s2 + k) * MB;
     return nullptr;
   };
-  chk(launch_stem_conv(h->fb, B, T, NB, h->sC[0], h->stem_w, h->stem_b, h->sbuf[0][0], lp, st, img_am(h->sbuf[0][0]), zc, zl),
+  chk(launch_stem_conv(h->fb, B, T, NB, h->sC[0], h->stem_w, h->stem_b, h->sbuf[0][0], st, img_am(h->sbuf[0][0]), zc, zl),
       "stem");
   for (int s = 0; s < 4; ++s) {
     const int Hs = h->sH[s], Ws = h->sW[s], Cc = h->sC[s];
@@ -1589,18 +1508,17 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
         return;
       }
       // stride-1 3x3 inside stage s: patch rows via tab1, two-level K = (dh | dw*C + ci)
-      dzn_gemm_desc d = gd(h, in, rc.l, eoff(out, interior, lp), M, 0, 0);
+      dzn_gemm_desc d = gd(h, in, rc.l, out + interior, M, 0, 0);
       d.a_rowoff = h->tab1[s];
       d.c_rowoff = h->tab1[s];
       d.kc = 3 * rc.cin;
       d.ldk = (int64_t)(Ws + 2) * rc.cin;
       d.act = act;
-      d.R = R ? eoff(R, interior, lp) : nullptr;
+      d.R = R ? R + interior : nullptr;
       d.post_relu = post_relu;
       d.nz = B;
       d.a_z0 = img;
       d.c_z0 = img;
-      d.a_bf16 = d.c_bf16 = d.r_bf16 = lp;
       d.a_amax = img_am(in);
       d.c_amax = img_am(out);
       d.z_count = zc;
@@ -1617,7 +1535,7 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
         float* midb = h->sbuf[s][0];
         float* outb = h->sbuf[s][1];
         float* scb = h->sbuf[s][2];
-        dzn_gemm_desc d = gd(h, prev, rb.c1.l, eoff(midb, interior, lp), M, 0, 0);
+        dzn_gemm_desc d = gd(h, prev, rb.c1.l, midb + interior, M, 0, 0);
         d.a_rowoff = h->tab2[s];
         d.c_rowoff = h->tab1[s];
         d.kc = 3 * Cpv;
@@ -1626,21 +1544,19 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
         d.nz = B;
         d.a_z0 = pimg;
         d.c_z0 = img;
-        d.a_bf16 = d.c_bf16 = lp;
         d.a_amax = img_am(prev);
         d.c_amax = img_am(midb);
         d.z_count = zc;
         d.z_list = zl;
         if (c.precision == DZN_PREC_F16 && ((h->f16_keep2 >> 14) & 1)) d.precision = DZN_PREC_F32_H2;
         chk(launch_gemm(d, st), "resnet conv3x3 s2");
-        dzn_gemm_desc e = gd(h, eoff(prev, ((int64_t)(Wp + 2) + 1) * Cpv, lp), rb.sc.l,
-                             eoff(scb, interior, lp), M, 0, 0);
+        dzn_gemm_desc e = gd(h, prev + ((int64_t)(Wp + 2) + 1) * Cpv, rb.sc.l,
+                             scb + interior, M, 0, 0);
         e.a_rowoff = h->tab2[s];
         e.c_rowoff = h->tab1[s];
         e.nz = B;
         e.a_z0 = pimg;
         e.c_z0 = img;
-        e.a_bf16 = e.c_bf16 = lp;
         e.a_amax = img_am(prev);
         e.c_amax = img_am(scb);
         e.z_count = zc;
@@ -1680,7 +1596,7 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
   }
   // ---- TSTP pooling for all S masks + seg_1 ----
   const int feat = h->sC[3] * h->sH[3];
-  chk(launch_stats_pool(prev, lp, B, h->sH[3], h->sW[3], h->sC[3], masks, S, L, h->pool, st, zflag), "stats_pool");
+  chk(launch_stats_pool(prev, B, h->sH[3], h->sW[3], h->sC[3], masks, S, L, h->pool, st, zflag), "stats_pool");
   tap(h, "pool", h->pool, (int64_t)B * S, 2 * feat, 2 * feat, st);
   {
     dzn_gemm_desc d = gd(h, h->pool, h->seg1, d_emb, (int64_t)B * S, 2 * feat, c.embed_out_dim);
@@ -1718,19 +1634,16 @@ int dzn_create(const dzn_config* cfg, dzn_handle** out) {
     last_create_error = "dzn_config.struct_size mismatch (ABI)";
     return DZN_E_INVALID;
   }
+  if (cfg->precision == DZN_PREC_BF16) {
+    last_create_error = "precision 1 (DZN_PREC_BF16) is not an engine mode: the bf16 engine was removed (reduced precision = DZN_PREC_F16)";
+    return DZN_E_INVALID;
+  }
   if (cfg->max_batch < 1 || cfg->max_samples < 400 ||
-      (cfg->precision != DZN_PREC_F32 && cfg->precision != DZN_PREC_BF16 &&
-       cfg->precision != DZN_PREC_F32_SPLIT && cfg->precision != DZN_PREC_F32_H2 &&
+      (cfg->precision != DZN_PREC_F32 && cfg->precision != DZN_PREC_F32_SPLIT && cfg->precision != DZN_PREC_F32_H2 &&
        cfg->precision != DZN_PREC_F16)) {
     last_create_error = "bad max_batch / max_samples / precision";
     return DZN_E_INVALID;
   }
-#ifndef DZN_TUNING
-  if (cfg->precision == DZN_PREC_BF16) {
-    last_create_error = "the bf16 engine mode is quarantined: it exists only in DZN_TUNING=1 builds (reduced precision = DZN_PREC_F16)";
-    return DZN_E_INVALID;
-  }
-#endif
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
     last_create_error = "no HIP device visible (libdzn_hip has no CPU fallback)";
@@ -1915,14 +1828,10 @@ int dzn_destroy(dzn_handle* h) {
 }
 
 const char* dzn_version(void) {
-#ifdef DZN_TUNING
-  return "dzn-hip 0.3.0 (gfx950, MFMA f32 / fp16x2 / bf16x3 / fp16 + MX fp8) [tuning build: probe tiles + the quarantined bf16 engine mode]";
-#else
 #ifdef DZN_CHECKED
   return "dzn-hip 0.3.0 (gfx950, MFMA f32 / fp16x2 / bf16x3 / fp16 + MX fp8) [checked build: device-side bounds assertions]";
 #else
   return "dzn-hip 0.3.0 (gfx950, MFMA f32 / fp16x2 / bf16x3 / fp16 + MX fp8)";
-#endif
 #endif
 }
 

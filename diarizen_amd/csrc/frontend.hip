@@ -6,27 +6,25 @@
 //           C0 channels of every frame (components.py:63-70) -> erf-GELU   (all fused here)
 //   base  : conv (raw) ; GroupNorm(C0, C0) = per-channel norm over TIME (components.py:1248-1253)
 //           needs whole-window statistics -> col_stats_kernel + gn_gelu_kernel
-// The stage is HBM-write bound (0.5 MB in, C0*T0*4 B out per window; half that in the bf16 engine
-// mode, which stores the activations as bf16).  Layout: channels-last [B, T0, Cp] so that the next
-// conv is a plain contraction over overlapping rows.  A workgroup stages a run of normalised
-// samples in LDS (coalesced), every lane keeps its channels' 10 taps in registers, a wavefront
-// produces one frame per iteration and stores 256 contiguous bytes per channel group.
-#include <type_traits>
-
+// The stage is HBM-write bound (0.5 MB in, C0*T0*4 B out per window).  Layout: channels-last
+// [B, T0, Cp] so that the next conv is a plain contraction over overlapping rows.  A workgroup
+// stages a run of normalised samples in LDS (coalesced), every lane keeps its channels' 10 taps in
+// registers, a wavefront produces one frame per iteration and stores 256 contiguous bytes per
+// channel group.
 #include "common.h"
 
 namespace {
 
 constexpr int FR_PER_BLOCK = 64;   // frames per workgroup (16 per wavefront)
 
-template <int CPL, bool LN, typename TO>
+template <int CPL, bool LN>
 __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wave, int N,
                                                     const float* __restrict__ stats,  // [B,2] or null
                                                     const float* __restrict__ w,      // [C0, k]
                                                     const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, int C0, int Cp,
                                                     int k, int s, int T0, float eps,
-                                                    TO* __restrict__ out,
+                                                    float* __restrict__ out,
                                                     const float* __restrict__ lnq /* [10 + 100] or null */) {
   __shared__ float sx[FR_PER_BLOCK * 8 + 32];
   __shared__ float2 sst[FR_PER_BLOCK];   // per-frame (mean, rstd) of the channel LayerNorm
@@ -90,7 +88,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wa
       acc[j] = a;
       sum += a;  // channels >= C0 have zero taps -> contribute 0
     }
-    TO* op = out + ((int64_t)b * T0 + f0 + f) * Cp;
+    float* op = out + ((int64_t)b * T0 + f0 + f) * Cp;
     float mu = 0.f, rs = 1.f;
     if (qstats) {
       const float2 st2 = sst[f];
@@ -117,14 +115,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wa
         float v = LN ? gelu_erf((acc[j] - mu) * rs * gr[j] + br[j]) : acc[j];
         o[e] = (c0 + e < C0) ? v : 0.f;
       }
-      if constexpr (sizeof(TO) == 4) {
-        *reinterpret_cast<float4*>(op + c0) = make_float4(o[0], o[1], o[2], o[3]);
-      } else {
-        u16 h[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) st_act(h, e, o[e]);
-        *reinterpret_cast<ushort4*>(op + c0) = make_ushort4(h[0], h[1], h[2], h[3]);
-      }
+      *reinterpret_cast<float4*>(op + c0) = make_float4(o[0], o[1], o[2], o[3]);
     }
   }
 }
@@ -205,10 +196,9 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
   stats[2 * (int64_t)i + 1] = 1.0f / sqrtf(m2 / (float)T + eps);
 }
 
-// y[b,t,c] = gelu((x - mean[b,c]) * rstd[b,c] * gamma[c] + beta[c]); y may alias x when TO = float;
+// y[b,t,c] = gelu((x - mean[b,c]) * rstd[b,c] * gamma[c] + beta[c]); y may alias x;
 // columns [C, Cp) of y are zeroed.  One float4 of channels per thread and step (Cp % 4 == 0, ld % 4 == 0).
-template <typename TO>
-__global__ __launch_bounds__(256) void gn_gelu_kernel(const float* x, TO* y, int T, int C, int Cp,
+__global__ __launch_bounds__(256) void gn_gelu_kernel(const float* x, float* y, int T, int C, int Cp,
                                                       int64_t ld, const float* __restrict__ stats,
                                                       const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, float* __restrict__ amax /* [B] or null */) {
@@ -233,12 +223,7 @@ __global__ __launch_bounds__(256) void gn_gelu_kernel(const float* x, TO* y, int
         o[e] = 0.f;
       }
     }
-    if constexpr (std::is_same<TO, float>::value) {
-      *reinterpret_cast<float4*>(y + off) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) st_act(y, off + e, o[e]);
-    }
+    *reinterpret_cast<float4*>(y + off) = make_float4(o[0], o[1], o[2], o[3]);
   }
   // per-window |max| of the output: the scale of conv1's fp16 two-term split (DZN_PREC_F32_H2).  One atomic per
   // WORKGROUP (wave maxima through LDS): per-wavefront atomics on 32 addresses cost 0.3 ms at BASELINE configs[1].
@@ -252,21 +237,20 @@ __global__ __launch_bounds__(256) void gn_gelu_kernel(const float* x, TO* y, int
 }
 
 // xpad[b, t + pad, :] = x[b, t, :], zero borders (input of the positional conv)
-template <typename TO>
-__global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__ x, TO* __restrict__ xpad,
+__global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__ x, float* __restrict__ xpad,
                                                        int L, int Lp, int pad, int D4) {
   const int b = blockIdx.y;
   const int64_t n = (int64_t)Lp * D4;
   const float4* xs = reinterpret_cast<const float4*>(x) + (int64_t)b * L * D4;
-  TO* xd = xpad + (int64_t)b * Lp * D4 * 4;
+  float* xd = xpad + (int64_t)b * Lp * D4 * 4;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int t = (int)(i / D4) - pad;
     const int c = (int)(i % D4);
     const float4 v = (t >= 0 && t < L) ? xs[(int64_t)t * D4 + c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    st_act(xd, 4 * i + 0, v.x);
-    st_act(xd, 4 * i + 1, v.y);
-    st_act(xd, 4 * i + 2, v.z);
-    st_act(xd, 4 * i + 3, v.w);
+    xd[4 * i + 0] = v.x;
+    xd[4 * i + 1] = v.y;
+    xd[4 * i + 2] = v.z;
+    xd[4 * i + 3] = v.w;
   }
 }
 
@@ -311,14 +295,13 @@ __global__ __launch_bounds__(256) void ws_sum_kernel(const WsSumArgs a, float* _
 }
 
 // x[r, c] *= scale[c]  (dummy_weight, components.py:208), columns >= C untouched
-template <typename T>
-__global__ __launch_bounds__(256) void col_scale_kernel(T* __restrict__ x, int64_t rows, int C,
+__global__ __launch_bounds__(256) void col_scale_kernel(float* __restrict__ x, int64_t rows, int C,
                                                         int64_t ld, const float* __restrict__ scale) {
   const int64_t n = rows * C;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int64_t r = i / C;
     const int c = (int)(i - r * C);
-    st_act(x, r * ld + c, ld_act(x, r * ld + c) * scale[c]);
+    x[r * ld + c] = x[r * ld + c] * scale[c];
   }
 }
 
@@ -327,19 +310,24 @@ inline unsigned grid_for(int64_t n, int per = 256, int cap = 4096) {
   return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-template <typename TO>
-int conv0_dispatch(const float* wave, int B, int N, const float* stats, const float* w,
-                   const float* gamma, const float* beta, int C0, int Cp, int k, int s, int T0,
-                   int layer_norm, float eps, TO* out, hipStream_t st, const float* lnq) {
+}  // namespace
+
+int launch_conv0(const float* wave, int B, int N, const float* stats, const float* w,
+                 const float* gamma, const float* beta, int C0, int Cp, int k, int s, int T0,
+                 int layer_norm, float eps, float* out, hipStream_t st, const float* lnq) {
+  if (k > 10 || C0 > 512 || s > 8) return DZN_E_INVALID;
+  // algorithmic HBM bytes: read the waveform once, write the [T0, C0] activations once
+  ProfScope prof_scope_(st, layer_norm ? "conv0_ln_gelu" : "conv0_raw", 2.0 * B * (double)T0 * C0 * k,
+                        B * (4.0 * N + 4.0 * (double)T0 * C0));
   dim3 grid((T0 + FR_PER_BLOCK - 1) / FR_PER_BLOCK, B);
   const int width = max(C0, Cp);   // a lane owns 4 consecutive channels per 256-channel group
 #define DZN_C0(CPLV)                                                                                  \
   do {                                                                                                \
     if (layer_norm)                                                                                   \
-      hipLaunchKernelGGL((conv0_kernel<CPLV, true, TO>), grid, dim3(256), 0, st, wave, N, stats, w,   \
+      hipLaunchKernelGGL((conv0_kernel<CPLV, true>), grid, dim3(256), 0, st, wave, N, stats, w,       \
                          gamma, beta, C0, Cp, k, s, T0, eps, out, lnq);                               \
     else                                                                                              \
-      hipLaunchKernelGGL((conv0_kernel<CPLV, false, TO>), grid, dim3(256), 0, st, wave, N, stats, w,  \
+      hipLaunchKernelGGL((conv0_kernel<CPLV, false>), grid, dim3(256), 0, st, wave, N, stats, w,      \
                          gamma, beta, C0, Cp, k, s, T0, eps, out, lnq);                               \
   } while (0)
   if (width <= 256) DZN_C0(4);
@@ -348,43 +336,18 @@ int conv0_dispatch(const float* wave, int B, int N, const float* stats, const fl
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
-}  // namespace
-
-int launch_conv0(const float* wave, int B, int N, const float* stats, const float* w,
-                 const float* gamma, const float* beta, int C0, int Cp, int k, int s, int T0,
-                 int layer_norm, float eps, void* out, int out_bf16, hipStream_t st, const float* lnq) {
-  if (k > 10 || C0 > 512 || s > 8) return DZN_E_INVALID;
-  // algorithmic HBM bytes: read the waveform once, write the [T0, C0] activations once
-  const double esz = out_bf16 ? 2.0 : 4.0;
-  const int pid = prof_begin(st, layer_norm ? "conv0_ln_gelu" : "conv0_raw",
-                             2.0 * B * (double)T0 * C0 * k, B * (4.0 * N + esz * (double)T0 * C0));
-  int rc;
-  if (out_bf16)
-    rc = conv0_dispatch(wave, B, N, stats, w, gamma, beta, C0, Cp, k, s, T0, layer_norm, eps,
-                        static_cast<u16*>(out), st, lnq);
-  else
-    rc = conv0_dispatch(wave, B, N, stats, w, gamma, beta, C0, Cp, k, s, T0, layer_norm, eps,
-                        static_cast<float*>(out), st, lnq);
-  prof_end(pid, st);
-  return rc;
-}
-
-int launch_groupnorm_gelu(const float* x, void* y, int y_bf16, int B, int T, int C, int Cp, int64_t ld,
+int launch_groupnorm_gelu(const float* x, float* y, int B, int T, int C, int Cp, int64_t ld,
                           const float* gamma, const float* beta, float eps, float* stats, hipStream_t st, float* amax) {
   // algorithmic bytes: x read once for the statistics, once for the element pass, y written once
-  ProfScope prof_scope_(st, "groupnorm_gelu", 0.0, (double)B * T * C * (y_bf16 ? 10.0 : 12.0));
+  ProfScope prof_scope_(st, "groupnorm_gelu", 0.0, (double)B * T * C * 12.0);
   if ((Cp & 3) || (ld & 3) || Cp > 1024) return DZN_E_INVALID;
   const int nchunk = (T + GN_ROWS - 1) / GN_ROWS;
   // scratch for the chunk partials: behind the [B, C, 2] statistics (the engine sizes `stats` for it: gn_stats_floats())
   float* part = stats + (int64_t)B * C * 2;
   hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, B), dim3(256), 0, st, x, T, C, Cp, ld, part);
   hipLaunchKernelGGL(gn_finalize_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, part, B, T, C, Cp, nchunk, eps, stats);
-  if (y_bf16)
-    hipLaunchKernelGGL(gn_gelu_kernel<u16>, dim3(grid_for((int64_t)T * (Cp / 4), 256, 512), B), dim3(256), 0, st, x,
-                       static_cast<u16*>(y), T, C, Cp, ld, stats, gamma, beta, amax);
-  else
-    hipLaunchKernelGGL(gn_gelu_kernel<float>, dim3(grid_for((int64_t)T * (Cp / 4), 256, 512), B), dim3(256), 0, st, x,
-                       static_cast<float*>(y), T, C, Cp, ld, stats, gamma, beta, amax);
+  hipLaunchKernelGGL(gn_gelu_kernel, dim3(grid_for((int64_t)T * (Cp / 4), 256, 512), B), dim3(256), 0, st, x, y, T, C, Cp, ld,
+                     stats, gamma, beta, amax);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
@@ -393,15 +356,9 @@ int64_t gn_stats_floats(int B, int T, int C, int Cp) {
   return (int64_t)B * C * 2 + (int64_t)B * ((T + GN_ROWS - 1) / GN_ROWS) * Cp * 2;
 }
 
-int launch_pad_rows(const float* x, void* xpad, int out_bf16, int B, int L, int Lp, int pad, int D,
-                    hipStream_t st) {
+int launch_pad_rows(const float* x, float* xpad, int B, int L, int Lp, int pad, int D, hipStream_t st) {
   ProfScope prof_scope_(st, "pad_rows", 0.0, (double)B * (L + Lp) * D * 4.0);
-  if (out_bf16)
-    hipLaunchKernelGGL(pad_rows_kernel<u16>, dim3(grid_for((int64_t)Lp * (D / 4)), B), dim3(256), 0, st,
-                       x, static_cast<u16*>(xpad), L, Lp, pad, D / 4);
-  else
-    hipLaunchKernelGGL(pad_rows_kernel<float>, dim3(grid_for((int64_t)Lp * (D / 4)), B), dim3(256), 0, st,
-                       x, static_cast<float*>(xpad), L, Lp, pad, D / 4);
+  hipLaunchKernelGGL(pad_rows_kernel, dim3(grid_for((int64_t)Lp * (D / 4)), B), dim3(256), 0, st, x, xpad, L, Lp, pad, D / 4);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
@@ -418,14 +375,8 @@ int launch_ws_sum(const WsSumArgs& a, float* ws, int64_t n, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
-int launch_col_scale(void* x, int x_bf16, int64_t rows, int C, int64_t ld, const float* scale,
-                     hipStream_t st) {
+int launch_col_scale(float* x, int64_t rows, int C, int64_t ld, const float* scale, hipStream_t st) {
   ProfScope prof_scope_(st, "col_scale", 0.0, (double)rows * C * 8.0);
-  if (x_bf16)
-    hipLaunchKernelGGL(col_scale_kernel<u16>, dim3(grid_for(rows * C)), dim3(256), 0, st,
-                       static_cast<u16*>(x), rows, C, ld, scale);
-  else
-    hipLaunchKernelGGL(col_scale_kernel<float>, dim3(grid_for(rows * C)), dim3(256), 0, st,
-                       static_cast<float*>(x), rows, C, ld, scale);
+  hipLaunchKernelGGL(col_scale_kernel, dim3(grid_for(rows * C)), dim3(256), 0, st, x, rows, C, ld, scale);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }

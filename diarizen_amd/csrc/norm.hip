@@ -1,5 +1,5 @@
-// norm.hip — row LayerNorm (+ optional erf-GELU, + optional per-column post-scale), element-type
-// cast, and per-window waveform statistics.
+// norm.hip — row LayerNorm (+ optional erf-GELU, + optional per-column post-scale) and per-window
+// waveform statistics.
 //
 // LayerNorm rows: torch.nn.functional.layer_norm over the last dim (biased variance, eps inside
 // the sqrt).  Sites: channel LN after conv1..6 of the WavLM extractor (W2V/components.py:63-70,
@@ -7,18 +7,17 @@
 // FeatureProjection.layer_norm (:305), EncoderLayer.layer_norm / final_layer_norm (:923-941),
 // Model.lnorm (model_wavlm_conformer.py:257) and every Conformer ln_norm (conformer.py).
 // HBM-bound: one wavefront per row, the row is held in registers between the two passes, so each
-// element is read once and written once.  Input / output may be fp32 or (bf16 engine mode) bf16.
+// element is read once and written once.
 #include <cstdint>
 #include <initializer_list>
-#include <type_traits>
 
 #include "common.h"
 
 namespace {
 
-template <int MAXI, typename TI, typename TO>
-__global__ __launch_bounds__(256) void layernorm_kernel(const TI* __restrict__ x, int64_t ldx,
-                                                        TO* __restrict__ y, int64_t ldy,
+template <int MAXI>
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t ldx,
+                                                        float* __restrict__ y, int64_t ldy,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta,
                                                         const float* __restrict__ post, int64_t rows,
@@ -31,13 +30,13 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TI* __restrict__ x
   float amax = 0.f;
   int64_t unit = amax_out && amax_unit > 0 && r0 < rows ? r0 / amax_unit : 0;
   for (int64_t row = r0; row < r0 + rows_per_wave && row < rows; ++row) {
-    const TI* xp = x + row * ldx;
+    const float* xp = x + row * ldx;
     float v[MAXI];
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXI; ++i) {
       const int idx = lane + 64 * i;
-      v[i] = idx < C ? ld_act(xp, idx) : 0.f;
+      v[i] = idx < C ? xp[idx] : 0.f;
       sum += v[i];
     }
     const float mean = wave_sum(sum) / (float)C;
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TI* __restrict__ x
       amax = 0.f;
       unit = row / amax_unit;
     }
-    TO* yp = y + row * ldy;
+    float* yp = y + row * ldy;
 #pragma unroll
     for (int i = 0; i < MAXI; ++i) {
       const int idx = lane + 64 * i;
@@ -64,10 +63,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TI* __restrict__ x
         if (gamma) o = o * gamma[idx] + beta[idx];
         if (gelu) o = gelu_erf(o);
         if (post) o *= post[idx];
-        st_act(yp, idx, o);
+        yp[idx] = o;
         amax = fmaxf(amax, fabsf(o));
       } else if (idx < Cpad) {
-        st_act(yp, idx, 0.f);
+        yp[idx] = 0.f;
       }
     }
   }
@@ -128,18 +127,6 @@ __global__ __launch_bounds__(256) void stats_finalize_kernel(const float2* __res
   stats[r] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
 }
 
-__global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ x, u16* __restrict__ y,
-                                                        int64_t n4) {
-  const float4* xs = reinterpret_cast<const float4*>(x);
-  ushort4* yd = reinterpret_cast<ushort4*>(y);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    const float4 v = xs[i];
-    u16 t[4];
-    st_act(t, 0, v.x); st_act(t, 1, v.y); st_act(t, 2, v.z); st_act(t, 3, v.w);
-    yd[i] = make_ushort4(t[0], t[1], t[2], t[3]);
-  }
-}
-
 // mean / rstd of each window's N samples (F.layer_norm(waveforms, waveforms.shape), W2V/model.py:113)
 __global__ __launch_bounds__(1024) void wave_stats_kernel(const float* __restrict__ w, int N,
                                                           float eps, float* __restrict__ stats) {
@@ -172,7 +159,7 @@ __global__ __launch_bounds__(1024) void wave_stats_kernel(const float* __restric
   }
 }
 
-// ---- float4 form (round 3), fp32 in / out ----
+// ---- float4 form (round 3) ----
 // One wavefront-per-row with 4-byte loads issues ~100 instructions for a 160-channel row (the conv LayerNorm sites): the
 // kernel ran at 2.8 TB/s, instruction-bound.  Here G lanes (16 / 32 / 64) own a row, NV float4s each, so a wavefront
 // processes 64 / G rows per step with NV 16-byte loads and stores per lane; the two reductions run over the G lanes of a
@@ -277,41 +264,43 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* x, int64
   }
 }
 
-template <typename TI, typename TO>
-int launch_ln_typed(const TI* x, int64_t ldx, TO* y, int64_t ldy, const float* g, const float* b,
-                    const float* post, int64_t rows, int C, int Cpad, float eps, int gelu, hipStream_t s,
-                    float* amax, int64_t amax_unit) {
-  if constexpr (std::is_same<TI, float>::value && std::is_same<TO, float>::value) {
-    const int needv = Cpad > C ? Cpad : C;
-    if (!(needv & 3) && !(ldx & 3) && !(ldy & 3) && needv <= 1024 && !(((uintptr_t)x | (uintptr_t)y) & 15)) {
-      // lanes per row / float4s per lane: least padding first, narrowest row group on ties
-      int G = 0, NV = 0, best = 1 << 30;
-      for (int gcand : {16, 32, 64}) {
-        const int nv = (needv + 4 * gcand - 1) / (4 * gcand);
-        if (nv <= 4 && nv * 4 * gcand < best) { best = nv * 4 * gcand; G = gcand; NV = nv; }
-      }
-      if (G) {
-        const int rpwv = 64 / G;
-        // ~8 wavefront steps per wavefront, at least 2048 workgroups when there are rows enough
-        int64_t steps = cdiv64(rows, rpwv);
-        int iters = (int)(steps / (2048 * 4));
-        iters = iters < 1 ? 1 : (iters > 8 ? 8 : iters);
-        const unsigned gridv = (unsigned)cdiv64(cdiv64(steps, iters), 4);
+}  // namespace
+
+int launch_layernorm_t(const float* x, int64_t ldx, float* y, int64_t ldy, const float* g, const float* b,
+                       const float* post, int64_t rows, int C, int Cpad, float eps, int gelu, hipStream_t s,
+                       float* amax, int64_t amax_unit) {
+  ProfScope prof_scope_(s, "layernorm", 0.0, (double)rows * C * 8.0);
+  if (rows <= 0) return DZN_OK;
+  if (C <= 0 || C > 2048 || Cpad > 2048) return DZN_E_INVALID;
+  const int needv = Cpad > C ? Cpad : C;
+  if (!(needv & 3) && !(ldx & 3) && !(ldy & 3) && needv <= 1024 && !(((uintptr_t)x | (uintptr_t)y) & 15)) {
+    // lanes per row / float4s per lane: least padding first, narrowest row group on ties
+    int G = 0, NV = 0, best = 1 << 30;
+    for (int gcand : {16, 32, 64}) {
+      const int nv = (needv + 4 * gcand - 1) / (4 * gcand);
+      if (nv <= 4 && nv * 4 * gcand < best) { best = nv * 4 * gcand; G = gcand; NV = nv; }
+    }
+    if (G) {
+      const int rpwv = 64 / G;
+      // ~8 wavefront steps per wavefront, at least 2048 workgroups when there are rows enough
+      int64_t steps = cdiv64(rows, rpwv);
+      int iters = (int)(steps / (2048 * 4));
+      iters = iters < 1 ? 1 : (iters > 8 ? 8 : iters);
+      const unsigned gridv = (unsigned)cdiv64(cdiv64(steps, iters), 4);
 #define DZN_LN4(GV, NVV)                                                                                         \
   hipLaunchKernelGGL((layernorm_v4_kernel<GV, NVV>), dim3(gridv), dim3(256), 0, s, x, ldx, y, ldy, g, b, post, rows, \
                      C, Cpad, eps, gelu, amax, amax_unit, iters)
-        if (G == 16 && NV == 1) DZN_LN4(16, 1);
-        else if (G == 16 && NV == 2) DZN_LN4(16, 2);
-        else if (G == 16 && NV == 3) DZN_LN4(16, 3);
-        else if (G == 16 && NV == 4) DZN_LN4(16, 4);
-        else if (G == 32 && NV == 3) DZN_LN4(32, 3);
-        else if (G == 32 && NV == 4) DZN_LN4(32, 4);
-        else if (G == 64 && NV == 3) DZN_LN4(64, 3);
-        else if (G == 64 && NV == 4) DZN_LN4(64, 4);
-        else G = 0;
+      if (G == 16 && NV == 1) DZN_LN4(16, 1);
+      else if (G == 16 && NV == 2) DZN_LN4(16, 2);
+      else if (G == 16 && NV == 3) DZN_LN4(16, 3);
+      else if (G == 16 && NV == 4) DZN_LN4(16, 4);
+      else if (G == 32 && NV == 3) DZN_LN4(32, 3);
+      else if (G == 32 && NV == 4) DZN_LN4(32, 4);
+      else if (G == 64 && NV == 3) DZN_LN4(64, 3);
+      else if (G == 64 && NV == 4) DZN_LN4(64, 4);
+      else G = 0;
 #undef DZN_LN4
-        if (G) return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
-      }
+      if (G) return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
     }
   }
   // with a tracker: contiguous runs of rows per wavefront, >= 8 waves per SIMD worth of wavefronts in flight
@@ -324,7 +313,7 @@ int launch_ln_typed(const TI* x, int64_t ldx, TO* y, int64_t ldy, const float* g
   const unsigned grid = (unsigned)cdiv64(cdiv64(rows, rpw), 4);
   const int need = (Cpad > C ? Cpad : C);
 #define DZN_LN(MAXI)                                                                               \
-  hipLaunchKernelGGL((layernorm_kernel<MAXI, TI, TO>), dim3(grid), dim3(256), 0, s, x, ldx, y, ldy, g, \
+  hipLaunchKernelGGL((layernorm_kernel<MAXI>), dim3(grid), dim3(256), 0, s, x, ldx, y, ldy, g, \
                      b, post, rows, C, Cpad, eps, gelu, amax, amax_unit, rpw)
   if (need <= 256) DZN_LN(4);
   else if (need <= 512) DZN_LN(8);
@@ -334,28 +323,10 @@ int launch_ln_typed(const TI* x, int64_t ldx, TO* y, int64_t ldy, const float* g
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
-}  // namespace
-
-int launch_layernorm_t(const void* x, int x_bf16, int64_t ldx, void* y, int y_bf16, int64_t ldy,
-                       const float* g, const float* b, const float* post, int64_t rows, int C, int Cpad,
-                       float eps, int gelu, hipStream_t s, float* amax, int64_t amax_unit) {
-  ProfScope prof_scope_(s, "layernorm", 0.0, (double)rows * C * 8.0);
-  if (rows <= 0) return DZN_OK;
-  if (C <= 0 || C > 2048 || Cpad > 2048) return DZN_E_INVALID;
-  const float* xf = static_cast<const float*>(x);
-  const u16* xh = static_cast<const u16*>(x);
-  float* yf = static_cast<float*>(y);
-  u16* yh = static_cast<u16*>(y);
-  if (!x_bf16 && !y_bf16) return launch_ln_typed(xf, ldx, yf, ldy, g, b, post, rows, C, Cpad, eps, gelu, s, amax, amax_unit);
-  if (!x_bf16 && y_bf16) return launch_ln_typed(xf, ldx, yh, ldy, g, b, post, rows, C, Cpad, eps, gelu, s, amax, amax_unit);
-  if (x_bf16 && !y_bf16) return launch_ln_typed(xh, ldx, yf, ldy, g, b, post, rows, C, Cpad, eps, gelu, s, amax, amax_unit);
-  return launch_ln_typed(xh, ldx, yh, ldy, g, b, post, rows, C, Cpad, eps, gelu, s, amax, amax_unit);
-}
-
 int launch_layernorm(const float* x, int64_t ldx, float* y, int64_t ldy, const float* g,
                      const float* b, int64_t rows, int C, int Cpad, float eps, int gelu,
                      hipStream_t s) {
-  return launch_layernorm_t(x, 0, ldx, y, 0, ldy, g, b, nullptr, rows, C, Cpad, eps, gelu, s);
+  return launch_layernorm_t(x, ldx, y, ldy, g, b, nullptr, rows, C, Cpad, eps, gelu, s);
 }
 
 int launch_stats_finalize(const float* partial, int64_t rows, int P, int C, float eps, float* stats, hipStream_t s) {
@@ -399,16 +370,6 @@ extern "C" int dzn_op_row_stats(const float* x, int64_t ldx, int64_t rows, int32
                                 void* stream) {
   if (!x || !stats) return DZN_E_INVALID;
   return launch_row_stats(x, ldx, rows, C, eps, stats, reinterpret_cast<hipStream_t>(stream));
-}
-
-int launch_cast_bf16(const float* x, void* y, int64_t n, hipStream_t s) {
-  ProfScope prof_scope_(s, "cast_bf16");
-  if (n <= 0) return DZN_OK;
-  if (n & 3) return DZN_E_INVALID;
-  int64_t g = cdiv64(n / 4, 256);
-  g = g > 8192 ? 8192 : g;
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3((unsigned)g), dim3(256), 0, s, x, static_cast<u16*>(y), n / 4);
-  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
 int launch_wave_stats(const float* w, int B, int N, float eps, float* stats, hipStream_t s) {

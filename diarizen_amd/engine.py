@@ -12,11 +12,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (DZN_F32, DZN_F64, DZN_I64, DZN_PREC_BF16, DZN_PREC_F32, DZN_PREC_F32_SPLIT, DznConfig,
+from ._lib import (DZN_F32, DZN_F64, DZN_I64, DZN_PREC_F32, DZN_PREC_F32_SPLIT, DznConfig,
                    check)
 from .configs import EmbConfig, SegConfig
 
-PRECISIONS = {"f32": DZN_PREC_F32, "fp32": DZN_PREC_F32, "bf16": DZN_PREC_BF16,
+PRECISIONS = {"f32": DZN_PREC_F32, "fp32": DZN_PREC_F32,
               "f32s": DZN_PREC_F32_SPLIT, "f32_split": DZN_PREC_F32_SPLIT, "f32h": _lib.DZN_PREC_F32_H2,
               "f16": _lib.DZN_PREC_F16, "fp16": _lib.DZN_PREC_F16}
 

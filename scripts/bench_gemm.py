@@ -23,4 +23,4 @@ for prec in (0, 1):
             ops.gemm(A, W, W16=W16, C_out=out, precision=prec)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / it
-        print(f"prec={'f32' if prec==0 else 'bf16'} M={M} N={N} K={K}: {dt*1e3:.3f} ms  {2*M*N*K/dt/1e12:.1f} TF/s", flush=True)
+        print(f"prec={'f32' if prec==0 else 'bf16 weights, f32 A'} M={M} N={N} K={K}: {dt*1e3:.3f} ms  {2*M*N*K/dt/1e12:.1f} TF/s", flush=True)

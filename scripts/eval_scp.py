@@ -44,7 +44,7 @@ def main(argv=None):
     ap.add_argument("--collar", type=float, default=0.0)
     ap.add_argument("--diarizen-hub", default=None, help="hub directory (config.toml, pytorch_model.bin, plda/)")
     ap.add_argument("--embedding-model", default=None)
-    ap.add_argument("--precision", default="f32h", choices=["f32h", "f32s", "f32", "f16", "bf16"])
+    ap.add_argument("--precision", default="f32h", choices=["f32h", "f32s", "f32", "f16"])
     ap.add_argument("--serial", action="store_true", help="one recording after the other (no host-stage overlap across recordings)")
     ap.add_argument("--synthetic-weights", action="store_true",
                     help="seeded turn-taking weights + the e2e fixture's configuration (no checkpoints offline)")

@@ -197,6 +197,22 @@ def test_c_abi_without_python(built_lib, gpu, tmp_path):
     assert "argmax flips=0" in r.stdout
 
 
+def test_create_refuses_the_removed_bf16_engine_mode(built_lib, gpu):
+    """precision 1 (DZN_PREC_BF16) is reserved, not an engine mode: dzn_create returns DZN_E_INVALID and leaves a message
+    for dzn_last_error(NULL); no handle is made."""
+    import ctypes as C
+    from diarizen_amd import _lib
+    from diarizen_amd.configs import get_seg_config
+    from diarizen_amd.engine import make_dzn_config
+    zc = make_dzn_config(get_seg_config("tiny_ln"), None, 1, 12000, "f32h")
+    zc.precision = _lib.DZN_PREC_BF16
+    assert _lib.DZN_PREC_BF16 == 1
+    h = C.c_void_p()
+    assert built_lib.dzn_create(C.byref(zc), C.byref(h)) == -1      # DZN_E_INVALID (include/dzn.h)
+    assert not h.value
+    assert built_lib.dzn_last_error(None)
+
+
 def test_device_postprocess_equals_numpy(built_lib, gpu):
     """row f2: speaker counting and cluster activations aggregated on the device (integer atomics over the u8
     decisions) are bit-identical to the numpy restatement of Inference.aggregate / reconstruct — on the e2e golden

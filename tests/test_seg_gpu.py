@@ -3,8 +3,8 @@ modules (tests/golden/seg_*.npz, made by oracle/gen_golden.py) and (b) the oracl
 on the same seeded weights + inputs.
 
 Tolerance, fp32 engine ("strict" mode of SURVEY.md §8d): max |d logp| <= 1e-3 and identical
-argmax (hence identical hard multilabel) on these fixtures.  bf16 engine: max |d logp| <= 1e-1 (random seeded weights amplify operand rounding),
-argmax agreement >= 99.5 %.
+argmax (hence identical hard multilabel) on these fixtures.  Reduced-precision engine (f16): SURVEY §8d's bar, stated at
+its tests (max |d logp| <= 5e-2, argmax agreement >= 99.5 %).
 """
 import os
 
@@ -221,18 +221,6 @@ def test_seg_loudness_extremes_in_one_batch(built_lib, gpu, name, precision):
         assert torch.equal(one.cpu()[0], logp[b]) and torch.equal(one_ml.cpu()[0], ml[b]), f"window {b} depends on its neighbours"
 
 
-@pytest.mark.parametrize("name", ["tiny_ln", "wavlm_large_s80_md"])
-def test_seg_bf16_within_tolerance(built_lib, gpu, name):
-    from conftest import needs_bf16_mode
-    needs_bf16_mode(built_lib)
-    cfg, sd, wave, g, eng, logp, ml = _run_case(name, gpu, "bf16")
-    ref = torch.from_numpy(g["logp"])
-    err = (logp - ref).abs().max().item()
-    agree = (logp.argmax(-1) == ref.argmax(-1)).float().mean().item()
-    assert err <= 1e-1, f"max |dlogp| = {err}"
-    assert agree >= 0.995
-
-
 @pytest.mark.parametrize("name", ["tiny_ln", "wavlm_large_s80_md", "wavlm_base_s80_md"])
 def test_seg_f16_within_tolerance(built_lib, gpu, name):
     """DZN_PREC_F16 (BASELINE configs[4] "fp16"): single-term fp16 contractions inside the f32h engine.  Reduced
@@ -428,23 +416,6 @@ def test_seg_from_a_checkpoint_embedded_config_end_to_end(built_lib, gpu, name, 
     torch.save({"state_dict": {}}, str(tmp_path / "noconfig.pt"))
     with pytest.raises(ValueError, match="must contain"):
         WavLMConformer(wavlm_src=str(tmp_path / "noconfig.pt"), wavlm_layer_num=head.wavlm_layer_num, wavlm_feat_dim=head.embed_dim)
-
-
-@pytest.mark.parametrize("name", ["tiny_gn", "wavlm_base_s80_md"])
-def test_seg_bf16_group_norm_models(built_lib, gpu, name):
-    """bf16 engine on the base-style models (group-norm extractor, post-norm encoder, 48-channel
-    positional-conv groups for base: that contraction stays on fp32 activations)"""
-    from conftest import needs_bf16_mode
-    needs_bf16_mode(built_lib)
-    cfg, sd, wave, g, eng, logp, ml = _run_case(name, gpu, "bf16")
-    ref = torch.from_numpy(g["logp"])
-    assert (logp - ref).abs().max().item() <= 1e-1
-    # decisions may only differ on frames where the reference's own top-2 margin is inside the tolerance
-    differ = logp.argmax(-1) != ref.argmax(-1)
-    top2 = ref.topk(2, dim=-1).values
-    margin = top2[..., 0] - top2[..., 1]
-    assert (margin[differ] <= 2e-1).all()
-    assert differ.float().mean().item() <= 0.03
 
 
 def test_conv01_fusion_matches_unfused(built_lib, gpu, monkeypatch):
