@@ -174,7 +174,7 @@ int launch_glu_dwconv(const float* u, int64_t ldu, const float* w, const float* 
                       int64_t ldo, int B, int L, int A, int ks, hipStream_t st);
 int launch_classify(const float* z, int64_t ldz, const float* W, const float* bias,
                     const uint8_t* mapping, int64_t rows, int A, int NC, int S, float* logp,
-                    uint8_t* multilabel, hipStream_t st);
+                    uint8_t* multilabel, float* soft, hipStream_t st);
 // embed.hip
 int launch_frame_prep(const float* wave, int B, int N, int T, int flen, int fshift, int Kp,
                       const float* window, float preemph, float* frames, hipStream_t st);

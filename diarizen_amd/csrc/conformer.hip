@@ -9,7 +9,9 @@
 // classify_kernel: classifier Linear(A -> n_classes) + LogSoftmax
 //   (model_wavlm_conformer.py:261-262) + Powerset.to_multilabel(soft=False)
 //   (PA/utils/powerset.py:120-128: one_hot(argmax) @ mapping).  One wavefront per frame; what
-//   leaves the device is 4 bytes per frame (u8 multilabel) and, optionally, the log-probs.
+//   leaves the device is 4 bytes per frame (u8 multilabel) and, optionally, the log-probs and the
+//   soft multilabel scores Powerset.to_multilabel(soft=True) (PA/utils/powerset.py:120-128:
+//   exp(powerset) @ mapping), summed from the log-probs the wavefront holds in registers.
 #include "common.h"
 
 namespace {
@@ -61,7 +63,8 @@ __global__ __launch_bounds__(256) void classify_kernel(const float* __restrict__
                                                        const uint8_t* __restrict__ mapping,  // [NC, S]
                                                        int64_t rows, int A, int NC, int S,
                                                        float* __restrict__ logp,
-                                                       uint8_t* __restrict__ multilabel) {
+                                                       uint8_t* __restrict__ multilabel,
+                                                       float* __restrict__ soft) {  // [rows, S] or null
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + wave;
   if (row >= rows) return;
@@ -95,6 +98,14 @@ __global__ __launch_bounds__(256) void classify_kernel(const float* __restrict__
       if (c < NC && lane == c) logp[row * NC + c] = logit[c] - lse;
   }
   if (multilabel && lane < S) multilabel[row * S + lane] = mapping[arg * S + lane];
+  if (soft && lane < S) {
+    // lane s: probabilities of the classes that contain speaker s, added in ascending class order
+    float p = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c)
+      if (c < NC && mapping[c * S + lane]) p += expf(logit[c] - lse);
+    soft[row * S + lane] = p;
+  }
 }
 
 }  // namespace
@@ -116,10 +127,11 @@ int launch_glu_dwconv(const float* u, int64_t ldu, const float* w, const float* 
 
 int launch_classify(const float* z, int64_t ldz, const float* W, const float* bias,
                     const uint8_t* mapping, int64_t rows, int A, int NC, int S, float* logp,
-                    uint8_t* multilabel, hipStream_t st) {
-  ProfScope prof_scope_(st, "classify", 2.0 * (double)rows * A * NC, (double)rows * (A * 4.0 + NC * 4.0 + S));
+                    uint8_t* multilabel, float* soft, hipStream_t st) {
+  ProfScope prof_scope_(st, "classify", 2.0 * (double)rows * A * NC,
+                        (double)rows * (A * 4.0 + NC * 4.0 + S + (soft ? S * 4.0 : 0.0)));
   if (NC > 16 || S > 64) return DZN_E_INVALID;
   hipLaunchKernelGGL(classify_kernel, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, st, z, ldz, W,
-                     bias, mapping, rows, A, NC, S, logp, multilabel);
+                     bias, mapping, rows, A, NC, S, logp, multilabel, soft);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }

@@ -1036,7 +1036,7 @@ void ensure_table(H* h, int L, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ segmentation forward
-void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* d_ml, hipStream_t st) {
+void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* d_ml, float* d_soft, hipStream_t st) {
   const dzn_config& c = h->cfg;
   const bool lnx = c.extractor_layer_norm != 0;
   int T[DZN_MAX_CONV];
@@ -1431,7 +1431,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
     }
   }
   chk(launch_classify(h->hz, A, h->cls_w, h->cls_b, h->mapping, ML, A, c.n_classes,
-                      c.max_speakers_per_chunk, d_logp, d_ml, st),
+                      c.max_speakers_per_chunk, d_logp, d_ml, d_soft, st),
       "classify");
 }
 
@@ -1728,6 +1728,11 @@ int dzn_num_frames(const dzn_handle* h, int32_t num_samples) {
 
 int dzn_segment_forward(dzn_handle* h, const float* d_wave, int32_t B, int32_t N, float* d_logp,
                         uint8_t* d_multilabel, void* hip_stream) {
+  return dzn_segment_forward_soft(h, d_wave, B, N, d_logp, d_multilabel, nullptr, hip_stream);
+}
+
+int dzn_segment_forward_soft(dzn_handle* h, const float* d_wave, int32_t B, int32_t N, float* d_logp,
+                             uint8_t* d_multilabel, float* d_soft, void* hip_stream) {
   if (!h) return DZN_E_INVALID;
   if (!h->finalized) {
     h->err = "dzn_segment_forward before dzn_finalize_weights";
@@ -1739,7 +1744,7 @@ int dzn_segment_forward(dzn_handle* h, const float* d_wave, int32_t B, int32_t N
   }
   DeviceGuard dg(h->device);
   return guarded(h, [&] {
-    seg_forward(h, d_wave, B, N, d_logp, d_multilabel, reinterpret_cast<hipStream_t>(hip_stream));
+    seg_forward(h, d_wave, B, N, d_logp, d_multilabel, d_soft, reinterpret_cast<hipStream_t>(hip_stream));
   });
 }
 

@@ -7,7 +7,8 @@
 //     speakers are zeroed ("clean" mask); a speaker falls back to its full mask when its clean
 //     mask has <= min_num_frames frames.
 // Integer/byte work, one workgroup per window, everything staged in LDS.
-// Also the two detection pipelines' aggregation and hysteresis (dzn_detect, below).
+// Also the two detection pipelines' aggregation and hysteresis (dzn_detect, below) and the aggregation of the soft scores
+// into per-speaker activity scores (dzn_speaker_scores).
 #include "common.h"
 #include "checked.h"
 
@@ -216,6 +217,65 @@ __global__ __launch_bounds__(kHystThreads) void hysteresis_kernel(const float* _
   }
 }
 
+// ---- per-speaker activity scores (dzn_speaker_scores) -----------------------------------------------------------------
+// SpeakerDiarization.reconstruct's clustered scores (PA/pipelines/speaker_diarization.py:400-423: max over the local
+// speakers of window c that belong to cluster k, NaN when there is none, hard < 0 skipped) through
+// Inference.aggregate(hamming=True, missing=0.0, skip_average=False, warm_up) (PA/core/inference.py:544-666).  The clustered
+// array is float64 holding float32 values and every window is added as
+//     acc[t,k] = f32(f64(acc[t,k]) + ((score * mask) * hamming[l]) * warm_up[l]),   cnt[t,k] likewise with mask alone
+// (mask = 0 and score = 0 for a NaN entry: both additions are of 0.0).  As in detect_scores_kernel one thread — here per
+// (t, k) — walks ITS covering windows in ascending order, so the rounding sequence is the reference's; the products and sums
+// are spelled __dmul_rn / __dadd_rn (no contraction), and the two weight tables stay apart because the score is not 0 / 1.
+__global__ __launch_bounds__(256) void speaker_scores_kernel(const float* __restrict__ soft, const int8_t* __restrict__ hard,
+                                                             int C, int L, int S, const int32_t* __restrict__ start,
+                                                             const double* __restrict__ ham, const double* __restrict__ wu,
+                                                             int T, int K, float* __restrict__ scores) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)T * K) return;
+  const int t = (int)(i / K), k = (int)(i - (int64_t)t * K);
+  DZN_CHECK(t >= 0 && t < T && k >= 0 && k < K, 0x812, t);
+  // covering windows: start[c] <= t < start[c] + L  ->  c in [c0, c1)
+  int lo = 0, hi = C;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (start[mid] > t - L) hi = mid; else lo = mid + 1;
+  }
+  const int c0 = lo;
+  hi = C;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (start[mid] > t) hi = mid; else lo = mid + 1;
+  }
+  const int c1 = lo;
+  float acc = 0.f, cnt = 0.f;
+  bool seen = false;
+  for (int c = c0; c < c1; ++c) {
+    const int l = t - start[c];
+    DZN_CHECK(l >= 0 && l < L, 0x810, c);
+    DZN_CHECK(c == 0 || start[c - 1] <= start[c], 0x811, c);
+    if (l < 0 || l >= L) continue;          // only reachable with a start[] that is not non-decreasing
+    const float* row = soft + ((int64_t)c * L + l) * S;
+    const int8_t* hc = hard + (int64_t)c * S;
+    bool has = false, isnan_ = false;
+    float v = 0.f;
+    for (int s = 0; s < S; ++s) {
+      if (hc[s] != k) continue;
+      const float x = row[s];
+      isnan_ |= x != x;                         // np.max propagates a NaN: the entry is then missing like an absent cluster
+      v = (!has || x > v) ? x : v;
+      has = true;
+    }
+    const bool valid = has && !isnan_;
+    const double sc = valid ? (double)v : 0.0, m = valid ? 1.0 : 0.0;
+    const double hl = ham[l], wl = wu[l];
+    acc = (float)__dadd_rn((double)acc, __dmul_rn(__dmul_rn(__dmul_rn(sc, m), hl), wl));
+    cnt = (float)__dadd_rn((double)cnt, __dmul_rn(__dmul_rn(m, hl), wl));
+    seen |= valid;
+  }
+  // average = acc / max(cnt, epsilon) in float32; `missing` = 0 where no non-NaN entry landed
+  scores[i] = seen ? __fdiv_rn(acc, fmaxf(cnt, 1e-12f)) : 0.f;
+}
+
 }  // namespace
 
 extern "C" int dzn_speaker_count(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame,
@@ -262,6 +322,19 @@ extern "C" int dzn_detect(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S,
                      tasks, K, d_scores);
   if (d_active)
     hipLaunchKernelGGL(hysteresis_kernel, dim3(K), dim3(kHystThreads), 0, st, d_scores, T, K, onset, offset, d_active);
+  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+extern "C" int dzn_speaker_scores(const float* d_soft, const int8_t* d_hard, int32_t C, int32_t L, int32_t S,
+                                  const int32_t* d_start_frame, const double* d_hamming, const double* d_warm_up,
+                                  int32_t T, int32_t K, float* d_scores, void* stream) {
+  if (!d_soft || !d_hard || !d_start_frame || !d_hamming || !d_warm_up || !d_scores || C < 0 || L < 1 || S < 1 || S > 8 ||
+      T < 1 || K < 1 || K > 32)
+    return DZN_E_INVALID;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = (int64_t)T * K;
+  hipLaunchKernelGGL(speaker_scores_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, st, d_soft, d_hard, C, L, S,
+                     d_start_frame, d_hamming, d_warm_up, T, K, d_scores);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 

@@ -128,9 +128,11 @@ class Engine:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ forwards
-    def segment(self, wave: torch.Tensor, want_logp: bool = True, want_multilabel: bool = True):
+    def segment(self, wave: torch.Tensor, want_logp: bool = True, want_multilabel: bool = True, want_soft: bool = False):
         """wave: f32 [B, N] on the device.  Returns (logp [B, L, n_classes] or None,
-        multilabel u8 [B, L, S] or None) — enqueue only, caller synchronises."""
+        multilabel u8 [B, L, S] or None) — enqueue only, caller synchronises.
+        want_soft: a third element, the soft multilabel scores f32 [B, L, S] = exp(logp) @ mapping
+        (Powerset.to_multilabel(soft=True), PA/utils/powerset.py:103-128), written by the classifier's own launch."""
         assert wave.is_cuda and wave.dtype == torch.float32 and wave.dim() == 2 and wave.is_contiguous()
         B, N = wave.shape
         L = self.num_frames(N)
@@ -138,12 +140,20 @@ class Engine:
                 if want_logp else None)
         ml = (torch.empty((B, L, self.seg.max_speakers_per_chunk), device=wave.device, dtype=torch.uint8)
               if want_multilabel else None)
-        check(self.lib.dzn_segment_forward(
+        if not want_soft:
+            check(self.lib.dzn_segment_forward(
+                self._h, C.c_void_p(wave.data_ptr()), B, N,
+                C.c_void_p(logp.data_ptr()) if logp is not None else None,
+                C.c_void_p(ml.data_ptr()) if ml is not None else None, self._stream()),
+                self._h, "dzn_segment_forward")
+            return logp, ml
+        soft = torch.empty((B, L, self.seg.max_speakers_per_chunk), device=wave.device, dtype=torch.float32)
+        check(self.lib.dzn_segment_forward_soft(
             self._h, C.c_void_p(wave.data_ptr()), B, N,
             C.c_void_p(logp.data_ptr()) if logp is not None else None,
-            C.c_void_p(ml.data_ptr()) if ml is not None else None, self._stream()),
-            self._h, "dzn_segment_forward")
-        return logp, ml
+            C.c_void_p(ml.data_ptr()) if ml is not None else None, C.c_void_p(soft.data_ptr()), self._stream()),
+            self._h, "dzn_segment_forward_soft")
+        return logp, ml, soft
 
     def embed(self, wave: torch.Tensor, masks: torch.Tensor) -> torch.Tensor:
         """wave f32 [B, N], masks f32 [B, S, L] (device) -> embeddings f32 [B, S, dim]."""

@@ -44,6 +44,7 @@ class SlideResult:
     window: int
     step: int
     num_frames: int
+    scores: Optional[torch.Tensor] = None  # f32 [C, L, S] soft multilabel scores (with_scores=True; never median-filtered), device
 
 
 class WindowRunner:
@@ -136,17 +137,20 @@ class WindowRunner:
         return torch.as_strided(wave, (C, self.window), (self.step, 1))
 
     def run(self, wave: torch.Tensor, with_embeddings: bool = True,
-            window_range: Optional[Tuple[int, int]] = None, hook=None) -> SlideResult:
+            window_range: Optional[Tuple[int, int]] = None, hook=None, with_scores: bool = False) -> SlideResult:
         """wave: f32 [N_total] on the device.  window_range=(c0, c1) restricts to a contiguous
         run of windows (multi-GPU sharding).  Enqueue only; results are device tensors.
         hook: the progress callback of `Inference.slide` (PA/core/inference.py:308-340), called as
         hook(completed=<windows done>, total=<windows>) before the first and after every batch; a hook makes the
-        call wait for each batch (otherwise "completed" would only mean "enqueued")."""
+        call wait for each batch (otherwise "completed" would only mean "enqueued").
+        with_scores: also keep the soft multilabel scores of every window (SlideResult.scores, `Inference.slide` with
+        soft=True: PA/core/inference.py:226, 319, 330); the median filter belongs to the hard decisions only."""
         views = self.windows_view(wave)
         c0, c1 = window_range if window_range is not None else (0, views.shape[0])
-        return self.run_views(views, c0, c1, with_embeddings=with_embeddings, hook=hook)
+        return self.run_views(views, c0, c1, with_embeddings=with_embeddings, hook=hook, with_scores=with_scores)
 
-    def run_views(self, views: torch.Tensor, c0: int, c1: int, with_embeddings: bool = True, hook=None) -> SlideResult:
+    def run_views(self, views: torch.Tensor, c0: int, c1: int, with_embeddings: bool = True, hook=None,
+                  with_scores: bool = False) -> SlideResult:
         """the batch loop of run() over rows c0 .. c1 of a [C, window] (strided) view of device samples — the streaming
         session hands in a view of its pre-zeroed device ring, so nothing is re-concatenated as audio arrives"""
         eng = self.engine
@@ -156,6 +160,7 @@ class WindowRunner:
         seg = torch.empty((C, self.num_frames, S), device=wave.device, dtype=torch.uint8)
         emb = (torch.empty((C, S, eng.emb.embed_dim), device=wave.device, dtype=torch.float32)
                if with_embeddings else None)
+        soft = torch.empty((C, self.num_frames, S), device=wave.device, dtype=torch.float32) if with_scores else None
         # balanced batches: ceil(C / batch_size) launches of (almost) equal size instead of full batches plus a short
         # tail (2241 windows at batch 256: 9 x 249 rather than 8 x 256 + 193) — windows are independent and the
         # engines are batch-invariant, so only the tail efficiency changes
@@ -178,7 +183,10 @@ class WindowRunner:
             e = self.engines[k]
             with torch.cuda.stream(self._streams[k]) if multi else _nullcontext():
                 chunk = views[s0:s1].contiguous()
-                _, ml = e.segment(chunk, want_logp=False)
+                if with_scores:
+                    _, ml, soft[s0 - c0:s1 - c0] = e.segment(chunk, want_logp=False, want_soft=True)
+                else:
+                    _, ml = e.segment(chunk, want_logp=False)
                 filt, masks = e.prepare_masks(ml, self.median_size, self.exclude_overlap,
                                               self.min_num_frames if self.exclude_overlap else -1,
                                               want_masks=with_embeddings)
@@ -191,4 +199,4 @@ class WindowRunner:
         if multi:
             for st in self._streams:
                 cur.wait_stream(st)                 # the caller's stream sees every batch's results
-        return SlideResult(seg, emb, self.window, self.step, self.num_frames)
+        return SlideResult(seg, emb, self.window, self.step, self.num_frames, soft)

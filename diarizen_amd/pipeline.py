@@ -22,11 +22,12 @@ import torch
 from . import audio as audio_io
 from .clustering import AgglomerativeClustering, VBxClustering, active_speakers
 from .configs import RESNET34
-from .core import Annotation, SlidingWindow
+from .core import Annotation, SlidingWindow, SlidingWindowFeature
 from .engine import Engine
-from .inference import WindowRunner
+from .inference import WindowRunner, window_plan
 from .models import SpeakerEmbedding, WavLMConformer, instantiate
-from .postprocess import DevicePost, binarize, receptive_field, reconstruct, speaker_count
+from .postprocess import (DevicePost, _frame_grid, binarize, crop_end, receptive_field, reconstruct, speaker_count,
+                          speaker_scores)
 
 try:
     import tomllib as _toml  # py311+
@@ -80,12 +81,17 @@ def _load_checkpoint(path: str) -> Dict[str, torch.Tensor]:
 
 def run_host_stage(seg: np.ndarray, emb: np.ndarray, *, chunks: SlidingWindow, clustering, min_speakers: int,
                    max_speakers: int, sample_rate: int = 16000, sess_name: Optional[str] = None,
-                   device=None, hook=None) -> Annotation:
+                   device=None, hook=None, soft=None, num_frames: Optional[int] = None):
     """The host half of `DiariZenPipeline.__call__` (diarizen/pipelines/inference.py:137-185): speaker
     counting -> clustering -> inactive speakers to -2 -> reconstruction -> Binarize.  Needs no device, so
     it is checked on the CPU against the oracle's loop-for-loop restatement (tests/test_host.py).
     hook(step_name, artifact): the per-step callback of `SpeakerDiarization.apply`
-    (PA/pipelines/speaker_diarization.py:498,572: "speaker_counting", "discrete_diarization")."""
+    (PA/pipelines/speaker_diarization.py:498,572: "speaker_counting", "discrete_diarization").
+    soft (optional): the soft multilabel scores f32 [C, L, S] of the same windows — a device tensor (it stays there; with
+    `device` given, dzn_speaker_scores aggregates it and only [T, K] comes back) or a host array.  The return value is then
+    (Annotation, per-speaker activity scores as a SlidingWindowFeature [T, K]): column k is cluster k = label k of the
+    Annotation, T = num_frames (the cropped length) or every frame of the aggregation; the hook sees them as
+    "speaker_scores".  The Annotation is the one a call without `soft` returns."""
     hook = hook or (lambda *a, **k: None)
     frames = receptive_field(sample_rate)
     hard_decisions = seg.dtype == np.uint8
@@ -107,7 +113,17 @@ def run_host_stage(seg: np.ndarray, emb: np.ndarray, *, chunks: SlidingWindow, c
         segf = seg.astype(np.float32)
     discrete, _ = res if res is not None else reconstruct(segf, chunks, hard, count)
     hook("discrete_diarization", discrete)
-    return binarize(discrete, onset=0.5, offset=0.5, uri=sess_name)
+    result = binarize(discrete, onset=0.5, offset=0.5, uri=sess_name)
+    if soft is None:
+        return result
+    if post is not None and isinstance(soft, torch.Tensor) and soft.is_cuda:
+        scores = post.speaker_scores(hard, soft, num_frames)
+    else:
+        scores = speaker_scores(soft.cpu().numpy() if isinstance(soft, torch.Tensor) else soft, chunks, frames, hard)
+        if num_frames is not None:
+            scores.data = np.ascontiguousarray(scores.data[:int(num_frames)])
+    hook("speaker_scores", scores)
+    return result, scores
 
 
 def load_hub_config(hub: Path) -> Dict[str, Any]:
@@ -255,9 +271,10 @@ class DiariZenPipeline:
         return SlidingWindow(start=0.0, duration=self.seg_duration,
                              step=self.segmentation_step * self.seg_duration)
 
-    def device_stage(self, waveform, hook=None):
+    def device_stage(self, waveform, hook=None, with_scores: bool = False):
         """host float32 [N] (or a lazy source with `.num_samples` and `.read(start, n)`, e.g. audio.WavSource) ->
         (segmentations u8 [C, L, 4], embeddings f32 [C, 4, 256]) on the host.
+        with_scores (one device only): a third element, the soft multilabel scores f32 [C, L, 4], which STAY on the device.
         With torch.distributed initialised, this rank reads / uploads ONLY the samples its contiguous window range touches
         (its slice + one window of halo), runs them, and the per-window results are all-gathered."""
         from . import dist as dz_dist
@@ -266,6 +283,9 @@ class DiariZenPipeline:
         total = int(waveform.num_samples) if lazy else len(waveform)
         C = r.num_windows(total)
         rng = dz_dist.my_window_range(C)
+        if with_scores and dz_dist.world_size() > 1:
+            raise RuntimeError(self._ONE_DEVICE % ("device_stage(with_scores=True)", dz_dist.world_size()))
+        soft_l = None
         if rng is not None:
             c0, c1 = rng
             lo, n = c0 * r.step, ((c1 - c0 - 1) * r.step + r.window if c1 > c0 else 0)
@@ -279,8 +299,8 @@ class DiariZenPipeline:
             x = np.ascontiguousarray(have, dtype=np.float32)
         if len(x):
             wave = torch.from_numpy(x).to(self.device)
-            res = r.run(wave, with_embeddings=True, hook=hook)
-            seg_l, emb_l = res.segmentations, res.embeddings
+            res = r.run(wave, with_embeddings=True, hook=hook, with_scores=with_scores)
+            seg_l, emb_l, soft_l = res.segmentations, res.embeddings, res.scores
         else:                                                      # more ranks than windows
             S = self.engine.seg.max_speakers_per_chunk
             seg_l = torch.empty((0, r.num_frames, S), device=self.device, dtype=torch.uint8)
@@ -289,14 +309,49 @@ class DiariZenPipeline:
         # handles' streams - not a device-wide synchronise, which would also wait for the host stage of the previous recording
         # on its own high-priority stream (diarize_many)
         seg, emb = dz_dist.gather_windows(seg_l, emb_l, expected_total=C, to_host=True)
+        if with_scores:
+            if soft_l is None:
+                soft_l = torch.empty((0, r.num_frames, seg_l.shape[2]), device=self.device, dtype=torch.float32)
+            return seg.numpy(), emb.numpy(), soft_l
         return seg.numpy(), emb.numpy()
 
-    def host_stage(self, seg: np.ndarray, emb: np.ndarray, sess_name: Optional[str] = None, hook=None) -> Annotation:
-        """counting -> clustering -> reconstruction -> Annotation (inference.py:137-185)."""
+    def host_stage(self, seg: np.ndarray, emb: np.ndarray, sess_name: Optional[str] = None, hook=None, soft=None,
+                   num_frames: Optional[int] = None):
+        """counting -> clustering -> reconstruction -> Annotation (inference.py:137-185); with `soft` (the device tensor of
+        device_stage(with_scores=True)) -> (Annotation, per-speaker activity scores [T, K]), see run_host_stage."""
         return run_host_stage(seg, emb, chunks=self.chunks_window(), clustering=self.clustering,
                               min_speakers=self.min_speakers, max_speakers=self.max_speakers,
                               sample_rate=self.segmentation_model.sample_rate, sess_name=sess_name,
-                              device=self.device if self.device_postprocess else None, hook=hook)
+                              device=self.device if self.device_postprocess else None, hook=hook, soft=soft,
+                              num_frames=num_frames)
+
+    _ONE_DEVICE = ("%s runs on one device: the soft scores of a recording sharded over torch.distributed ranks are not "
+                   "gathered (world size %d)")
+
+    # ------------------------------------------------------------------ soft / raw segmentation
+    def get_segmentations(self, file, soft: bool = False, hook=None) -> SlidingWindowFeature:
+        """SpeakerDiarization.get_segmentations(file, hook=None, soft=False) (PA/pipelines/speaker_diarization.py:209-226):
+        the per-window output of the segmentation model as a SlidingWindowFeature [C, L, S] float32 on the windows' grid.
+        soft=False: the hard decisions BEFORE the median filter (the reference applies its filter in `__call__`,
+        diarizen/pipelines/inference.py:131-132, not here); soft=True: Powerset.to_multilabel(soft=True)
+        (PA/utils/powerset.py:103-128), written by the classifier kernel.  hook: progress per batch of windows, as
+        hook("segmentation", None, file=..., completed=..., total=...)."""
+        import functools
+        from . import dist as dz_dist
+        if dz_dist.world_size() > 1:
+            raise RuntimeError(self._ONE_DEVICE % ("get_segmentations", dz_dist.world_size()))
+        file = file if isinstance(file, Mapping) else {"audio": file}
+        if hook is not None:
+            hook = functools.partial(hook, "segmentation", None, file=file)
+        x = np.ascontiguousarray(open_recording(file["audio"], self.segmentation_model.sample_rate), dtype=np.float32)
+        # the raw decisions: a runner without the median filter on this pipeline's engine handle(s), as detection._Detection
+        raw = WindowRunner(self.engine, self.seg_duration, self.segmentation_step, self.batch_size, median_size=0,
+                           exclude_overlap=False, sample_rate=self.segmentation_model.sample_rate,
+                           extra_engines=self.extra_engines)
+        with torch.cuda.device(self.device):
+            res = raw.run(torch.from_numpy(x).to(self.device), with_embeddings=False, hook=hook, with_scores=soft)
+            data = (res.scores if soft else res.segmentations).cpu().numpy().astype(np.float32, copy=False)
+        return SlidingWindowFeature(data, self.chunks_window())
 
     # ------------------------------------------------------------------ online use
     def stream(self, chunks, sess_name: Optional[str] = None, **kw):
@@ -384,13 +439,19 @@ class DiariZenPipeline:
         return open_recording(in_wav, self.segmentation_model.sample_rate, lazy=dz_dist.world_size() > 1)
 
     # ------------------------------------------------------------------ __call__
-    def __call__(self, in_wav, sess_name: Optional[str] = None, hook=None) -> Annotation:
+    def __call__(self, in_wav, sess_name: Optional[str] = None, hook=None, return_scores: bool = False):
         """`hook` (optional, not in the reference's DiariZenPipeline signature but in the pyannote pipeline it
         derives from): hook(step_name, step_artifact, file=..., total=..., completed=...) as
         PA/pipelines/utils/hook.py:36-224 expects (ProgressHook / ArtifactHook / TimingHook work unchanged).
         Steps: "segmentation" (progress per batch of windows, then the SlidingWindowFeature), "speaker_counting",
         "embeddings" (the [C, S, 256] array — computed in the same device pass as the segmentation, so it has no
-        progress of its own), "discrete_diarization"."""
+        progress of its own), "discrete_diarization".
+        return_scores=True: -> (Annotation, scores), scores a SlidingWindowFeature f32 [T, K] of per-speaker activity scores on
+        the frame grid of the discrete diarization: the soft multilabel scores of every window (Powerset.to_multilabel(
+        soft=True)) mapped to the clusters as reconstruct does and aggregated with Inference.aggregate(hamming=True,
+        missing=0.0).  Column k is cluster k, the integer label k of the Annotation (K = max(hard_clusters) + 1: a cluster
+        that never wins a frame keeps its column); T is cropped at the end of the audio when the last window was zero-padded.
+        The Annotation and the RTTM file are those of a call without the flag; the hook also sees "speaker_scores"."""
         import functools
         import time
         file = in_wav if isinstance(in_wav, Mapping) else {"audio": in_wav}
@@ -400,19 +461,32 @@ class DiariZenPipeline:
             in_wav = in_wav["audio"]
         t0 = time.perf_counter()
         from . import dist as dz_dist
+        if return_scores and dz_dist.world_size() > 1:
+            raise RuntimeError(self._ONE_DEVICE % ("return_scores=True", dz_dist.world_size()))
         waveform = self._open(in_wav)
         num_samples = int(waveform.num_samples) if hasattr(waveform, "num_samples") else len(waveform)
         t1 = time.perf_counter()
-        seg, emb = self.device_stage(
-            waveform, hook=functools.partial(hook, "segmentation", None) if hook is not None else None)
+        soft = None
+        seg_hook = functools.partial(hook, "segmentation", None) if hook is not None else None
+        if return_scores:
+            seg, emb, soft = self.device_stage(waveform, hook=seg_hook, with_scores=True)
+        else:
+            seg, emb = self.device_stage(waveform, hook=seg_hook)
         if hook is not None:
-            from .core import SlidingWindowFeature
             hook("segmentation", SlidingWindowFeature(seg, self.chunks_window()))
             hook("embeddings", emb)
         t2 = time.perf_counter()
-        result = None
+        result = scores = None
         if dz_dist.rank() == 0:
-            result = self.host_stage(seg, emb, sess_name, hook=hook)
+            if return_scores:
+                r = self._runner
+                grid, _, T = _frame_grid(seg.shape[0], seg.shape[1], self.chunks_window(),
+                                         receptive_field(self.segmentation_model.sample_rate))
+                if window_plan(num_samples, r.window, r.step)[1]:
+                    T = crop_end(T, grid, num_samples / self.segmentation_model.sample_rate)   # PA/core/inference.py:400-403
+                result, scores = self.host_stage(seg, emb, sess_name, hook=hook, soft=soft, num_frames=T)
+            else:
+                result = self.host_stage(seg, emb, sess_name, hook=hook)
             if self.rttm_out_dir is not None:
                 assert sess_name is not None
                 with open(os.path.join(self.rttm_out_dir, sess_name + ".rttm"), "w") as f:
@@ -421,4 +495,4 @@ class DiariZenPipeline:
         self.streams_in_use = len(self._runner.engines)       # <= num_streams (WindowRunner.grow_declined says why when fewer)
         self.timings = {"load_s": t1 - t0, "device_s": t2 - t1, "host_s": t3 - t2,
                         "audio_s": num_samples / self.segmentation_model.sample_rate}
-        return result
+        return (result, scores) if return_scores else result

@@ -7,6 +7,7 @@ Restates, with numpy vector ops instead of per-frame Python loops ("f2" row of S
   * SpeakerDiarizationMixin.to_diarization   PA/pipelines/utils/diarization.py:192-239
   * SpeakerDiarization.reconstruct           PA/pipelines/speaker_diarization.py:377-425
   * Binarize.__call__ (onset = offset = 0.5) PA/utils/signal.py:254-317
+  * Powerset.to_multilabel(soft=True)        PA/utils/powerset.py:103-128   (soft_multilabel, speaker_scores)
 The frame grid is SlidingWindow(start = chunks.start, duration = 0.025, step = 0.02): the
 receptive-field START is discarded by aggregate() (inference.py:577-581) — kept as is.
 """
@@ -102,6 +103,70 @@ def reconstruct(segmentations: np.ndarray, chunks: SlidingWindow, hard_clusters:
     return to_diarization(clustered, chunks, count)
 
 
+# ----------------------------------------------------------------------------- per-speaker activity scores
+def soft_multilabel(logp: np.ndarray, mapping: np.ndarray) -> np.ndarray:
+    """Powerset.to_multilabel(powerset, soft=True) (PA/utils/powerset.py:120-128): exp(logp) @ mapping in float32.
+    logp [..., n_classes] log-probabilities, mapping [n_classes, S] {0,1} -> [..., S]."""
+    return np.matmul(np.exp(np.asarray(logp, dtype=np.float32)), np.asarray(mapping, dtype=np.float32))
+
+
+def aggregation_windows(L: int, duration: float, warm_up=(0.0, 0.0), epsilon: float = 1e-12):
+    """the two float64 [L] factors of Inference.aggregate(hamming=True, warm_up) (PA/core/inference.py:586-607), kept apart:
+    the reference multiplies (score * hamming) * warm_up, and for scores that are not 0 / 1 a pre-multiplied table does not
+    round the same way"""
+    wu = np.ones(L, dtype=np.float64)
+    left = round(warm_up[0] / duration * L)
+    wu[:left] = epsilon
+    right = round(warm_up[1] / duration * L)
+    wu[L - right:] = epsilon
+    return np.ascontiguousarray(np.hamming(L), dtype=np.float64), wu
+
+
+def clustered_scores(soft: np.ndarray, hard_clusters: np.ndarray) -> np.ndarray:
+    """the clustered segmentations of SpeakerDiarization.reconstruct (PA/pipelines/speaker_diarization.py:400-423) on soft
+    scores: float64 [C, L, K], K = max(hard) + 1, clustered[c, :, k] = max over the local speakers s of window c with
+    hard[c, s] == k, NaN when there is none (hard < 0 = inactive is skipped)"""
+    soft = np.asarray(soft, dtype=np.float32)
+    hard_clusters = np.asarray(hard_clusters)
+    C, L, S = soft.shape
+    K = max(int(np.max(hard_clusters)) + 1, 0) if hard_clusters.size else 0
+    clustered = np.full((C, L, K), np.nan, dtype=np.float64)
+    for k in range(K):
+        sel = hard_clusters == k                                    # [C, S]
+        has = sel.any(axis=1)
+        if not has.any():
+            continue
+        vals = np.where(sel[:, None, :], soft, np.float32(-np.inf)).max(axis=2)     # [C, L] float32 (NaN propagates like np.max)
+        clustered[has, :, k] = vals[has]
+    return clustered
+
+
+def speaker_scores(soft: np.ndarray, chunks: SlidingWindow, frames: SlidingWindow, hard_clusters: np.ndarray,
+                   warm_up=(0.0, 0.0), epsilon: float = 1e-12) -> SlidingWindowFeature:
+    """soft f32 [C, L, S] (soft multilabel scores of every window), hard_clusters [C, S] (-2 = inactive) -> per-speaker
+    activity scores f32 [T, K]: reconstruct's clustered scores through Inference.aggregate(hamming=True, missing=0.0,
+    skip_average=False, warm_up) (PA/core/inference.py:544-666), with its arithmetic: float64 operands added window after
+    window into float32 arrays, (score * mask) * hamming * warm_up in that order.  Needs no device; dzn_speaker_scores
+    (csrc/post.hip) is checked against it bit for bit."""
+    clustered = clustered_scores(soft, hard_clusters)
+    C, L, K = clustered.shape
+    grid, starts, T = _frame_grid(C, L, chunks, frames)
+    mask = 1 - np.isnan(clustered)                                  # int64, as in the reference
+    data = np.nan_to_num(clustered, copy=True, nan=0.0)
+    ham, wu = (w.reshape(-1, 1) for w in aggregation_windows(L, chunks.duration, warm_up, epsilon))
+    out = np.zeros((T, K), dtype=np.float32)
+    cnt = np.zeros((T, K), dtype=np.float32)
+    seen = np.zeros((T, K), dtype=np.float32)
+    for c in range(C):
+        s0 = int(starts[c])
+        out[s0:s0 + L] += data[c] * mask[c] * ham * wu
+        cnt[s0:s0 + L] += mask[c] * ham * wu
+        np.maximum(seen[s0:s0 + L], mask[c], out=seen[s0:s0 + L])
+    avg = out / np.maximum(cnt, np.float32(epsilon))
+    avg[seen == 0.0] = 0.0
+    return SlidingWindowFeature(avg, grid)
+
+
 # ----------------------------------------------------------------------------- device versions (row f2)
 def _frame_grid(C: int, L: int, chunks: SlidingWindow, frames: SlidingWindow):
     """(frame grid of aggregate(), start frame of every window, number of output frames) — the reference's float64
@@ -144,7 +209,7 @@ class DevicePost:
                 raise ValueError("DevicePost needs hard {0,1} decisions")
             seg = seg.astype(np.uint8)
         self.C, self.L, self.S = seg.shape
-        self.chunks = chunks
+        self.chunks, self.frames = chunks, frames
         self.grid, starts, self.T = _frame_grid(self.C, self.L, chunks, frames)
         # (r5) the host stage's own stream: it may run in a second thread while the engine executes the next recording's
         # device stage (pipeline.diarize_many), and work queued on the default stream would wait behind the engine's
@@ -180,6 +245,34 @@ class DevicePost:
                        "dzn_cluster_activations")
             a = act.cpu().numpy().astype(np.float32)
         return _select_top_count(SlidingWindowFeature(a, count.sliding_window), count)
+
+    def speaker_scores(self, hard_clusters: np.ndarray, soft_device, num_frames: Optional[int] = None,
+                       warm_up=(0.0, 0.0)) -> SlidingWindowFeature:
+        """per-speaker activity scores f32 [T, K] (dzn_speaker_scores) from the soft scores f32 [C, L, S] that are still on
+        the device; T = num_frames (the cropped length) or the full aggregate length.  Only [T, K] comes back.  K > 32 takes
+        the numpy function, as reconstruct does."""
+        torch = self.torch
+        T = self.T if num_frames is None else int(num_frames)
+        K = max(int(np.max(hard_clusters)) + 1, 0) if hard_clusters.size else 0
+        if K < 1 or T < 1:
+            return SlidingWindowFeature(np.zeros((max(T, 0), K), dtype=np.float32), self.grid)
+        if K > 32:
+            host = speaker_scores(soft_device.cpu().numpy(), self.chunks, self.frames, hard_clusters, warm_up)
+            return SlidingWindowFeature(np.ascontiguousarray(host.data[:T]), self.grid)
+        assert soft_device.is_cuda and soft_device.dtype == torch.float32 and soft_device.is_contiguous()
+        assert tuple(soft_device.shape) == (self.C, self.L, self.S)
+        ham, wu = aggregation_windows(self.L, self.chunks.duration, warm_up)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))     # the soft scores were produced there
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            soft_device.record_stream(self.stream)
+            hard = torch.from_numpy(np.ascontiguousarray(hard_clusters, dtype=np.int8)).to(self.device)
+            d_ham, d_wu = torch.from_numpy(ham).to(self.device), torch.from_numpy(wu).to(self.device)
+            out = torch.empty((T, K), device=self.device, dtype=torch.float32)
+            st = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self.check(self.lib.dzn_speaker_scores(self._p(soft_device), self._p(hard), self.C, self.L, self.S,
+                                                   self._p(self.starts), self._p(d_ham), self._p(d_wu), T, K, self._p(out), st),
+                       None, "dzn_speaker_scores")
+            return SlidingWindowFeature(out.cpu().numpy(), self.grid)
 
 
 # ----------------------------------------------------------------------------- detection (VAD / OSD) scores

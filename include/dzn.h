@@ -171,6 +171,19 @@ int dzn_segment_forward(dzn_handle* h, const float* d_wave, int32_t B, int32_t N
                         float* d_logp, uint8_t* d_multilabel, void* hip_stream);
 
 /*
+ * Segmentation forward with the soft multilabel scores as a third optional output: d_soft f32
+ * [B, L, max_speakers_per_chunk] (may be NULL: then this is dzn_segment_forward),
+ *     soft[b, l, s] = sum over the powerset classes c that contain speaker s, in ascending c, of expf(logp[b, l, c])
+ * i.e. Powerset.to_multilabel(powerset, soft=True) = exp(powerset) @ mapping (PA/utils/powerset.py:103-128), the soft
+ * path the reference carries through SpeakerDiarization.get_segmentations(file, soft=...)
+ * (PA/pipelines/speaker_diarization.py:209-226) and Inference.__call__ / slide / infer (PA/core/inference.py:197-226,
+ * 242, 319, 330, 412-444).  Written by the classifier's own launch from the log-probabilities it holds in registers.
+ * Enqueue-only, every precision mode.
+ */
+int dzn_segment_forward_soft(dzn_handle* h, const float* d_wave, int32_t B, int32_t N,
+                             float* d_logp, uint8_t* d_multilabel, float* d_soft, void* hip_stream);
+
+/*
  * Embedding forward with the ResNet trunk shared by the S masks of a window.
  * d_wave f32 [B, N]; d_masks f32 [B, S, L]; d_emb f32 [B, S, embed_out_dim].
  */
@@ -225,6 +238,25 @@ int dzn_cluster_activations(const uint8_t* d_seg, const int8_t* d_hard, int32_t 
  */
 int dzn_detect(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame, const double* d_weight,
                int32_t T, int32_t tasks, float onset, float offset, float* d_scores, uint8_t* d_active, void* hip_stream);
+
+/*
+ * Per-speaker activity scores (stateless, no handle): the soft scores of every window, mapped to the global clusters and
+ * overlap-added.
+ *   clustered[c, :, k] = max_{s : hard[c,s] == k} soft[c, :, s], NaN when window c has no local speaker in cluster k
+ *                        (hard < 0 is skipped)      SpeakerDiarization.reconstruct, PA/pipelines/speaker_diarization.py:400-423
+ *   scores <- Inference.aggregate(clustered, frames, hamming=True, missing=0.0, skip_average=False, warm_up=warm_up)
+ *                                                   PA/core/inference.py:544-666
+ * with the reference's arithmetic: per window, in window order, acc[t,k] = f32(f64(acc[t,k]) + ((score * mask) *
+ * hamming[l]) * warm_up[l]) and cnt[t,k] likewise with the mask alone (a NaN entry adds nothing to either), then
+ * acc / max(cnt, 1e-12) in float32, 0.0 where no non-NaN entry ever landed.
+ * d_soft f32 [C,L,S] (S <= 8), d_hard int8 [C,S], d_start_frame int32 [C] non-decreasing (closest_frame, host float64, as for
+ * dzn_detect), d_hamming / d_warm_up f64 [L]: two tables, multiplied in the reference's order (a pre-multiplied table does
+ * not give the same bits for non-binary scores), T = output frames (frames >= T are not computed), 1 <= K <= 32,
+ * d_scores f32 [T,K].  One thread per (t, k) walks its covering windows in ascending order; no atomics.
+ */
+int dzn_speaker_scores(const float* d_soft, const int8_t* d_hard, int32_t C, int32_t L, int32_t S,
+                       const int32_t* d_start_frame, const double* d_hamming, const double* d_warm_up,
+                       int32_t T, int32_t K, float* d_scores, void* hip_stream);
 
 /* Copy a named intermediate activation of the LAST forward to host (debug / parity
  * tests).  *n_elems receives the element count; host_out may be NULL to query. */
