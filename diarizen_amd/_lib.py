@@ -98,6 +98,8 @@ class DznGemmDesc(C.Structure):
         ("amax_count", C.c_int32),
         ("kv_planes", C.c_void_p), ("kv_plane_stride", C.c_int64), ("kv_scale", C.c_void_p), ("kv_ld", C.c_int32),
         ("kv_col0", C.c_int32),
+        ("A2", C.c_void_p), ("a2_rowoff", C.c_void_p), ("a2_amax", C.c_void_p), ("a2_z0", C.c_int64),
+        ("k1", C.c_int32), ("k2", C.c_int32),
     ]
 
 

@@ -234,6 +234,7 @@ static inline double gemm_alg_bytes(const dzn_gemm_desc& d, int w_bytes_per_elem
   const double nz = d.nz > 0 ? d.nz : 1;
   const double a_cols = d.a_rowoff ? (double)d.kc : (d.lda > 0 && d.lda < d.K ? (double)d.lda : (double)d.K);
   double b = (double)d.M * a_cols * 4.0 * nz;
+  if (d.A2) b += (double)d.M * d.k2 * 4.0 * nz;   // second A segment: k2 columns per row
   b += (double)d.N * d.K * w_bytes_per_elem * ((d.w_z0 || d.w_z1) ? nz : 1.0);
   b += (double)d.M * d.N * 4.0 * nz;
   if (d.R) b += (double)d.M * d.N * 4.0 * nz;

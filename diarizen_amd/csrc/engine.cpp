@@ -83,6 +83,7 @@ struct ConfLayer {
 struct ResConv {
   Lin l;
   int cin = 0, cout = 0, ksz = 3, stride = 1;
+  int k2 = 0;   // > 0: conv2 of a down-sampling block with the 1x1 shortcut folded in — k2 more K columns from the previous stage's image
   float l1max = 0.f, bmax = 0.f;   // max_oc sum_k |W[oc][k]| and max_oc |shift[oc]| of the folded conv: |out| <= amax(in) l1max + bmax
 };
 struct ResBlock {
@@ -214,6 +215,7 @@ struct dzn_handle {
   // AND the fused stride-1 BasicBlocks of stages 1-2 (resblock_fused.hip / resblock_ws.hip, which have a single-term form
   // since r5; in r4 they were two-term whatever the bit said).
   bool fuse_resblock = true;  // DZN_NO_RESBLOCK_FUSION (read once, at dzn_create)
+  bool fuse_shortcut = true;  // DZN_NO_SHORTCUT_FUSION (read once, at dzn_create): keep the shortcut of a down-sampling block as its own launch
   int resblock_ws = 2;        // DZN_RESBLOCK_WS bit mask: 1 = 32-plane blocks, 2 = 64-plane blocks on the producer / consumer form
   // (r5) with the cross terms in fp8 everywhere else, the Conformer head (bits 8-13, 8 % of the segmentation flops) keeps two
   // fp16 terms as well: max |dlogp| does not move (1.01e-2 vs 1.03e-2) but the decisions next to the classifier do — DER of the
@@ -817,6 +819,39 @@ ResConv make_resconv(H* h, const std::string& conv, const std::string& bn, int c
   return r;
 }
 
+// conv2 (3x3, stride 1, cout -> cout) of a down-sampling block with the block's 1x1 stride-2 shortcut (cprev -> cout) folded
+// in: out = relu(conv2(mid) + b2 + Ws x_centre + bs) is ONE sum over K = 9 cout + cprev.  Weight row = [W2 | Ws | 0-pad to a
+// multiple of 64], bias = b2 + bs, both with their BatchNorm folded; the planes and their per-row scales are taken over the
+// whole concatenated row (make_lin).  Built once: the weights do not change between calls.
+ResConv make_resconv_shortcut(H* h, const std::string& conv, const std::string& bn, const std::string& sconv,
+                              const std::string& sbn, int cprev, int cout) {
+  const HostT& w = need(h, conv + ".weight");
+  expect_numel(w, (int64_t)cout * cout * 9, conv + ".weight");
+  const HostT& ws = need(h, sconv + ".weight");
+  expect_numel(ws, (int64_t)cout * cprev, sconv + ".weight");
+  std::vector<float> sc, sh, ssc, ssh;
+  fold_bn(h, bn, cout, sc, sh);
+  fold_bn(h, sbn, cout, ssc, ssh);
+  const int K1 = 9 * cout, Kp = K1 + (cprev + 63) / 64 * 64;
+  if (K1 % 64 != 0 || cprev % 32 != 0) throw EngineError(DZN_E_INVALID, "shortcut fusion: channel counts");
+  std::vector<float> wp((size_t)cout * Kp, 0.f), bias(cout);
+  for (int o = 0; o < cout; ++o) {
+    for (int ci = 0; ci < cout; ++ci)
+      for (int dh = 0; dh < 3; ++dh)
+        for (int dw = 0; dw < 3; ++dw)
+          wp[(size_t)o * Kp + (dh * 3 + dw) * cout + ci] = w.v[(((size_t)o * cout + ci) * 3 + dh) * 3 + dw] * sc[o];
+    for (int ci = 0; ci < cprev; ++ci) wp[(size_t)o * Kp + K1 + ci] = ws.v[(size_t)o * cprev + ci] * ssc[o];
+    bias[o] = sh[o] + ssh[o];
+  }
+  ResConv r;
+  r.cin = cout;
+  r.cout = cout;
+  r.k2 = cprev;
+  r.l = make_lin(h, wp, bias.data(), cout, Kp, cout, Kp);
+  r.l.Kt = K1 + cprev;   // algorithmic flops: the columns that exist
+  return r;
+}
+
 void finalize_emb(H* h) {
   const dzn_config& c = h->cfg;
   const std::string E = "embedding.resnet.";
@@ -881,9 +916,13 @@ void finalize_emb(H* h) {
       ResBlock& rb = h->stages[s][j];
       const int stride = (j == 0 && s > 0) ? 2 : 1;
       rb.c1 = make_resconv(h, bp + ".conv1", bp + ".bn1", cin, cout, 3, stride);
-      rb.c2 = make_resconv(h, bp + ".conv2", bp + ".bn2", cout, cout, 3, 1);
       rb.has_sc = (stride != 1 || cin != cout);
-      if (rb.has_sc) rb.sc = make_resconv(h, bp + ".shortcut.0", bp + ".shortcut.1", cin, cout, 1, stride);
+      if (rb.has_sc && h->fuse_shortcut) {
+        rb.c2 = make_resconv_shortcut(h, bp + ".conv2", bp + ".bn2", bp + ".shortcut.0", bp + ".shortcut.1", cin, cout);
+      } else {
+        rb.c2 = make_resconv(h, bp + ".conv2", bp + ".bn2", cout, cout, 3, 1);
+        if (rb.has_sc) rb.sc = make_resconv(h, bp + ".shortcut.0", bp + ".shortcut.1", cin, cout, 1, stride);
+      }
       cin = cout;
     }
   }
@@ -1497,8 +1536,9 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
     const int64_t img = h->simg[s];
     const int64_t interior = ((int64_t)(Ws + 2) + 1) * Cc;
     const int M = Hs * Ws;
+    // x2 (rc.k2 > 0): the previous stage's image, whose centre pixels are the second A segment (the folded shortcut)
     auto conv3 = [&](const float* in, const ResConv& rc, float* out, const float* R, int act,
-                     int post_relu) {
+                     int post_relu, const float* x2 = nullptr) {
       if (prec_is_split(c.precision) && rc.cin == 32 && rc.cout == 32 && rc.l.W3 &&
           (act == DZN_ACT_NONE || act == DZN_ACT_RELU)) {
         // first ResNet stage: dedicated kernel, every input pixel split once instead of once per tap
@@ -1523,6 +1563,14 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
       d.c_amax = img_am(out);
       d.z_count = zc;
       d.z_list = zl;
+      if (rc.k2 > 0) {
+        d.A2 = x2 + ((int64_t)(h->sW[s - 1] + 2) + 1) * rc.k2;   // pixel (2y, 2x) = centre of conv1's stride-2 patch
+        d.a2_rowoff = h->tab2[s];
+        d.a2_z0 = h->simg[s - 1];
+        d.a2_amax = img_am(x2);
+        d.k1 = 9 * rc.cin;
+        d.k2 = rc.k2;
+      }
       if (c.precision == DZN_PREC_F16 && ((h->f16_keep2 >> 14) & 1)) d.precision = DZN_PREC_F32_H2;
       chk(launch_gemm(d, st), "resnet conv3x3");
     };
@@ -1550,6 +1598,12 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
         d.z_list = zl;
         if (c.precision == DZN_PREC_F16 && ((h->f16_keep2 >> 14) & 1)) d.precision = DZN_PREC_F32_H2;
         chk(launch_gemm(d, st), "resnet conv3x3 s2");
+        if (rb.c2.k2 > 0) {
+          // the 1x1 shortcut is k2 more K columns of conv2 (make_resconv_shortcut): no shortcut image, no residual read
+          conv3(midb, rb.c2, outb, nullptr, DZN_ACT_NONE, 1, prev);
+          cur = 1;
+          continue;
+        }
         dzn_gemm_desc e = gd(h, prev + ((int64_t)(Wp + 2) + 1) * Cpv, rb.sc.l,
                              scb + interior, M, 0, 0);
         e.a_rowoff = h->tab2[s];
@@ -1655,6 +1709,7 @@ int dzn_create(const dzn_config* cfg, dzn_handle** out) {
   if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
   h->emb_skip = getenv("DZN_EMB_NO_SKIP") == nullptr;
   h->fuse_resblock = getenv("DZN_NO_RESBLOCK_FUSION") == nullptr;
+  h->fuse_shortcut = getenv("DZN_NO_SHORTCUT_FUSION") == nullptr;
   if (const char* e = getenv("DZN_RESBLOCK_WS")) h->resblock_ws = atoi(e);
   if (const char* e = getenv("DZN_F16_KEEP2")) h->f16_keep2 = (unsigned)strtoul(e, nullptr, 0);
   if (const char* e = getenv("DZN_F16_MX")) h->f16_mx = (unsigned)strtoul(e, nullptr, 0);

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const dzn_gemm_desc d) {
     if (z0 >= d.z_count[0]) return;
     z0 = d.z_list[z0];
   }
-  const float* __restrict__ A = d.A + z0 * d.a_z0 + z1 * d.a_z1;
+  const float* A = d.A + z0 * d.a_z0 + z1 * d.a_z1;
   const float* __restrict__ W = d.W + z0 * d.w_z0 + z1 * d.w_z1;
   const int64_t cz = z0 * d.c_z0 + z1 * d.c_z1;
   const int64_t bz = z0 * d.b_z0 + z1 * d.b_z1;
@@ -280,11 +280,27 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const dzn_gemm_desc d) {
     n = n < d.N ? n : d.N - 1;
     wbase[i] = (int64_t)n * d.ldw + csw * 4;
   }
+  // second A segment (dzn_gemm_desc.A2): its row table of this tile's BM rows waits in LDS behind the two stages; the
+  // barrier after tile 0 publishes it (k1 >= 128: tile 0 is never past k1)
+  int* a2tab = reinterpret_cast<int*>(smem + 2 * BUF);
+  if (d.A2 && tid < BM) {
+    int m = tm * BM + tid;
+    m = m < d.M ? m : d.M - 1;
+    a2tab[tid] = d.a2_rowoff[m];
+  }
 
   auto issue = [&](int k0, int buf) {
     // k0 is a multiple of 32 and kc % 32 == 0: the whole K tile sits inside one kc chunk
     const int ch = k0 / d.kc;
-    const int64_t koff = (int64_t)ch * d.ldk + (k0 - ch * d.kc);
+    int64_t koff = (int64_t)ch * d.ldk + (k0 - ch * d.kc);
+    if (d.A2 && k0 >= d.k1) {   // tile-uniform: the K tiles from k1 on are one run of k2 columns of the second source
+      if (k0 == d.k1) {
+        A = d.A2 + z0 * d.a2_z0;
+#pragma unroll
+        for (int i = 0; i < ACH; ++i) abase[i] = (int64_t)a2tab[r0 + 32 * i] + csw * 4;
+      }
+      koff = k0 - d.k1;
+    }
     unsigned char* sA = smem + buf * BUF + wave * 1024;
     unsigned char* sW = smem + buf * BUF + BM * 128 + wave * 1024;
 #pragma unroll
@@ -336,7 +352,8 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const dzn_gemm_desc d) {
   // Software pipeline: every batch of LDS fragment reads is followed by the 4*MI*NI MFMAs of the
   // OTHER K block, so ds_read latency and the barrier never sit in front of an idle matrix pipe:
   //   [glds tile k+1] [read kb1(k)] [mma kb0(k)] [barrier: tile k+1 landed] [read kb0(k+1)] [mma kb1(k)]
-  const int nk = d.K / BK;
+  // two segments: the loop ends at k1 + k2 — the zero-padded weight columns behind it are neither fetched nor multiplied
+  const int nk = (d.A2 ? d.k1 + d.k2 : d.K) / BK;
   f32x4 a0[MI], b0[NI], a1[MI], b1[NI];
   issue(0, 0);
   __syncthreads();  // drains the LDS-DMA (vmcnt(0)) and publishes tile 0
@@ -361,7 +378,7 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const dzn_gemm_desc d) {
 template <int BM, int BN, int WGM, int WGN, bool LOWP>
 int launch_cfg(const dzn_gemm_desc& d, hipStream_t s) {
   const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
-  const size_t lds = 2 * (BM + BN) * 128;
+  const size_t lds = 2 * (BM + BN) * 128 + (d.A2 ? BM * 4 : 0);   // + the second segment's row table (LDS-DMA kernel)
   auto kern = gemm_kernel<BM, BN, WGM, WGN, LOWP>;
   static unsigned long long attr_mask = 0;  // one bit per HIP device: function attributes are per device
   if (first_use_on_device(attr_mask)) {
@@ -373,6 +390,7 @@ int launch_cfg(const dzn_gemm_desc& d, hipStream_t s) {
   }
   static const bool no_glds = getenv("DZN_NO_GLDS") != nullptr;
   const bool use_glds = !LOWP && !no_glds && (d.K % 32 == 0) && (d.kc % 32 == 0);
+  if (d.A2 && !use_glds) return DZN_E_INVALID;   // only the LDS-DMA kernel reads a second A segment
   dim3 grid(tilesM * tilesN, d.nz > 0 ? d.nz : 1, 1);
   int pid = -1;
   if (prof_enabled()) {
@@ -456,6 +474,13 @@ int launch_gemm(const dzn_gemm_desc& din, hipStream_t s) {
                     !(d.kc & 31) && d.ldw == d.K && !d.a_split3 && d.nz == 1 && !d.c_rowoff && d.kv_col0 >= 0 &&
                     d.kv_col0 < d.N && !(d.kv_col0 & 63) && !(d.N & 63) && d.kv_ld == d.N - d.kv_col0 &&
                     !(d.kv_plane_stride & 3) && d.N > 32 && !getenv("DZN_GEMM_CFG") && !getenv("DZN_NO_H2");
+    if (!ok) return DZN_E_INVALID;
+  }
+  if (d.A2) {
+    // second A segment: k1 a whole number of 64-column tiles (and past every prologue tile), k2 whole 32-column tiles, and the
+    // weight row = [k1 | k2 | zero pad up to the next multiple of 64)
+    const bool ok = d.a2_rowoff && d.k1 >= 128 && !(d.k1 & 63) && d.k2 > 0 && !(d.k2 & 31) && d.k1 + d.k2 <= d.K &&
+                    d.K - (d.k1 + d.k2) < 64 && !(d.K & 31) && !(d.kc & 31) && !d.a_split3 && !d.kv_planes && !(d.a2_z0 & 3);
     if (!ok) return DZN_E_INVALID;
   }
   if (d.a_split3) return prec_is_split(d.precision) ? launch_gemm_split_pre(d, s) : DZN_E_INVALID;

@@ -463,6 +463,7 @@ extern "C" int dzn_op_set_gemm_mx_cfg(const char* cfg) {
 // the reduced-precision contraction: caller (launch_gemm_split) has checked K % 32 == 0, kc % 32 == 0, ldw == K
 int launch_gemm_mx(const dzn_gemm_desc& d, hipStream_t s) {
   if (!d.Wmx || !d.col_scale_mx || !d.a_amax || d.w_z0 || d.w_z1) return DZN_E_INVALID;
+  if (d.A2) return DZN_E_INVALID;   // a second A segment is not read by this kernel: refuse rather than drop its columns
   const int cols128 = (d.N + 127) / 128 * 128;
   // 128 x 128 tiles unless the launch is narrow or too small to fill the chip with them.  gemm_split.hip's other rules — narrow
   // tiles for K <= 512 and for widths that 64-wide tiles pad less — do NOT carry over: measured at M = 223 839 (first GPU run of

@@ -57,6 +57,9 @@ __device__ __forceinline__ void wait_vm_lgkm0() {
   __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4));
 }
 
+// the second A segment's row table (BM x 4 bytes) rides in LDS unless it would push one of the OCC resident workgroups out
+constexpr bool a2_tab_in_lds(int stage_bytes, int BM, int OCC) { return (stage_bytes + BM * 4) * OCC <= 160 * 1024; }
+
 // BM x BN tile per workgroup of WGM x WGN wavefronts, S LDS stages of one 32-k tile each.
 //
 // Pipeline.  The matrix pipe retires a K tile in ~1.5k cycles per wavefront-tile while an LDS-DMA
@@ -83,6 +86,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
   constexpr int LPT = ACH + NP * WR;      // LDS-DMA instructions per thread per tile (NP fewer for the
                                           // wavefronts that sit out a partial last W round)
   constexpr bool WPART = BN % WROWS != 0;
+  constexpr bool A2_TAB_LDS = a2_tab_in_lds(S * BUF, BM, OCC);
   static_assert(BM * 128 % RB == 0, "A tile must be whole rounds");
   static_assert(MI % 2 == 0, "two row halves per wavefront tile");
   static_assert(S >= 2 && (S - 1) * LPT < 64, "vmcnt range");
@@ -127,7 +131,10 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
       m = m < d.M ? m : d.M - 1;
       const int unit = d.amax_unit > 0 ? m / d.amax_unit : z0;
       DZN_CHECK(d.amax_count <= 0 || (unit >= 0 && unit < d.amax_count), 0x101, unit);   // tracker index inside its array
-      h2_scale(d.a_amax[unit], a_scale[i], row_inv[i]);
+      // two sources (dzn_gemm_desc.A2): ONE scale for both segments, from the larger of the two bounds
+      float am = d.a_amax[unit];
+      if (d.A2) am = fmaxf(am, d.a2_amax[unit]);
+      h2_scale(am, a_scale[i], row_inv[i]);
     }
   }
   const int64_t cz = z0 * d.c_z0 + z1 * d.c_z1;
@@ -142,6 +149,16 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
     int m = tm * BM + r0 + 8 * NW * i;
     m = m < d.M ? m : d.M - 1;
     aptr[i] = A + (d.a_rowoff ? (int64_t)d.a_rowoff[m] : (int64_t)m * d.lda) + csw * 4;
+  }
+  // second A segment (dzn_gemm_desc.A2): the row table of this tile's BM rows waits in LDS behind the stages, so the K loop
+  // carries no second set of row pointers; the first barrier publishes it (k1 >= 128: no prologue tile is past k1).  Where
+  // those BM x 4 bytes would cost a resident workgroup (three bf16 planes of a 128 x 128 tile fill the LDS exactly) the rows
+  // are read from the table in memory at the switch instead.
+  int* a2tab = reinterpret_cast<int*>(smem + S * BUF);
+  if (A2_TAB_LDS && d.A2 && tid < BM) {
+    int m = tm * BM + tid;
+    m = m < d.M ? m : d.M - 1;
+    a2tab[tid] = d.a2_rowoff[m];
   }
   // W planes: thread -> (row = 16 wave + lane/4 + 16 NW i, physical slot lane%4); rows past N re-read
   // row N-1 (their accumulators are never stored); a partial last round is fetched by the first waves only
@@ -166,6 +183,22 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
     DZN_CHECK(stage >= 0 && stage < S && ik < d.K, 0x102, stage);                              // a stage of the ring, a k tile of the operand
     DZN_CHECK(wave * 1024 + (ACH - 1) * RB + 1024 <= ABYTES, 0x103, wave);                      // A fill stays inside the A image
     DZN_CHECK(!wfull || wave * 1024 + (WR - 1) * RB + 1024 <= WPLANE, 0x104, wave);                  // W fill stays inside its plane image
+    if (d.A2 && ik == d.k1) {   // tile-uniform, once per workgroup: from this K tile on the rows come from the second source
+      const float* A2 = d.A2 + z0 * d.a2_z0;
+#pragma unroll
+      for (int i = 0; i < ACH; ++i) {
+        int off;
+        if constexpr (A2_TAB_LDS) {
+          off = a2tab[r0 + 8 * NW * i];
+        } else {
+          int m = tm * BM + r0 + 8 * NW * i;
+          off = d.a2_rowoff[m < d.M ? m : d.M - 1];
+        }
+        aptr[i] = A2 + off + csw * 4;
+      }
+      ikoff = 0;
+      irem = -(1 << 30);        // one run of k2 columns: the two-level wrap never fires again
+    }
 #pragma unroll
     for (int i = 0; i < ACH; ++i)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(aptr[i] + ikoff),
@@ -259,7 +292,8 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
     }
   };
 
-  const int nk = d.K / BK;
+  // two segments: the loop ends at k1 + k2 — the zero-padded weight columns behind it are neither fetched nor multiplied
+  const int nk = (d.A2 ? d.k1 + d.k2 : d.K) / BK;
 #pragma unroll
   for (int s = 0; s < S; ++s)
     if (s < nk) issue(s);
@@ -323,7 +357,8 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
 template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1>
 int launch_split_cfg(const dzn_gemm_desc& d, hipStream_t s) {
   const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
-  const size_t lds = (size_t)S * (BM * 128 + NP * BN * 64);
+  size_t lds = (size_t)S * (BM * 128 + NP * BN * 64);
+  if (d.A2 && a2_tab_in_lds((int)lds, BM, OCC)) lds += BM * 4;   // + the second segment's row table
   auto kern = gemm_split_kernel<BM, BN, WGM, WGN, S, NP, OCC>;
   static unsigned long long attr_mask = 0;  // one bit per HIP device: function attributes are per device
   if (first_use_on_device(attr_mask)) {
@@ -470,6 +505,7 @@ __global__ __launch_bounds__(256) void split_weights_h2_kernel(const float* __re
 
 int launch_gemm_split(const dzn_gemm_desc& d, hipStream_t s) {
   if ((d.K & 31) || (d.kc & 31) || d.ldw != d.K) return DZN_E_INVALID;
+  if (d.A2 && prec_is_h2(d.precision) && d.a_amax && !d.a2_amax) return DZN_E_INVALID;   // one scale from BOTH bounds
   // fp16 two-term path: needs the fp16 planes + their row scales, the producer-tracked |max| of A, and weights
   // that do not move with z (col_scale is indexed by the output column alone)
   static const bool no_h2 = getenv("DZN_NO_H2") != nullptr;

@@ -352,6 +352,7 @@ int launch_gemm_split_pre_np(const dzn_gemm_desc& d, hipStream_t s) {
 
 int launch_gemm_split_pre(const dzn_gemm_desc& d, hipStream_t s) {
   if ((d.K & 31) || (d.kc & 31) || d.ldw != d.K || !d.a_split3 || d.a_plane <= 0) return DZN_E_INVALID;
+  if (d.A2) return DZN_E_INVALID;   // a second A segment is not read by this kernel: refuse rather than drop its columns
   if (d.a_split3 == 2) {   // two fp16 planes
     if (!d.W2h || !d.col_scale || !d.a_amax || d.w_z0 * 1 != d.w_z0) return DZN_E_INVALID;
     return d.precision == DZN_PREC_F16 ? launch_gemm_split_pre_np<1>(d, s) : launch_gemm_split_pre_np<2>(d, s);

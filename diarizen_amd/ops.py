@@ -26,8 +26,9 @@ def gemm(A, W, *, M=None, N=None, K=None, bias=None, R=None, C_out=None, WS=None
          ldws=0, act=0, alpha=1.0, post_relu=False, nz=1, zdiv=1, zs=None, precision=0,
          W16=None, W3=None, a_planes=None, ln_stats=None, ln_colsum=None, W2h=None, col_scale=None,
          a_amax=None, c_amax=None, amax_unit=None, want_row_stats=False, stat_eps=1e-5, mx=False, Wmx=None,
-         col_scale_mx=None, kv_col0=None):
-    """C = epilogue(A @ W^T); see dzn_gemm_desc.  kv_col0 (r6): columns >= kv_col0 leave as fp16 two-term planes with per-(row,
+         col_scale_mx=None, kv_col0=None, A2=None, a2_rowoff=None, a2_z0=0, k1=0, k2=0, a2_amax=None):
+    """C = epilogue(A @ W^T); see dzn_gemm_desc.  A2 / a2_rowoff / a2_z0 / k1 / k2 / a2_amax: the second A segment (K columns
+    k1 .. k1 + k2 read A2[z * a2_z0 + a2_rowoff[m] + k - k1]; a2_amax = its per-unit |max|, computed here when omitted).  kv_col0 (r6): columns >= kv_col0 leave as fp16 two-term planes with per-(row,
     64-column slot) scales instead of fp32 (dzn_gemm_desc.kv_planes) -> returns (C, planes int16 [2, M, N - kv_col0], inv f32
     [M, (N - kv_col0) / 64]).  A: [M, K] (or raw buffer with lda / rowoff),
     W: [N, K] fp32 (and optionally W16 bf16)."""
@@ -78,6 +79,12 @@ def gemm(A, W, *, M=None, N=None, K=None, bias=None, R=None, C_out=None, WS=None
         Wmx, col_scale_mx = split_weights_mx(W.reshape(-1, K))
     d.W2h, d.col_scale, d.a_amax, d.c_amax = _p(W2h), _p(col_scale), _p(a_amax), _p(c_amax)
     d.Wmx, d.col_scale_mx = _p(Wmx), _p(col_scale_mx)
+    if A2 is not None:
+        assert A2.is_cuda and A2.dtype == torch.float32
+        if a2_amax is None and a_amax is not None:
+            a2_amax = amax(A2.contiguous().reshape(-1)).repeat(max(1, nz // max(zdiv, 1)))
+        d.A2, d.a2_rowoff, d.a2_amax = _p(A2), _p(a2_rowoff), _p(a2_amax)
+        d.a2_z0, d.k1, d.k2 = a2_z0, k1, k2
     # one scale unit for the whole tensor unless told otherwise (engines use one unit per window)
     d.amax_unit = int(amax_unit) if amax_unit is not None else (max(M, 1) if nz == 1 else 0)
     stats = None

@@ -125,6 +125,20 @@ typedef struct dzn_gemm_desc {
   float* kv_scale;
   int32_t kv_ld;
   int32_t kv_col0;
+  /* A SECOND A segment (the 1x1 stride-2 shortcut of a ResNet down-sampling block folded into conv2: one sum over a longer K,
+   * no shortcut image in memory).  K columns k < k1 address A as above; columns k1 <= k < k1 + k2 read
+   *   A2[ z0 * a2_z0 + a2_rowoff[m] + (k - k1) ]
+   * and the columns from k1 + k2 up to K (the zero-padded weight columns of the last tile) are NEVER read or multiplied, so a
+   * non-finite neighbour of the k2 run cannot reach the sum.  a2_amax = the per-unit |max| array of the second source, indexed
+   * like a_amax: the fp16 forms scale BOTH segments by the power of two of max(a_amax[u], a2_amax[u]).  NULL A2 = one segment.
+   * Requirements (DZN_E_INVALID otherwise): k1 % 64 == 0, k1 >= 128, k2 % 32 == 0, k1 + k2 <= K < k1 + k2 + 64, a2_rowoff set,
+   * a2_amax set where a_amax is used; taken by the fp32 LDS-DMA kernel (csrc/gemm.hip) and by csrc/gemm_split.hip — the MX
+   * (csrc/gemm_mx.hip) and pre-split (a_split3) forms refuse it. */
+  const float* A2;
+  const int32_t* a2_rowoff;
+  const float* a2_amax;
+  int64_t a2_z0;
+  int32_t k1, k2;
 } dzn_gemm_desc;
 
 /* (r4) One BasicBlock of the 32-channel ResNet stage in one kernel (csrc/resblock_fused.hip):
