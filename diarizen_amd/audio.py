@@ -7,11 +7,17 @@ directly with numpy, and the resampler restates torchaudio's default algorithm
 (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99; torchaudio==2.1.1 functional/functional.py
 `_get_sinc_resample_kernel` / `_apply_sinc_resample_kernel`).  Parity of the resampler is UNPINNED
 (no torchaudio here, no fixture in the reference); tests pin its properties instead.
+
+The resampler exists twice over ONE filter bank (`resample_bank`): `resample`, a strided convolution on the host (the default
+everywhere), and `resample_device` (csrc/resample.hip, `dzn_resample`), which turns a span of input samples — float32, or the
+int16 interleaved frames of a PCM16 file as stored (`WavSource.read_raw`) — into a range of output samples on the GPU, with
+the bits of the same slice of a whole-recording call (`resample_input_span` says which input a range reads).
+`ResampledSource` wraps a file at another rate on top of it; `pipeline.open_recording(resample="device")` returns one.
 """
 from __future__ import annotations
 
 import io
-from typing import BinaryIO, Tuple, Union
+from typing import BinaryIO, Optional, Tuple, Union
 
 import numpy as np
 
@@ -94,7 +100,8 @@ class WavSource:
     """Lazy reader of ONE channel of a RIFF/WAVE file: parses the header, then decodes only the byte range a caller
     asks for — with N ranks sharding one recording (pipeline.device_stage) every rank reads 1/N of the file (+ one
     window of halo) instead of decoding all of it.  Same formats and the same float conversion as
-    load_wav(); `needs_resampling` sources fall back to the full decode (the polyphase resampler needs context)."""
+    load_wav(); a source at another rate is decoded whole and resampled on the host unless the caller asks for the device
+    resampler (ResampledSource, which reads only the input span of a range)."""
 
     def __init__(self, path, channel: int = 0):
         self.path = str(path)
@@ -140,6 +147,17 @@ class WavSource:
         self._frame = self._width * self.channels
         self.num_samples = self._data_len // self._frame
 
+    def read_raw(self, start: int, n: int):
+        """int16 [m, channels] = the interleaved frames start .. start + n of a PCM16 file as stored, not converted
+        (m < n at the end of the file); None for every other format, which goes through `read`"""
+        if (self._tag, self._width) != (1, 2):
+            return None
+        start = max(0, min(int(start), self.num_samples))
+        n = max(0, min(int(n), self.num_samples - start))
+        with open(self.path, "rb") as f:
+            f.seek(self._data_off + start * self._frame)
+            return np.fromfile(f, dtype="<i2", count=n * self.channels).reshape(-1, self.channels)
+
     def read(self, start: int, n: int) -> np.ndarray:
         """float32 [m] = samples start .. start + n of the channel (m < n at the end of the file)"""
         start = max(0, min(int(start), self.num_samples))
@@ -163,16 +181,13 @@ class WavSource:
         return np.ascontiguousarray(np.frombuffer(body, dtype=dt).reshape(-1, nch)[:, c].astype(np.float32))
 
 
-def resample(x: np.ndarray, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
-             rolloff: float = 0.99) -> np.ndarray:
-    """float32 [..., T] -> [..., ceil(T * new / orig)]: band-limited sinc interpolation with a Hann
-    window, evaluated as one strided convolution with `new/gcd` polyphase filters (torchaudio's default
-    `functional.resample`).  The filter bank is built in float64 and applied in float32, like torchaudio."""
+def resample_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """-> (kernels float32 [n, K], o, n, width): the polyphase filter bank of `resample` (torchaudio's
+    `_get_sinc_resample_kernel`), o = orig / gcd, n = new / gcd, K = 2 width + o; built in float64, cast to float32.
+    Output sample m = f n + p is  sum_j kernels[p, j] x[f o + j - width]  (x = 0 outside the recording)."""
     import math
     import torch
     orig_freq, new_freq = int(orig_freq), int(new_freq)
-    if orig_freq == new_freq:
-        return np.ascontiguousarray(x, dtype=np.float32)
     g = math.gcd(orig_freq, new_freq)
     o, n = orig_freq // g, new_freq // g
     base = min(o, n) * rolloff
@@ -183,7 +198,30 @@ def resample(x: np.ndarray, orig_freq: int, new_freq: int, lowpass_filter_width:
     window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
     t = t * math.pi
     kernels = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * window * (base / o)
-    kernels = kernels.to(torch.float32)                                  # [n, 1, 2 width + o]
+    return kernels.to(torch.float32)[:, 0].numpy(), o, n, width             # [n, 2 width + o]
+
+
+def resample_input_span(m0: int, m1: int, o: int, n: int, width: int):
+    """-> (lo, hi): the half-open range of input indices that the output samples [m0, m1) read (see resample_bank); it may
+    extend below 0 or beyond the recording, where the input counts as zero.  An empty output range reads nothing."""
+    m0, m1 = int(m0), int(m1)
+    if m1 <= m0:
+        return 0, 0
+    return (m0 // n) * o - width, ((m1 - 1) // n) * o + width + o
+
+
+def resample(x: np.ndarray, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
+             rolloff: float = 0.99) -> np.ndarray:
+    """float32 [..., T] -> [..., ceil(T * new / orig)]: band-limited sinc interpolation with a Hann
+    window, evaluated as one strided convolution with `new/gcd` polyphase filters (torchaudio's default
+    `functional.resample`).  The filter bank is built in float64 and applied in float32, like torchaudio."""
+    import math
+    import torch
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq == new_freq:
+        return np.ascontiguousarray(x, dtype=np.float32)
+    bank, o, n, width = resample_bank(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    kernels = torch.from_numpy(bank)[:, None]                            # [n, 1, 2 width + o]
     w = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
     shape = w.shape
     w = w.reshape(-1, shape[-1])
@@ -193,6 +231,118 @@ def resample(x: np.ndarray, orig_freq: int, new_freq: int, lowpass_filter_width:
     y = y.transpose(1, 2).reshape(w.shape[0], -1)
     target = math.ceil(n * length / o)
     return y[..., :target].reshape(shape[:-1] + (target,)).numpy()
+
+
+def resampled_length(num_samples: int, o: int, n: int) -> int:
+    """ceil(n T / o): the output length of `resample` for T input samples"""
+    return -((-n * int(num_samples)) // o)
+
+
+_DEVICE_BANKS: dict = {}
+
+
+def _device_bank(orig_freq: int, new_freq: int, device):
+    """the filter bank on `device`, tap-major ([K, n]: what dzn_resample reads), uploaded once per (orig, new, device)"""
+    import torch
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(orig_freq), int(new_freq), str(device))
+    hit = _DEVICE_BANKS.get(key)
+    if hit is None:
+        bank, o, n, width = resample_bank(orig_freq, new_freq)
+        hit = (torch.from_numpy(np.ascontiguousarray(bank.T)).to(device), o, n, width)
+        _DEVICE_BANKS[key] = hit
+    return hit
+
+
+def resample_tile() -> int:
+    """output samples per workgroup of the device resampler (csrc/resample.hip)"""
+    from . import _lib
+    return int(_lib.load().dzn_resample_tile())
+
+
+def resample_device(x, orig_freq: int, new_freq: int, *, device, out_range=None, total=None, first_index: int = 0,
+                    channels: int = 1, channel: int = 0):
+    """`resample` on the device (csrc/resample.hip, one launch on the current stream) -> float32 device tensor [m1 - m0].
+    x: a host array or a device tensor, float32 mono, or int16 frames interleaved over `channels` (flat or
+    [frames, channels]; sample * 2^-15 of `channel` is what load_wav makes of it).  x holds the input samples
+    first_index .. first_index + frames of a recording of `total` samples (default: x is the whole recording);
+    out_range = (m0, m1) selects the output samples (default: all ceil(n total / o)); x must cover
+    resample_input_span(m0, m1, ...) inside [0, total) (the library refuses otherwise).  A range call returns the bits of the
+    same slice of a whole-recording call.  The result differs from the host `resample` in the last bits (another order of
+    the same float32 sums)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    device = torch.device(device)
+    if isinstance(x, torch.Tensor):
+        xd = x.to(device)
+    else:
+        x = np.ascontiguousarray(x)
+        xd = torch.from_numpy(x if x.flags.writeable else x.copy()).to(device)      # (torch refuses read-only arrays)
+    if xd.dtype == torch.int16:
+        fmt = 1
+    elif xd.dtype == torch.float32:
+        fmt = 0
+        if channels != 1:
+            raise ValueError("resample_device: float32 input is mono (select the channel on the host)")
+    else:
+        raise ValueError(f"resample_device: float32 or int16 input, not {xd.dtype}")
+    xd = xd.contiguous().reshape(-1)
+    if xd.numel() % max(1, int(channels)):
+        raise ValueError("resample_device: the input is not a whole number of frames")
+    frames = xd.numel() // max(1, int(channels))
+    total = frames + int(first_index) if total is None else int(total)
+    bank, o, n, width = _device_bank(orig_freq, new_freq, device)
+    m0, m1 = (0, resampled_length(total, o, n)) if out_range is None else (int(out_range[0]), int(out_range[1]))
+    out = torch.empty(max(0, m1 - m0), device=device, dtype=torch.float32)
+    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    dev = device.index if device.index is not None else -1
+    _lib.check(_lib.load().dzn_resample(dev, C.c_void_p(xd.data_ptr()), fmt, int(channels), int(channel), int(first_index),
+                                        frames, total, C.c_void_p(bank.data_ptr()), o, n, width, m0, m1,
+                                        C.c_void_p(out.data_ptr()), st), None, "dzn_resample")
+    return out
+
+
+class ResampledSource:
+    """A recording at another rate, resampled on the device range by range: wraps a WavSource (PCM16 files are uploaded as
+    their raw interleaved frames, the kernel selects the channel and converts) or a decoded one-channel float32 array
+    (`orig_rate` says its rate).  `.sample_rate` is the new rate, `.num_samples` = ceil(n T / o) as `resample` gives, and
+    `.read_device(start, n)` reads only resample_input_span of the range, uploads it and resamples it: the bits of the same
+    slice of read_device(0, num_samples), so every rank of a sharded run touches only the span of its windows."""
+
+    def __init__(self, src, new_rate: int, device, orig_rate: Optional[int] = None):
+        self.src, self.device = src, "cuda" if device is None else device      # None: the current HIP device
+        self._array = not isinstance(src, WavSource)
+        if self._array:
+            if orig_rate is None:
+                raise ValueError("ResampledSource: a decoded array needs orig_rate")
+            self.src = np.ascontiguousarray(src, dtype=np.float32).reshape(-1)
+            self.orig_rate, self._total = int(orig_rate), len(self.src)
+        else:
+            self.orig_rate, self._total = int(src.sample_rate), int(src.num_samples)
+        self.sample_rate = int(new_rate)
+        if self.orig_rate == self.sample_rate:
+            raise ValueError("ResampledSource: the source is already at the requested rate")
+        _, self._o, self._n, self._width = resample_bank(self.orig_rate, self.sample_rate)
+        self.num_samples = resampled_length(self._total, self._o, self._n)
+
+    def read_device(self, start: int, n: int):
+        """float32 device tensor [m] = output samples start .. start + n (m < n at the end of the recording)"""
+        m0 = max(0, min(int(start), self.num_samples))
+        m1 = max(m0, min(m0 + int(n), self.num_samples))
+        lo, hi = resample_input_span(m0, m1, self._o, self._n, self._width)
+        lo, hi = max(lo, 0), max(min(hi, self._total), 0)
+        hi = max(hi, lo)
+        kw = dict(device=self.device, out_range=(m0, m1), total=self._total, first_index=lo)
+        if self._array:
+            return resample_device(self.src[lo:hi], self.orig_rate, self.sample_rate, **kw)
+        raw = self.src.read_raw(lo, hi - lo)
+        if raw is not None:
+            return resample_device(raw, self.orig_rate, self.sample_rate, channels=self.src.channels,
+                                   channel=self.src._channel, **kw)
+        return resample_device(self.src.read(lo, hi - lo), self.orig_rate, self.sample_rate, **kw)
 
 
 def _read_all(src) -> bytes:

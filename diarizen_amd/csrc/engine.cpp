@@ -1887,6 +1887,40 @@ int dzn_destroy(dzn_handle* h) {
   return DZN_OK;
 }
 
+int dzn_resample(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int32_t channel,
+                 int64_t src_first_index, int64_t src_len, int64_t total_len, const float* d_bank, int32_t o, int32_t n,
+                 int32_t width, int64_t m0, int64_t m1, float* d_dst, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_resample: " + why;
+    return DZN_E_INVALID;
+  };
+  if (o < 1 || n < 1 || width < 0 || total_len < 0 || src_len < 0 || m0 < 0 || m1 < m0 || !d_bank)
+    return refuse("bad o / n / width / lengths / range");
+  if ((src_format != 0 && src_format != 1) || channels < 1 || (src_format == 0 && channels != 1))
+    return refuse("src_format is 0 (float32 mono) or 1 (int16 interleaved over channels >= 1)");
+  if (channel < 0 || channel >= channels)
+    return refuse("channel " + std::to_string(channel) + " of a source with " + std::to_string(channels) + " channel(s)");
+  if (total_len > INT64_MAX / n) return refuse("total_len * n overflows");
+  const int64_t out_len = (total_len * n + o - 1) / o;
+  if (m1 > out_len)
+    return refuse("m1 = " + std::to_string(m1) + " is beyond the output length " + std::to_string(out_len));
+  if (m1 == m0) return DZN_OK;
+  if (!resample_lds_bytes(o, n, width))
+    return refuse("o / n = " + std::to_string(o) + " / " + std::to_string(n) + ": the input of one tile does not fit in LDS");
+  // what [m0, m1) reads inside the recording
+  int64_t lo = (m0 / n) * o - width, hi = ((m1 - 1) / n) * o + width + o;
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > total_len ? total_len : hi;
+  if (lo < hi && (src_first_index > lo || src_first_index + src_len < hi))
+    return refuse("the span given, [" + std::to_string(src_first_index) + ", " + std::to_string(src_first_index + src_len) +
+                  "), does not cover the input [" + std::to_string(lo) + ", " + std::to_string(hi) + ") that the range reads");
+  if (!d_dst || (lo < hi && !d_src)) return refuse("null pointer");
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  return launch_resample(d_src, src_format, channels, channel, src_first_index, src_len, total_len, d_bank, o, n, width, m0,
+                         m1, d_dst, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
 const char* dzn_version(void) {
 #ifdef DZN_CHECKED
   return "dzn-hip 0.3.0 (gfx950, MFMA f32 / fp16x2 / bf16x3 / fp16 + MX fp8) [checked build: device-side bounds assertions]";
@@ -1909,6 +1943,7 @@ int dzn_checked_collect_attention_split(unsigned int*, int);
 int dzn_checked_collect_attention_planes(unsigned int*, int);
 int dzn_checked_collect_frontend_fused(unsigned int*, int);
 int dzn_checked_collect_post(unsigned int*, int);
+int dzn_checked_collect_resample(unsigned int*, int);
 }
 #endif
 int dzn_checked_status(uint32_t* out4, int32_t reset) {
@@ -1917,7 +1952,8 @@ int dzn_checked_status(uint32_t* out4, int32_t reset) {
   const collect_fn fns[] = {dzn_checked_collect_gemm_split, dzn_checked_collect_gemm_mx, dzn_checked_collect_gemm_split_pre,
                             dzn_checked_collect_resblock_fused, dzn_checked_collect_resblock_ws,
                             dzn_checked_collect_attention_split, dzn_checked_collect_attention_planes,
-                            dzn_checked_collect_frontend_fused, dzn_checked_collect_post};
+                            dzn_checked_collect_frontend_fused, dzn_checked_collect_post,
+                            dzn_checked_collect_resample};
   unsigned int tot[4] = {0u, 0u, 0u, 0u};
   for (collect_fn f : fns) {
     unsigned int w[4] = {0u, 0u, 0u, 0u};

@@ -44,14 +44,20 @@ class _Detection:
     LABEL = ""
 
     def __init__(self, segmentation, *, rttm_out_dir: Optional[str] = None, device: Optional[torch.device] = None,
-                 precision: str = "f32h", batch_size: Optional[int] = None):
+                 precision: str = "f32h", batch_size: Optional[int] = None, resample: Optional[str] = None):
         """segmentation: a DiariZen hub directory (config.toml + pytorch_model.bin; a segmentation-only engine is created,
         without the ResNet34 embedding model) or a `DiariZenPipeline`, whose engine handle(s) are reused (no second copy of
         the weights; its device and precision apply).  batch_size: windows per launch (default: the hub's
-        [inference.args] batch_size, capped by the engine's max_batch)."""
+        [inference.args] batch_size, capped by the engine's max_batch).  resample: "host" | "device", where a recording at
+        another rate is resampled (pipeline.open_recording; default: the DiariZenPipeline's setting, else "host")."""
         from .pipeline import DiariZenPipeline, _load_checkpoint, load_hub_config
         extra = ()
         self._owned: Optional[Engine] = None
+        if resample is None:
+            resample = segmentation.resample if isinstance(segmentation, DiariZenPipeline) else "host"
+        if resample not in ("host", "device"):
+            raise ValueError(f'resample is "host" or "device", not {resample!r}')
+        self.resample = resample
         if isinstance(segmentation, DiariZenPipeline):
             pipe = segmentation
             self.device = pipe.device
@@ -131,7 +137,7 @@ class _Detection:
         aggregated scores as a SlidingWindowFeature [T, 1] (PA/pipelines/voice_activity_detection.py:188-214).
         -> Annotation of the regions, labelled "SPEECH" / "OVERLAP", uri = file["uri"] or the path's stem."""
         from . import dist as dz_dist
-        from .pipeline import open_recording
+        from .pipeline import open_recording, recording_on_device
         if dz_dist.world_size() > 1:
             raise RuntimeError(f"{type(self).__name__} runs on one device: sharding a recording over torch.distributed ranks "
                                f"is not supported (world size {dz_dist.world_size()})")
@@ -142,10 +148,10 @@ class _Detection:
             uri = Path(audio).stem
         want_scores = hook is not None
         hook = functools.partial(hook or _noop, file=file)            # Pipeline.setup_hook (PA/core/pipeline.py:267-271)
-        x = np.ascontiguousarray(open_recording(audio, self.sample_rate), dtype=np.float32)
-        n = len(x)
+        x = open_recording(audio, self.sample_rate, resample=self.resample, device=self.device)
+        n = int(x.num_samples) if hasattr(x, "num_samples") else len(x)
         with torch.cuda.device(self.device):
-            wave = torch.from_numpy(x).to(self.device)
+            wave = recording_on_device(x, self.device)
             res = self._runner.run(wave, with_embeddings=False,
                                    hook=functools.partial(hook, "segmentation", None) if want_scores else None)
             chunks, frames = self.chunks_window(), receptive_field(self.sample_rate)

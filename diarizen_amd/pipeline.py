@@ -141,22 +141,59 @@ def resolve_hub(repo_id: str, cache_dir: Optional[str] = None) -> Path:
                                   local_files_only=cache_dir is not None)).expanduser().absolute()
 
 
-def open_recording(in_wav, sample_rate: int, lazy: bool = False):
+def open_recording(in_wav, sample_rate: int, lazy: bool = False, resample: str = "host", device=None):
     """what `DiariZenPipeline.__call__` accepts (path, BytesIO, bytes or a ProtocolFile mapping with "audio") -> first channel
     at `sample_rate`, float32.  lazy=True (sharded runs): a WAV file at that rate is opened as an audio.WavSource, so that
-    every rank decodes only the byte range of its windows (other files need the resampler's context and are decoded whole)."""
+    every rank decodes only the byte range of its windows (other files need the resampler's context and are decoded whole).
+    resample="device": a file at ANOTHER rate comes back as an audio.ResampledSource on `device` — nothing is resampled on the
+    host, `read_device(start, n)` reads, uploads and resamples (csrc/resample.hip) only the input span of the range, so the
+    ranks of a sharded run do that for their own windows only; a WAV file is not decoded here at all.  Files at `sample_rate`
+    are returned as with "host", which is the default: the device resampler differs from the host one in the last bits."""
+    if resample not in ("host", "device"):
+        raise ValueError(f'resample is "host" or "device", not {resample!r}')
     if isinstance(in_wav, Mapping):                    # pyannote ProtocolFile (a Mapping, not a dict)
         in_wav = in_wav["audio"]
     assert isinstance(in_wav, (str, os.PathLike, BytesIO, bytes)), \
         f"input must be either a str, BytesIO or a ProtocolFile; there was {type(in_wav)}"
-    if lazy and isinstance(in_wav, (str, os.PathLike)):
+    if (lazy or resample == "device") and isinstance(in_wav, (str, os.PathLike)):
         try:
             src = audio_io.WavSource(in_wav)
             if src.sample_rate == sample_rate:
-                return src
+                if lazy:
+                    return src
+            elif resample == "device":
+                return audio_io.ResampledSource(src, sample_rate, device)
         except ValueError:
             pass
+    if resample == "device":
+        x, sr = audio_io.load_audio(in_wav)
+        x0 = np.ascontiguousarray(x[0])                # channel 0, as first_channel_16k
+        return x0 if sr == sample_rate else audio_io.ResampledSource(x0, sample_rate, device, orig_rate=sr)
     return audio_io.first_channel_16k(in_wav, sample_rate)
+
+
+def recording_on_device(waveform, device, lo: int = 0, n: Optional[int] = None, zero_extend: bool = False) -> torch.Tensor:
+    """samples lo .. lo + n of what open_recording returned (a host array, a lazy source with `.read`, or a source with
+    `.read_device`, whose samples are made on the device) as a float32 tensor on `device`; zero_extend: padded with zeros to n
+    samples when the recording ends before lo + n (a rank's last window, inference.py:293-299)"""
+    if hasattr(waveform, "read_device"):
+        n = int(waveform.num_samples) - lo if n is None else n
+        wave = waveform.read_device(lo, n)
+        if zero_extend and len(wave) < n:
+            wave = torch.nn.functional.pad(wave, (0, n - len(wave)))
+        return wave
+    if hasattr(waveform, "read") and hasattr(waveform, "num_samples"):
+        n = int(waveform.num_samples) - lo if n is None else n
+        have = waveform.read(lo, n)
+    else:
+        n = len(waveform) - lo if n is None else n
+        have = np.asarray(waveform[lo:lo + n], dtype=np.float32)
+    if zero_extend:
+        x = np.zeros(n, dtype=np.float32)                      # zero-extended like the last window (inference.py:293-299)
+        x[:len(have)] = have
+    else:
+        x = np.ascontiguousarray(have, dtype=np.float32)
+    return torch.from_numpy(x).to(device)
 
 
 class DiariZenPipeline:
@@ -164,10 +201,13 @@ class DiariZenPipeline:
                  rttm_out_dir: Optional[str] = None, *, device: Optional[torch.device] = None,
                  precision: str = "f32h", seg_state: Optional[Mapping[str, torch.Tensor]] = None,
                  emb_state: Optional[Mapping[str, torch.Tensor]] = None,
-                 config: Optional[Dict[str, Any]] = None, num_streams: int = 2):
+                 config: Optional[Dict[str, Any]] = None, num_streams: int = 2, resample: str = "host"):
         """diarizen_hub: directory with config.toml / pytorch_model.bin / plda ; embedding_model: path of
         the WeSpeaker checkpoint.  `seg_state` / `emb_state` / `config` let callers (tests, bench)
         inject in-memory weights instead of files.
+        resample: where a recording at another rate than the model's is resampled — "host" (audio.resample, the default) or
+        "device" (audio.ResampledSource: the file's samples are uploaded as stored and resampled by csrc/resample.hip, in a
+        sharded run every rank only its windows' span; the waveform differs from the host one in its last bits).
         num_streams (r4): engine handles that consecutive batches of windows alternate over, each on its own HIP stream
         (inference.WindowRunner): independent batches overlap on the device — +2.6 % on the 30-min workload,
         +44 % at 32-window batches (profiles/r4_*), same bits.  Each extra handle costs one more copy of the weights and a
@@ -181,6 +221,9 @@ class DiariZenPipeline:
             config["inference"]["args"] = config_parse["inference"]["args"]
             config["clustering"]["args"] = config_parse["clustering"]["args"]
         self.config = config
+        if resample not in ("host", "device"):
+            raise ValueError(f'resample is "host" or "device", not {resample!r}')
+        self.resample = resample
         inf, clu = config["inference"]["args"], config["clustering"]["args"]
         if not torch.cuda.is_available():
             raise RuntimeError("DiariZenPipeline (diarizen_amd) needs a HIP device; no CPU fallback")
@@ -272,15 +315,15 @@ class DiariZenPipeline:
                              step=self.segmentation_step * self.seg_duration)
 
     def device_stage(self, waveform, hook=None, with_scores: bool = False):
-        """host float32 [N] (or a lazy source with `.num_samples` and `.read(start, n)`, e.g. audio.WavSource) ->
+        """host float32 [N] (or a lazy source with `.num_samples` and `.read(start, n)`, e.g. audio.WavSource, or
+        `.read_device(start, n)`, e.g. audio.ResampledSource: its samples are made on the device) ->
         (segmentations u8 [C, L, 4], embeddings f32 [C, 4, 256]) on the host.
         with_scores (one device only): a third element, the soft multilabel scores f32 [C, L, 4], which STAY on the device.
         With torch.distributed initialised, this rank reads / uploads ONLY the samples its contiguous window range touches
         (its slice + one window of halo), runs them, and the per-window results are all-gathered."""
         from . import dist as dz_dist
         r = self._runner
-        lazy = hasattr(waveform, "read") and hasattr(waveform, "num_samples")
-        total = int(waveform.num_samples) if lazy else len(waveform)
+        total = int(waveform.num_samples) if hasattr(waveform, "num_samples") else len(waveform)
         C = r.num_windows(total)
         rng = dz_dist.my_window_range(C)
         if with_scores and dz_dist.world_size() > 1:
@@ -291,14 +334,8 @@ class DiariZenPipeline:
             lo, n = c0 * r.step, ((c1 - c0 - 1) * r.step + r.window if c1 > c0 else 0)
         else:
             lo, n = 0, total
-        have = waveform.read(lo, n) if lazy else np.asarray(waveform[lo:lo + n], dtype=np.float32)
-        if rng is not None:
-            x = np.zeros(n, dtype=np.float32)                      # zero-extended like the last window (inference.py:293-299)
-            x[:len(have)] = have
-        else:
-            x = np.ascontiguousarray(have, dtype=np.float32)
-        if len(x):
-            wave = torch.from_numpy(x).to(self.device)
+        if n:
+            wave = recording_on_device(waveform, self.device, lo, n, zero_extend=rng is not None)
             res = r.run(wave, with_embeddings=True, hook=hook, with_scores=with_scores)
             seg_l, emb_l, soft_l = res.segmentations, res.embeddings, res.scores
         else:                                                      # more ranks than windows
@@ -343,13 +380,13 @@ class DiariZenPipeline:
         file = file if isinstance(file, Mapping) else {"audio": file}
         if hook is not None:
             hook = functools.partial(hook, "segmentation", None, file=file)
-        x = np.ascontiguousarray(open_recording(file["audio"], self.segmentation_model.sample_rate), dtype=np.float32)
+        x = open_recording(file["audio"], self.segmentation_model.sample_rate, resample=self.resample, device=self.device)
         # the raw decisions: a runner without the median filter on this pipeline's engine handle(s), as detection._Detection
         raw = WindowRunner(self.engine, self.seg_duration, self.segmentation_step, self.batch_size, median_size=0,
                            exclude_overlap=False, sample_rate=self.segmentation_model.sample_rate,
                            extra_engines=self.extra_engines)
         with torch.cuda.device(self.device):
-            res = raw.run(torch.from_numpy(x).to(self.device), with_embeddings=False, hook=hook, with_scores=soft)
+            res = raw.run(recording_on_device(x, self.device), with_embeddings=False, hook=hook, with_scores=soft)
             data = (res.scores if soft else res.segmentations).cpu().numpy().astype(np.float32, copy=False)
         return SlidingWindowFeature(data, self.chunks_window())
 
@@ -436,7 +473,8 @@ class DiariZenPipeline:
     def _open(self, in_wav):
         """decode (or, in a sharded run, lazily open) one recording: the first lines of `__call__`"""
         from . import dist as dz_dist
-        return open_recording(in_wav, self.segmentation_model.sample_rate, lazy=dz_dist.world_size() > 1)
+        return open_recording(in_wav, self.segmentation_model.sample_rate, lazy=dz_dist.world_size() > 1,
+                              resample=self.resample, device=self.device)
 
     # ------------------------------------------------------------------ __call__
     def __call__(self, in_wav, sess_name: Optional[str] = None, hook=None, return_scores: bool = False):

@@ -333,6 +333,26 @@ int dzn_flac_info(const uint8_t* data, size_t n, int32_t* sample_rate, int32_t* 
                   int64_t* total_samples, uint8_t* md5_16);
 int dzn_flac_decode(const uint8_t* data, size_t n, int32_t* out, int64_t capacity_samples, int64_t* decoded);
 
+/* Row f3, audio ingest: the polyphase sinc resampler on the device (csrc/resample.hip; stateless, no handle), i.e.
+ * torchaudio.functional.resample as Audio.downmix_and_resample applies it, PA/core/io.py:214-218 (sinc_interp_hann,
+ * lowpass_filter_width 6, rolloff 0.99; the host form is diarizen_amd/audio.py:resample).  With o = orig / gcd, n = new / gcd,
+ * K = 2 width + o, output sample m = f n + p of a recording of total_len = T input samples is
+ *     y[m] = sum_{j < K} bank[p][j] * x[f o + j - width],      x = 0 outside [0, T),      0 <= m < ceil(n T / o)
+ * in float32: one accumulator, acc = fmaf(bank[p][j], x[..], acc) for j = 0 .. K-1.  That order depends on m alone, so a call
+ * for a range of a recording returns the bits of the same slice of a call for all of it.  One launch, enqueue-only, on
+ * `hip_stream` of `device` (< 0 = current) writes d_dst f32 [m1 - m0] = y[m0 .. m1).
+ *   d_src            device samples src_first_index .. src_first_index + src_len of the recording:
+ *                    src_format 0: float32 mono (channels = 1); 1: int16 frames interleaved over `channels`, of which
+ *                    `channel` is read as sample * 2^-15 (exact: what audio.load_wav makes of a PCM16 file)
+ *   d_bank           device f32 [K][n], TAP-major: d_bank[j * n + p] = bank[p][j] (audio.resample_bank, transposed)
+ * Returns DZN_E_INVALID with a dzn_last_error(NULL) message, and launches nothing, when the span given does not cover what
+ * [m0, m1) reads inside [0, T), when channel >= channels, when m1 > ceil(n T / o), or when o / n is so large that the input
+ * of one tile does not fit in 64 KiB of LDS.  dzn_resample_tile: output samples per workgroup (tests place ranges on it). */
+int dzn_resample(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int32_t channel,
+                 int64_t src_first_index, int64_t src_len, int64_t total_len, const float* d_bank, int32_t o, int32_t n,
+                 int32_t width, int64_t m0, int64_t m1, float* d_dst, void* hip_stream);
+int32_t dzn_resample_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

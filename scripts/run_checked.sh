@@ -7,5 +7,7 @@ rm -f gpurun_out/checked_build_status.txt
 python -m pytest tests/test_ops_gpu.py tests/test_seg_gpu.py tests/test_emb_gpu.py -m gpu -q -x -k "not linkage and not vbx and not cdist and not clustering" 2>&1 | tail -15 > gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 # the per-speaker score kernels (post.hip, ids 0x81x): a session of its own, its status line joins the first one's below
 python -m pytest tests/test_scores_gpu.py -m gpu -q -x 2>&1 | tail -3
+# the device resampler (resample.hip, ids 0x82x): likewise
+python -m pytest tests/test_resample_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
