@@ -74,7 +74,7 @@ class DznConfig(C.Structure):
 
 class DznGemmDesc(C.Structure):
     _fields_ = [
-        ("A", C.c_void_p), ("W", C.c_void_p), ("W16", C.c_void_p), ("C", C.c_void_p),
+        ("A", C.c_void_p), ("W", C.c_void_p), ("C", C.c_void_p),
         ("bias", C.c_void_p), ("R", C.c_void_p), ("WS", C.c_void_p),
         ("a_rowoff", C.c_void_p), ("c_rowoff", C.c_void_p),
         ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),

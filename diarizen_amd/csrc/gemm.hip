@@ -10,52 +10,31 @@
 // of kaldi fbank, all 3x3 / 1x1 convs of ResNet34 (wespeaker/resnet.py:139-144) and seg_1.
 //
 // Design (CDNA4): 256 threads = 4 wavefronts of 64; each wavefront owns a TM x TN
-// sub-tile built from 16x16 MFMA blocks.  Two arithmetic modes share one structure,
-// because both read a 16-byte K-run per lane from a 128-byte LDS row:
-//   f32 : v_mfma_f32_16x16x4_f32   (exact fp32 == fmaf chain), 32 k per tile
-//   bf16: v_mfma_f32_16x16x32_bf16 (fp32 accumulate),           64 k per tile
+// sub-tile built from 16x16 MFMA blocks of v_mfma_f32_16x16x4_f32 (exact fp32 == fmaf chain),
+// 32 k per tile: a lane reads a 16-byte K-run from a 128-byte LDS row.
 // The K order inside a 16-float block is permuted (lane group q supplies k = 4q+s at
 // step s) identically for both operands, which lets every fragment be one ds_read_b128.
 // LDS rows are XOR-swizzled on the 16-B slot ((row>>1)&7) so that the four 16-lane
 // groups of ds_read_b128 hit 16 distinct slots (conflict free) and the ds_write_b128
-// of the staging pass stays conflict free too.  Global->register->LDS double buffering
-// with one barrier per K tile; workgroup ids are remapped so each XCD (private L2)
-// walks a contiguous run of tiles.
-#include <cstdio>
-#include <cstdlib>
-
+// of the staging pass stays conflict free too.  Two kernels: gemm_glds_kernel fills LDS by
+// LDS-DMA and runs wherever K % 32 == 0 and kc % 32 == 0; gemm_kernel (global->register->LDS
+// double buffering, one barrier per K tile) serves every other K and DZN_NO_GLDS.
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_launch.h"
 
 namespace {
 
-template <bool LOWP>
-struct Frag {
-  using type = f32x4;
-};
-template <>
-struct Frag<true> {
-  using type = bf16x8;
-};
-
-__device__ __forceinline__ uint4 pack_bf16x8(const float4& a, const float4& b) {
-  bf16x8 v;
-  v[0] = (__bf16)a.x; v[1] = (__bf16)a.y; v[2] = (__bf16)a.z; v[3] = (__bf16)a.w;
-  v[4] = (__bf16)b.x; v[5] = (__bf16)b.y; v[6] = (__bf16)b.z; v[7] = (__bf16)b.w;
-  return *reinterpret_cast<uint4*>(&v);
-}
-
-template <int BM, int BN, int WGM, int WGN, bool LOWP>
+template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(256) void gemm_kernel(const dzn_gemm_desc d) {
   static_assert(WGM * WGN == 4, "4 wavefronts per workgroup");
-  constexpr int BK = LOWP ? 64 : 32;   // k per tile; an LDS row is 128 B in both modes
-  constexpr int KV = LOWP ? 8 : 4;     // k per 16-B LDS chunk
+  constexpr int BK = 32;               // k per tile: an LDS row is 128 B
+  constexpr int KV = 4;                // k per 16-B LDS chunk
   constexpr int TM = BM / WGM, TN = BN / WGN;
   constexpr int MI = TM / 16, NI = TN / 16;
   constexpr int ACH = BM / 32;         // 16-B LDS chunks per thread, A tile
   constexpr int WCH = BN / 32;         // same, W tile
   constexpr int BUF = (BM + BN) * 128; // bytes per LDS stage
-  using frag_t = typename Frag<LOWP>::type;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -64,27 +43,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(const dzn_gemm_desc d) {
   const int wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
 
-  // ---- tile id, XCD-contiguous remap (bijective for any grid size) ----
-  const int tilesN = (d.N + BN - 1) / BN;
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int tm = t / tilesN, tn = t % tilesN;
-
-  const int z = blockIdx.y;
-  int z0 = z / d.zdiv;
-  const int z1 = z - z0 * d.zdiv;
-  if (d.z_list) {   // device-chosen subset of the batch (dzn_gemm_desc.z_count / z_list)
-    if (z0 >= d.z_count[0]) return;
-    z0 = d.z_list[z0];
-  }
+  int tm, tn, z0, z1;
+  if (!gemm_tile(d, (d.N + BN - 1) / BN, tm, tn, z0, z1)) return;
   const float* __restrict__ A = d.A + z0 * d.a_z0 + z1 * d.a_z1;
-  const int64_t wz = z0 * d.w_z0 + z1 * d.w_z1;
-  const float* __restrict__ W = d.W + (LOWP ? 0 : wz);
-  const u16* __restrict__ W16 = reinterpret_cast<const u16*>(d.W16) + (LOWP ? wz : 0);
+  const float* __restrict__ W = d.W + z0 * d.w_z0 + z1 * d.w_z1;
   const int64_t cz = z0 * d.c_z0 + z1 * d.c_z1;
   const int64_t bz = z0 * d.b_z0 + z1 * d.b_z1;
 
@@ -109,7 +71,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const dzn_gemm_desc d) {
     wbase[i] = (int64_t)(wval[i] ? n : 0) * d.ldw;
   }
 
-  float4 ra[ACH][LOWP ? 2 : 1];
+  float4 ra[ACH];
   uint4 rw[WCH];
 
   auto load_tile = [&](int k0) {
@@ -119,25 +81,13 @@ __global__ __launch_bounds__(256) void gemm_kernel(const dzn_gemm_desc d) {
     const int64_t koff = (int64_t)ch * d.ldk + (k - ch * d.kc);
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
-      if (aval[i] && kval) {
-        const float4* p = reinterpret_cast<const float4*>(A + abase[i] + koff);
-        ra[i][0] = p[0];
-        if constexpr (LOWP) ra[i][1] = p[1];
-      } else {
-        ra[i][0] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (LOWP) ra[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
+      if (aval[i] && kval) ra[i] = *reinterpret_cast<const float4*>(A + abase[i] + koff);
+      else ra[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int i = 0; i < WCH; ++i) {
-      if (wval[i] && kval) {
-        if constexpr (LOWP)
-          rw[i] = *reinterpret_cast<const uint4*>(W16 + wbase[i] + k);
-        else
-          rw[i] = *reinterpret_cast<const uint4*>(W + wbase[i] + k);
-      } else {
-        rw[i] = make_uint4(0u, 0u, 0u, 0u);
-      }
+      if (wval[i] && kval) rw[i] = *reinterpret_cast<const uint4*>(W + wbase[i] + k);
+      else rw[i] = make_uint4(0u, 0u, 0u, 0u);
     }
   };
 
@@ -148,10 +98,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const dzn_gemm_desc d) {
     for (int i = 0; i < ACH; ++i) {
       const int r = r0 + 32 * i;
       const int off = r * 128 + ((c ^ ((r >> 1) & 7)) << 4);
-      if constexpr (LOWP)
-        *reinterpret_cast<uint4*>(sA + off) = pack_bf16x8(ra[i][0], ra[i][1]);
-      else
-        *reinterpret_cast<float4*>(sA + off) = ra[i][0];
+      *reinterpret_cast<float4*>(sA + off) = ra[i];
     }
 #pragma unroll
     for (int i = 0; i < WCH; ++i) {
@@ -175,36 +122,28 @@ __global__ __launch_bounds__(256) void gemm_kernel(const dzn_gemm_desc d) {
     const unsigned char* sW = sA + BM * 128;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      frag_t af[MI], bf[NI];
+      f32x4 af[MI], bf[NI];
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
         const int row = wm * TM + i * 16 + lr;
         const int slot = (kb * 4 + lq) ^ ((row >> 1) & 7);
-        af[i] = *reinterpret_cast<const frag_t*>(sA + row * 128 + (slot << 4));
+        af[i] = *reinterpret_cast<const f32x4*>(sA + row * 128 + (slot << 4));
       }
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         const int row = wn * TN + j * 16 + lr;
         const int slot = (kb * 4 + lq) ^ ((row >> 1) & 7);
-        bf[j] = *reinterpret_cast<const frag_t*>(sW + row * 128 + (slot << 4));
+        bf[j] = *reinterpret_cast<const f32x4*>(sW + row * 128 + (slot << 4));
       }
       // operands swapped (W fragment as the MFMA "A"): the accumulator block is C^T, i.e. lane
       // (lr, lq) holds C[m = lr][n = 4*lq + 0..3] -> 4 consecutive columns per lane, float4 epilogue
-      if constexpr (LOWP) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
           for (int j = 0; j < NI; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af[i], acc[i][j], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[j][s], af[i][s], acc[i][j], 0, 0, 0);
-      }
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[j][s], af[i][s], acc[i][j], 0, 0, 0);
     }
   };
 
@@ -243,21 +182,8 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const dzn_gemm_desc d) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
-  const int tilesN = (d.N + BN - 1) / BN;
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int tm = t / tilesN, tn = t % tilesN;
-  const int z = blockIdx.y;
-  int z0 = z / d.zdiv;
-  const int z1 = z - z0 * d.zdiv;
-  if (d.z_list) {   // device-chosen subset of the batch (dzn_gemm_desc.z_count / z_list)
-    if (z0 >= d.z_count[0]) return;
-    z0 = d.z_list[z0];
-  }
+  int tm, tn, z0, z1;
+  if (!gemm_tile(d, (d.N + BN - 1) / BN, tm, tn, z0, z1)) return;
   const float* A = d.A + z0 * d.a_z0 + z1 * d.a_z1;
   const float* __restrict__ W = d.W + z0 * d.w_z0 + z1 * d.w_z1;
   const int64_t cz = z0 * d.c_z0 + z1 * d.c_z1;
@@ -375,65 +301,29 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const dzn_gemm_desc d) {
   gemm_epilogue<BM, BN, TM, TN, MI, NI>(d, acc, tm, tn, wm, wn, lr, lq, cz, bz, z0);
 }
 
-template <int BM, int BN, int WGM, int WGN, bool LOWP>
+template <int BM, int BN, int WGM, int WGN>
 int launch_cfg(const dzn_gemm_desc& d, hipStream_t s) {
-  const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
   const size_t lds = 2 * (BM + BN) * 128 + (d.A2 ? BM * 4 : 0);   // + the second segment's row table (LDS-DMA kernel)
-  auto kern = gemm_kernel<BM, BN, WGM, WGN, LOWP>;
-  static unsigned long long attr_mask = 0;  // one bit per HIP device: function attributes are per device
-  if (first_use_on_device(attr_mask)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if constexpr (!LOWP)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_glds_kernel<BM, BN, WGM, WGN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
   static const bool no_glds = getenv("DZN_NO_GLDS") != nullptr;
-  const bool use_glds = !LOWP && !no_glds && (d.K % 32 == 0) && (d.kc % 32 == 0);
+  const bool use_glds = !no_glds && (d.K % 32 == 0) && (d.kc % 32 == 0);
   if (d.A2 && !use_glds) return DZN_E_INVALID;   // only the LDS-DMA kernel reads a second A segment
-  dim3 grid(tilesM * tilesN, d.nz > 0 ? d.nz : 1, 1);
-  int pid = -1;
-  if (prof_enabled()) {
-    char cls[64];
-    static const bool by_shape = getenv("DZN_PROFILE_SHAPES") != nullptr;
-    if (by_shape)
-      snprintf(cls, sizeof(cls), "gemm_%s_%dx%d M%d N%d K%d z%d", LOWP ? "bf16" : "f32", BM, BN, d.M, d.N,
-               d.K, d.nz);
-    else
-      snprintf(cls, sizeof(cls), "gemm_%s_%dx%d", LOWP ? "bf16" : "f32", BM, BN);
-    const double fl = d.alg_flops > 0 ? d.alg_flops * d.nz : 2.0 * d.M * d.N * d.K * d.nz;
-    pid = prof_begin(s, cls, fl, gemm_alg_bytes(d, LOWP ? 2 : 4));
-  }
-  if constexpr (!LOWP) {
-    if (use_glds)
-      hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WGM, WGN>), grid, dim3(256), lds, s, d);
-    else
-      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, d);
-  } else {
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, d);
-  }
-  prof_end(pid, s);
-  if (hipGetLastError() != hipSuccess) return DZN_E_HIP;
-  if (d.stat_partial && d.stat_final)
-    return launch_stats_finalize(d.stat_partial, d.M, ((d.N + BN - 1) / BN) * WGN, d.stat_C, d.stat_eps, d.stat_final, s);
-  return DZN_OK;
+  if (use_glds) return launch_contraction<gemm_glds_kernel<BM, BN, WGM, WGN>>(d, s, 256, lds, BM, BN, WGN, "f32", 4);
+  return launch_contraction<gemm_kernel<BM, BN, WGM, WGN>>(d, s, 256, lds, BM, BN, WGN, "f32", 4);
 }
 
-template <bool LOWP>
-int launch_prec(const dzn_gemm_desc& d, hipStream_t s) {
-  static const char* force = getenv("DZN_GEMM_CFG");   // tuning knob: force one tile shape
-  if (force) {
-    if (!strcmp(force, "128x32")) return launch_cfg<128, 32, 4, 1, LOWP>(d, s);
-    if (!strcmp(force, "256x32")) return launch_cfg<256, 32, 4, 1, LOWP>(d, s);
-    if (!strcmp(force, "256x64")) return launch_cfg<256, 64, 4, 1, LOWP>(d, s);
-    if (!strcmp(force, "128x64")) return launch_cfg<128, 64, 2, 2, LOWP>(d, s);
-    if (!strcmp(force, "64x64")) return launch_cfg<64, 64, 2, 2, LOWP>(d, s);
-    if (!strcmp(force, "128x128")) return launch_cfg<128, 128, 2, 2, LOWP>(d, s);
+int launch_f32(const dzn_gemm_desc& d, hipStream_t s) {
+  if (const char* force = g_gemm_cfg.get()) {   // tuning knob: force one tile shape
+    if (!strcmp(force, "128x32")) return launch_cfg<128, 32, 4, 1>(d, s);
+    if (!strcmp(force, "256x32")) return launch_cfg<256, 32, 4, 1>(d, s);
+    if (!strcmp(force, "256x64")) return launch_cfg<256, 64, 4, 1>(d, s);
+    if (!strcmp(force, "128x64")) return launch_cfg<128, 64, 2, 2>(d, s);
+    if (!strcmp(force, "64x64")) return launch_cfg<64, 64, 2, 2>(d, s);
+    if (!strcmp(force, "128x128")) return launch_cfg<128, 128, 2, 2>(d, s);
   }
-  if (d.N <= 32) return launch_cfg<256, 32, 4, 1, LOWP>(d, s);
-  if (d.N <= 64) return launch_cfg<128, 64, 2, 2, LOWP>(d, s);
+  if (d.N <= 32) return launch_cfg<256, 32, 4, 1>(d, s);
+  if (d.N <= 64) return launch_cfg<128, 64, 2, 2>(d, s);
   // short contractions are epilogue-bound: narrower tiles -> 3 resident workgroups per CU hide it
-  if (d.K <= 512 && (d.N % 64) == 0) return launch_cfg<128, 64, 2, 2, LOWP>(d, s);
+  if (d.K <= 512 && (d.N % 64) == 0) return launch_cfg<128, 64, 2, 2>(d, s);
   // pick the column-tile width that wastes the fewest padded columns (irregular pruned widths:
   // 153 -> 160, q/k/v = 192 h, FFN 96..1770); ties go to the wider tile (more reuse per A fragment)
   const int cand[4] = {192, 160, 128, 96};
@@ -443,10 +333,10 @@ int launch_prec(const dzn_gemm_desc& d, hipStream_t s) {
     if (cols < best_cols) { best_cols = cols; best = c; }
   }
   switch (best) {
-    case 192: return launch_cfg<128, 192, 2, 2, LOWP>(d, s);
-    case 160: return launch_cfg<128, 160, 2, 2, LOWP>(d, s);
-    case 96: return launch_cfg<128, 96, 2, 2, LOWP>(d, s);
-    default: return launch_cfg<128, 128, 2, 2, LOWP>(d, s);
+    case 192: return launch_cfg<128, 192, 2, 2>(d, s);
+    case 160: return launch_cfg<128, 160, 2, 2>(d, s);
+    case 96: return launch_cfg<128, 96, 2, 2>(d, s);
+    default: return launch_cfg<128, 128, 2, 2>(d, s);
   }
 }
 
@@ -461,10 +351,7 @@ int launch_gemm(const dzn_gemm_desc& din, hipStream_t s) {
   if (d.zdiv <= 0) d.zdiv = 1;
   if (d.nz <= 0) d.nz = 1;
   if (d.alpha == 0.f) d.alpha = 1.f;
-  if (d.precision == DZN_PREC_BF16) {
-    if (!d.W16) return DZN_E_INVALID;
-    return launch_prec<true>(d, s);   // op-level leftover (dzn_op_gemm): bf16 weights, fp32 activations; no engine mode runs it
-  }
+  if (d.precision == DZN_PREC_BF16) return DZN_E_INVALID;   // reserved: no kernel computes it (dzn_create refuses it too)
   if (!d.W) return DZN_E_INVALID;
   if (d.kv_planes) {
     // (r6) K / V slots as pre-split planes: written by the epilogue of the 16x16-block split contractions only, whose automatic
@@ -473,7 +360,7 @@ int launch_gemm(const dzn_gemm_desc& din, hipStream_t s) {
     const bool ok = d.kv_scale && d.precision == DZN_PREC_F32_H2 && d.W3 && d.W2h && d.col_scale && d.a_amax && !(d.K & 31) &&
                     !(d.kc & 31) && d.ldw == d.K && !d.a_split3 && d.nz == 1 && !d.c_rowoff && d.kv_col0 >= 0 &&
                     d.kv_col0 < d.N && !(d.kv_col0 & 63) && !(d.N & 63) && d.kv_ld == d.N - d.kv_col0 &&
-                    !(d.kv_plane_stride & 3) && d.N > 32 && !getenv("DZN_GEMM_CFG") && !getenv("DZN_NO_H2");
+                    !(d.kv_plane_stride & 3) && d.N > 32 && !g_gemm_cfg.get() && !gemm_no_h2();
     if (!ok) return DZN_E_INVALID;
   }
   if (d.A2) {
@@ -486,7 +373,12 @@ int launch_gemm(const dzn_gemm_desc& din, hipStream_t s) {
   if (d.a_split3) return prec_is_split(d.precision) ? launch_gemm_split_pre(d, s) : DZN_E_INVALID;
   if (prec_is_split(d.precision) && d.W3 && !(d.K & 31) && !(d.kc & 31) && d.ldw == d.K)
     return launch_gemm_split(d, s);
-  return launch_prec<false>(d, s);
+  return launch_f32(d, s);
+}
+
+extern "C" int dzn_op_set_gemm_cfg(const char* cfg) {
+  g_gemm_cfg.set(cfg);
+  return DZN_OK;
 }
 
 extern "C" int dzn_op_gemm(const dzn_gemm_desc* d, void* stream) {

@@ -31,13 +31,12 @@
 // the scale semantics and the fp8 conversion on the device).
 // The 32 x 32 block shape is what makes the register budget: an fp8 operand register covers 32 rows (16x16x128 would need twice
 // the operand registers for the same wavefront tile: 128 for the 32 x 128 tile's weight side alone).
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "checked.h"
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_launch.h"
 #include "split.h"
 
 DZN_CHECKED_TU(gemm_mx)
@@ -119,20 +118,8 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_mx_kernel(const dzn_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WGN, wn = wave % WGN;
   const int tilesN = (d.N + BN - 1) / BN;
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;   // XCD-contiguous tile ranges
-  }
-  const int tm = t / tilesN, tn = t % tilesN;
-  const int z = blockIdx.y;
-  int z0 = z / d.zdiv;
-  const int z1 = z - z0 * d.zdiv;
-  if (d.z_list) {
-    if (z0 >= d.z_count[0]) return;
-    z0 = d.z_list[z0];
-  }
+  int tm, tn, z0, z1;
+  if (!gemm_tile(d, tilesN, tm, tn, z0, z1)) return;
   const float* __restrict__ A = d.A + z0 * d.a_z0 + z1 * d.a_z1;
   const u16* __restrict__ Wm = reinterpret_cast<const u16*>(d.Wmx);
   const int l31 = lane & 31, lh = lane >> 5;
@@ -238,7 +225,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_mx_kernel(const dzn_
   for (int i = 0; i < MI; ++i)
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) DZN_CHECK(aoff0[i][kh] + 16 <= ABYTES && aoff1[i][kh] + 16 <= ABYTES, 0x203, aoff1[i][kh]);
-  DZN_CHECK(tm * BM < d.M && tn * BN < d.N, 0x204, t);
+  DZN_CHECK(tm * BM < d.M && tn * BN < d.N, 0x204, tm * tilesN + tn);
   auto read_w16 = [&](int stage, u32x4 (&wf)[NJ][2]) {
     const unsigned char* base = smem + stage * BUF;
 #pragma unroll
@@ -388,28 +375,9 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_mx_kernel(const dzn_
 
 template <int BM, int BN, int WGM, int WGN, int S, int OCC>
 int launch_mx_cfg(const dzn_gemm_desc& d, hipStream_t s) {
-  const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
   const size_t lds = (size_t)S * (BM * 128 + 2 * BN * 64);
-  auto kern = gemm_mx_kernel<BM, BN, WGM, WGN, S, OCC>;
-  static unsigned long long attr_mask = 0;
-  if (first_use_on_device(attr_mask))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  dim3 grid(tilesM * tilesN, d.nz > 0 ? d.nz : 1, 1);
-  int pid = -1;
-  if (prof_enabled()) {
-    char cls[64];
-    static const bool by_shape = getenv("DZN_PROFILE_SHAPES") != nullptr;
-    if (by_shape) snprintf(cls, sizeof(cls), "gemm_mx_%dx%d M%d N%d K%d z%d", BM, BN, d.M, d.N, d.K, d.nz);
-    else snprintf(cls, sizeof(cls), "gemm_mx_%dx%d", BM, BN);
-    const double fl = d.alg_flops > 0 ? d.alg_flops * d.nz : 2.0 * d.M * d.N * d.K * d.nz;
-    pid = prof_begin(s, cls, fl, gemm_alg_bytes(d, 4));
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, d, MX_SCALE_ONE, MX_SCALE_LO);
-  prof_end(pid, s);
-  if (hipGetLastError() != hipSuccess) return DZN_E_HIP;
-  if (d.stat_partial && d.stat_final)
-    return launch_stats_finalize(d.stat_partial, d.M, tilesN * WGN, d.stat_C, d.stat_eps, d.stat_final, s);
-  return DZN_OK;
+  return launch_contraction<gemm_mx_kernel<BM, BN, WGM, WGN, S, OCC>>(d, s, WGM * WGN * 64, lds, BM, BN, WGN, "mx", 4, MX_SCALE_ONE,
+                                                                      MX_SCALE_LO);
 }
 
 // W [rows][K] fp32 -> Wmx [rows][K/32][128 B]: bytes 0..63 = fp16 of w 2^e_row in gemm_split.hip's fragment order, bytes
@@ -440,23 +408,10 @@ __global__ __launch_bounds__(256) void split_weights_mx_kernel(const float* __re
   }
 }
 
-// DZN_GEMM_MX_CFG (read once) or dzn_op_set_gemm_mx_cfg() (tests / tuning scripts): force one tile shape
-char g_mx_force_buf[32] = {0};
-bool g_mx_force_init = false;
-const char* g_mx_force() {
-  if (!g_mx_force_init) {
-    const char* e = getenv("DZN_GEMM_MX_CFG");
-    if (e) snprintf(g_mx_force_buf, sizeof(g_mx_force_buf), "%s", e);
-    g_mx_force_init = true;
-  }
-  return g_mx_force_buf[0] ? g_mx_force_buf : nullptr;
-}
-
 }  // namespace
 
 extern "C" int dzn_op_set_gemm_mx_cfg(const char* cfg) {
-  g_mx_force_init = true;
-  snprintf(g_mx_force_buf, sizeof(g_mx_force_buf), "%s", cfg && strcmp(cfg, "auto") ? cfg : "");
+  g_gemm_mx_cfg.set(cfg);
   return DZN_OK;
 }
 
@@ -470,7 +425,7 @@ int launch_gemm_mx(const dzn_gemm_desc& d, hipStream_t s) {
   // the round, profiles/r5_gemm_mx_first_bench.txt) the wide tile wins on all of them (N 1024 K 256: 186 vs 166 TFLOP/s, K 480:
   // 243 vs 214, N 320 K 1024: 256 vs 244): a 32 x 64 wavefront tile has half the MFMAs per converted A value.
   const bool narrow = d.N <= 64 || (int64_t)((d.M + 127) / 128) * (cols128 / 128) * (d.nz > 0 ? d.nz : 1) < 448;
-  const char* force = g_mx_force();
+  const char* force = g_gemm_mx_cfg.get();   // tuning knob: force one tile shape
   if (force && !strcmp(force, "128x64")) return launch_mx_cfg<128, 64, 4, 1, 2, 3>(d, s);
   if (force && !strcmp(force, "128x128")) return launch_mx_cfg<128, 128, 4, 1, 2, 2>(d, s);
   if (force && !strcmp(force, "256x128")) return launch_mx_cfg<256, 128, 8, 1, 2, 2>(d, s);     // probe: 8 wavefronts, one workgroup per CU

@@ -35,13 +35,12 @@
 // Elements more than 2^17 below the tensor's maximum keep a lo term in fp16's subnormal range: their ABSOLUTE
 // error stays <= 2^-25 * max / 2^14, i.e. below fp32 resolution of any dot product that contains the maximum.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "checked.h"
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_launch.h"
 #include "split.h"
 
 DZN_CHECKED_TU(gemm_split)
@@ -95,26 +94,14 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: LDS-DMA bases stay scalar
   const int wm = wave / WGN, wn = wave % WGN;
-  const int tilesN = (d.N + BN - 1) / BN;
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  // t walks the tiles XCD by XCD (contiguous ranges) in row-block-major order: an XCD works on a few row blocks with ALL their
+  // the tiles are walked XCD by XCD (contiguous ranges) in row-block-major order: an XCD works on a few row blocks with ALL their
   // column tiles, so it streams the whole weight-plane set (N x K x 2 NP bytes) once per row block.  From ~4 MB on that set no
   // longer survives in the XCD's 4 MB L2 between two row blocks, but the re-fetched planes come from the Infinity Cache at no
   // measurable cost in time: a group-major order that cut the fabric reads as modelled left the step unchanged and was removed
   // (DESIGN.md §5 "Switch retirement", profiles/r4_gemm_refetch_probe.txt).
-  const int tm = t / tilesN, tn = t % tilesN;
-  const int z = blockIdx.y;
-  int z0 = z / d.zdiv;
-  const int z1 = z - z0 * d.zdiv;
-  if (d.z_list) {   // device-chosen subset of the batch (dzn_gemm_desc.z_count / z_list)
-    if (z0 >= d.z_count[0]) return;
-    z0 = d.z_list[z0];
-  }
+  const int tilesN = (d.N + BN - 1) / BN;
+  int tm, tn, z0, z1;
+  if (!gemm_tile(d, tilesN, tm, tn, z0, z1)) return;
   const float* __restrict__ A = d.A + z0 * d.a_z0 + z1 * d.a_z1;
   const u16* __restrict__ W3 =
       reinterpret_cast<const u16*>(NP == 3 ? d.W3 : d.W2h) + SP * (z0 * d.w_z0 + z1 * d.w_z1);
@@ -242,7 +229,7 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
   for (int j = 0; j < NI; ++j) DZN_CHECK(woff[j] >= ABYTES && woff[j] + (NP - 1) * WPLANE + 16 <= BUF, 0x105, woff[j]);   // fragment reads inside the stage
 #pragma unroll
   for (int i = 0; i < MI; ++i) DZN_CHECK(aoff0[i] + 16 <= ABYTES && aoff1[i] + 16 <= ABYTES, 0x106, aoff1[i]);
-  DZN_CHECK(tm * BM < d.M && tn * BN < d.N, 0x107, t);                                            // the tile exists
+  DZN_CHECK(tm * BM < d.M && tn * BN < d.N, 0x107, tm * tilesN + tn);                              // the tile exists
   auto read_w = [&](int stage, u32x4 (&wf)[NI][NP]) {
     const unsigned char* base = smem + stage * BUF;
 #pragma unroll
@@ -356,34 +343,10 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
 
 template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1>
 int launch_split_cfg(const dzn_gemm_desc& d, hipStream_t s) {
-  const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
   size_t lds = (size_t)S * (BM * 128 + NP * BN * 64);
   if (d.A2 && a2_tab_in_lds((int)lds, BM, OCC)) lds += BM * 4;   // + the second segment's row table
-  auto kern = gemm_split_kernel<BM, BN, WGM, WGN, S, NP, OCC>;
-  static unsigned long long attr_mask = 0;  // one bit per HIP device: function attributes are per device
-  if (first_use_on_device(attr_mask)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-  }
-  dim3 grid(tilesM * tilesN, d.nz > 0 ? d.nz : 1, 1);
-  int pid = -1;
-  if (prof_enabled()) {
-    char cls[64];
-    static const bool by_shape = getenv("DZN_PROFILE_SHAPES") != nullptr;
-    if (by_shape)
-      snprintf(cls, sizeof(cls), "gemm_%s_%dx%d M%d N%d K%d z%d", NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", BM, BN, d.M,
-               d.N, d.K, d.nz);
-    else
-      snprintf(cls, sizeof(cls), "gemm_%s_%dx%d", NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", BM, BN);
-    const double fl = d.alg_flops > 0 ? d.alg_flops * d.nz : 2.0 * d.M * d.N * d.K * d.nz;
-    pid = prof_begin(s, cls, fl, gemm_alg_bytes(d, NP * 2));
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, d);
-  prof_end(pid, s);
-  if (hipGetLastError() != hipSuccess) return DZN_E_HIP;
-  if (d.stat_partial && d.stat_final)
-    return launch_stats_finalize(d.stat_partial, d.M, tilesN * WGN, d.stat_C, d.stat_eps, d.stat_final, s);
-  return DZN_OK;
+  return launch_contraction<gemm_split_kernel<BM, BN, WGM, WGN, S, NP, OCC>>(d, s, WGM * WGN * 64, lds, BM, BN, WGN,
+                                                                             NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", NP * 2);
 }
 
 // W [rows][K] fp32 (row stride ldw)  ->  W3 [rows][K/32][3][32] bf16, k permuted inside each block
@@ -408,22 +371,9 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
   }
 }
 
-// DZN_GEMM_CFG (read once) or dzn_op_set_gemm_cfg() (tuning scripts: several shapes in one process)
-char g_force_buf[32] = {0};
-bool g_force_init = false;
-const char* g_force_cfg() {
-  if (!g_force_init) {
-    const char* e = getenv("DZN_GEMM_CFG");
-    if (e) snprintf(g_force_buf, sizeof(g_force_buf), "%s", e);
-    g_force_init = true;
-  }
-  return g_force_buf[0] ? g_force_buf : nullptr;
-}
-
 template <int NP>
 int launch_gemm_split_np(const dzn_gemm_desc& d, hipStream_t s) {
-  const char* force = g_force_cfg();                    // tuning knob: force one tile shape
-  if (force) {
+  if (const char* force = g_gemm_cfg.get()) {            // tuning knob: force one tile shape
     // production tiles by name
     if (!strcmp(force, "128x64")) return launch_split_cfg<128, 64, 4, 1, 2, NP, NP <= 2 ? 3 : 2>(d, s);
     if (!strcmp(force, "128x80")) return launch_split_cfg<128, 80, 4, 1, 2, NP, 2>(d, s);
@@ -508,7 +458,7 @@ int launch_gemm_split(const dzn_gemm_desc& d, hipStream_t s) {
   if (d.A2 && prec_is_h2(d.precision) && d.a_amax && !d.a2_amax) return DZN_E_INVALID;   // one scale from BOTH bounds
   // fp16 two-term path: needs the fp16 planes + their row scales, the producer-tracked |max| of A, and weights
   // that do not move with z (col_scale is indexed by the output column alone)
-  static const bool no_h2 = getenv("DZN_NO_H2") != nullptr;
+  const bool no_h2 = gemm_no_h2();
   // DZN_PREC_F16 with the MX planes: fp16 hi*hi + fp8 cross terms (gemm_mx.hip); without them the single-term fp16 kernel
   if (d.precision == DZN_PREC_F16 && d.Wmx && d.col_scale_mx && d.a_amax && !d.w_z0 && !d.w_z1 && !no_h2)
     return launch_gemm_mx(d, s);
@@ -518,12 +468,6 @@ int launch_gemm_split(const dzn_gemm_desc& d, hipStream_t s) {
   }
   if (!d.W3) return DZN_E_INVALID;
   return launch_gemm_split_np<3>(d, s);
-}
-
-extern "C" int dzn_op_set_gemm_cfg(const char* cfg) {
-  g_force_init = true;
-  snprintf(g_force_buf, sizeof(g_force_buf), "%s", cfg && strcmp(cfg, "auto") ? cfg : "");
-  return DZN_OK;
 }
 
 int launch_split_weights_h2(const float* W, int64_t rows, int K, int64_t ldw, void* W2, float* col_scale, hipStream_t s) {

@@ -9,13 +9,12 @@
 // as [rows][64 B] plane images (slot XOR g((row >> 2) & 3), conflict free), 6 products per block.
 // Same pipeline as gemm_split.hip (mid-tile raw barrier, younger LDS-DMA tiles stay in flight,
 // fragments of tile kt+1 read during the second half of tile kt), same fused epilogue.
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "checked.h"
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_launch.h"
 #include "split.h"
 
 DZN_CHECKED_TU(gemm_split_pre)
@@ -53,21 +52,8 @@ __global__ __launch_bounds__(WGM * WGN * 64) void gemm_split_pre_kernel(const dz
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WGN, wn = wave % WGN;
-  const int tilesN = (d.N + BN - 1) / BN;
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int tm = t / tilesN, tn = t % tilesN;
-  const int z = blockIdx.y;
-  int z0 = z / d.zdiv;
-  const int z1 = z - z0 * d.zdiv;
-  if (d.z_list) {   // device-chosen subset of the batch (dzn_gemm_desc.z_count / z_list)
-    if (z0 >= d.z_count[0]) return;
-    z0 = d.z_list[z0];
-  }
+  int tm, tn, z0, z1;
+  if (!gemm_tile(d, (d.N + BN - 1) / BN, tm, tn, z0, z1)) return;
   const u16* __restrict__ A3 = reinterpret_cast<const u16*>(d.A) + z0 * d.a_z0 + z1 * d.a_z1;
   const u16* __restrict__ W3 =
       reinterpret_cast<const u16*>(NP == 3 ? d.W3 : d.W2h) + SP * (z0 * d.w_z0 + z1 * d.w_z1);
@@ -219,44 +205,37 @@ __global__ __launch_bounds__(WGM * WGN * 64) void gemm_split_pre_kernel(const dz
     step(kt, wfa, wfb);
     if (kt + 1 < nk) step(kt + 1, wfb, wfa);
   }
-  if constexpr (true) {
-    // column vectors of the epilogue in LDS (48 registers less than holding them; the stages are dead by now)
-    __syncthreads();
-    gemm_epilogue<BM, BN, TM, TN, MI, NI, true>(d, acc, tm, tn, wm, wn, lr, lq, cz, bz, z0, row_inv,
-                                                NP <= 2 ? d.col_scale + z0 * d.b_z0 + z1 * d.b_z1 : nullptr,
-                                                reinterpret_cast<float*>(smem) + (wm * WGN + wn) * 3 * TN);
-  } else {
-    gemm_epilogue<BM, BN, TM, TN, MI, NI>(d, acc, tm, tn, wm, wn, lr, lq, cz, bz, z0, row_inv,
-                                          NP <= 2 ? d.col_scale + z0 * d.b_z0 + z1 * d.b_z1 : nullptr);
-  }
+  // column vectors of the epilogue in LDS (48 registers less than holding them; the stages are dead by now)
+  __syncthreads();
+  gemm_epilogue<BM, BN, TM, TN, MI, NI, true>(d, acc, tm, tn, wm, wn, lr, lq, cz, bz, z0, row_inv,
+                                              NP <= 2 ? d.col_scale + z0 * d.b_z0 + z1 * d.b_z1 : nullptr,
+                                              reinterpret_cast<float*>(smem) + (wm * WGN + wn) * 3 * TN);
 }
 
 template <int BM, int BN, int WGM, int WGN, int S, int NP>
 int launch_pre_cfg(const dzn_gemm_desc& d, hipStream_t s) {
-  const int tilesM = (d.M + BM - 1) / BM, tilesN = (d.N + BN - 1) / BN;
   const size_t lds = (size_t)S * NP * (BM + BN) * 64;
-  auto kern = gemm_split_pre_kernel<BM, BN, WGM, WGN, S, NP>;
-  static unsigned long long attr_mask = 0;  // one bit per HIP device: function attributes are per device
-  if (first_use_on_device(attr_mask)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
+  return launch_contraction<gemm_split_pre_kernel<BM, BN, WGM, WGN, S, NP>>(
+      d, s, WGM * WGN * 64, lds, BM, BN, WGN, NP == 3 ? "f32s_pre" : NP == 2 ? "f32h_pre" : "f16_pre", NP * 2);
+}
+
+// the two float4s of plane chunk (row t of window b, 32-block blk, lane group q): source channels blk * 32 + 4 q .. + 3 and
+// 16 further; zero outside the row range [0, L) and in the pad channels cg .. cgp-1 of a group
+__device__ __forceinline__ void load_plane_chunk(const float* __restrict__ x, int b, int t, int L, int Ds, int blk, int q, int cg,
+                                                 int cgp, f32x4& u, f32x4& v) {
+  u = v = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if (t < 0 || t >= L) return;
+  const float* row = x + ((int64_t)b * L + t) * Ds;
+  const int c0 = blk * 32 + 4 * q, c1 = c0 + 16;            // plane channels of the two float4s
+  const int g0 = c0 / cgp, i0 = c0 - g0 * cgp, g1 = c1 / cgp, i1 = c1 - g1 * cgp;
+  if (i0 < cg) {
+    const float4 a = *reinterpret_cast<const float4*>(row + g0 * cg + i0);
+    u = (f32x4){a.x, a.y, a.z, a.w};
   }
-  dim3 grid(tilesM * tilesN, d.nz > 0 ? d.nz : 1, 1);
-  int pid = -1;
-  if (prof_enabled()) {
-    char cls[64];
-    static const bool by_shape = getenv("DZN_PROFILE_SHAPES") != nullptr;
-    if (by_shape)
-      snprintf(cls, sizeof(cls), "gemm_%s_pre_%dx%d M%d N%d K%d z%d", NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", BM, BN,
-               d.M, d.N, d.K, d.nz);
-    else
-      snprintf(cls, sizeof(cls), "gemm_%s_pre_%dx%d", NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", BM, BN);
-    const double fl = d.alg_flops > 0 ? d.alg_flops * d.nz : 2.0 * d.M * d.N * d.K * d.nz;
-    pid = prof_begin(s, cls, fl, gemm_alg_bytes(d, NP * 2));
+  if (i1 < cg) {
+    const float4 e = *reinterpret_cast<const float4*>(row + g1 * cg + i1);
+    v = (f32x4){e.x, e.y, e.z, e.w};
   }
-  hipLaunchKernelGGL(kern, grid, dim3(WGM * WGN * 64), lds, s, d);
-  prof_end(pid, s);
-  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
 // x fp32 [B, L, D] -> three bf16 planes of the zero-padded copy [B, Lp, D] (rows shifted by `pad`), the 32
@@ -273,21 +252,8 @@ __global__ __launch_bounds__(256) void pad_rows_split3_kernel(const float* __res
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int r = (int)(i / chunks), c = (int)(i - (int64_t)r * chunks);
     const int blk = c >> 2, q = c & 3;
-    const int t = r - pad;
-    f32x4 u = (f32x4){0.f, 0.f, 0.f, 0.f}, v = u;
-    if (t >= 0 && t < L) {
-      const float* row = x + ((int64_t)b * L + t) * Ds;
-      const int c0 = blk * 32 + 4 * q, c1 = c0 + 16;          // plane channels of the two float4s
-      const int g0 = c0 / cgp, i0 = c0 - g0 * cgp, g1 = c1 / cgp, i1 = c1 - g1 * cgp;
-      if (i0 < cg) {
-        const float4 a = *reinterpret_cast<const float4*>(row + g0 * cg + i0);
-        u = (f32x4){a.x, a.y, a.z, a.w};
-      }
-      if (i1 < cg) {
-        const float4 e = *reinterpret_cast<const float4*>(row + g1 * cg + i1);
-        v = (f32x4){e.x, e.y, e.z, e.w};
-      }
-    }
+    f32x4 u, v;
+    load_plane_chunk(x, b, r - pad, L, Ds, blk, q, cg, cgp, u, v);
     bf16x8 ph, pm, pl;
     split8(u, v, ph, pm, pl);
     u16* dst = planes + ((int64_t)b * Lp + r) * D + blk * 32 + q * 8;
@@ -313,21 +279,8 @@ __global__ __launch_bounds__(256) void pad_rows_split2_kernel(const float* __res
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int r = (int)(i / chunks), c = (int)(i - (int64_t)r * chunks);
     const int blk = c >> 2, q = c & 3;
-    const int t = r - pad;
-    f32x4 u = (f32x4){0.f, 0.f, 0.f, 0.f}, v = u;
-    if (t >= 0 && t < L) {
-      const float* row = x + ((int64_t)b * L + t) * Ds;
-      const int c0 = blk * 32 + 4 * q, c1 = c0 + 16;          // plane channels of the two float4s
-      const int g0 = c0 / cgp, i0 = c0 - g0 * cgp, g1 = c1 / cgp, i1 = c1 - g1 * cgp;
-      if (i0 < cg) {
-        const float4 a = *reinterpret_cast<const float4*>(row + g0 * cg + i0);
-        u = (f32x4){a.x, a.y, a.z, a.w};
-      }
-      if (i1 < cg) {
-        const float4 e = *reinterpret_cast<const float4*>(row + g1 * cg + i1);
-        v = (f32x4){e.x, e.y, e.z, e.w};
-      }
-    }
+    f32x4 u, v;
+    load_plane_chunk(x, b, r - pad, L, Ds, blk, q, cg, cgp, u, v);
     u32x4 ph, pl;
     split8_h2(u, v, sc, ph, pl);
     u16* dst = planes + ((int64_t)b * Lp + r) * D + blk * 32 + q * 8;
@@ -342,7 +295,7 @@ __global__ __launch_bounds__(256) void pad_rows_split2_kernel(const float* __res
 // kc % 32 == 0, ldw == K, all A offsets multiples of 8 elements.
 template <int NP>
 int launch_gemm_split_pre_np(const dzn_gemm_desc& d, hipStream_t s) {
-  static const char* force = getenv("DZN_GEMM_CFG");   // tuning knob
+  const char* force = g_gemm_cfg.get();   // tuning knob: force one tile shape
   if (force && !strcmp(force, "256x128")) return launch_pre_cfg<256, 128, 4, 2, 2, NP>(d, s);
   if (force && !strcmp(force, "128x128")) return launch_pre_cfg<128, 128, 2, 2, 2, NP>(d, s);
   if (force && !strcmp(force, "128x64")) return launch_pre_cfg<128, 64, 4, 1, 2, NP>(d, s);
@@ -353,8 +306,9 @@ int launch_gemm_split_pre_np(const dzn_gemm_desc& d, hipStream_t s) {
 int launch_gemm_split_pre(const dzn_gemm_desc& d, hipStream_t s) {
   if ((d.K & 31) || (d.kc & 31) || d.ldw != d.K || !d.a_split3 || d.a_plane <= 0) return DZN_E_INVALID;
   if (d.A2) return DZN_E_INVALID;   // a second A segment is not read by this kernel: refuse rather than drop its columns
+  if (d.stat_partial) return DZN_E_INVALID;   // row statistics are not finalized for this family: refuse rather than leave stat_final unwritten
   if (d.a_split3 == 2) {   // two fp16 planes
-    if (!d.W2h || !d.col_scale || !d.a_amax || d.w_z0 * 1 != d.w_z0) return DZN_E_INVALID;
+    if (!d.W2h || !d.col_scale || !d.a_amax) return DZN_E_INVALID;
     return d.precision == DZN_PREC_F16 ? launch_gemm_split_pre_np<1>(d, s) : launch_gemm_split_pre_np<2>(d, s);
   }
   if (!d.W3) return DZN_E_INVALID;
@@ -373,9 +327,6 @@ int launch_pad_rows_split2(const float* x, void* planes, int64_t plane_stride, i
                      plane_stride, L, Lp, pad, D, amax, snapshot, cg, cgp);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
-
-extern "C" int dzn_op_split_rows(const float* x, void* planes, int64_t plane_stride, int64_t rows, int32_t D,
-                                 void* stream);
 
 int launch_pad_rows_split3(const float* x, void* planes, int64_t plane_stride, int B, int L, int Lp, int pad, int D,
                            hipStream_t st, int cg, int cgp) {

@@ -24,14 +24,14 @@ def _p(t):
 def gemm(A, W, *, M=None, N=None, K=None, bias=None, R=None, C_out=None, WS=None, ws_w=0.0,
          ws_init=False, a_rowoff=None, c_rowoff=None, lda=None, kc=0, ldk=0, ldw=None, ldc=None,
          ldws=0, act=0, alpha=1.0, post_relu=False, nz=1, zdiv=1, zs=None, precision=0,
-         W16=None, W3=None, a_planes=None, ln_stats=None, ln_colsum=None, W2h=None, col_scale=None,
+         W3=None, a_planes=None, ln_stats=None, ln_colsum=None, W2h=None, col_scale=None,
          a_amax=None, c_amax=None, amax_unit=None, want_row_stats=False, stat_eps=1e-5, mx=False, Wmx=None,
          col_scale_mx=None, kv_col0=None, A2=None, a2_rowoff=None, a2_z0=0, k1=0, k2=0, a2_amax=None):
     """C = epilogue(A @ W^T); see dzn_gemm_desc.  A2 / a2_rowoff / a2_z0 / k1 / k2 / a2_amax: the second A segment (K columns
     k1 .. k1 + k2 read A2[z * a2_z0 + a2_rowoff[m] + k - k1]; a2_amax = its per-unit |max|, computed here when omitted).  kv_col0 (r6): columns >= kv_col0 leave as fp16 two-term planes with per-(row,
     64-column slot) scales instead of fp32 (dzn_gemm_desc.kv_planes) -> returns (C, planes int16 [2, M, N - kv_col0], inv f32
     [M, (N - kv_col0) / 64]).  A: [M, K] (or raw buffer with lda / rowoff),
-    W: [N, K] fp32 (and optionally W16 bf16)."""
+    W: [N, K] fp32."""
     lib = _lib.load()
     if A.dtype == torch.bfloat16:
         raise ValueError("bf16 A: activations are fp32 (the bf16 engine mode and its contraction are gone)")
@@ -45,7 +45,7 @@ def gemm(A, W, *, M=None, N=None, K=None, bias=None, R=None, C_out=None, WS=None
     if lda is None:
         lda = A.stride(0) if A.dim() == 2 else K
     if ldw is None:
-        ldw = W.stride(0) if W is not None else W16.stride(0)
+        ldw = W.stride(0)
     if C_out is None:
         C_out = torch.empty((M, N), device=A.device, dtype=torch.float32)
     if ldc is None:
@@ -53,7 +53,7 @@ def gemm(A, W, *, M=None, N=None, K=None, bias=None, R=None, C_out=None, WS=None
     if precision in (_lib.DZN_PREC_F32_SPLIT, _lib.DZN_PREC_F32_H2, _lib.DZN_PREC_F16) and W3 is None and K % 32 == 0 and ldw == K and W.is_contiguous():
         W3 = split_weights(W.reshape(-1, K))   # convenience for tests: engines split once at load
     d = DznGemmDesc()
-    d.A, d.W, d.W16, d.C = _p(A), _p(W), _p(W16), _p(C_out)
+    d.A, d.W, d.C = _p(A), _p(W), _p(C_out)
     d.bias, d.R, d.WS = _p(bias), _p(R), _p(WS)
     d.a_rowoff, d.c_rowoff = _p(a_rowoff), _p(c_rowoff)
     d.M, d.N, d.K = M, N, K

@@ -44,8 +44,7 @@ extern "C" {
  */
 typedef struct dzn_gemm_desc {
   const float* A;
-  const float* W;        /* fp32 weights (precision f32) */
-  const void* W16;       /* bf16 weights, same layout (precision bf16); may be NULL */
+  const float* W;        /* fp32 weights */
   float* C;
   const float* bias;
   const float* R;
@@ -66,7 +65,7 @@ typedef struct dzn_gemm_desc {
   int32_t ws_init;
   int32_t nz, zdiv;
   int64_t a_z0, a_z1, w_z0, w_z1, c_z0, c_z1, b_z0, b_z1;
-  int32_t precision;     /* DZN_PREC_* */
+  int32_t precision;     /* DZN_PREC_* (DZN_PREC_BF16 is reserved: DZN_E_INVALID) */
   double alg_flops;      /* algorithmic flops of this launch for profiling (0 -> 2*M*N*K*nz) */
   /* DZN_PREC_F32_SPLIT only: the weights pre-split into three bf16 planes by dzn_op_split_weights
    * (same z / row offsets as W, times 3); NULL, K % 32 or kc % 32 != 0 -> fp32 MFMA kernel */
@@ -184,12 +183,17 @@ int dzn_op_split_weights_mx(const float* W, int64_t rows, int32_t K, int64_t ldw
  * checks (0 = clean), DZN_E_STATE in a release build. */
 int dzn_checked_status(uint32_t* out4, int32_t reset);
 
-/* tests / tuning: force one tile shape of csrc/gemm_mx.hip ("128x128", "128x64"; "auto" / NULL = the shape rule) */
+/* tests / tuning: force one tile shape of csrc/gemm_mx.hip ("128x128", "128x64", "256x128"; "auto" / "" / NULL = the shape
+ * rule) for the calls that follow.  Same effect as the DZN_GEMM_MX_CFG environment variable, which is read on first use. */
 int dzn_op_set_gemm_mx_cfg(const char* cfg);
 
-/* tuning knob (scripts/bench_gemm_h2.py): force one of the production tiles of csrc/gemm_split.hip for the calls that
- * follow ("128x64", "128x80", "128x32", "128x128" (f32s) / "128x128w4" (f32h, f16), "256x128w8s3" (f16); "auto" / NULL =
- * the shape heuristic).  Same effect as the DZN_GEMM_CFG environment variable, which is read once per process. */
+/* tests / tuning: force one tile shape, by name, for the calls that follow; "auto" / "" / NULL = the shape heuristic.  Same effect
+ * as the DZN_GEMM_CFG environment variable, which is read on first use.  One name reaches all three non-MX families, and a
+ * family that does not know it keeps its heuristic:
+ *   csrc/gemm.hip            "128x32", "256x32", "256x64", "128x64", "64x64", "128x128"
+ *   csrc/gemm_split.hip      "128x64", "128x80", "128x32", "128x128" (f32s) / "128x128w4" (f32h, f16), "256x128w8s3" (f16)
+ *   csrc/gemm_split_pre.hip  "256x128", "128x128", "128x64"
+ * While a name is set, launches that ask for K / V planes (kv_planes) are refused: only the automatic tiles write them. */
 int dzn_op_set_gemm_cfg(const char* cfg);
 
 /* amax[0] = max(amax[0], max |x[0..n)|) — the |max| tracker of a tensor whose producer has no fused tracker */

@@ -6,8 +6,8 @@ import torch
 from diarizen_amd import ops
 M, N, K, prec, it = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
 dev = torch.device("cuda:0")
-A = torch.randn(M, K, device=dev); W = torch.randn(N, K, device=dev) * 0.05; W16 = W.bfloat16()
+A = torch.randn(M, K, device=dev); W = torch.randn(N, K, device=dev) * 0.05
 out = torch.empty(M, N, device=dev)
 for _ in range(it):
-    ops.gemm(A, W, W16=W16, C_out=out, precision=prec)
+    ops.gemm(A, W, C_out=out, precision=prec)
 torch.cuda.synchronize()

@@ -2,8 +2,8 @@
 
 Tolerances (fp32 mode): the MFMA f32 path is an fmaf chain, so it differs from a float64
 reference only by fp32 round-off: |err| <= 2e-5 * sqrt(K)-ish; we assert 1e-4 relative to the
-output scale.  bf16 weights (test_gemm_bf16, an op-level leftover): checked against the same bf16-rounded
-operands, 1e-4 relative.
+output scale.  precision 1 (DZN_PREC_BF16) is reserved: dzn_op_gemm refuses it
+(test_gemm_rejects_bf16_precision).
 """
 import math
 
@@ -260,17 +260,83 @@ def test_gemm_mx_layernorm_folded_and_row_stats(built_lib, gpu):
     assert abs(camax.item() - out.abs().max().item()) < 1e-6
 
 
-def test_gemm_bf16(built_lib, gpu):
-    from diarizen_amd import ops
+def test_gemm_rejects_bf16_precision(built_lib, gpu):
+    """precision 1 (DZN_PREC_BF16) is reserved: dzn_op_gemm returns DZN_E_INVALID, as dzn_create does, and C stays untouched"""
+    from diarizen_amd import _lib, ops
     g = torch.Generator().manual_seed(9)
     M, N, K = 300, 200, 256
-    A = torch.randn(M, K, generator=g)
-    W = torch.randn(N, K, generator=g) * 0.1
-    ref = A.bfloat16().double() @ W.bfloat16().double().T
-    out = ops.gemm(A.to(gpu), None, N=N, K=K, ldw=K, W16=W.bfloat16().to(gpu), precision=1)
+    A = torch.randn(M, K, generator=g).to(gpu)
+    W = (torch.randn(N, K, generator=g) * 0.1).to(gpu)
+    C = torch.full((M, N), 7.0, device=gpu)
+    with pytest.raises(_lib.DznError, match="invalid argument"):
+        ops.gemm(A, W, C_out=C, precision=_lib.DZN_PREC_BF16)
     torch.cuda.synchronize()
-    assert _rel_err(out.cpu(), ref) < 1e-4  # vs the same bf16-rounded operands
-    assert _rel_err(out.cpu(), A.double() @ W.double().T) < 2e-2
+    assert torch.equal(C, torch.full_like(C, 7.0))
+
+
+@pytest.mark.parametrize("M,N,K", [(70, 40, 40), (257, 153, 72)])
+def test_gemm_register_staged_k_not_multiple_of_32(built_lib, gpu, M, N, K):
+    """K % 32 != 0 takes gemm_kernel (global -> register -> LDS staging, zero-filled K tail) instead of the LDS-DMA kernel: one
+    tile and several, vector and scalar epilogue (N % 4), against float64 at test_gemm_plain's bound"""
+    from diarizen_amd import ops
+    g = torch.Generator().manual_seed(M * 7 + N)
+    A = torch.randn(M, K, generator=g)
+    W = torch.randn(N, K, generator=g) * torch.linspace(0.5, 1.5, N)[:, None]
+    bias = torch.randn(N, generator=g)
+    ref = A.double() @ W.double().T + bias.double()
+    out = ops.gemm(A.to(gpu), W.to(gpu), bias=bias.to(gpu), precision=0)
+    torch.cuda.synchronize()
+    assert _rel_err(out.cpu(), ref) < 1e-5
+
+
+def _profiled_gemm(**kw):
+    """ops.gemm under the in-situ profiler: (C, the contraction classes it recorded)"""
+    from diarizen_amd import _lib, ops
+    _lib.profile_enable(True)
+    try:
+        out = ops.gemm(**kw)
+        names = [p["name"] for p in _lib.profile_collect() if p["name"].startswith("gemm_")]
+    finally:
+        _lib.profile_enable(False)
+    return out, names
+
+
+@pytest.mark.parametrize("family,prec,cfg", [("f32", 0, "128x32"), ("f32s", 2, "128x32"), ("f32h", 3, "128x32"),
+                                             ("f32s_pre", 2, "128x128")])
+def test_gemm_cfg_setter_reaches_every_family(built_lib, gpu, family, prec, cfg):
+    """dzn_op_set_gemm_cfg forces the tile of the plain (gemm.hip), split (gemm_split.hip) and pre-split (gemm_split_pre.hip)
+    families alike: the profiler class carries the forced tile, the result keeps the family's tolerance against float64 (partial
+    tiles in M and N), and "auto" brings the automatic class back"""
+    from diarizen_amd import _lib, ops
+    lib = _lib.load()
+    M, N, K = 257, 200, 96
+    g = torch.Generator().manual_seed(M + N + K)
+    pre = family.endswith("_pre")
+    A = torch.randn(M, K, generator=g)
+    if pre:     # test_gemm_presplit_operand's operands
+        A = A * torch.exp(torch.randn(M, K, generator=g))
+        W = torch.randn(N, K, generator=g) * 0.1
+    else:       # test_gemm_plain's
+        W = torch.randn(N, K, generator=g) * torch.linspace(0.5, 1.5, N)[:, None]
+    bias = torch.randn(N, generator=g)
+    ref = A.double() @ W.double().T + bias.double()
+    kw = dict(A=A.to(gpu), W=W.to(gpu), bias=bias.to(gpu), precision=prec)
+    if pre:
+        kw["a_planes"] = ops.split_rows(kw["A"])
+    try:
+        _, auto = _profiled_gemm(**kw)
+        lib.dzn_op_set_gemm_cfg(cfg.encode())
+        out, forced = _profiled_gemm(**kw)
+        lib.dzn_op_set_gemm_cfg(b"auto")
+        out_auto, again = _profiled_gemm(**kw)
+    finally:
+        lib.dzn_op_set_gemm_cfg(b"auto")
+    forced_cls = f"gemm_{family}_{cfg}"
+    assert len(auto) == 1 and auto[0].startswith(f"gemm_{family}_") and not auto[0].startswith(forced_cls), auto
+    assert len(forced) == 1 and (forced[0] + " ").startswith(forced_cls + " "), forced
+    assert again == auto
+    assert _rel_err(out.cpu(), ref) < 1e-5
+    assert _rel_err(out_auto.cpu(), ref) < 1e-5
 
 
 @pytest.mark.parametrize("C,Cpad", [(153, 160), (1024, 1024), (256, 256), (211, 224), (512, 512)])
@@ -415,17 +481,17 @@ def _lib_prec(name):
     return {"f32h": _lib.DZN_PREC_F32_H2, "f32s": _lib.DZN_PREC_F32_SPLIT, "f32": _lib.DZN_PREC_F32}[name]
 
 
-@pytest.mark.parametrize("M,N,K,col0", [(399 * 2, 3 * 5 * 64, 256, 5 * 64), (1000, 3 * 16 * 64, 1024, 16 * 64), (130, 192, 64, 64)])
-def test_gemm_epilogue_writes_kv_planes(built_lib, gpu, M, N, K, col0):
-    """(r6) dzn_gemm_desc.kv_planes: the f32h contraction stores the columns >= kv_col0 as fp16 two-term planes with one exact
-    power-of-two scale per (row, 64-column slot) and leaves the columns below as fp32.  (hi + lo) * inv reproduces the plain
-    launch's fp32 value to 2^-21 of the slot's |max| (two fp16 terms = 22 bits), the slot |max| lands in [2^14, 2^15) and the Q
-    columns are bit-identical to the plain launch; with a bias and a folded LayerNorm as the engine's q/k/v site has them."""
-    from diarizen_amd import _lib, ops
+def _kv_planes_operands(gpu, M, N, K):
     g = torch.Generator().manual_seed(M + N)
     A = (torch.randn(M, K, generator=g) * torch.exp2(torch.randint(-3, 4, (M, 1), generator=g).float())).to(gpu)
     W = (torch.randn(N, K, generator=g) / K ** 0.5).to(gpu)
     bias = torch.randn(N, generator=g).to(gpu)
+    return A, W, bias
+
+
+def _check_kv_planes(A, W, bias, col0):
+    from diarizen_amd import _lib, ops
+    M, N = A.shape[0], W.shape[0]
     prec = _lib.DZN_PREC_F32_H2
     plain = ops.gemm(A, W, bias=bias, precision=prec)
     C, planes, inv = ops.gemm(A, W, bias=bias, precision=prec, kv_col0=col0)
@@ -442,6 +508,32 @@ def test_gemm_epilogue_writes_kv_planes(built_lib, gpu, M, N, K, col0):
     assert err <= 2.0 ** -21, err
     assert float(scaled.min()) >= 2.0 ** 14 - 8 and float(scaled.max()) < 2.0 ** 15 + 1
     assert torch.all(inv > 0) and torch.equal(inv, torch.exp2(torch.floor(torch.log2(inv))))     # exact powers of two
+
+
+@pytest.mark.parametrize("M,N,K,col0", [(399 * 2, 3 * 5 * 64, 256, 5 * 64), (1000, 3 * 16 * 64, 1024, 16 * 64), (130, 192, 64, 64)])
+def test_gemm_epilogue_writes_kv_planes(built_lib, gpu, M, N, K, col0):
+    """(r6) dzn_gemm_desc.kv_planes: the f32h contraction stores the columns >= kv_col0 as fp16 two-term planes with one exact
+    power-of-two scale per (row, 64-column slot) and leaves the columns below as fp32.  (hi + lo) * inv reproduces the plain
+    launch's fp32 value to 2^-21 of the slot's |max| (two fp16 terms = 22 bits), the slot |max| lands in [2^14, 2^15) and the Q
+    columns are bit-identical to the plain launch; with a bias and a folded LayerNorm as the engine's q/k/v site has them."""
+    _check_kv_planes(*_kv_planes_operands(gpu, M, N, K), col0)
+
+
+def test_kv_planes_refused_under_forced_cfg(built_lib, gpu):
+    """only the automatic tiles of the split contraction write K / V planes: under a tile forced through dzn_op_set_gemm_cfg the
+    launch is refused (DZN_E_INVALID) rather than left to store fp32 where the attention kernel expects planes; after "auto" the
+    same launch passes test_gemm_epilogue_writes_kv_planes's checks"""
+    from diarizen_amd import _lib, ops
+    lib = _lib.load()
+    M, N, K, col0 = 130, 192, 64, 64
+    A, W, bias = _kv_planes_operands(gpu, M, N, K)
+    lib.dzn_op_set_gemm_cfg(b"128x32")
+    try:
+        with pytest.raises(_lib.DznError, match="invalid argument"):
+            ops.gemm(A, W, bias=bias, precision=_lib.DZN_PREC_F32_H2, kv_col0=col0)
+    finally:
+        lib.dzn_op_set_gemm_cfg(b"auto")
+    _check_kv_planes(A, W, bias, col0)
 
 
 def test_gate(built_lib, gpu):
