@@ -656,11 +656,13 @@ def test_linkage_centroid_30k_equals_scipy_golden(built_lib, gpu):
         assert np.array_equal(fcluster(Zs, thr, "distance"), fcluster(Zg, thr, "distance"))
 
 
-def test_linkage_step_loop_equals_two_kernel_loop(built_lib, gpu, monkeypatch):
-    """r3: one launch per step (merge or rescan, every workgroup selecting redundantly from the published records)
-    against the r2 loop (single-workgroup selection + wide update): bit-identical dendrograms, also for n that is not a
-    multiple of the 256-row block, n = 2, and duplicated embeddings (zero distances, ties broken by the lowest row)."""
+def test_linkage_edge_sizes_and_ties_equal_scipy(built_lib, gpu):
+    """The step loop at the sizes where its indexing can go wrong — n = 2, n = 3, n around the 256-row workgroup, several
+    workgroups, one row past a multiple of 256 — and with duplicated embeddings (zero distances, exact ties broken by the
+    lowest row): the dendrogram of scipy.cluster.hierarchy.linkage(e, "centroid", "euclidean") (ids and sizes exactly,
+    distances to 1e-12), and identical bits from a second call."""
     import numpy as np
+    from scipy.cluster.hierarchy import linkage
     from diarizen_amd import ops
     from oracle.gen_golden import linkage_scale_case
     for n in (2, 3, 255, 256, 257, 1000, 4097):
@@ -668,19 +670,11 @@ def test_linkage_step_loop_equals_two_kernel_loop(built_lib, gpu, monkeypatch):
         if n >= 255:
             e[7] = e[3]
             e[100] = e[3]
-        Za = ops.linkage_centroid(e)                 # r6 default: the step loop with two remembered neighbours per row
-        monkeypatch.setenv("DZN_LINKAGE_PERSIST", "1")     # r6b: the same rules in ONE persistent launch (opt-in: measured slower)
-        Zd = ops.linkage_centroid(e)
-        monkeypatch.delenv("DZN_LINKAGE_PERSIST")
-        assert np.array_equal(Za, Zd), n
-        monkeypatch.setenv("DZN_LINKAGE_TWO_KERNEL", "1")
-        Zb = ops.linkage_centroid(e)
-        monkeypatch.delenv("DZN_LINKAGE_TWO_KERNEL")
-        monkeypatch.setenv("DZN_LINKAGE_TOP1", "1")  # r3-r5: the step loop with one remembered neighbour
-        Zc = ops.linkage_centroid(e)
-        monkeypatch.delenv("DZN_LINKAGE_TOP1")
-        assert np.array_equal(Zc, Zb), n
-        assert np.array_equal(Za, Zb), n
+        Zg = ops.linkage_centroid(e)
+        Zs = linkage(e, "centroid", "euclidean")
+        assert np.array_equal(Zs[:, [0, 1, 3]], Zg[:, [0, 1, 3]]), n
+        assert np.abs(Zs[:, 2] - Zg[:, 2]).max() <= 1e-12, n
+        assert np.array_equal(Zg, ops.linkage_centroid(e)), n
 
 
 def test_cdist_cosine_equals_scipy(built_lib, gpu):
