@@ -124,9 +124,9 @@ struct dzn_handle {
   int D = 0, H = 0, A = 0, Fh = 0;
   // ---- segmentation: weights ----
   float* conv0_w = nullptr;
-  float* conv0_lnq = nullptr;
-  u16* conv1_W2n = nullptr;     // conv1's fp16 planes in natural k order + row scales: the fused conv0 -> conv1 kernel
-  float* conv1_wscn = nullptr;   // [10 + 100]: mean and covariance over channels of conv0's taps (frontend.hip)
+  float* conv0_lnq = nullptr;    // [10 + 100]: mean and covariance factor over channels of conv0's taps (frontend.hip)
+  u16* conv1_W2f = nullptr;      // conv1's fp16 planes in fragment-major order [K/32][Cp1/16][2][16][32] and
+  float* conv1_wscf = nullptr;   // their row scales [Cp1]: the fused conv0 -> conv1 kernel (frontend_fused.hip); null = not fused
   LNp conv_ln[DZN_MAX_CONV];
   Lin conv[DZN_MAX_CONV];
   float* dummy_w = nullptr;
@@ -484,15 +484,13 @@ void finalize_seg(H* h) {
     h->conv[i].Kt = k * ci;
     if (c.extractor_layer_norm) h->conv_ln[i] = ln_from_sd(h, pre + ".layer_norm", co);
     if (i == 1 && prec_is_h2(c.precision) && c.extractor_layer_norm && h->conv0_lnq && c.conv_k[0] == 10 &&
-        c.conv_s[0] == 5 && k == 3 && c.conv_s[1] == 2 && h->C[0] % 64 == 0 && h->Cp[0] == h->C[0] &&
-        h->Cp[1] == 160 && !getenv("DZN_NO_CONV01_FUSION")) {
-      // two copies of the planes: [row][K/32][2][32] (phase-alternating kernel), then fragment-major (producer / consumer kernel)
-      h->conv1_W2n = dalloc<u16>(h, (int64_t)4 * h->Cp[1] * k * cip, false);
-      h->conv1_wscn = dalloc<float>(h, h->Cp[1], false);
-      if (launch_split_weights_h2_natural(h->conv[1].W, h->Cp[1], k * cip, h->conv1_W2n, h->conv1_wscn, nullptr) != DZN_OK)
-        throw EngineError(DZN_E_HIP, "split_weights_h2_natural launch failed");
-      if (launch_fragment_major(h->conv1_W2n, h->Cp[1], k * cip, h->conv1_W2n + (int64_t)2 * h->Cp[1] * k * cip, nullptr) != DZN_OK)
-        throw EngineError(DZN_E_HIP, "fragment_major launch failed");
+        c.conv_s[0] == 5 && k == 3 && c.conv_s[1] == 2 && h->C[0] % 64 == 0 && h->C[0] >= 128 &&
+        h->Cp[0] == h->C[0] && h->Cp[1] == 160 && !getenv("DZN_NO_CONV01_FUSION")) {
+      // (C[0] >= 128: with a single 64-channel slab the kernel's epilogue statistics would race, frontend_fused.hip)
+      h->conv1_W2f = dalloc<u16>(h, (int64_t)2 * h->Cp[1] * k * cip, false);
+      h->conv1_wscf = dalloc<float>(h, h->Cp[1], false);
+      if (launch_split_weights_h2_frag(h->conv[1].W, h->Cp[1], k * cip, h->conv1_W2f, h->conv1_wscf, nullptr) != DZN_OK)
+        throw EngineError(DZN_E_HIP, "split_weights_h2_frag launch failed");
       HIPCHK(hipDeviceSynchronize());
     }
   }
@@ -1129,7 +1127,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
   }
   // DZN_PREC_F32_H2: conv0 + LN + GELU + conv1 in one kernel (frontend_fused.hip): conv0's 52 MB / window never
   // reach HBM.  (debug taps need the intermediate -> unfused)
-  const bool fuse01 = prec_is_h2(c.precision) && lnx && h->conv1_W2n && !h->debug && c.n_conv > 1 && T[1] > 0;
+  const bool fuse01 = prec_is_h2(c.precision) && lnx && h->conv1_W2f && !h->debug && c.n_conv > 1 && T[1] > 0;
   if (lnx && fuse01) {
   } else if (lnx) {
     chk(launch_conv0(wave, B, N, stats, h->conv0_w, h->conv_ln[0].g, h->conv_ln[0].b, h->C[0], h->Cp[0],
@@ -1160,7 +1158,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
     const bool ln_in_01 = i == 1 && fuse01 && lnx && i != last && !getenv("DZN_CONV01_NO_LN");
     if (i == 1 && fuse01)
       chk(launch_conv01_fused(wave, B, N, stats, h->conv0_w, h->conv_ln[0].g, h->conv_ln[0].b, h->conv0_lnq, h->C[0],
-                              T[0], T[1], h->conv1_W2n, h->conv1_wscn, h->Cp[1], h->conv0_bound, 1e-5f, nxt,
+                              T[0], T[1], h->conv1_W2f, h->conv1_wscf, h->Cp[1], h->conv0_bound, 1e-5f, nxt,
                               st, ln_in_01 ? h->conv_ln[1].g : nullptr, ln_in_01 ? h->conv_ln[1].b : nullptr, h->C[1],
                               ln_in_01 ? am(conv_slot(nxt)) : nullptr),
           "conv01 fused");

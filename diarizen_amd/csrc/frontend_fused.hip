@@ -4,25 +4,51 @@
 //     W2V/model.py:113, W2V/components.py:119-122, :63-70, :182-209
 //
 // Unfused, conv0's [T0 = 25 599, 512] fp32 activations are written to HBM (52.4 MB per 8 s window, 13.2 GB per
-// batch of 256) and read straight back as the A operand of conv1's contraction.  Here a workgroup owns 128 conv1
-// output frames of one window: it recomputes the 257 conv0 frames they touch, 64 channels at a time, as TWO fp16 planes
-// (the two-term split of gemm_split.hip, scaled by the exact power of two of conv0's static bound) in LDS, and feeds
-// conv1's MFMAs from there.  Only the waveform (0.5 MB / window) is read and conv1's raw output ([T1, Cp1] fp32,
-// 8.2 MB / window) is written.
+// batch of 256) and read straight back as the A operand of conv1's contraction.  Here they only ever exist in LDS, 64
+// channels (one "slab") at a time, as TWO fp16 planes (the two-term split of gemm_split.hip, scaled by the exact power of
+// two of conv0's static bound), and conv1's MFMAs are fed from there.  Only the waveform (0.5 MB / window) is read and
+// conv1's output ([T1, Cp1] fp32, 8.2 MB / window) is written.
+//
+// conv01_ws_kernel: one 512-thread workgroup per CU walks over (window, tile) items; a tile is 127 conv1 frames, i.e.
+// 255 conv0 frames + one spare = 256 lanes (row 127 of the 128-row MFMA tile is dead).  In every step of a slab-granular
+// pipeline, with ONE s_barrier per step and two plane buffers,
+//   * wavefronts 0-3 (producers) compute conv0 + LayerNorm + GELU + split of slab s + 1 into one buffer with one lane per
+//     FRAME: the frame's 10 samples, mean and 1/std stay in registers for the whole tile, the weights of two channels at a
+//     time arrive as scalars (s_load: w0 is [C0][10], two channels are 20 consecutive floats), conv0's 10 products are
+//     summed as (even taps, odd taps) on v_pk_fma_f32, the two channels share the LayerNorm / erf polynomial as one float2
+//     (packed fp32: two results per lane and issue slot), and 8 channels leave as ONE ds_write_b128 per plane — no LDS
+//     reads, ~30 issue slots per activation;
+//   * wavefronts 4-7 (consumers, 2 x 2 over the 128 x 160 tile, 64 x 80 outputs each) multiply slab s from the other
+//     buffer: 6 k-steps (3 taps x 2 blocks of 32 channels), W fragments straight from L2 into registers (a slab's W would
+//     not fit LDS next to the planes) — on every SIMD one VALU wavefront and one MFMA wavefront, by construction.
 //
 //   * LayerNorm statistics of a conv0 frame come from its 10 input samples: mean_c y = wbar . x, var_c y = x^T Q x
-//     (wbar / Q = mean / covariance over channels of the taps, built in double at load) -> no pass over the 512
-//     outputs, so a 64-channel slab can be normalised on its own.
-//   * K order of conv1 is (tap j, channel c) -> k = j * C0 + c, natural order inside every 32-block (the planes are
-//     written by lanes that own one channel each); the fp16 weight planes W2h [Cp1][K/32][2][32] are split in that
-//     order by split_weights_h2_natural_kernel.  A fragments: frame 2 t + j, 16-byte slot (kb * 4 + lq) ^ ((frame >> 1)
-//     & 7): the 16 lanes of a fragment read 8 distinct slots (rows two frames apart would all hit the same banks).
-//   * phases per 64-channel slab: [VALU] 4 wavefronts x 65 frames x 64 lanes = conv0 + LN + GELU + split -> LDS;
-//     [MFMA] 2 x 2 wavefronts, 64 x 80 outputs each, 6 k-steps (3 taps x 2 blocks), W fragments straight from L2 into
-//     registers (the slab's W would not fit LDS next to the planes).  Two workgroups per CU (74 KB of LDS each), so one
-//     multiplies while the other computes activations.
-#include <cstdlib>
-
+//     (wbar / Q = mean / covariance over channels of the taps, built in double at load; Q is kept as its factor F,
+//     Q = F^T F, so the variance is a sum of squares) -> no pass over the 512 outputs, so a slab can be normalised on its
+//     own.
+//   * K order of conv1 is (tap j, channel c) -> k = j * C0 + c, natural order inside every 32-block (a producer lane writes
+//     8 consecutive channels of its frame).  A fragments: frame 2 t + j, 16-byte slot (kb * 4 + lq) ^ ((frame >> 1) & 7):
+//     the 16 lanes of a fragment read 8 distinct slots (rows two frames apart would all hit the same banks).
+//   * W: fp16 planes in FRAGMENT-MAJOR order [K/32][Cp1/16][2 planes][16 rows][32] (split_weights_h2_frag_kernel, once
+//     per engine) — the 64 lanes of one fragment load (row lr, 16-byte piece lq) read ONE contiguous KB, a wavefront's
+//     whole k-step 10 contiguous KB.  In [row][K/32][2][32] order a fragment load touches sixteen 64-byte pieces 6 KB apart,
+//     and the consumers' W stream (40 KB per k-step and CU through the vector L1) then set the pace: 15.0 ms per
+//     561-window launch for the consumers alone against 11.3 ms with this order and 8.3 ms without any W traffic
+//     (profiles/r6_conv01_ws_probe.txt).
+//   * conv1's own LayerNorm + GELU is finished in the epilogue (the tile holds whole rows; the stand-alone pass re-read and
+//     re-wrote conv1's 3.1 GB per 374 windows).  The 160 channels of a row live in two wavefronts, so it needs one
+//     exchange: each leaves the mean and the centred sum of squares of ITS 80 (C1 - 80) channels in red[] before the
+//     step's barrier, both combine them after it (Chan et al.'s pairwise update: as stable as the two-pass form, one
+//     exchange instead of two) and finish the tile at the start of the next step, while the producers are already a slab
+//     into the next tile.  red[] is single-buffered: a tile's statistics are written in the LAST slab step and read in the
+//     next tile's FIRST, and only with two or more slabs does a barrier lie between that read and the next write — hence
+//     C0 >= 128 (launch_conv01_fused and the engine's eligibility test refuse one slab).
+//
+// Retired form: the phase-alternating kernel of rounds 2-5, which alternated a VALU phase (one lane per channel) and an
+// MFMA phase in 256-thread workgroups, two per CU, overlapping only by chance: 21.3 ms per 561-window launch against this
+// kernel's 17.9 (which names it).  Its records are profiles/r3_conv01_phase_probe.txt,
+// profiles/r5_conv01_probe.txt and profiles/r6_conv01_ws_probe.txt; its source, the environment switch that selected it and
+// the [row][K/32][2][32] weight planes it read were last in the tree at commit 153a62a (profiles/conv01_retirement_ab.txt).
 #include "checked.h"
 #include "common.h"
 #include "split.h"
@@ -31,11 +57,6 @@ DZN_CHECKED_TU(frontend_fused)
 
 namespace {
 
-constexpr int FF_BM = 128;                 // conv1 output frames per workgroup
-constexpr int FF_FR = 2 * FF_BM + 1;       // conv0 frames they read (k 3, s 2)
-constexpr int FF_ROW = 128;                // bytes per frame per plane: 64 channels fp16
-constexpr int FF_PLANE = (FF_FR + 3) * FF_ROW;
-
 struct FusedArgs {
   const float* wave;      // [B, N]
   const float* wstats;    // [B, 2] waveform (mean, rstd) or null
@@ -43,7 +64,7 @@ struct FusedArgs {
   const float* gamma0;    // [C0]
   const float* beta0;     // [C0]
   const float* lnq;       // [10 + 100]
-  const u16* W2h;         // conv1 fp16 planes, natural k order: [N1p][K/32][2][32], K = 3 * C0
+  const u16* W2h;         // conv1 fp16 planes, fragment-major: [K/32][N1p/16][2][16][32], K = 3 * C0
   const float* col_scale; // [N1p]
   float* out;             // [B, T1, N1p] raw conv1 output
   int N, T0, T1, C0, N1p;
@@ -54,256 +75,7 @@ struct FusedArgs {
   int C1;                      // real conv1 channels (<= N1p)
 };
 
-// Two independent 256-thread workgroups per CU: their phases overlap only by chance.  The form that forced the overlap (one
-// 512-thread workgroup carrying two tiles in anti-phase) measured slower and was removed: DESIGN.md §4.9,
-// profiles/r3_conv01_phase_probe.txt, profiles/r5_conv01_probe.txt.
-// UF: conv0 frames a wavefront carries through the VALU phase at once (independent 10-FMA -> LayerNorm -> erf chains that
-// interleave; 8 against 4: 22.03 -> 21.65 ms per 561-window launch, profiles/r5_conv01_probe.txt).
-constexpr int FF_UF = 8;
-constexpr int FF_LDS = (2 * FF_PLANE + (int)sizeof(float) * (5 * (FF_FR - 1) + 10 + 6 + 112) + (int)sizeof(float2) * FF_FR + 15) / 16 * 16;
-
-__global__ __launch_bounds__(256, 2) void conv01_fused_kernel(const FusedArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* pl0 = smem;                                   // hi plane  [FF_FR][64 ch] fp16, slots swizzled
-  unsigned char* pl1 = smem + FF_PLANE;                        // lo plane
-  float* sx = reinterpret_cast<float*>(smem + 2 * FF_PLANE);   // normalised samples of the strip
-  float2* sst = reinterpret_cast<float2*>(sx + (5 * (FF_FR - 1) + 10 + 6));   // (mean, rstd) per conv0 frame
-  // (r5) the 110 LayerNorm-statistics coefficients live in LDS (behind sst): as kernel-argument scalars they needed more SGPRs
-  // than a wavefront has (r2-r4: 153 spilled SGPRs, ~200 v_readlane reloads in the statistics loop; now 0 —
-  // profiles/r5_conv01_resources.txt)
-  float* slnq = reinterpret_cast<float*>(sst + FF_FR);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lr = lane & 15, lq = lane >> 4;
-  const int b = blockIdx.y;
-  const int t1_0 = (int)blockIdx.x * FF_BM;            // first conv1 frame of the tile
-  const int f0 = 2 * t1_0;                             // first conv0 frame
-  const int nfr = min(FF_FR, a.T0 - f0);               // conv0 frames that exist
-  const int nsamp = 5 * (nfr - 1) + 10;
-  const float wmean = a.wstats ? a.wstats[2 * b] : 0.f;
-  const float wrstd = a.wstats ? a.wstats[2 * b + 1] : 1.f;
-  const float* wp = a.wave + (int64_t)b * a.N + (int64_t)f0 * 5;
-  for (int i = tid; i < nsamp; i += 256) sx[i] = (wp[i] - wmean) * wrstd;
-  if (tid < 110) slnq[tid] = a.lnq[tid];
-  __syncthreads();
-  for (int f = tid; f < nfr; f += 256) {     // LayerNorm statistics from the 10 samples of the frame (see header)
-    float xv[10];
-#pragma unroll
-    for (int t = 0; t < 10; ++t) xv[t] = sx[f * 5 + t];
-    float mu = 0.f, var = 0.f;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-      mu = fmaf(slnq[i], xv[i], mu);
-      float q = 0.f;
-#pragma unroll
-      for (int j = 0; j < 10; ++j) q = fmaf(slnq[10 + i * 10 + j], xv[j], q);
-      var = fmaf(q, q, var);     // lnq rows are the factor F of Q = F^T F: a sum of squares
-    }
-    sst[f] = make_float2(mu, 1.0f / sqrtf(fmaxf(var, 0.f) + a.eps));
-  }
-
-  // MFMA roles: 2 x 2 wavefronts over the 128 x 160 tile
-  const int wm = wave >> 1, wn = wave & 1;
-  constexpr int MI = 4, NI = 5;
-  f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int KB = 3 * a.C0 / 32;            // 32-blocks of conv1's K
-  const int nslab = a.C0 / 64;
-
-  for (int slab = 0; slab < nslab; ++slab) {
-    __syncthreads();   // statistics written (first slab) / previous slab's planes fully consumed
-    // ---- VALU phase: conv0 + LayerNorm + GELU + two-term split of channel (slab * 64 + lane).  A wavefront takes
-    // frames wave, wave + 4, ...; FF_UF of them per iteration so that the long dependent chains (10 FMAs -> LayerNorm ->
-    // erf) of different frames interleave — with one frame at a time the chain latency, not the VALU rate, set the pace.
-    {
-      const int ch = slab * 64 + lane;
-      float w0[10];
-#pragma unroll
-      for (int t = 0; t < 10; ++t) w0[t] = a.w0[ch * 10 + t];
-      const float g0 = a.gamma0[ch], b0 = a.beta0[ch];
-      const int cslot = lane >> 3, cbyte = (lane & 7) * 2;
-      for (int fb = wave; fb < FF_FR; fb += 4 * FF_UF) {
-        float o[FF_UF];
-#pragma unroll
-        for (int u = 0; u < FF_UF; ++u) {
-          const int f = fb + 4 * u;
-          const int fc = f < nfr ? f : nfr - 1;            // clamped: results of frames past the strip are zeroed below
-          float acc0 = 0.f;
-#pragma unroll
-          for (int t = 0; t < 10; ++t) acc0 = fmaf(sx[fc * 5 + t], w0[t], acc0);
-          const float2 st = sst[fc];
-          o[u] = (acc0 - st.x) * st.y * g0 + b0;
-        }
-#pragma unroll
-        for (int u = 0; u < FF_UF; ++u) o[u] = gelu_erf(o[u]);
-#pragma unroll
-        for (int u = 0; u < FF_UF; ++u) {
-          const int f = fb + 4 * u;
-          if (f < FF_FR) {                                  // wave-uniform
-            const float xs = (f < nfr ? o[u] : 0.f) * a.a_scale;
-            const _Float16 hi = (_Float16)xs;
-            const _Float16 lo = (_Float16)(xs - (float)hi);
-            const int off = f * FF_ROW + ((cslot ^ ((f >> 1) & 7)) << 4) + cbyte;
-            DZN_CHECK(off + 2 <= FF_PLANE, 0x701, off);                                          // activation written inside its plane
-            *reinterpret_cast<_Float16*>(pl0 + off) = hi;
-            *reinterpret_cast<_Float16*>(pl1 + off) = lo;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    // ---- MFMA phase: 6 k-steps = 3 taps x 2 blocks of 32 channels; the W fragments of step ks + 1 are fetched
-    // (L2 -> registers) while step ks multiplies ----
-    auto load_w = [&](int ks, u32x4 (&wf)[NI][2]) {
-      const int j = ks >> 1, kb = ks & 1;
-      const int kblk = j * (a.C0 / 32) + slab * 2 + kb;
-#pragma unroll
-      for (int jn = 0; jn < NI; ++jn) {
-        const int n = wn * 80 + jn * 16 + lr;
-        const u16* wpn = a.W2h + ((int64_t)n * KB + kblk) * 64 + lq * 8;
-        DZN_CHECK(n < a.N1p && kblk < KB, 0x703, kblk);                                              // weight fragment inside the planes
-        wf[jn][0] = *reinterpret_cast<const u32x4*>(wpn);
-        wf[jn][1] = *reinterpret_cast<const u32x4*>(wpn + 32);
-      }
-    };
-    auto mma_step = [&](int ks, const u32x4 (&wf)[NI][2]) {
-      const int j = ks >> 1, kb = ks & 1;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int f = 2 * (wm * 64 + i * 16 + lr) + j;
-        const int off = f * FF_ROW + (((kb * 4 + lq) ^ ((f >> 1) & 7)) << 4);
-        DZN_CHECK(f < FF_FR + 3 && off + 16 <= FF_PLANE, 0x702, f);                                  // conv1 fragment (frame 2 t + tap) inside the plane
-        u32x4 af[2];
-        af[0] = *reinterpret_cast<const u32x4*>(pl0 + off);
-        af[1] = *reinterpret_cast<const u32x4*>(pl1 + off);
-#pragma unroll
-        for (int tt = 0; tt < 3; ++tt)
-#pragma unroll
-          for (int jn = 0; jn < NI; ++jn)
-            acc[i][jn] = mfma_np<2>(wf[jn][SplitTerms<2>::A[tt]], af[SplitTerms<2>::B[tt]], acc[i][jn]);
-      }
-    };
-    u32x4 wfa[NI][2], wfb[NI][2];
-    load_w(0, wfa);
-#pragma unroll
-    for (int ks = 0; ks < 6; ks += 2) {
-      load_w(ks + 1, wfb);
-      mma_step(ks, wfa);
-      if (ks + 2 < 6) load_w(ks + 2, wfa);
-      mma_step(ks + 1, wfb);
-    }
-  }
-
-  // ---- epilogue: lane (lr, lq) of block (i, jn) holds frame t1_0 + wm*64 + i*16 + lr, channels n0 .. n0 + 3 ----
-  float* ob = a.out + (int64_t)b * a.T1 * a.N1p;
-  // undo the exact power-of-two operand scales first
-#pragma unroll
-  for (int jn = 0; jn < NI; ++jn) {
-    const float4 c4 = *reinterpret_cast<const float4*>(a.col_scale + wn * 80 + jn * 16 + lq * 4);
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      acc[i][jn][0] *= a.a_inv * c4.x; acc[i][jn][1] *= a.a_inv * c4.y;
-      acc[i][jn][2] *= a.a_inv * c4.z; acc[i][jn][3] *= a.a_inv * c4.w;
-    }
-  }
-  if (a.gamma1) {
-    // r3: conv1's channel LayerNorm + GELU (W2V/components.py:63-70, 119-122) finished HERE: the 160 channels of a frame
-    // live in the two wavefronts wn = 0 / 1 of its row half, so the two row reductions (mean, then centred squares: the
-    // same two-pass arithmetic as norm.hip) go lane group -> wavefront (xor shuffles) -> the sibling wavefront through
-    // LDS.  The stand-alone pass it replaces re-read and re-wrote conv1's 3.1 GB per 374 windows.
-    __syncthreads();                                   // the planes are dead: their LDS carries the row partials now
-    float* red = reinterpret_cast<float*>(smem);       // [2 wn][128 rows]
-    float mean[MI], rstd[MI];
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        float s1 = 0.f;
-#pragma unroll
-        for (int jn = 0; jn < NI; ++jn)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const bool in = wn * 80 + jn * 16 + lq * 4 + e < a.C1;
-            const float d = pass == 0 ? acc[i][jn][e] : acc[i][jn][e] - mean[i];
-            s1 += in ? (pass == 0 ? d : d * d) : 0.f;
-          }
-        s1 += __shfl_xor(s1, 16, 64);
-        s1 += __shfl_xor(s1, 32, 64);
-        if (lq == 0) red[wn * 128 + wm * 64 + i * 16 + lr] = s1;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int r = wm * 64 + i * 16 + lr;
-        const float tot = red[r] + red[128 + r];        // fixed order: wn 0 then wn 1 on both wavefronts
-        if (pass == 0) mean[i] = tot / (float)a.C1;
-        else rstd[i] = 1.0f / sqrtf(tot / (float)a.C1 + a.eps);
-      }
-      __syncthreads();
-    }
-    float mx = 0.f;   // |max| over the rows that exist (rows past the strip hold finite junk from clamped frames)
-#pragma unroll
-    for (int jn = 0; jn < NI; ++jn) {
-      const int n0 = wn * 80 + jn * 16 + lq * 4;
-      float g[4], be[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        g[e] = n0 + e < a.C1 ? a.gamma1[n0 + e] : 0.f;
-        be[e] = n0 + e < a.C1 ? a.beta1[n0 + e] : 0.f;
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int t1 = t1_0 + wm * 64 + i * 16 + lr;
-        if (t1 >= a.T1) continue;
-        float o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          o[e] = n0 + e < a.C1 ? gelu_erf((acc[i][jn][e] - mean[i]) * rstd[i] * g[e] + be[e]) : 0.f;
-          mx = fmaxf(mx, fabsf(o[e]));
-        }
-        *reinterpret_cast<float4*>(ob + (int64_t)t1 * a.N1p + n0) = make_float4(o[0], o[1], o[2], o[3]);
-      }
-    }
-    if (a.amax1) track_amax(a.amax1 + b, mx);
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int t1 = t1_0 + wm * 64 + i * 16 + lr;
-    if (t1 >= a.T1) continue;
-#pragma unroll
-    for (int jn = 0; jn < NI; ++jn) {
-      const int n0 = wn * 80 + jn * 16 + lq * 4;
-      const f32x4 v = acc[i][jn];
-      *reinterpret_cast<float4*>(ob + (int64_t)t1 * a.N1p + n0) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
-}
-
-// ---- r6: producer / consumer wavefronts, persistent workgroups (conv01_ws_kernel) ---------------------------------------
-// conv01_fused_kernel above alternates its two phases per workgroup and relies on a second workgroup of the CU being in the
-// other phase: measured alone the VALU phase takes 11.7 ms and the MFMA phase 12.5 ms per 561-window launch, together 21.3 —
-// they overlap by chance, and BOTH are inefficient on their own (the VALU phase issues ~47 slots per activation, 14 of them LDS
-// traffic with one lane per CHANNEL: 10 broadcast sample reads and two 2-byte plane writes per frame; the MFMA phase keeps the
-// matrix pipe 36 % busy).  Here one 512-thread workgroup per CU walks over (window, tile) items, and in every step of a
-// slab-granular pipeline
-//   * wavefronts 0-3 (producers) compute conv0 + LayerNorm + GELU + split of slab s + 1 into one of two plane buffers with one
-//     lane per FRAME: the frame's 10 samples, mean and 1/std stay in registers for the whole tile, the weights of two channels
-//     at a time arrive as scalars (s_load: w0 is [C0][10], two channels are 20 consecutive floats), conv0's 10 products are
-//     summed as (even taps, odd taps) on v_pk_fma_f32, the two channels share the LayerNorm / erf polynomial as one float2
-//     (packed fp32: two results per lane and issue slot), and 8 channels leave as ONE ds_write_b128 per plane — no LDS reads,
-//     ~30 issue slots per activation;
-//   * wavefronts 4-7 (consumers) multiply slab s from the other buffer (same fragments and MFMA order as above) — on every
-//     SIMD one VALU wavefront and one MFMA wavefront, by construction, with ONE s_barrier per step;
-//   * a tile is 127 conv1 frames (255 conv0 frames + one spare = 256 lanes; row 127 of the 128-row MFMA tile is dead), and
-//     conv1's LayerNorm + GELU epilogue needs one exchange between the two wavefronts that share a row: each leaves the mean and
-//     the centred sum of squares of ITS 80 (73) channels before the step's barrier, both combine them after it (Chan et al.'s
-//     pairwise update: as stable as the two-pass form, one exchange instead of two) and finish the tile at the start of the next
-//     step, while the producers are already a slab into the next tile.
+constexpr int FF_ROW = 128;                    // bytes per frame per plane: 64 channels fp16
 constexpr int WS_OUT = 127;                    // conv1 frames stored per tile
 constexpr int WS_ROWS = 258;                   // plane rows: frames 0 .. 256 are read (row 256 only by the dead MFMA row), one slack
 constexpr int WS_PLANE = WS_ROWS * FF_ROW;
@@ -444,8 +216,8 @@ __global__ __launch_bounds__(512, 1) void conv01_ws_kernel(const FusedArgs a, co
   bool pending = false;                              // the previous tile's epilogue waits for the sibling's row statistics
   int p_b = 0, p_t1 = 0;
   u32x4 wfa[NI][2], wfb[NI][2];                      // W fragments of two consecutive k-steps (wfa lives across the step barrier)
-  // fragment-major copy of the planes (fragment_major_kernel, behind the natural-order copy): [kblk][n / 16][plane][16][32]
-  const u16* wbase = a.W2h + (int64_t)2 * a.N1p * 3 * a.C0 + (wn * 5) * 1024 + lr * 32 + lq * 8;
+  // fragment-major planes: [kblk][n / 16][plane][16][32]
+  const u16* wbase = a.W2h + (wn * 5) * 1024 + lr * 32 + lq * 8;
   // finish the LayerNorm + GELU epilogue of the pending tile: the sibling's (mean, M2) were written before the last barrier
   auto finish = [&]() {
     float* ob = a.out + (int64_t)p_b * a.T1 * a.N1p;
@@ -621,75 +393,49 @@ __global__ __launch_bounds__(512, 1) void conv01_ws_kernel(const FusedArgs a, co
   if (pending) finish();
 }
 
-// W [rows][K] fp32 -> fp16 planes [rows][K/32][2][32] in NATURAL k order (the fused kernel writes its A planes channel
-// by channel), w * 2^e_row with max |row| in [2^14, 2^15); col_scale[row] = 2^-e_row
-__global__ __launch_bounds__(256) void split_weights_h2_natural_kernel(const float* __restrict__ W, int64_t rows, int K,
-                                                                       u16* __restrict__ W2, float* __restrict__ col_scale) {
+// W [rows][K] fp32 -> conv1's fp16 planes in fragment-major order [K/32][rows/16][2][16][32] (header of this file), natural
+// k order inside every 32-block: w * 2^e_row with max |row| in [2^14, 2^15); col_scale[row] = 2^-e_row.  One wavefront per row.
+__global__ __launch_bounds__(256) void split_weights_h2_frag_kernel(const float* __restrict__ W, int rows, int K,
+                                                                    u16* __restrict__ W2, float* __restrict__ col_scale) {
   const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int r = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   float m = 0.f;
-  for (int k = lane; k < K; k += 64) m = fmaxf(m, fabsf(W[r * K + k]));
+  for (int k = lane; k < K; k += 64) m = fmaxf(m, fabsf(W[(int64_t)r * K + k]));
   m = wave_max(m);
   float sc, inv;
   h2_scale(m, sc, inv);
   if (lane == 0) col_scale[r] = inv;
   for (int k = lane; k < K; k += 64) {
-    const float x = W[r * K + k] * sc;
+    const float x = W[(int64_t)r * K + k] * sc;
     const _Float16 h = (_Float16)x;
     const _Float16 l = (_Float16)(x - (float)h);
-    u16* o = W2 + r * 2 * K + (int64_t)(k >> 5) * 64 + (k & 31);
+    u16* o = W2 + ((int64_t)(k >> 5) * (rows / 16) + (r >> 4)) * 1024 + (r & 15) * 32 + (k & 31);
     o[0] = __builtin_bit_cast(u16, h);
-    o[32] = __builtin_bit_cast(u16, l);
+    o[512] = __builtin_bit_cast(u16, l);
   }
-}
-
-// conv1's planes for conv01_ws_kernel: [K/32][N/16][2 planes][16 rows][32] — the 64 lanes of one fragment load
-// (row lr, 16-byte piece lq) read ONE contiguous KB, a wavefront's whole k-step 10 contiguous KB.  In the [row][K/32][2][32]
-// order above a fragment load touches sixteen 64-byte pieces 6 KB apart, and the consumers' W stream (40 KB per k-step and CU
-// through the vector L1) then set the pace: 15.0 ms per 561-window launch for the consumers alone against 11.3 ms with this
-// order and 8.3 ms without any W traffic (profiles/r6_conv01_ws_probe.txt).
-__global__ __launch_bounds__(256) void fragment_major_kernel(const u16* __restrict__ W2, int rows, int KB, u16* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;      // one 16-byte piece each
-  const int64_t total = (int64_t)rows * KB * 2 * 4;
-  if (idx >= total) return;
-  const int lq = (int)(idx & 3);
-  const int lr = (int)((idx >> 2) & 15);
-  const int pl = (int)((idx >> 6) & 1);
-  const int64_t rest = idx >> 7;
-  const int nb = (int)(rest % (rows / 16)), kblk = (int)(rest / (rows / 16));
-  const int n = nb * 16 + lr;
-  const u32x4 v = *reinterpret_cast<const u32x4*>(W2 + ((int64_t)n * KB + kblk) * 64 + pl * 32 + lq * 8);
-  *reinterpret_cast<u32x4*>(out + idx * 8) = v;
 }
 
 }  // namespace
 
-// second copy of conv1's planes in fragment-major order (rows % 16 == 0), written behind the first: out = W2 + 2 rows K
-int launch_fragment_major(const void* W2, int rows, int K, void* out, hipStream_t s) {
+int launch_split_weights_h2_frag(const float* W, int rows, int K, void* W2, float* col_scale, hipStream_t s) {
   if (rows <= 0 || (rows & 15) || K <= 0 || (K & 31)) return DZN_E_INVALID;
-  const int64_t total = (int64_t)rows * (K / 32) * 8;
-  hipLaunchKernelGGL(fragment_major_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, s, static_cast<const u16*>(W2), rows, K / 32,
-                     static_cast<u16*>(out));
+  hipLaunchKernelGGL(split_weights_h2_frag_kernel, dim3((unsigned)(rows / 4)), dim3(256), 0, s, W, rows, K, static_cast<u16*>(W2),
+                     col_scale);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
-int launch_split_weights_h2_natural(const float* W, int64_t rows, int K, void* W2, float* col_scale, hipStream_t s) {
-  if (rows <= 0) return DZN_OK;
-  if (K <= 0 || (K & 31)) return DZN_E_INVALID;
-  hipLaunchKernelGGL(split_weights_h2_natural_kernel, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, s, W, rows, K,
-                     static_cast<u16*>(W2), col_scale);
-  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
-}
-
-// conv0 (k 10, s 5, C0 % 64 == 0) + LN + GELU + conv1 (k 3, s 2, 160 padded outputs): out = raw conv1 [B, T1, 160]
+// conv0 (k 10, s 5, C0 % 64 == 0, at least two slabs) + LN + GELU + conv1 (k 3, s 2, 160 padded outputs): out = conv1
+// [B, T1, 160], raw or (gamma1) through its LayerNorm + GELU
 int launch_conv01_fused(const float* wave, int B, int N, const float* wstats, const float* w0, const float* gamma0,
                         const float* beta0, const float* lnq, int C0, int T0, int T1, const void* W2h,
                         const float* col_scale, int N1p, float act_bound, float eps, float* out, hipStream_t st,
                         const float* gamma1, const float* beta1, int C1, float* amax1) {
   if (B <= 0 || T1 <= 0) return DZN_OK;
-  if (gamma1 && (!beta1 || C1 <= 0 || C1 > N1p)) return DZN_E_INVALID;
-  if ((C0 & 63) || N1p != 160 || !lnq || !W2h || !col_scale || !(act_bound > 0.f)) return DZN_E_INVALID;
+  // the epilogue's second wavefront of a row owns C1 - 80 channels
+  if (gamma1 && (!beta1 || C1 <= 80 || C1 > N1p)) return DZN_E_INVALID;
+  // one slab (C0 == 64) would race on red[]: header of this file
+  if (C0 < 128 || (C0 & 63) || N1p != 160 || !lnq || !W2h || !col_scale || !(act_bound > 0.f)) return DZN_E_INVALID;
   FusedArgs a{};
   a.wave = wave; a.wstats = wstats; a.w0 = w0; a.gamma0 = gamma0; a.beta0 = beta0; a.lnq = lnq;
   a.W2h = static_cast<const u16*>(W2h); a.col_scale = col_scale; a.out = out;
@@ -701,34 +447,23 @@ int launch_conv01_fused(const float* wave, int B, int N, const float* wstats, co
     a.a_scale = ldexpf(1.0f, 15 - e);
     a.a_inv = ldexpf(1.0f, e - 15);
   }
-  static unsigned long long attr_mask = 0;
-  if (first_use_on_device(attr_mask))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv01_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  const int ntile = (T1 + FF_BM - 1) / FF_BM;
   // algorithmic work: conv0 + conv1 flops; algorithmic HBM bytes: waveform in, conv1's raw output out
   const int pid = prof_begin(st, "conv01_fused", 2.0 * B * ((double)T0 * C0 * 10 + (double)T1 * 153.0 * 3 * C0),
                              B * (4.0 * N + 4.0 * (double)T1 * N1p));
-  // (r6) producer / consumer wavefronts in persistent workgroups (conv01_ws_kernel); DZN_CONV01_WS=0: the phase-alternating kernel
-  const char* ws_env = getenv("DZN_CONV01_WS");      // read per call (tests compare the two kernels in one process)
-  const bool ws = !(ws_env && atoi(ws_env) == 0);
-  if (ws && (!gamma1 || (C1 > 80 && C1 <= 160))) {
-    static unsigned long long ws_mask = 0;
-    static int cus[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (first_use_on_device(ws_mask)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv01_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      int n = 0;
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      cus[dev & 63] = n;
-    }
-    const int wtile = (T1 + WS_OUT - 1) / WS_OUT;
-    const int64_t items = (int64_t)B * wtile;
-    const int grid = (int)(items < cus[dev & 63] ? items : cus[dev & 63]);
-    hipLaunchKernelGGL(conv01_ws_kernel, dim3(grid), dim3(512), WS_LDS, st, a, B, wtile);
-  } else {
-    hipLaunchKernelGGL(conv01_fused_kernel, dim3(ntile, B), dim3(256), FF_LDS, st, a);
+  static unsigned long long attr_mask = 0;
+  static int cus[64];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (first_use_on_device(attr_mask)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv01_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev & 63] = n;
   }
+  const int ntile = (T1 + WS_OUT - 1) / WS_OUT;
+  const int64_t items = (int64_t)B * ntile;
+  const int grid = (int)(items < cus[dev & 63] ? items : cus[dev & 63]);
+  hipLaunchKernelGGL(conv01_ws_kernel, dim3(grid), dim3(512), WS_LDS, st, a, B, ntile);
   prof_end(pid, st);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }

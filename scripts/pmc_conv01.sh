@@ -1,5 +1,5 @@
 #!/bin/bash
-# hardware counters of the fused front end (conv01_ws_kernel / conv01_fused_kernel) inside one 561-window forward:
+# hardware counters of the fused front end (conv01_ws_kernel) inside one 561-window forward:
 # three rocprofv3 --pmc passes (kernel trace only), summarised per kernel by scripts/pmc_kernel_summary.py
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_conv01; rm -rf $O; mkdir -p $O

@@ -421,7 +421,7 @@ def test_seg_from_a_checkpoint_embedded_config_end_to_end(built_lib, gpu, name, 
 def test_conv01_fusion_matches_unfused(built_lib, gpu, monkeypatch):
     """frontend_fused.hip (f32h): conv0 + LN + GELU + conv1 in one kernel (conv0's activations never reach HBM) against
     the same engine with the fusion switched off — both run through the oracle-checked f32h path; windows of different
-    lengths exercise the ragged last tile (T1 % 128 != 0) and conv0 frames past the end of the strip."""
+    lengths exercise the ragged last tile (T1 % 127 != 0) and conv0 frames past the end of the window."""
     from diarizen_amd.configs import get_seg_config
     from diarizen_amd.engine import Engine
     from testkit.weights import turn_taking_state_dict
@@ -442,28 +442,83 @@ def test_conv01_fusion_matches_unfused(built_lib, gpu, monkeypatch):
         monkeypatch.setenv("DZN_CONV01_NO_LN", "1")
         l2, m2 = fused.segment(wave.to(gpu))
         monkeypatch.delenv("DZN_CONV01_NO_LN")
-        # (r6) the default is the producer / consumer kernel (conv01_ws_kernel: 127-frame tiles, one lane per conv0 frame, packed
-        # fp32, pairwise LayerNorm statistics in the epilogue); DZN_CONV01_WS=0 (read per call) runs the phase-alternating kernel it
-        # replaced, with and without the LayerNorm epilogue
-        monkeypatch.setenv("DZN_CONV01_WS", "0")
-        l3, m3 = fused.segment(wave.to(gpu))
-        monkeypatch.setenv("DZN_CONV01_NO_LN", "1")
-        l4, m4 = fused.segment(wave.to(gpu))
-        monkeypatch.delenv("DZN_CONV01_NO_LN")
-        monkeypatch.delenv("DZN_CONV01_WS")
         torch.cuda.synchronize()
         d = (lf - lp_).abs().max().item()
         d2 = (lf - l2).abs().max().item()
-        d3 = max((lf - l3).abs().max().item(), (l2 - l4).abs().max().item())
-        print(f"N={N}: max |logp fused - unfused| = {d:.2e}; LN in the epilogue vs stand-alone = {d2:.2e}; "
-              f"producer / consumer kernel vs the phase-alternating one = {d3:.2e}")
-        assert d <= 2e-4 and d2 <= 2e-4 and d3 <= 2e-4
-        assert torch.equal(mf, mp) and torch.equal(mf, m2) and torch.equal(mf, m3) and torch.equal(mf, m4)
-        if N == 33333:
-            ref = seg_model.seg_forward(sd, cfg, wave)
-            assert (lf.cpu() - ref).abs().max().item() <= 1e-3
+        print(f"N={N}: max |logp fused - unfused| = {d:.2e}; LN in the epilogue vs stand-alone = {d2:.2e}")
+        assert d <= 2e-4 and d2 <= 2e-4
+        assert torch.equal(mf, mp) and torch.equal(mf, m2)
+        ref = seg_model.seg_forward(sd, cfg, wave)
+        assert (lf.cpu() - ref).abs().max().item() <= 1e-3
         fused.close()
         plain.close()
+
+
+def _segment_profiled(eng, wave):
+    """(logp, multilabel, kernel classes the in-situ profiler recorded) of one segment() call"""
+    from diarizen_amd import _lib
+    _lib.profile_enable(True)
+    try:
+        logp, ml = eng.segment(wave)
+        torch.cuda.synchronize()
+        names = {p["name"] for p in _lib.profile_collect()}
+    finally:
+        _lib.profile_enable(False)
+    return logp.cpu(), ml.cpu(), names
+
+
+def _fused_and_generic(cfg, sd, wave, gpu, monkeypatch):
+    """the default f32h engine and one created under DZN_NO_CONV01_FUSION=1 on the same input"""
+    from diarizen_amd.engine import Engine
+    B, N = wave.shape
+    out = []
+    for no_fusion in (False, True):
+        if no_fusion:
+            monkeypatch.setenv("DZN_NO_CONV01_FUSION", "1")
+        eng = Engine(cfg, sd, max_batch=B, max_samples=N, precision="f32h", device=gpu)
+        monkeypatch.delenv("DZN_NO_CONV01_FUSION", raising=False)
+        out.append(_segment_profiled(eng, wave.to(gpu)))
+        eng.close()
+    return out
+
+
+@pytest.mark.parametrize("B,N", [(24, 16000), (2, 2000)])
+def test_conv01_fusion_at_the_smallest_channel_count(built_lib, gpu, monkeypatch, B, N):
+    """The fused front end at the fewest conv0 channels it accepts: C0 = 128 (two 64-channel slabs: one barrier lies between
+    reading a tile's row statistics and writing the next tile's), C1 = 153 in Cp1 = 160.  B = 24 x N = 16000: T1 = 1599 = 12
+    tiles of 127 + a ragged 13th, 312 (window, tile) items on at most 256 workgroups, so workgroups take a second item;
+    B = 2 x N = 2000: 4 items, a grid smaller than the CU count.  Bars of this file: the oracle's 1e-3, and no more than
+    2e-4 beyond the generic path's own error."""
+    from dataclasses import replace
+    from diarizen_amd.configs import TINY_LN
+    from oracle import seg_model
+    from oracle.gen_golden import synth_wave
+    cfg = replace(TINY_LN, name="tiny_ln_c128", conv_channels=(128, 153, 40, 45, 52, 33, 43))
+    sd = seg_model.seg_state_dict(cfg, 0)
+    wave = synth_wave(B, N, 7)
+    (lf, mf, kf), (lu, mu, ku) = _fused_and_generic(cfg, sd, wave, gpu, monkeypatch)
+    assert "conv01_fused" in kf and "conv01_fused" not in ku
+    ref = seg_model.seg_forward(sd, cfg, wave)
+    e_f, e_u = (lf - ref).abs().max().item(), (lu - ref).abs().max().item()
+    print(f"B={B} N={N}: max |logp - oracle| fused {e_f:.2e}, generic {e_u:.2e}")
+    assert e_f <= 1e-3 and e_f <= e_u + 2e-4
+    assert torch.equal(mf, mu)
+
+
+def test_conv01_not_fused_with_one_slab(built_lib, gpu, monkeypatch):
+    """C0 = 64 is one slab: the fused kernel's single-buffered row statistics would be overwritten while the sibling
+    wavefront still reads them, so the engine takes the generic path — the same bits as under DZN_NO_CONV01_FUSION=1."""
+    from dataclasses import replace
+    from diarizen_amd.configs import TINY_LN
+    from oracle import seg_model
+    from oracle.gen_golden import synth_wave
+    cfg = replace(TINY_LN, name="tiny_ln_c64", conv_channels=(64, 153, 40, 45, 52, 33, 43))
+    sd = seg_model.seg_state_dict(cfg, 0)
+    wave = synth_wave(3, 16000, 7)
+    (ld, md, kd), (lu, mu, ku) = _fused_and_generic(cfg, sd, wave, gpu, monkeypatch)
+    assert "conv01_fused" not in kd and "conv01_fused" not in ku
+    assert torch.equal(ld, lu) and torch.equal(md, mu)
+    assert (ld - seg_model.seg_forward(sd, cfg, wave)).abs().max().item() <= 1e-3
 
 
 def test_conv0_layernorm_statistics_survive_band_pass_taps_on_low_frequency_audio(built_lib, gpu, monkeypatch):
