@@ -136,11 +136,15 @@ __global__ __launch_bounds__(256) void cluster_accum_kernel(const uint8_t* __res
 // (start[] is non-decreasing: closest_frame of increasing times) and reproduces that sequence; the file is compiled with
 // -ffp-contract=off, and the float64 adds are spelled __dadd_rn so no contraction can creep in.  score * mask is 0 or 1, so the
 // float64 product is the host's weight table w[l] = hamming[l] * warm_up[l] (the same two factors, the same product) or 0.
+// The kernel computes frames [t0, t1) into rows t - t0 (dzn_detect: t0 = 0; dzn_detect_range: the frames a new window
+// changed): a frame's walk depends on nothing but t, so a range is the same bits as the same rows of the whole.
 __global__ __launch_bounds__(256) void detect_scores_kernel(const uint8_t* __restrict__ seg, int C, int L, int S,
                                                             const int32_t* __restrict__ start, const double* __restrict__ w,
-                                                            int T, int tasks, int K, float* __restrict__ scores) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= T) return;
+                                                            int t0, int t1, int tasks, int K, float* __restrict__ scores) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= t1 - t0) return;
+  const int t = t0 + row;
+  DZN_CHECK(row >= 0 && t >= t0 && t < t1, 0x804, row);
   // covering windows: start[c] <= t < start[c] + L  ->  c in [c0, c1)
   int lo = 0, hi = C;
   while (lo < hi) {
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(256) void detect_scores_kernel(const uint8_t* __res
   }
   // average = acc / max(cnt, epsilon) in float32 (count_finalize_kernel); frames no window covers are `missing` = 0
   const float den = fmaxf(cnt, 1e-12f);
-  float* out = scores + (int64_t)t * K;
+  float* out = scores + (int64_t)row * K;
   int k = 0;
   if (tasks & 1) out[k++] = c1 > c0 ? __fdiv_rn(sp, den) : 0.f;
   if (tasks & 2) out[k++] = c1 > c0 ? __fdiv_rn(ov, den) : 0.f;
@@ -183,18 +187,23 @@ __global__ __launch_bounds__(256) void detect_scores_kernel(const uint8_t* __res
 // the reference compares numpy float32 scalars with Python floats, which numpy >= 2 (NEP 50) evaluates in float32.
 // One workgroup per task column; each thread owns a contiguous chunk, chunk summaries (-1 = no decisive frame) are combined
 // by a Hillis-Steele scan in LDS (right-most defined value wins), then every thread re-walks its chunk from its entry state.
+// The scan runs over the n frames [t0, t0 + n) held in rows 0 .. n of scores / active.  Only GLOBAL frame 0 decides
+// unconditionally; for t0 > 0 the state before the first decisive frame of the range is entry[k], the state of frame
+// t0 - 1 (a range with no decisive frame keeps it throughout).
 constexpr int kHystThreads = 1024;
 
-__global__ __launch_bounds__(kHystThreads) void hysteresis_kernel(const float* __restrict__ scores, int T, int K,
-                                                                  float onset, float offset, uint8_t* __restrict__ active) {
+__global__ __launch_bounds__(kHystThreads) void hysteresis_kernel(const float* __restrict__ scores, int t0, int n, int K,
+                                                                  float onset, float offset,
+                                                                  const uint8_t* __restrict__ entry,
+                                                                  uint8_t* __restrict__ active) {
   __shared__ int8_t sv[kHystThreads];
   const int k = blockIdx.x, tid = threadIdx.x;
-  const int per = (T + kHystThreads - 1) / kHystThreads;
-  const int t0 = min(tid * per, T), t1 = min(t0 + per, T);
+  const int per = (n + kHystThreads - 1) / kHystThreads;
+  const int r0 = min(tid * per, n), r1 = min(r0 + per, n);
   int v = -1;
-  for (int t = t0; t < t1; ++t) {
-    const float y = scores[(int64_t)t * K + k];
-    if (t == 0) v = y > onset;
+  for (int r = r0; r < r1; ++r) {
+    const float y = scores[(int64_t)r * K + k];
+    if (t0 + r == 0) v = y > onset;
     else if (y > onset) v = 1;
     else if (y < offset) v = 0;
   }
@@ -206,14 +215,21 @@ __global__ __launch_bounds__(kHystThreads) void hysteresis_kernel(const float* _
     sv[tid] = mine >= 0 ? mine : left;
     __syncthreads();
   }
-  int state = tid > 0 ? sv[tid - 1] : -1;       // entry state of this chunk: defined whenever the chunk is not empty
-  DZN_CHECK(t0 == t1 || tid == 0 || state >= 0, 0x803, tid);
-  for (int t = t0; t < t1; ++t) {
-    const float y = scores[(int64_t)t * K + k];
-    if (t == 0) state = y > onset;
+  // entry state of this chunk: the last decisive frame to its left in the range, else the caller's (t0 > 0); with t0 == 0
+  // frame 0 is decisive, so every later chunk finds one and thread 0 needs none
+  int state = tid > 0 ? sv[tid - 1] : -1;
+  if (state < 0 && t0 > 0) {
+    DZN_CHECK(entry[k] <= 1, 0x805, entry[k]);
+    state = entry[k] != 0;
+  }
+  DZN_CHECK(r0 == r1 || (t0 == 0 && tid == 0) || state >= 0, 0x803, tid);
+  for (int r = r0; r < r1; ++r) {
+    const float y = scores[(int64_t)r * K + k];
+    if (t0 + r == 0) state = y > onset;
     else if (y > onset) state = 1;
     else if (y < offset) state = 0;
-    active[(int64_t)t * K + k] = (uint8_t)state;
+    DZN_CHECK(r >= 0 && r < n && state >= 0, 0x806, r);
+    active[(int64_t)r * K + k] = (uint8_t)state;
   }
 }
 
@@ -310,19 +326,31 @@ extern "C" int dzn_cluster_activations(const uint8_t* d_seg, const int8_t* d_har
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
+extern "C" int dzn_detect_range(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame,
+                                const double* d_weight, int32_t t0, int32_t t1, int32_t tasks, float onset, float offset,
+                                const uint8_t* d_entry, float* d_scores, uint8_t* d_active, void* stream) {
+  if (!d_seg || !d_start_frame || !d_weight || !d_scores || C < 0 || L < 1 || S < 1 || S > 8 || t0 < 0 || t1 < t0 ||
+      (tasks & 3) == 0 || (tasks & ~3) != 0 || !(offset <= onset) || (t0 > 0 && !d_entry))
+    return DZN_E_INVALID;
+  if (t1 == t0) return DZN_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int K = (tasks & 1) + ((tasks >> 1) & 1);
+  const int n = t1 - t0;
+  hipLaunchKernelGGL(detect_scores_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_seg, C, L, S, d_start_frame, d_weight, t0,
+                     t1, tasks, K, d_scores);
+  if (d_active)
+    hipLaunchKernelGGL(hysteresis_kernel, dim3(K), dim3(kHystThreads), 0, st, d_scores, t0, n, K, onset, offset, d_entry,
+                       d_active);
+  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+// the whole recording is the range [0, T) with no entry state
 extern "C" int dzn_detect(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame,
                           const double* d_weight, int32_t T, int32_t tasks, float onset, float offset, float* d_scores,
                           uint8_t* d_active, void* stream) {
-  if (!d_seg || !d_start_frame || !d_weight || !d_scores || C < 0 || L < 1 || S < 1 || S > 8 || T < 1 ||
-      (tasks & 3) == 0 || (tasks & ~3) != 0 || !(offset <= onset))
-    return DZN_E_INVALID;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int K = (tasks & 1) + ((tasks >> 1) & 1);
-  hipLaunchKernelGGL(detect_scores_kernel, dim3((T + 255) / 256), dim3(256), 0, st, d_seg, C, L, S, d_start_frame, d_weight, T,
-                     tasks, K, d_scores);
-  if (d_active)
-    hipLaunchKernelGGL(hysteresis_kernel, dim3(K), dim3(kHystThreads), 0, st, d_scores, T, K, onset, offset, d_active);
-  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+  if (T < 1) return DZN_E_INVALID;
+  return dzn_detect_range(d_seg, C, L, S, d_start_frame, d_weight, 0, T, tasks, onset, offset, nullptr, d_scores, d_active,
+                          stream);
 }
 
 extern "C" int dzn_speaker_scores(const float* d_soft, const int8_t* d_hard, int32_t C, int32_t L, int32_t S,

@@ -13,6 +13,12 @@ post-processing of Binarize (PA/utils/signal.py:207-317) and the RTTM are made o
 
     vad = VoiceActivityDetection.from_pretrained("path/to/hub_dir")      # or VoiceActivityDetection(diarizen_pipeline)
     speech = vad("audio.wav")                                            # Annotation, label "SPEECH"
+
+Live audio (DetectionStream): windows run as the samples arrive, and because detection needs no speaker labels the output has
+a COMMITTED PREFIX — the offline bits, never revised — followed by a provisional tail one window long:
+
+    for seconds, committed_seconds, speech in vad.stream(chunks, uri="meeting"):     # chunks: iterable of float32 arrays
+        ...                                                              # final before committed_seconds, provisional after
 """
 from __future__ import annotations
 
@@ -20,19 +26,20 @@ import functools
 import math
 import os
 from pathlib import Path
-from typing import Any, Callable, Dict, Mapping, Optional
+from typing import Any, Callable, Dict, Iterable, Iterator, Mapping, Optional, Tuple
 
 import numpy as np
 import torch
 
-from .core import SlidingWindow, SlidingWindowFeature
+from .core import Annotation, SlidingWindow, SlidingWindowFeature
 from .engine import Engine
 from .inference import WindowRunner, window_plan
 from .models import instantiate as instantiate_model
-from .postprocess import (DETECT_OVERLAP, DETECT_SPEECH, _frame_grid, activity_regions, crop_end, detect_device,
-                          receptive_field)
+from .postprocess import (DETECT_OVERLAP, DETECT_SPEECH, _frame_grid, activity_regions, committed_frames, crop_end,
+                          detect_device, detect_range_launch, detection_weights, receptive_field)
 
 ONSET = OFFSET = 0.5        # powerset models: fixed thresholds (voice_activity_detection.py:131, overlapped_speech_detection.py:138)
+TASK_LABELS = {DETECT_SPEECH: "SPEECH", DETECT_OVERLAP: "OVERLAP"}
 
 
 def _noop(*args, **kwargs):
@@ -163,7 +170,15 @@ class _Detection:
                                                  onset=self.onset, offset=self.offset, want_scores=want_scores)
         if want_scores:
             hook("segmentation", SlidingWindowFeature(scores, grid))
-        ann = activity_regions(active.astype(bool), grid, uri=uri, labels=[self.LABEL])
+        ann = self._regions(active, grid, uri, [self.LABEL])
+        self._write_rttm(ann, uri)
+        return ann
+
+    __call__ = apply
+
+    def _regions(self, active: np.ndarray, grid: SlidingWindow, uri: Optional[str], labels):
+        """per-frame activity [n, K] -> Annotation: the regions, then Binarize's post-processing"""
+        ann = activity_regions(active.astype(bool), grid, uri=uri, labels=labels)
         # Binarize's post-processing (PA/utils/signal.py:302-315): fill short gaps, then drop short regions
         if self.min_duration_off > 0.0:
             ann = ann.support(collar=self.min_duration_off)
@@ -172,14 +187,33 @@ class _Detection:
                 if segment.duration < self.min_duration_on:
                     del ann[segment, track]
         ann.uri = uri
+        return ann
+
+    def _write_rttm(self, ann, uri: Optional[str]) -> None:
         if self.rttm_out_dir is not None:
             if uri is None:
                 raise ValueError("rttm_out_dir needs a uri: pass {'audio': ..., 'uri': ...} for in-memory audio")
             with open(os.path.join(self.rttm_out_dir, f"{uri}.rttm"), "w") as f:
                 f.write(ann.to_rttm())
-        return ann
 
-    __call__ = apply
+    # ------------------------------------------------------------------ live audio
+    def open_stream(self, uri: Optional[str] = None, tasks: Optional[int] = None, scores: bool = False, **kw) -> "DetectionStream":
+        """push form for audio that is still arriving: `DetectionStream.feed(samples)` / `.finish()`.  tasks: the dzn_detect
+        bitmask (DETECT_SPEECH | DETECT_OVERLAP gives both detections from one pass over the windows, one label per column;
+        default: this pipeline's own task).  scores: also keep the aggregated scores (`committed_scores`).  Further keywords:
+        max_seconds, slot_seconds, slots (the ingest ring, streaming.WaveIngest)."""
+        return DetectionStream(self, uri=uri, tasks=tasks, scores=scores, **kw)
+
+    def stream(self, chunks: Iterable, uri: Optional[str] = None, **kw) -> Iterator[Tuple[float, float, Any]]:
+        """generator form: chunks of float32 samples at the pipeline's rate -> (seconds received, committed seconds,
+        Annotation) for every feed that produced an annotation, then the final triple (the offline result)"""
+        sess = self.open_stream(uri=uri, **kw)
+        for c in chunks:
+            ann = sess.feed(c)
+            if ann is not None:
+                yield sess.seconds, sess.committed_seconds, ann
+        ann = sess.finish()
+        yield sess.seconds, sess.committed_seconds, ann
 
 
 class VoiceActivityDetection(_Detection):
@@ -192,3 +226,167 @@ class OverlappedSpeechDetection(_Detection):
     """overlapped speech regions (label "OVERLAP"): a frame scores 1 when at least two speakers are active in a window"""
     TASK = DETECT_OVERLAP
     LABEL = "OVERLAP"
+
+
+class DetectionStream:
+    """Voice activity / overlapped speech detection on audio that is still arriving.
+
+    Ingest is the streaming session's (streaming.WaveIngest: pinned host ring, copy stream, one pre-zeroed device buffer whose
+    windows are rows of a strided view); the windows run through the detection pipeline's own runner (median filter off, no
+    embeddings) once each, when their last sample has arrived, and their u8 decisions are kept in one device buffer.
+
+    A frame's aggregated score depends only on the windows that cover it, and window start frames do not depend on how many
+    windows exist.  With windows 0 .. C - 1 computed, every frame before the start frame of window C (the FRONTIER,
+    postprocess.committed_frames) therefore has its final score, and — the hysteresis being a left-to-right scan — its final
+    activity: `committed_activity` / `committed_scores` are the offline bits and only ever grow.  Frames from the frontier to
+    the end of window C - 1 are the provisional tail; the next window revises them.  Per feed one dzn_detect_range call computes
+    [previous frontier, frames covered so far) with the committed activity of the frame before it as the entry state — nothing
+    that is already final is derived again.
+
+    feed() returns None until the first window is complete, then an Annotation over every frame computed so far.  With
+    min_duration_on / min_duration_off set, provisional annotations get the same post-processing as the final one; it acts on
+    regions, not frames, so the region or gap that touches the frontier may still change (a short gap there may yet be filled, a
+    short region there may yet grow) — only the per-frame arrays are final.  finish() gives what apply() gives on the whole
+    recording."""
+
+    def __init__(self, detection: _Detection, uri: Optional[str] = None, tasks: Optional[int] = None, scores: bool = False,
+                 max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0, slots: int = 4):
+        from . import dist as dz_dist
+        from .streaming import WaveIngest
+        if dz_dist.world_size() > 1:
+            raise RuntimeError(f"{type(self).__name__} runs on one device: sharding a recording over torch.distributed ranks "
+                               f"is not supported (world size {dz_dist.world_size()})")
+        self.det = detection
+        self.uri = uri
+        self.tasks = int(detection.TASK if tasks is None else tasks)
+        if self.tasks & ~3 or not self.tasks & 3:
+            raise ValueError(f"tasks is a bitmask of DETECT_SPEECH (1) and DETECT_OVERLAP (2), not {tasks!r}")
+        self.labels = [TASK_LABELS[b] for b in (DETECT_SPEECH, DETECT_OVERLAP) if self.tasks & b]
+        self.want_scores = bool(scores)
+        r = detection._runner
+        self.runner = r
+        self.sr = r.sample_rate
+        self.device = dev = detection.device
+        self.chunks, self.frames = detection.chunks_window(), receptive_field(self.sr)
+        with torch.cuda.device(dev):
+            self.ingest = WaveIngest(dev, self.sr, r.window, r.step, max_seconds, slot_seconds, slots)
+            cmax = self.ingest.views.shape[0]
+            L, S = r.num_frames, detection.engine.seg.max_speakers_per_chunk
+            self.grid, starts, _ = _frame_grid(cmax, L, self.chunks, self.frames)
+            self.seg = torch.zeros((cmax, L, S), device=dev, dtype=torch.uint8)       # decisions of every window so far
+            self.d_start = torch.from_numpy(starts).to(dev)
+            self.d_weight = torch.from_numpy(detection_weights(L, self.chunks.duration)).to(dev)
+        K = len(self.labels)
+        self.done = 0                                                   # windows computed
+        self.frontier = 0                                               # frames committed
+        self.covered = 0                                                # frames computed (committed + provisional tail)
+        self._act = np.zeros((1024, K), dtype=np.uint8)                 # rows < frontier final, rows < covered valid
+        self._sc = np.zeros((1024, K), dtype=np.float32) if self.want_scores else None
+        self._entry = None                                              # device u8 [K]: activity of frame frontier - 1
+        self._last = None
+        self.finished = False
+        self.stats = {"uploads": 0, "windows": 0, "launches": 0, "range_calls": 0}
+
+    # ------------------------------------------------------------------ state
+    @property
+    def n(self) -> int:
+        return self.ingest.n
+
+    @property
+    def seconds(self) -> float:
+        """seconds of audio received"""
+        return self.ingest.n / self.sr
+
+    @property
+    def committed_seconds(self) -> float:
+        """start time of the first frame that may still change"""
+        return self.grid.start + self.frontier * self.grid.step
+
+    @property
+    def committed_activity(self) -> np.ndarray:
+        """u8 [F, K]: the activity of the F committed frames (a copy)"""
+        return self._act[:self.frontier].copy()
+
+    @property
+    def committed_scores(self) -> Optional[np.ndarray]:
+        """f32 [F, K]: the aggregated scores of the committed frames (a copy), when the stream was opened with scores=True"""
+        return self._sc[:self.frontier].copy() if self.want_scores else None
+
+    def _covered_frames(self, num_windows: int) -> int:
+        """number of frames Inference.aggregate gives for `num_windows` windows (as _frame_grid)"""
+        c, g = self.chunks, self.grid
+        return int(g.closest_frame(c.start + c.duration + (num_windows - 1) * c.step + 0.5 * g.duration) + 1)
+
+    # ------------------------------------------------------------------ device work
+    def _compute(self, upto: int) -> None:
+        """run windows done .. upto behind the newest upload and append their decisions to the device buffer"""
+        if upto <= self.done:
+            return
+        self.ingest.wait()
+        res = self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=False)
+        self.seg[self.done:upto] = res.segmentations
+        self.stats["windows"] += upto - self.done
+        self.stats["launches"] += 1
+        self.done = upto
+
+    def _detect(self, upto_frames: int, frontier: int) -> None:
+        """one range call over [self.frontier, upto_frames); frames below `frontier` are committed"""
+        t0, t1 = self.frontier, max(int(upto_frames), self.frontier)
+        frontier = min(max(frontier, t0), t1)
+        if t1 > len(self._act):
+            cap = max(t1, 2 * len(self._act))
+            self._act = np.concatenate([self._act, np.zeros((cap - len(self._act), self._act.shape[1]), np.uint8)])
+            if self.want_scores:
+                self._sc = np.concatenate([self._sc, np.zeros((cap - len(self._sc), self._sc.shape[1]), np.float32)])
+        if t1 > t0:
+            sc, act = detect_range_launch(self.seg, self.done, self.d_start, self.d_weight, t0, t1, self.tasks,
+                                          self.det.onset, self.det.offset, self._entry)
+            self.stats["range_calls"] += 1
+            self._act[t0:t1] = act.cpu().numpy()
+            if self.want_scores:
+                self._sc[t0:t1] = sc.cpu().numpy()
+            if frontier > t0:
+                self._entry = act[frontier - 1 - t0]
+        self.frontier, self.covered = frontier, t1
+
+    def _annotate(self):
+        return self.det._regions(self._act[:self.covered], self.grid, self.uri, self.labels)
+
+    # ------------------------------------------------------------------ feed / finish
+    def feed(self, samples):
+        """append float32 samples (mono, the pipeline's rate).  -> None while no window is complete, else the Annotation over
+        every frame computed so far (final before `committed_seconds`, provisional after)"""
+        from .streaming import complete_windows
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        with torch.cuda.device(self.device):
+            taken = self.ingest.append(samples)
+            self.stats["uploads"] = self.ingest.uploads
+            upto = complete_windows(self.ingest.n, self.runner.window, self.runner.step)
+            if taken and upto > self.done:
+                self._compute(upto)
+                self._detect(self._covered_frames(self.done), committed_frames(self.done, self.chunks, self.frames))
+                self._last = self._annotate()
+        return self._last
+
+    def finish(self):
+        """end of stream: the zero-padded last window if the reference would run one, the crop apply() makes, everything
+        committed -> the Annotation apply() gives on the whole recording (and its RTTM file when rttm_out_dir is set)"""
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        r = self.runner
+        n = self.ingest.n
+        n_full, has_last = window_plan(n, r.window, r.step)
+        self.finished = True
+        if n == 0:
+            return Annotation(uri=self.uri)
+        with torch.cuda.device(self.device):
+            self._compute(n_full + int(has_last))
+            T = self._covered_frames(self.done)
+            if has_last:
+                T = crop_end(T, self.grid, n / self.sr)          # zero-padded last window: PA/core/inference.py:400-403
+            assert self.frontier <= T, "committed frames beyond the offline output"
+            self._detect(T, T)
+        ann = self._last = self._annotate()
+        self.det._write_rttm(ann, self.uri)
+        return ann

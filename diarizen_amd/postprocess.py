@@ -178,6 +178,14 @@ def _frame_grid(C: int, L: int, chunks: SlidingWindow, frames: SlidingWindow):
     return grid, starts, int(T)
 
 
+def committed_frames(num_windows: int, chunks: SlidingWindow, frames: SlidingWindow) -> int:
+    """the start frame of window index `num_windows` (the closest_frame arithmetic of _frame_grid): with windows
+    0 .. num_windows - 1 computed, every frame before it is covered by computed windows only, so its aggregated score — and
+    the hysteresis up to it — is final; the frame itself is the first that the next window changes (detection.DetectionStream)"""
+    grid = SlidingWindow(start=chunks.start, duration=frames.duration, step=frames.step)
+    return int(grid.closest_frame(chunks.start + num_windows * chunks.step + 0.5 * grid.duration))
+
+
 _HOST_STREAMS = {}
 
 
@@ -321,10 +329,13 @@ def detection_scores_host(seg: np.ndarray, chunks: SlidingWindow, frames: Slidin
 
 
 def detect_device(seg, chunks: SlidingWindow, frames: SlidingWindow, tasks: int, num_frames: Optional[int] = None,
-                  onset: float = 0.5, offset: Optional[float] = None, want_scores: bool = False, warm_up=(0.0, 0.0)):
+                  onset: float = 0.5, offset: Optional[float] = None, want_scores: bool = False, warm_up=(0.0, 0.0),
+                  frame_range: Optional[Tuple[int, int]] = None, entry=None):
     """dzn_detect on the current stream: seg u8 [C, L, S] (device tensor or host array) -> (activity u8 [T, K] host,
     scores f32 [T, K] host or None, frame grid).  T = num_frames (the cropped length) or the full aggregate length; the
-    window start frames and the weight table are computed on the host with the reference's float64 arithmetic."""
+    window start frames and the weight table are computed on the host with the reference's float64 arithmetic.
+    frame_range = (t0, t1): dzn_detect_range instead — only frames t0 .. t1 - 1 (rows t - t0 of the two arrays), the
+    hysteresis continuing from `entry`, u8 [K]: the activity of frame t0 - 1 (needed when t0 > 0)."""
     import ctypes as C_
     import torch
     from . import _lib
@@ -341,15 +352,46 @@ def detect_device(seg, chunks: SlidingWindow, frames: SlidingWindow, tasks: int,
         st = torch.cuda.current_stream(dev)
         d_start = torch.from_numpy(starts).to(dev, non_blocking=False)
         d_w = torch.from_numpy(detection_weights(L, chunks.duration, warm_up)).to(dev)
-        scores = torch.empty((T, K), device=dev, dtype=torch.float32)
-        active = torch.empty((T, K), device=dev, dtype=torch.uint8)
-        p = lambda t: C_.c_void_p(t.data_ptr())      # noqa: E731
-        _lib.check(lib.dzn_detect(p(seg_t), Cn, L, S, p(d_start), p(d_w), T, tasks, float(np.float32(onset)),
-                                  float(np.float32(offset)), p(scores), p(active), C_.c_void_p(st.cuda_stream)),
-                   None, "dzn_detect")
+        if frame_range is None:
+            scores = torch.empty((T, K), device=dev, dtype=torch.float32)
+            active = torch.empty((T, K), device=dev, dtype=torch.uint8)
+            p = lambda t: C_.c_void_p(t.data_ptr())      # noqa: E731
+            _lib.check(lib.dzn_detect(p(seg_t), Cn, L, S, p(d_start), p(d_w), T, tasks, float(np.float32(onset)),
+                                      float(np.float32(offset)), p(scores), p(active), C_.c_void_p(st.cuda_stream)),
+                       None, "dzn_detect")
+        else:
+            t0, t1 = int(frame_range[0]), int(frame_range[1])
+            d_entry = None
+            if entry is not None:
+                d_entry = torch.from_numpy(np.ascontiguousarray(entry, dtype=np.uint8).reshape(K)).to(dev)
+            scores, active = detect_range_launch(seg_t, Cn, d_start, d_w, t0, t1, tasks, onset, offset, d_entry)
         act = active.cpu().numpy()
         sc = scores.cpu().numpy() if want_scores else None
     return act, sc, grid
+
+
+def detect_range_launch(seg_t, num_windows: int, d_start, d_weight, t0: int, t1: int, tasks: int, onset: float, offset: float,
+                        d_entry):
+    """one dzn_detect_range call on the current stream over device operands: seg_t u8 [>= num_windows, L, S], d_start int32
+    [>= num_windows], d_weight f64 [L], d_entry u8 [K] or None -> (scores f32 [t1 - t0, K], activity u8 [t1 - t0, K]), both
+    device tensors.  Enqueue only."""
+    import ctypes as C_
+    import torch
+    from . import _lib
+    dev = seg_t.device
+    _, L, S = seg_t.shape
+    K = bin(tasks & 3).count("1")
+    n = max(int(t1) - int(t0), 0)
+    scores = torch.empty((n, K), device=dev, dtype=torch.float32)
+    active = torch.empty((n, K), device=dev, dtype=torch.uint8)
+    if n == 0:
+        return scores, active                   # nothing to compute (an empty tensor has no address to hand over)
+    p = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    st = torch.cuda.current_stream(dev)
+    _lib.check(_lib.load().dzn_detect_range(p(seg_t), int(num_windows), L, S, p(d_start), p(d_weight), int(t0), int(t1), tasks,
+                                            float(np.float32(onset)), float(np.float32(offset)), p(d_entry), p(scores),
+                                            p(active), C_.c_void_p(st.cuda_stream)), None, "dzn_detect_range")
+    return scores, active
 
 
 def _select_top_count(act: SlidingWindowFeature, count: SlidingWindowFeature):

@@ -35,40 +35,39 @@ def complete_windows(num_samples: int, window: int, step: int) -> int:
     return 0 if num_samples < window else (num_samples - window) // step + 1
 
 
-class StreamingSession:
-    def __init__(self, pipeline, sess_name: Optional[str] = None, max_seconds: float = 4 * 3600.0, refresh_s: Optional[float] = 8.0,
+class WaveIngest:
+    """The ingest half of a streaming session (shared by StreamingSession and detection.DetectionStream): a PINNED host ring,
+    a dedicated copy stream and ONE pre-zeroed device buffer that holds the recording so far; `views` are its windows as rows
+    of a strided view.  append() stages a chunk slot by slot and queues the H2D copies; wait() makes the current stream wait
+    for the newest one."""
+
+    def __init__(self, device, sample_rate: int, window: int, step: int, max_seconds: float = 4 * 3600.0,
                  slot_seconds: float = 10.0, slots: int = 4):
-        self.pipe = pipeline
-        self.sess_name = sess_name
-        self.refresh_s = refresh_s
-        r = pipeline._runner
-        self.runner = r
-        self.sr = r.sample_rate
-        dev = pipeline.device
-        self.capacity = int(max_seconds * self.sr) + r.window           # + one window of zeros behind the last sample
-        self.dev_wave = torch.zeros(self.capacity, device=dev, dtype=torch.float32)
-        self.views = torch.as_strided(self.dev_wave, ((self.capacity - r.window) // r.step + 1, r.window), (r.step, 1))
+        self.device = device
+        self.sr = sample_rate
+        self.window = window
+        self.capacity = int(max_seconds * self.sr) + window             # + one window of zeros behind the last sample
+        self.dev_wave = torch.zeros(self.capacity, device=device, dtype=torch.float32)
+        self.views = torch.as_strided(self.dev_wave, ((self.capacity - window) // step + 1, window), (step, 1))
         self.slot_samples = int(slot_seconds * self.sr)
         self.ring = [torch.empty(self.slot_samples, dtype=torch.float32).pin_memory() for _ in range(slots)]
         self.slot_free = [None] * slots                                 # event: the slot's H2D copy has completed
         self.next_slot = 0
-        self.copy_stream = torch.cuda.Stream(device=dev)
+        self.copy_stream = torch.cuda.Stream(device=device)
         # the zero fill of dev_wave above is queued on the CURRENT stream; the chunk copies run on copy_stream — without this
         # edge the first copies could land before the memset and be zeroed by it.  record_stream: the caching allocator
         # must not recycle dev_wave while copies on the other stream are pending.
-        self.copy_stream.wait_stream(torch.cuda.current_stream(dev))
+        self.copy_stream.wait_stream(torch.cuda.current_stream(device))
         self.dev_wave.record_stream(self.copy_stream)
         self.n = 0                                                      # samples received
-        self.done = 0                                                   # windows computed
-        self.seg = []                                                   # per batch: u8 [c, L, S] host arrays
-        self.emb = []
-        self.last_refresh_n = 0
+        self.uploads = 0
         self.last_copy = None
-        self.finished = False
-        self.stats = {"uploads": 0, "launches": 0, "refreshes": 0}
 
-    # ------------------------------------------------------------------ ingest
-    def _upload(self, x: np.ndarray) -> None:
+    def append(self, samples) -> int:
+        """stage float32 samples and queue their copies behind the recording so far; -> number of samples taken"""
+        x = np.ascontiguousarray(np.asarray(samples, dtype=np.float32).reshape(-1))
+        if self.n + len(x) + self.window > self.capacity:
+            raise MemoryError(f"stream longer than max_seconds = {(self.capacity - self.window) / self.sr:.0f} s")
         off = 0
         while off < len(x):
             k = min(self.slot_samples, len(x) - off)
@@ -83,15 +82,45 @@ class StreamingSession:
             self.slot_free[i] = ev
             self.last_copy = ev
             self.next_slot = (i + 1) % len(self.ring)
-            self.stats["uploads"] += 1
+            self.uploads += 1
             off += k
+        self.n += len(x)
+        return len(x)
+
+    def wait(self) -> None:
+        """the current (compute) stream runs behind the newest upload"""
+        if self.last_copy is not None:
+            torch.cuda.current_stream(self.device).wait_event(self.last_copy)
+
+
+class StreamingSession:
+    def __init__(self, pipeline, sess_name: Optional[str] = None, max_seconds: float = 4 * 3600.0, refresh_s: Optional[float] = 8.0,
+                 slot_seconds: float = 10.0, slots: int = 4):
+        self.pipe = pipeline
+        self.sess_name = sess_name
+        self.refresh_s = refresh_s
+        r = pipeline._runner
+        self.runner = r
+        self.sr = r.sample_rate
+        self.ingest = WaveIngest(pipeline.device, self.sr, r.window, r.step, max_seconds, slot_seconds, slots)
+        self.done = 0                                                   # windows computed
+        self.seg = []                                                   # per batch: u8 [c, L, S] host arrays
+        self.emb = []
+        self.last_refresh_n = 0
+        self.finished = False
+        self.stats = {"uploads": 0, "launches": 0, "refreshes": 0}
+
+    @property
+    def n(self) -> int:
+        """samples received"""
+        return self.ingest.n
 
     def _compute(self, upto: int) -> None:
         """run windows done .. upto on the compute stream, behind the newest upload"""
         if upto <= self.done:
             return
-        torch.cuda.current_stream(self.pipe.device).wait_event(self.last_copy)
-        res = self.runner.run_views(self.views, self.done, upto, with_embeddings=True)
+        self.ingest.wait()
+        res = self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=True)
         self.seg.append(res.segmentations.cpu().numpy())               # 5.7 KB per window
         self.emb.append(res.embeddings.cpu().numpy())
         self.done = upto
@@ -102,13 +131,9 @@ class StreamingSession:
         due, else None"""
         if self.finished:
             raise RuntimeError("stream already finished")
-        x = np.ascontiguousarray(np.asarray(samples, dtype=np.float32).reshape(-1))
-        if self.n + len(x) + self.runner.window > self.capacity:
-            raise MemoryError(f"stream longer than max_seconds = {(self.capacity - self.runner.window) / self.sr:.0f} s")
-        if len(x) == 0:
+        if self.ingest.append(samples) == 0:
             return None
-        self._upload(x)
-        self.n += len(x)
+        self.stats["uploads"] = self.ingest.uploads
         self._compute(complete_windows(self.n, self.runner.window, self.runner.step))
         if (self.refresh_s is not None and self.done > 0
                 and self.n - self.last_refresh_n >= self.refresh_s * self.sr):

@@ -240,6 +240,23 @@ int dzn_detect(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int3
                int32_t T, int32_t tasks, float onset, float offset, float* d_scores, uint8_t* d_active, void* hip_stream);
 
 /*
+ * The range form of dzn_detect, for a recording that is still arriving (diarizen_amd/detection.py, DetectionStream): frames
+ * [t0, t1) only, into rows t - t0 of d_scores f32 [t1-t0, K] / d_active u8 [t1-t0, K] (may be NULL).
+ *   scores  the same per-frame walk over the windows d_start_frame[0..C) that cover t, in ascending window order
+ *           (Inference.aggregate, PA/core/inference.py:544-666): a frame's score depends on t and on those windows only, so
+ *           it is final once every window covering it is among the C — every t < the start frame of window C
+ *   active  Binarize's hysteresis (PA/utils/signal.py:254-296) continued across calls: "frame 0 decides by y > onset" holds
+ *           for global frame 0 only; for t0 > 0, d_entry u8 [K] is the state of frame t0 - 1 (0 / 1), which the range keeps
+ *           until its first decisive frame (throughout, if it has none)
+ * The concatenation of range calls over a partition of [0, T) is dzn_detect's output bit for bit; dzn_detect is the range
+ * [0, T).  DZN_E_INVALID for t0 < 0, t1 < t0, or d_entry == NULL with t0 > 0 (d_entry is ignored when
+ * t0 == 0); t1 == t0 returns DZN_OK without a launch.  Other arguments as for dzn_detect.
+ */
+int dzn_detect_range(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame,
+                     const double* d_weight, int32_t t0, int32_t t1, int32_t tasks, float onset, float offset,
+                     const uint8_t* d_entry, float* d_scores, uint8_t* d_active, void* hip_stream);
+
+/*
  * Per-speaker activity scores (stateless, no handle): the soft scores of every window, mapped to the global clusters and
  * overlap-added.
  *   clustered[c, :, k] = max_{s : hard[c,s] == k} soft[c, :, s], NaN when window c has no local speaker in cluster k

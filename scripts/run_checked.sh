@@ -9,5 +9,7 @@ python -m pytest tests/test_ops_gpu.py tests/test_seg_gpu.py tests/test_emb_gpu.
 python -m pytest tests/test_scores_gpu.py -m gpu -q -x 2>&1 | tail -3
 # the device resampler (resample.hip, ids 0x82x): likewise
 python -m pytest tests/test_resample_gpu.py -m gpu -q -x 2>&1 | tail -3
+# detection: whole-recording and range form, and the stream on top of it (post.hip, ids 0x80x): likewise
+python -m pytest tests/test_detection_gpu.py tests/test_detection_stream_op_gpu.py tests/test_detection_stream_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
