@@ -26,8 +26,15 @@ def gemm(A, W, *, M=None, N=None, K=None, bias=None, R=None, C_out=None, WS=None
          ldws=0, act=0, alpha=1.0, post_relu=False, nz=1, zdiv=1, zs=None, precision=0,
          W3=None, a_planes=None, ln_stats=None, ln_colsum=None, W2h=None, col_scale=None,
          a_amax=None, c_amax=None, amax_unit=None, want_row_stats=False, stat_eps=1e-5, mx=False, Wmx=None,
-         col_scale_mx=None, kv_col0=None, A2=None, a2_rowoff=None, a2_z0=0, k1=0, k2=0, a2_amax=None):
-    """C = epilogue(A @ W^T); see dzn_gemm_desc.  A2 / a2_rowoff / a2_z0 / k1 / k2 / a2_amax: the second A segment (K columns
+         col_scale_mx=None, kv_col0=None, A2=None, a2_rowoff=None, a2_z0=0, k1=0, k2=0, a2_amax=None,
+         stat_bufs=None, kv_bufs=None, amax_guard=0):
+    """C = epilogue(A @ W^T); see dzn_gemm_desc.  zs: further descriptor fields by name — the z strides (a_z0, a_z1, w_z0, w_z1,
+    c_z0, c_z1, b_z0, b_z1) and the device-chosen subset of the batch, zs=dict(z_list=<int32 tensor>.data_ptr(),
+    z_count=<int32 tensor [1]>.data_ptr()): grid row y runs z0 = z_list[y / zdiv] when y / zdiv < z_count[0] and exits otherwise.
+    stat_bufs=(partial f32 [M, P, 2], final f32 [M, 2]): caller-owned scratch / result of want_row_stats (else allocated here,
+    P = 32); kv_bufs=(planes, inv): caller-owned outputs of kv_col0, planes int16 [2, rows >= M, N - kv_col0].  amax_count (what a
+    checked build holds the unit index of a_amax / c_amax against) = the shortest tracker array given, minus amax_guard trailing
+    guard entries.  A2 / a2_rowoff / a2_z0 / k1 / k2 / a2_amax: the second A segment (K columns
     k1 .. k1 + k2 read A2[z * a2_z0 + a2_rowoff[m] + k - k1]; a2_amax = its per-unit |max|, computed here when omitted).  kv_col0 (r6): columns >= kv_col0 leave as fp16 two-term planes with per-(row,
     64-column slot) scales instead of fp32 (dzn_gemm_desc.kv_planes) -> returns (C, planes int16 [2, M, N - kv_col0], inv f32
     [M, (N - kv_col0) / 64]).  A: [M, K] (or raw buffer with lda / rowoff),
@@ -87,15 +94,33 @@ def gemm(A, W, *, M=None, N=None, K=None, bias=None, R=None, C_out=None, WS=None
         d.a2_z0, d.k1, d.k2 = a2_z0, k1, k2
     # one scale unit for the whole tensor unless told otherwise (engines use one unit per window)
     d.amax_unit = int(amax_unit) if amax_unit is not None else (max(M, 1) if nz == 1 else 0)
+    trackers = [t for t in (a_amax, c_amax, a2_amax if A2 is not None else None) if t is not None]
+    if trackers:
+        d.amax_count = max(min(t.numel() for t in trackers) - int(amax_guard), 0)
     stats = None
     if want_row_stats:      # LayerNorm statistics of the output rows, left by the epilogue + finalize kernel
-        part = torch.empty((M, 32, 2), device=A.device, dtype=torch.float32)
-        stats = torch.empty((M, 2), device=A.device, dtype=torch.float32)
+        # the epilogue leaves P = column tiles x wavefront columns partials per row; the narrowest wavefront tile of any
+        # family is 32 columns, as 64-wide tiles of two wavefront columns or 32-wide tiles of one
+        p_max = 2 * ((N + 63) // 64)
+        if stat_bufs is not None:
+            part, stats = stat_bufs
+            assert part.dtype == torch.float32 and stats.dtype == torch.float32
+            if part.numel() < M * p_max * 2 or stats.numel() < M * 2:
+                raise ValueError(f"want_row_stats: stat_bufs too small for M = {M}, up to {p_max} partials per row")
+        else:
+            if p_max > 32:
+                raise ValueError(f"want_row_stats: N = {N} may leave {p_max} > 32 partials per row; pass stat_bufs")
+            part = torch.empty((M, 32, 2), device=A.device, dtype=torch.float32)
+            stats = torch.empty((M, 2), device=A.device, dtype=torch.float32)
         d.stat_partial, d.stat_final, d.stat_C, d.stat_eps = _p(part), _p(stats), N, stat_eps
     kvp = kvs = None
     if kv_col0 is not None:
-        kvp = torch.zeros((2, M, N - kv_col0), device=A.device, dtype=torch.int16)
-        kvs = torch.zeros((M, (N - kv_col0) // 64), device=A.device, dtype=torch.float32)
+        if kv_bufs is not None:
+            kvp, kvs = kv_bufs
+            assert kvp.dtype == torch.int16 and kvp.dim() == 3 and kvp.shape[1] >= M and kvp.shape[2] == N - kv_col0
+        else:
+            kvp = torch.zeros((2, M, N - kv_col0), device=A.device, dtype=torch.int16)
+            kvs = torch.zeros((M, (N - kv_col0) // 64), device=A.device, dtype=torch.float32)
         d.kv_planes, d.kv_plane_stride, d.kv_scale, d.kv_ld, d.kv_col0 = _p(kvp), kvp.stride(0), _p(kvs), N - kv_col0, kv_col0
     check(lib.dzn_op_gemm(C.byref(d), _stream()), what="dzn_op_gemm")
     if kv_col0 is not None:

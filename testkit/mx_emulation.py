@@ -45,3 +45,35 @@ def single_term_gemm(A: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     ah = (A.double() * sa).float().to(torch.float16).double()
     wh = (W.double() * sw).float().to(torch.float16).double()
     return (ah @ wh.T) / sa / sw.T
+
+
+def _pow2_scale_h2(amax: torch.Tensor) -> torch.Tensor:
+    """split.h h2_scale: the exact power of two that puts amax into [2^14, 2^15)"""
+    e = torch.floor(torch.log2(amax.double().clamp_min(1e-300)))
+    return torch.exp2(14.0 - e)
+
+
+def h2_terms(x: torch.Tensor, scale: torch.Tensor):
+    """two-term fp16 split of gemm_split.hip (NP = 2): x float32, scale float64 broadcastable -> (hi, lo) as float64 in
+    UNSCALED units; hi = fp16(x s), lo = fp16(x s - hi), both round to nearest even, the subtraction exact in fp32"""
+    xs = (x.double() * scale).float()
+    hi = xs.to(torch.float16).float()
+    lo = (xs - hi).to(torch.float16).float()
+    return hi.double() / scale, lo.double() / scale
+
+
+def bf16x3_terms(x: torch.Tensor):
+    """exact three-term bf16 split of split.h: x float32 -> (hi, mid, lo) as float64, hi + mid + lo == x"""
+    hi = x.to(torch.bfloat16).float()
+    r1 = x - hi
+    mid = r1.to(torch.bfloat16).float()
+    r2 = r1 - mid
+    lo = r2.to(torch.bfloat16).float()
+    return hi.double(), mid.double(), lo.double()
+
+
+def mx_operand_terms(x: torch.Tensor, amax: torch.Tensor):
+    """(hi16, hi8, lo8) of gemm_mx.hip in UNSCALED units for x float32 [rows, K] with the per-row |max| bound `amax` [rows, 1]"""
+    s = _pow2_scale(amax)
+    hi, hi8, lo8 = mx_terms(x, s)
+    return hi / s, hi8 / s, lo8 / s
