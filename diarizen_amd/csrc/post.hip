@@ -292,7 +292,96 @@ __global__ __launch_bounds__(256) void speaker_scores_kernel(const float* __rest
   scores[i] = seen ? __fdiv_rn(acc, fmaxf(cnt, 1e-12f)) : 0.f;
 }
 
+// ---- live diarization: count -> reconstruct -> top-count over a frame range (dzn_diarize_range) ------------------------
+// The chain count_accum/count_finalize -> cluster_accum -> to_diarization's selection (PA/pipelines/utils/diarization.py:
+// 121-157, 213-236; PA/pipelines/speaker_diarization.py:400-425) for frames [t0, t1) into rows t - t0.  As in
+// detect_scores_kernel a frame's walk over ITS covering windows depends on nothing but t, so a range is the same bytes as the
+// same rows of the whole, and there is nothing to zero and nothing to add atomically.  A workgroup holds 256 >> kp_log2 frames
+// of KP = 1 << kp_log2 >= K lanes each; lane (f, k) adds up act[t, k] — and, the row of decisions being in its registers
+// anyway, the frame's total of active local speakers, so every lane of a frame knows count[t] without an exchange.  The K
+// activations of a frame then meet in LDS and lane k takes its rank among them,
+//     rank = #{j : act_j > act_k or (act_j == act_k and j < k)},
+// which is k's position in np.argsort(-act, kind="stable"); it is active when rank < min(count, K).  KP is a power of two
+// <= 32, so a frame never straddles a wave64 and the lanes of a frame read one LDS address (a broadcast).
+__global__ __launch_bounds__(256) void diarize_range_kernel(const uint8_t* __restrict__ seg, const int8_t* __restrict__ hard,
+                                                            int C, int L, int S, const int32_t* __restrict__ start, int t0,
+                                                            int t1, int K, int kp_log2, int max_count,
+                                                            uint8_t* __restrict__ count, uint8_t* __restrict__ active,
+                                                            int32_t* __restrict__ act_out) {
+  __shared__ int32_t sa[256];
+  const int tid = threadIdx.x;
+  const int f = tid >> kp_log2, k = tid & ((1 << kp_log2) - 1);
+  const int64_t row = (int64_t)blockIdx.x * (256 >> kp_log2) + f;
+  const bool live = row < (int64_t)(t1 - t0) && k < K;
+  const int t = t0 + (int)(live ? row : 0);
+  int a = 0, tot = 0, cover = 0;
+  if (live) {
+    // covering windows: start[c] <= t < start[c] + L  ->  c in [c0, c1)
+    int lo = 0, hi = C;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (start[mid] > t - L) hi = mid; else lo = mid + 1;
+    }
+    const int c0 = lo;
+    hi = C;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (start[mid] > t) hi = mid; else lo = mid + 1;
+    }
+    const int c1 = lo;
+    for (int c = c0; c < c1; ++c) {
+      const int l = t - start[c];
+      DZN_CHECK(l >= 0 && l < L, 0x830, c);
+      DZN_CHECK(c == 0 || start[c - 1] <= start[c], 0x831, c);
+      if (l < 0 || l >= L) continue;          // only reachable with a start[] that is not non-decreasing
+      const uint8_t* r = seg + ((int64_t)c * L + l) * S;
+      const int8_t* hc = hard + (int64_t)c * S;
+      int v = 0;
+      for (int s = 0; s < S; ++s) {
+        const int x = r[s];
+        tot += x;
+        if (hc[s] == k) v = x > v ? x : v;      // k >= 0: an inactive local speaker (hard < 0) matches no lane
+      }
+      a += v;
+      ++cover;
+    }
+  }
+  sa[tid] = a;
+  __syncthreads();
+  if (!live) return;
+  // count_finalize_kernel's arithmetic, then the cap (count.data = np.minimum(count.data, max_speakers))
+  const float avg = cover ? __fdiv_rn((float)tot, fmaxf((float)cover, 1e-12f)) : 0.f;
+  const int cnt = min((int)(uint8_t)rintf(avg), max_count);
+  const int32_t* fa = sa + (f << kp_log2);
+  int rank = 0;
+  for (int j = 0; j < K; ++j) {
+    const int aj = fa[j];
+    rank += (aj > a || (aj == a && j < k)) ? 1 : 0;
+  }
+  DZN_CHECK(row >= 0 && row < t1 - t0 && rank < K, 0x832, (int)row);
+  if (k == 0) count[row] = (uint8_t)cnt;
+  active[row * K + k] = rank < min(cnt, K) ? 1 : 0;
+  if (act_out) act_out[row * K + k] = a;
+}
+
 }  // namespace
+
+extern "C" int dzn_diarize_range(const uint8_t* d_seg, const int8_t* d_hard, int32_t C, int32_t L, int32_t S,
+                                 const int32_t* d_start_frame, int32_t t0, int32_t t1, int32_t K, int32_t max_count,
+                                 uint8_t* d_count, uint8_t* d_active, int32_t* d_act, void* stream) {
+  if (!d_seg || !d_hard || !d_start_frame || !d_count || !d_active || C < 0 || L < 1 || S < 1 || S > 8 || t0 < 0 || t1 < t0 ||
+      K < 1 || K > 32 || max_count < 0)
+    return DZN_E_INVALID;
+  if (t1 == t0) return DZN_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int kp_log2 = 0;
+  while ((1 << kp_log2) < K) ++kp_log2;         // lanes per frame: the power of two >= K (<= 32)
+  const int per_block = 256 >> kp_log2;
+  const int n = t1 - t0;
+  hipLaunchKernelGGL(diarize_range_kernel, dim3((unsigned)cdiv64(n, per_block)), dim3(256), 0, st, d_seg, d_hard, C, L, S,
+                     d_start_frame, t0, t1, K, kp_log2, max_count, d_count, d_active, d_act);
+  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
 
 extern "C" int dzn_speaker_count(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame,
                                  int32_t T, int32_t* d_work, uint8_t* d_count, void* stream) {

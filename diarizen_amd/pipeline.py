@@ -398,6 +398,24 @@ class DiariZenPipeline:
         from .streaming import stream as _stream
         return _stream(self, chunks, sess_name, **kw)
 
+    def open_live(self, sess_name: Optional[str] = None, delta_new: Optional[float] = None,
+                  max_speakers: Optional[int] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
+                  slots: int = 4):
+        """live diarization with stable labels and a committed prefix: a live.LiveDiarization to `feed(samples)` /
+        `finish()`.  delta_new: the centroid distance beyond which a clean local speaker opens a new label (default: the
+        config's ahc_threshold); max_speakers: the cap on labels (default: the config's, at most 32); the other keywords size
+        the ingest ring (streaming.WaveIngest).  `stream` / StreamingSession stay what they are: provisional re-clusterings
+        whose last annotation is the offline result."""
+        from .live import LiveDiarization
+        return LiveDiarization(self, sess_name, delta_new=delta_new, max_speakers=max_speakers, max_seconds=max_seconds,
+                               slot_seconds=slot_seconds, slots=slots)
+
+    def stream_live(self, chunks, sess_name: Optional[str] = None, **kw):
+        """generator form of open_live: yields (seconds received, committed seconds, Annotation) for every feed that has an
+        annotation, then the final triple.  Keywords as open_live, and recluster (live.LiveDiarization.finish)."""
+        from .live import stream_live as _stream_live
+        return _stream_live(self, chunks, sess_name, **kw)
+
     # ------------------------------------------------------------------ many recordings
     def diarize_many(self, recordings, sess_names=None, overlap: bool = True):
         """The loop the reference's entry points run over a corpus (diarizen/pipelines/inference.py:365-368: `for audio_file in

@@ -394,6 +394,56 @@ def detect_range_launch(seg_t, num_windows: int, d_start, d_weight, t0: int, t1:
     return scores, active
 
 
+def diarize_range_launch(seg_t, hard_t, num_windows: int, d_start, t0: int, t1: int, K: int, max_count: int,
+                         want_activations: bool = False):
+    """one dzn_diarize_range call on the current stream over device operands: seg_t u8 [>= num_windows, L, S], hard_t int8
+    [>= num_windows, S], d_start int32 [>= num_windows] -> (count u8 [t1 - t0], active u8 [t1 - t0, K], activations int32
+    [t1 - t0, K] or None), device tensors.  Enqueue only."""
+    import ctypes as C_
+    import torch
+    from . import _lib
+    dev = seg_t.device
+    _, L, S = seg_t.shape
+    assert seg_t.is_cuda and seg_t.dtype == torch.uint8 and seg_t.is_contiguous()
+    assert hard_t.is_cuda and hard_t.dtype == torch.int8 and hard_t.is_contiguous() and hard_t.shape[1] == S
+    assert d_start.dtype == torch.int32 and min(len(seg_t), len(hard_t), len(d_start)) >= int(num_windows)
+    n = max(int(t1) - int(t0), 0)
+    count = torch.empty((n,), device=dev, dtype=torch.uint8)
+    active = torch.empty((n, int(K)), device=dev, dtype=torch.uint8)
+    act = torch.empty((n, int(K)), device=dev, dtype=torch.int32) if want_activations else None
+    if n == 0:
+        return count, active, act               # nothing to compute (an empty tensor has no address to hand over)
+    p = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    st = torch.cuda.current_stream(dev)
+    _lib.check(_lib.load().dzn_diarize_range(p(seg_t), p(hard_t), int(num_windows), L, S, p(d_start), int(t0), int(t1), int(K),
+                                             int(max_count), p(count), p(active), p(act), C_.c_void_p(st.cuda_stream)),
+               None, "dzn_diarize_range")
+    return count, active, act
+
+
+def diarize_range_host(seg: np.ndarray, hard: np.ndarray, starts: np.ndarray, t0: int, t1: int, K: int, max_count: int):
+    """numpy restatement of dzn_diarize_range (needs no device; the kernel is checked against it): seg u8 [C, L, S], hard
+    [C, S], starts int [C] -> (count u8 [t1 - t0], active u8 [t1 - t0, K], activations int32 [t1 - t0, K])"""
+    C, L, S = seg.shape
+    T = max(int(t1), int(starts[-1]) + L if C else 0)
+    tot, cover = np.zeros(T, np.int64), np.zeros(T, np.int64)
+    act = np.zeros((T, K), np.int32)
+    for c in range(C):
+        s0 = int(starts[c])
+        tot[s0:s0 + L] += seg[c].sum(axis=1, dtype=np.int64)
+        cover[s0:s0 + L] += 1
+        for k in range(K):
+            sel = hard[c] == k
+            if sel.any():
+                act[s0:s0 + L, k] += seg[c][:, sel].max(axis=1)
+    avg = np.where(cover > 0, tot.astype(np.float32) / np.maximum(cover, 1).astype(np.float32), np.float32(0))
+    count = np.minimum(np.rint(avg).astype(np.uint8).astype(np.int64), int(max_count))
+    order = np.argsort(-act, axis=1, kind="stable")
+    active = np.zeros((T, K), np.uint8)
+    np.put_along_axis(active, order, (np.arange(K)[None, :] < np.minimum(count, K)[:, None]).astype(np.uint8), axis=1)
+    return count[t0:t1].astype(np.uint8), active[t0:t1], act[t0:t1]
+
+
 def _select_top_count(act: SlidingWindowFeature, count: SlidingWindowFeature):
     """tail of to_diarization (PA/pipelines/utils/diarization.py:222-239) on aggregated activations"""
     K = act.data.shape[1]

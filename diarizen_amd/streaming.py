@@ -17,7 +17,8 @@ Design (MI355X-first, same kernels as the offline path):
     and the final RTTM — equal the offline ones bit for bit;
   * provisional output: every `refresh_s` seconds of new audio the host stage (counting, clustering, reconstruction,
     Binarize) runs over the windows finished so far.  Speaker labels of provisional annotations are NOT stable across
-    refreshes (each is a fresh clustering), the final one is the offline result.
+    refreshes (each is a fresh clustering), the final one is the offline result.  Labels that never change and a committed
+    prefix are what live.LiveDiarization (pipeline.open_live) gives instead, on the same ingest.
 """
 from __future__ import annotations
 

@@ -257,6 +257,29 @@ int dzn_detect_range(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, cons
                      const uint8_t* d_entry, float* d_scores, uint8_t* d_active, void* hip_stream);
 
 /*
+ * The range form of the count -> reconstruct -> top-count chain (dzn_speaker_count + dzn_cluster_activations + the selection
+ * of to_diarization), for a recording that is still arriving (diarizen_amd/live.py, LiveDiarization): frames [t0, t1) only, in
+ * one call, into rows t - t0.  Per frame t, over the windows d_start_frame[0..C) that cover it:
+ *   count[t]    = min(uint8(rint(sum_c sum_s seg / #covering windows)), max_count), 0 where no window covers t
+ *                 SpeakerDiarizationMixin.speaker_count, PA/pipelines/utils/diarization.py:121-157 (float32 division as
+ *                 dzn_speaker_count) and the cap of diarizen/pipelines/inference.py:163
+ *   act[t,k]    = sum_c max_s{seg[c,t-start_c,s] : hard[c,s]==k}, integer and exact; hard < 0 or >= K is skipped
+ *                 SpeakerDiarization.reconstruct, PA/pipelines/speaker_diarization.py:400-425; diarization.py:213-220
+ *   active[t,k] = 1 for the min(count[t], K) largest act[t,.]     `binary[t, speakers[:c]] = 1`, diarization.py:228-236 —
+ *                 zero activations are selected too when count asks for them.  Equal activations are taken in ascending k
+ *                 (np.argsort(-act, kind="stable")): a fixed rule in place of numpy's build-dependent order for ties.
+ * A frame's three results depend on t and on the windows covering it only, so they are final once every such window is
+ * among the C — every t < the start frame of window C — and the concatenation of range calls over a partition of [0, T) is
+ * the [0, T) call byte for byte.  d_seg u8 [C,L,S] (S <= 8), d_hard int8 [C,S], d_start_frame int32 [C] non-decreasing (as
+ * for dzn_detect_range), 1 <= K <= 32, max_count >= 0.  d_count u8 [t1-t0], d_active u8 [t1-t0,K], d_act int32 [t1-t0,K]
+ * (may be NULL).  One lane per (t, k) walks its covering windows; no atomics, no sort.  DZN_E_INVALID for t0 < 0, t1 < t0,
+ * K < 1, K > 32, S > 8, max_count < 0 or NULL d_count / d_active; t1 == t0 returns DZN_OK without a launch.
+ */
+int dzn_diarize_range(const uint8_t* d_seg, const int8_t* d_hard, int32_t C, int32_t L, int32_t S,
+                      const int32_t* d_start_frame, int32_t t0, int32_t t1, int32_t K, int32_t max_count,
+                      uint8_t* d_count, uint8_t* d_active, int32_t* d_act, void* hip_stream);
+
+/*
  * Per-speaker activity scores (stateless, no handle): the soft scores of every window, mapped to the global clusters and
  * overlap-added.
  *   clustered[c, :, k] = max_{s : hard[c,s] == k} soft[c, :, s], NaN when window c has no local speaker in cluster k
