@@ -31,12 +31,14 @@ from typing import Any, Callable, Dict, Iterable, Iterator, Mapping, Optional, T
 import numpy as np
 import torch
 
-from .core import Annotation, SlidingWindow, SlidingWindowFeature
+from . import dist as dz_dist
+from .core import SlidingWindow, SlidingWindowFeature
 from .engine import Engine
 from .inference import WindowRunner, window_plan
 from .models import instantiate as instantiate_model
-from .postprocess import (DETECT_OVERLAP, DETECT_SPEECH, _frame_grid, activity_regions, committed_frames, crop_end,
-                          detect_device, detect_range_launch, detection_weights, receptive_field)
+from .postprocess import (DETECT_OVERLAP, DETECT_SPEECH, _frame_grid, activity_regions, crop_end, detect_device,
+                          detect_range_launch, detection_weights, receptive_field)
+from .streaming import CommittedStream, stream_committed
 
 ONSET = OFFSET = 0.5        # powerset models: fixed thresholds (voice_activity_detection.py:131, overlapped_speech_detection.py:138)
 TASK_LABELS = {DETECT_SPEECH: "SPEECH", DETECT_OVERLAP: "OVERLAP"}
@@ -143,11 +145,8 @@ class _Detection:
         hook(step_name, artifact, file=file, [completed=, total=]): "segmentation" progress per batch of windows, then the
         aggregated scores as a SlidingWindowFeature [T, 1] (PA/pipelines/voice_activity_detection.py:188-214).
         -> Annotation of the regions, labelled "SPEECH" / "OVERLAP", uri = file["uri"] or the path's stem."""
-        from . import dist as dz_dist
         from .pipeline import open_recording, recording_on_device
-        if dz_dist.world_size() > 1:
-            raise RuntimeError(f"{type(self).__name__} runs on one device: sharding a recording over torch.distributed ranks "
-                               f"is not supported (world size {dz_dist.world_size()})")
+        dz_dist.require_single_rank(type(self).__name__)
         file = file if isinstance(file, Mapping) else {"audio": file}
         audio = file["audio"]
         uri = file.get("uri")
@@ -207,13 +206,7 @@ class _Detection:
     def stream(self, chunks: Iterable, uri: Optional[str] = None, **kw) -> Iterator[Tuple[float, float, Any]]:
         """generator form: chunks of float32 samples at the pipeline's rate -> (seconds received, committed seconds,
         Annotation) for every feed that produced an annotation, then the final triple (the offline result)"""
-        sess = self.open_stream(uri=uri, **kw)
-        for c in chunks:
-            ann = sess.feed(c)
-            if ann is not None:
-                yield sess.seconds, sess.committed_seconds, ann
-        ann = sess.finish()
-        yield sess.seconds, sess.committed_seconds, ann
+        yield from stream_committed(self.open_stream(uri=uri, **kw), chunks)
 
 
 class VoiceActivityDetection(_Detection):
@@ -228,12 +221,11 @@ class OverlappedSpeechDetection(_Detection):
     LABEL = "OVERLAP"
 
 
-class DetectionStream:
+class DetectionStream(CommittedStream):
     """Voice activity / overlapped speech detection on audio that is still arriving.
 
-    Ingest is the streaming session's (streaming.WaveIngest: pinned host ring, copy stream, one pre-zeroed device buffer whose
-    windows are rows of a strided view); the windows run through the detection pipeline's own runner (median filter off, no
-    embeddings) once each, when their last sample has arrived, and their u8 decisions are kept in one device buffer.
+    The session is a streaming.CommittedStream (ingest, window schedule, frontier bookkeeping, feed / finish); the windows run
+    through the detection pipeline's own runner (median filter off, no embeddings) once each, when their last sample has arrived.
 
     A frame's aggregated score depends only on the windows that cover it, and window start frames do not depend on how many
     windows exist.  With windows 0 .. C - 1 computed, every frame before the start frame of window C (the FRONTIER,
@@ -249,144 +241,48 @@ class DetectionStream:
     short region there may yet grow) — only the per-frame arrays are final.  finish() gives what apply() gives on the whole
     recording."""
 
+    EMBEDDINGS = False
+
     def __init__(self, detection: _Detection, uri: Optional[str] = None, tasks: Optional[int] = None, scores: bool = False,
                  max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0, slots: int = 4):
-        from . import dist as dz_dist
-        from .streaming import WaveIngest
-        if dz_dist.world_size() > 1:
-            raise RuntimeError(f"{type(self).__name__} runs on one device: sharding a recording over torch.distributed ranks "
-                               f"is not supported (world size {dz_dist.world_size()})")
-        self.det = detection
-        self.uri = uri
         self.tasks = int(detection.TASK if tasks is None else tasks)
         if self.tasks & ~3 or not self.tasks & 3:
             raise ValueError(f"tasks is a bitmask of DETECT_SPEECH (1) and DETECT_OVERLAP (2), not {tasks!r}")
         self.labels = [TASK_LABELS[b] for b in (DETECT_SPEECH, DETECT_OVERLAP) if self.tasks & b]
         self.want_scores = bool(scores)
-        r = detection._runner
-        self.runner = r
-        self.sr = r.sample_rate
-        self.device = dev = detection.device
-        self.chunks, self.frames = detection.chunks_window(), receptive_field(self.sr)
-        with torch.cuda.device(dev):
-            self.ingest = WaveIngest(dev, self.sr, r.window, r.step, max_seconds, slot_seconds, slots)
-            cmax = self.ingest.views.shape[0]
-            L, S = r.num_frames, detection.engine.seg.max_speakers_per_chunk
-            self.grid, starts, _ = _frame_grid(cmax, L, self.chunks, self.frames)
-            self.seg = torch.zeros((cmax, L, S), device=dev, dtype=torch.uint8)       # decisions of every window so far
-            self.d_start = torch.from_numpy(starts).to(dev)
-            self.d_weight = torch.from_numpy(detection_weights(L, self.chunks.duration)).to(dev)
         K = len(self.labels)
-        self.done = 0                                                   # windows computed
-        self.frontier = 0                                               # frames committed
-        self.covered = 0                                                # frames computed (committed + provisional tail)
-        self._act = np.zeros((1024, K), dtype=np.uint8)                 # rows < frontier final, rows < covered valid
-        self._sc = np.zeros((1024, K), dtype=np.float32) if self.want_scores else None
+        rows = {"act": (np.uint8, (K,))}
+        if self.want_scores:
+            rows["sc"] = (np.float32, (K,))
+        super().__init__(detection, uri, rows, max_seconds, slot_seconds, slots)
+        self.det = detection
+        self.d_weight = torch.from_numpy(detection_weights(self.runner.num_frames, self.chunks.duration)).to(self.device)
         self._entry = None                                              # device u8 [K]: activity of frame frontier - 1
-        self._last = None
-        self.finished = False
-        self.stats = {"uploads": 0, "windows": 0, "launches": 0, "range_calls": 0}
-
-    # ------------------------------------------------------------------ state
-    @property
-    def n(self) -> int:
-        return self.ingest.n
-
-    @property
-    def seconds(self) -> float:
-        """seconds of audio received"""
-        return self.ingest.n / self.sr
-
-    @property
-    def committed_seconds(self) -> float:
-        """start time of the first frame that may still change"""
-        return self.grid.start + self.frontier * self.grid.step
 
     @property
     def committed_activity(self) -> np.ndarray:
         """u8 [F, K]: the activity of the F committed frames (a copy)"""
-        return self._act[:self.frontier].copy()
+        return self.rows.committed("act")
 
     @property
     def committed_scores(self) -> Optional[np.ndarray]:
         """f32 [F, K]: the aggregated scores of the committed frames (a copy), when the stream was opened with scores=True"""
-        return self._sc[:self.frontier].copy() if self.want_scores else None
+        return self.rows.committed("sc") if self.want_scores else None
 
-    def _covered_frames(self, num_windows: int) -> int:
-        """number of frames Inference.aggregate gives for `num_windows` windows (as _frame_grid)"""
-        c, g = self.chunks, self.grid
-        return int(g.closest_frame(c.start + c.duration + (num_windows - 1) * c.step + 0.5 * g.duration) + 1)
-
-    # ------------------------------------------------------------------ device work
-    def _compute(self, upto: int) -> None:
-        """run windows done .. upto behind the newest upload and append their decisions to the device buffer"""
-        if upto <= self.done:
-            return
-        self.ingest.wait()
-        res = self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=False)
-        self.seg[self.done:upto] = res.segmentations
-        self.stats["windows"] += upto - self.done
-        self.stats["launches"] += 1
-        self.done = upto
-
-    def _detect(self, upto_frames: int, frontier: int) -> None:
-        """one range call over [self.frontier, upto_frames); frames below `frontier` are committed"""
-        t0, t1 = self.frontier, max(int(upto_frames), self.frontier)
-        frontier = min(max(frontier, t0), t1)
-        if t1 > len(self._act):
-            cap = max(t1, 2 * len(self._act))
-            self._act = np.concatenate([self._act, np.zeros((cap - len(self._act), self._act.shape[1]), np.uint8)])
-            if self.want_scores:
-                self._sc = np.concatenate([self._sc, np.zeros((cap - len(self._sc), self._sc.shape[1]), np.float32)])
-        if t1 > t0:
-            sc, act = detect_range_launch(self.seg, self.done, self.d_start, self.d_weight, t0, t1, self.tasks,
-                                          self.det.onset, self.det.offset, self._entry)
-            self.stats["range_calls"] += 1
-            self._act[t0:t1] = act.cpu().numpy()
-            if self.want_scores:
-                self._sc[t0:t1] = sc.cpu().numpy()
-            if frontier > t0:
-                self._entry = act[frontier - 1 - t0]
-        self.frontier, self.covered = frontier, t1
+    def _range(self, t0: int, t1: int, frontier: int) -> dict:
+        """one dzn_detect_range call; the activity of frame frontier - 1 is the next call's entry state"""
+        sc, act = detect_range_launch(self.seg, self.done, self.d_start, self.d_weight, t0, t1, self.tasks,
+                                      self.det.onset, self.det.offset, self._entry)
+        if frontier > t0:
+            self._entry = act[frontier - 1 - t0]
+        return {"act": act, "sc": sc} if self.want_scores else {"act": act}
 
     def _annotate(self):
-        return self.det._regions(self._act[:self.covered], self.grid, self.uri, self.labels)
+        return self.det._regions(self.rows.valid("act"), self.grid, self.name, self.labels)
 
-    # ------------------------------------------------------------------ feed / finish
-    def feed(self, samples):
-        """append float32 samples (mono, the pipeline's rate).  -> None while no window is complete, else the Annotation over
-        every frame computed so far (final before `committed_seconds`, provisional after)"""
-        from .streaming import complete_windows
-        if self.finished:
-            raise RuntimeError("stream already finished")
-        with torch.cuda.device(self.device):
-            taken = self.ingest.append(samples)
-            self.stats["uploads"] = self.ingest.uploads
-            upto = complete_windows(self.ingest.n, self.runner.window, self.runner.step)
-            if taken and upto > self.done:
-                self._compute(upto)
-                self._detect(self._covered_frames(self.done), committed_frames(self.done, self.chunks, self.frames))
-                self._last = self._annotate()
-        return self._last
+    def _final_frames(self, T: int, has_last: bool) -> int:
+        """the crop apply() makes after a zero-padded last window (PA/core/inference.py:400-403)"""
+        return crop_end(T, self.grid, self.n / self.sr) if has_last else T
 
-    def finish(self):
-        """end of stream: the zero-padded last window if the reference would run one, the crop apply() makes, everything
-        committed -> the Annotation apply() gives on the whole recording (and its RTTM file when rttm_out_dir is set)"""
-        if self.finished:
-            raise RuntimeError("stream already finished")
-        r = self.runner
-        n = self.ingest.n
-        n_full, has_last = window_plan(n, r.window, r.step)
-        self.finished = True
-        if n == 0:
-            return Annotation(uri=self.uri)
-        with torch.cuda.device(self.device):
-            self._compute(n_full + int(has_last))
-            T = self._covered_frames(self.done)
-            if has_last:
-                T = crop_end(T, self.grid, n / self.sr)          # zero-padded last window: PA/core/inference.py:400-403
-            assert self.frontier <= T, "committed frames beyond the offline output"
-            self._detect(T, T)
-        ann = self._last = self._annotate()
-        self.det._write_rttm(ann, self.uri)
-        return ann
+    def _write_rttm(self, ann) -> None:
+        self.det._write_rttm(ann, self.name)

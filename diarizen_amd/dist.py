@@ -32,6 +32,13 @@ def world_size() -> int:
     return d.get_world_size() if d else 1
 
 
+def require_single_rank(who: str) -> None:
+    """refuse what runs on one device only (the detection pipelines, the sessions with a committed prefix)"""
+    if world_size() > 1:                # looked up in the module at call time
+        raise RuntimeError(f"{who} runs on one device: sharding a recording over torch.distributed ranks "
+                           f"is not supported (world size {world_size()})")
+
+
 def shard_range(num_windows: int, r: int, g: int) -> Tuple[int, int]:
     """contiguous block partition; trailing ranks may be empty"""
     per = -(-num_windows // g) if g > 0 else num_windows

@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from . import _lib
 from .core import HAVE_PYANNOTE_CORE, Annotation, Segment, SlidingWindow, SlidingWindowFeature
 
 
@@ -168,22 +169,40 @@ def speaker_scores(soft: np.ndarray, chunks: SlidingWindow, frames: SlidingWindo
 
 
 # ----------------------------------------------------------------------------- device versions (row f2)
-def _frame_grid(C: int, L: int, chunks: SlidingWindow, frames: SlidingWindow):
-    """(frame grid of aggregate(), start frame of every window, number of output frames) — the reference's float64
-    closest_frame arithmetic (PA/core/inference.py:577-581, 611-620, 645) stays on the host."""
-    grid = SlidingWindow(start=chunks.start, duration=frames.duration, step=frames.step)
-    starts = np.array([grid.closest_frame(chunks.start + c * chunks.step + 0.5 * grid.duration) for c in range(C)],
-                      dtype=np.int32)
-    T = grid.closest_frame(chunks.start + chunks.duration + (C - 1) * chunks.step + 0.5 * grid.duration) + 1
-    return grid, starts, int(T)
+def _aggregate_grid(chunks: SlidingWindow, frames: SlidingWindow) -> SlidingWindow:
+    """the frame grid of aggregate(): the receptive field's duration and step from the chunks' start"""
+    return SlidingWindow(start=chunks.start, duration=frames.duration, step=frames.step)
 
 
-def committed_frames(num_windows: int, chunks: SlidingWindow, frames: SlidingWindow) -> int:
-    """the start frame of window index `num_windows` (the closest_frame arithmetic of _frame_grid): with windows
-    0 .. num_windows - 1 computed, every frame before it is covered by computed windows only, so its aggregated score — and
-    the hysteresis up to it — is final; the frame itself is the first that the next window changes (detection.DetectionStream)"""
-    grid = SlidingWindow(start=chunks.start, duration=frames.duration, step=frames.step)
+def committed_frames(num_windows: int, chunks: SlidingWindow, frames: SlidingWindow, grid: Optional[SlidingWindow] = None) -> int:
+    """the start frame of window index `num_windows` — the reference's float64 closest_frame arithmetic
+    (PA/core/inference.py:611-620): with windows 0 .. num_windows - 1 computed, every frame before it is covered by computed
+    windows only, so its aggregated score — and the hysteresis up to it — is final; the frame itself is the first that the
+    next window changes (streaming.CommittedStream).  grid: aggregate's grid when the caller has it already."""
+    grid = _aggregate_grid(chunks, frames) if grid is None else grid
     return int(grid.closest_frame(chunks.start + num_windows * chunks.step + 0.5 * grid.duration))
+
+
+def covered_frames(num_windows: int, chunks: SlidingWindow, frames: SlidingWindow, grid: Optional[SlidingWindow] = None) -> int:
+    """number of frames Inference.aggregate gives for `num_windows` windows (PA/core/inference.py:577-581, 645)"""
+    grid = _aggregate_grid(chunks, frames) if grid is None else grid
+    return int(grid.closest_frame(chunks.start + chunks.duration + (num_windows - 1) * chunks.step + 0.5 * grid.duration) + 1)
+
+
+def _frame_grid(C: int, L: int, chunks: SlidingWindow, frames: SlidingWindow):
+    """(frame grid of aggregate(), start frame of every window, number of output frames): the arithmetic stays on the host"""
+    grid = _aggregate_grid(chunks, frames)
+    starts = np.array([committed_frames(c, chunks, frames, grid) for c in range(C)], dtype=np.int32)
+    return grid, starts, covered_frames(C, chunks, frames, grid)
+
+
+def _call(name: str, *args) -> None:
+    """one C-ABI launch (include/dzn.h) on the current stream of the operands' device (that of the first, a tensor): numbers
+    go over as they are, None as a null pointer, everything else is a device tensor and goes over as its address; the stream
+    handle is appended and the status goes through _lib.check"""
+    import torch
+    argv = [a if a is None or isinstance(a, (int, float)) else a.data_ptr() for a in args]
+    _lib.check(getattr(_lib.load(), name)(*argv, torch.cuda.current_stream(args[0].device).cuda_stream), None, name)
 
 
 _HOST_STREAMS = {}
@@ -206,10 +225,9 @@ class DevicePost:
     30 min); the top-`count` selection per frame keeps the reference's numpy call on the downloaded activations."""
 
     def __init__(self, segmentations: np.ndarray, chunks: SlidingWindow, frames: SlidingWindow, device):
-        import ctypes as C_
         import torch
-        from . import _lib
-        self._C, self.torch, self.lib, self.check = C_, torch, _lib.load(), _lib.check
+        self.torch = torch
+        _lib.load()                                                 # a missing library is an error here, not at the first launch
         self.device = torch.device(device)
         seg = np.ascontiguousarray(segmentations)
         if seg.dtype != np.uint8:
@@ -226,17 +244,12 @@ class DevicePost:
             self.seg = torch.from_numpy(seg).to(self.device)
             self.starts = torch.from_numpy(starts).to(self.device)
 
-    def _p(self, t):
-        return self._C.c_void_p(t.data_ptr())
-
     def speaker_count(self) -> SlidingWindowFeature:
         torch = self.torch
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             work = torch.empty(2 * self.T, device=self.device, dtype=torch.int32)
             out = torch.empty(self.T, device=self.device, dtype=torch.uint8)
-            st = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self.check(self.lib.dzn_speaker_count(self._p(self.seg), self.C, self.L, self.S, self._p(self.starts), self.T,
-                                                  self._p(work), self._p(out), st), None, "dzn_speaker_count")
+            _call("dzn_speaker_count", self.seg, self.C, self.L, self.S, self.starts, self.T, work, out)
             return SlidingWindowFeature(out.cpu().numpy().reshape(-1, 1), self.grid)
 
     def reconstruct(self, hard_clusters: np.ndarray, count: SlidingWindowFeature):
@@ -247,10 +260,7 @@ class DevicePost:
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
             hard = torch.from_numpy(np.ascontiguousarray(hard_clusters, dtype=np.int8)).to(self.device)
             act = torch.empty((self.T, K), device=self.device, dtype=torch.int32)
-            st = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self.check(self.lib.dzn_cluster_activations(self._p(self.seg), self._p(hard), self.C, self.L, self.S,
-                                                        self._p(self.starts), self.T, K, self._p(act), st), None,
-                       "dzn_cluster_activations")
+            _call("dzn_cluster_activations", self.seg, hard, self.C, self.L, self.S, self.starts, self.T, K, act)
             a = act.cpu().numpy().astype(np.float32)
         return _select_top_count(SlidingWindowFeature(a, count.sliding_window), count)
 
@@ -276,10 +286,7 @@ class DevicePost:
             hard = torch.from_numpy(np.ascontiguousarray(hard_clusters, dtype=np.int8)).to(self.device)
             d_ham, d_wu = torch.from_numpy(ham).to(self.device), torch.from_numpy(wu).to(self.device)
             out = torch.empty((T, K), device=self.device, dtype=torch.float32)
-            st = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self.check(self.lib.dzn_speaker_scores(self._p(soft_device), self._p(hard), self.C, self.L, self.S,
-                                                   self._p(self.starts), self._p(d_ham), self._p(d_wu), T, K, self._p(out), st),
-                       None, "dzn_speaker_scores")
+            _call("dzn_speaker_scores", soft_device, hard, self.C, self.L, self.S, self.starts, d_ham, d_wu, T, K, out)
             return SlidingWindowFeature(out.cpu().numpy(), self.grid)
 
 
@@ -336,9 +343,7 @@ def detect_device(seg, chunks: SlidingWindow, frames: SlidingWindow, tasks: int,
     window start frames and the weight table are computed on the host with the reference's float64 arithmetic.
     frame_range = (t0, t1): dzn_detect_range instead — only frames t0 .. t1 - 1 (rows t - t0 of the two arrays), the
     hysteresis continuing from `entry`, u8 [K]: the activity of frame t0 - 1 (needed when t0 > 0)."""
-    import ctypes as C_
     import torch
-    from . import _lib
     offset = onset if offset is None else offset
     seg_t = seg if isinstance(seg, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(seg, dtype=np.uint8)).cuda()
     assert seg_t.is_cuda and seg_t.dtype == torch.uint8 and seg_t.is_contiguous()
@@ -347,18 +352,14 @@ def detect_device(seg, chunks: SlidingWindow, frames: SlidingWindow, tasks: int,
     grid, starts, T = _frame_grid(Cn, L, chunks, frames)
     T = T if num_frames is None else int(num_frames)
     K = bin(tasks & 3).count("1")
-    lib = _lib.load()
     with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev)
         d_start = torch.from_numpy(starts).to(dev, non_blocking=False)
         d_w = torch.from_numpy(detection_weights(L, chunks.duration, warm_up)).to(dev)
         if frame_range is None:
             scores = torch.empty((T, K), device=dev, dtype=torch.float32)
             active = torch.empty((T, K), device=dev, dtype=torch.uint8)
-            p = lambda t: C_.c_void_p(t.data_ptr())      # noqa: E731
-            _lib.check(lib.dzn_detect(p(seg_t), Cn, L, S, p(d_start), p(d_w), T, tasks, float(np.float32(onset)),
-                                      float(np.float32(offset)), p(scores), p(active), C_.c_void_p(st.cuda_stream)),
-                       None, "dzn_detect")
+            _call("dzn_detect", seg_t, Cn, L, S, d_start, d_w, T, tasks, float(np.float32(onset)), float(np.float32(offset)),
+                  scores, active)
         else:
             t0, t1 = int(frame_range[0]), int(frame_range[1])
             d_entry = None
@@ -375,9 +376,7 @@ def detect_range_launch(seg_t, num_windows: int, d_start, d_weight, t0: int, t1:
     """one dzn_detect_range call on the current stream over device operands: seg_t u8 [>= num_windows, L, S], d_start int32
     [>= num_windows], d_weight f64 [L], d_entry u8 [K] or None -> (scores f32 [t1 - t0, K], activity u8 [t1 - t0, K]), both
     device tensors.  Enqueue only."""
-    import ctypes as C_
     import torch
-    from . import _lib
     dev = seg_t.device
     _, L, S = seg_t.shape
     K = bin(tasks & 3).count("1")
@@ -386,11 +385,8 @@ def detect_range_launch(seg_t, num_windows: int, d_start, d_weight, t0: int, t1:
     active = torch.empty((n, K), device=dev, dtype=torch.uint8)
     if n == 0:
         return scores, active                   # nothing to compute (an empty tensor has no address to hand over)
-    p = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    st = torch.cuda.current_stream(dev)
-    _lib.check(_lib.load().dzn_detect_range(p(seg_t), int(num_windows), L, S, p(d_start), p(d_weight), int(t0), int(t1), tasks,
-                                            float(np.float32(onset)), float(np.float32(offset)), p(d_entry), p(scores),
-                                            p(active), C_.c_void_p(st.cuda_stream)), None, "dzn_detect_range")
+    _call("dzn_detect_range", seg_t, int(num_windows), L, S, d_start, d_weight, int(t0), int(t1), tasks,
+          float(np.float32(onset)), float(np.float32(offset)), d_entry, scores, active)
     return scores, active
 
 
@@ -399,9 +395,7 @@ def diarize_range_launch(seg_t, hard_t, num_windows: int, d_start, t0: int, t1: 
     """one dzn_diarize_range call on the current stream over device operands: seg_t u8 [>= num_windows, L, S], hard_t int8
     [>= num_windows, S], d_start int32 [>= num_windows] -> (count u8 [t1 - t0], active u8 [t1 - t0, K], activations int32
     [t1 - t0, K] or None), device tensors.  Enqueue only."""
-    import ctypes as C_
     import torch
-    from . import _lib
     dev = seg_t.device
     _, L, S = seg_t.shape
     assert seg_t.is_cuda and seg_t.dtype == torch.uint8 and seg_t.is_contiguous()
@@ -413,11 +407,8 @@ def diarize_range_launch(seg_t, hard_t, num_windows: int, d_start, t0: int, t1: 
     act = torch.empty((n, int(K)), device=dev, dtype=torch.int32) if want_activations else None
     if n == 0:
         return count, active, act               # nothing to compute (an empty tensor has no address to hand over)
-    p = lambda t: C_.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    st = torch.cuda.current_stream(dev)
-    _lib.check(_lib.load().dzn_diarize_range(p(seg_t), p(hard_t), int(num_windows), L, S, p(d_start), int(t0), int(t1), int(K),
-                                             int(max_count), p(count), p(active), p(act), C_.c_void_p(st.cuda_stream)),
-               None, "dzn_diarize_range")
+    _call("dzn_diarize_range", seg_t, hard_t, int(num_windows), L, S, d_start, int(t0), int(t1), int(K), int(max_count),
+          count, active, act)
     return count, active, act
 
 

@@ -22,13 +22,16 @@ Design (MI355X-first, same kernels as the offline path):
 """
 from __future__ import annotations
 
-from typing import Iterable, Iterator, Optional, Tuple
+import os
+from typing import Callable, Dict, Iterable, Iterator, Optional, Tuple
 
 import numpy as np
 import torch
 
+from . import dist as dz_dist
 from .core import Annotation
 from .inference import window_plan
+from .postprocess import _frame_grid, committed_frames, covered_frames, receptive_field
 
 
 def complete_windows(num_samples: int, window: int, step: int) -> int:
@@ -37,7 +40,7 @@ def complete_windows(num_samples: int, window: int, step: int) -> int:
 
 
 class WaveIngest:
-    """The ingest half of a streaming session (shared by StreamingSession and detection.DetectionStream): a PINNED host ring,
+    """The ingest half of a streaming session (WindowStream): a PINNED host ring,
     a dedicated copy stream and ONE pre-zeroed device buffer that holds the recording so far; `views` are its windows as rows
     of a strided view.  append() stages a chunk slot by slot and queues the H2D copies; wait() makes the current stream wait
     for the newest one."""
@@ -94,47 +97,90 @@ class WaveIngest:
             torch.cuda.current_stream(self.device).wait_event(self.last_copy)
 
 
-class StreamingSession:
-    def __init__(self, pipeline, sess_name: Optional[str] = None, max_seconds: float = 4 * 3600.0, refresh_s: Optional[float] = 8.0,
-                 slot_seconds: float = 10.0, slots: int = 4):
+class WindowStream:
+    """What every feed / finish session shares: the ingest, each complete window run ONCE through the runner (`_compute`; the
+    subclass takes the results in `_windows`), the feed-after-finish guard, the reference's final-window rule and the RTTM file."""
+    EMBEDDINGS = True                                                   # run_views(with_embeddings=...)
+
+    def __init__(self, pipeline, name: Optional[str] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
+                 slots: int = 4):
+        """pipeline: a DiariZenPipeline or a detection pipeline (its _runner, device and rttm_out_dir are used); name: the
+        session name / uri of the annotations and of the RTTM file"""
         self.pipe = pipeline
-        self.sess_name = sess_name
-        self.refresh_s = refresh_s
-        r = pipeline._runner
-        self.runner = r
+        self.name = name
+        self.runner = r = pipeline._runner
         self.sr = r.sample_rate
-        self.ingest = WaveIngest(pipeline.device, self.sr, r.window, r.step, max_seconds, slot_seconds, slots)
+        self.device = pipeline.device
+        with torch.cuda.device(self.device):
+            self.ingest = WaveIngest(self.device, self.sr, r.window, r.step, max_seconds, slot_seconds, slots)
         self.done = 0                                                   # windows computed
-        self.seg = []                                                   # per batch: u8 [c, L, S] host arrays
-        self.emb = []
-        self.last_refresh_n = 0
         self.finished = False
-        self.stats = {"uploads": 0, "launches": 0, "refreshes": 0}
+        self.stats = {"uploads": 0, "windows": 0, "launches": 0}
 
     @property
     def n(self) -> int:
         """samples received"""
         return self.ingest.n
 
+    @property
+    def seconds(self) -> float:
+        """seconds of audio received"""
+        return self.ingest.n / self.sr
+
+    def _append(self, samples) -> int:
+        """stage float32 samples (mono, the runner's rate) -> number of samples taken"""
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        taken = self.ingest.append(samples)
+        self.stats["uploads"] = self.ingest.uploads
+        return taken
+
     def _compute(self, upto: int) -> None:
         """run windows done .. upto on the compute stream, behind the newest upload"""
         if upto <= self.done:
             return
         self.ingest.wait()
-        res = self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=True)
+        res = self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=self.EMBEDDINGS)
+        self._windows(res, self.done, upto)
+        self.stats["launches"] += 1
+        self.stats["windows"] += upto - self.done
+        self.done = upto
+
+    def _windows(self, res, lo: int, hi: int) -> None:
+        """keep the results of windows lo .. hi - 1"""
+        raise NotImplementedError
+
+    def _final_windows(self) -> Tuple[int, bool]:
+        """(windows of the whole recording, the last of them is zero-padded): the reference's rule, PA/core/inference.py:293-299"""
+        n_full, has_last = window_plan(self.n, self.runner.window, self.runner.step)
+        return n_full + int(has_last), has_last
+
+    def _write_rttm(self, ann: Annotation) -> None:
+        """the final annotation as <rttm_out_dir>/<name>.rttm, when the pipeline has the one and the session the other"""
+        if self.pipe.rttm_out_dir is not None and self.name is not None:
+            with open(os.path.join(self.pipe.rttm_out_dir, self.name + ".rttm"), "w") as f:
+                f.write(ann.to_rttm())
+
+
+class StreamingSession(WindowStream):
+    def __init__(self, pipeline, sess_name: Optional[str] = None, max_seconds: float = 4 * 3600.0, refresh_s: Optional[float] = 8.0,
+                 slot_seconds: float = 10.0, slots: int = 4):
+        super().__init__(pipeline, sess_name, max_seconds, slot_seconds, slots)
+        self.refresh_s = refresh_s
+        self.seg = []                                                   # per batch: u8 [c, L, S] host arrays
+        self.emb = []
+        self.last_refresh_n = 0
+        self.stats["refreshes"] = 0
+
+    def _windows(self, res, lo: int, hi: int) -> None:
         self.seg.append(res.segmentations.cpu().numpy())               # 5.7 KB per window
         self.emb.append(res.embeddings.cpu().numpy())
-        self.done = upto
-        self.stats["launches"] += 1
 
     def feed(self, samples) -> Optional[Annotation]:
         """append float32 samples (16 kHz mono, the pipeline's rate); returns a provisional annotation when a refresh is
         due, else None"""
-        if self.finished:
-            raise RuntimeError("stream already finished")
-        if self.ingest.append(samples) == 0:
+        if self._append(samples) == 0:
             return None
-        self.stats["uploads"] = self.ingest.uploads
         self._compute(complete_windows(self.n, self.runner.window, self.runner.step))
         if (self.refresh_s is not None and self.done > 0
                 and self.n - self.last_refresh_n >= self.refresh_s * self.sr):
@@ -145,27 +191,18 @@ class StreamingSession:
 
     def _annotate(self) -> Annotation:
         seg, emb = np.concatenate(self.seg), np.concatenate(self.emb)
-        return self.pipe.host_stage(seg, emb, self.sess_name)
+        return self.pipe.host_stage(seg, emb, self.name)
 
     def finish(self) -> Annotation:
         """end of stream: the zero-padded tail window (if the reference would run one), then the final host stage"""
-        r = self.runner
-        n_full, has_last = window_plan(self.n, r.window, r.step)
         if self.n > 0:
-            self._compute(n_full + int(has_last))
+            self._compute(self._final_windows()[0])
         self.finished = True
         if self.done == 0:
-            return Annotation(uri=self.sess_name)
+            return Annotation(uri=self.name)
         ann = self._annotate()
-        if self.pipe.rttm_out_dir is not None and self.sess_name is not None:
-            import os
-            with open(os.path.join(self.pipe.rttm_out_dir, self.sess_name + ".rttm"), "w") as f:
-                f.write(ann.to_rttm())
+        self._write_rttm(ann)
         return ann
-
-    @property
-    def seconds(self) -> float:
-        return self.n / self.sr
 
 
 def stream(pipeline, chunks: Iterable, sess_name: Optional[str] = None, **kw) -> Iterator[Tuple[float, Annotation]]:
@@ -177,3 +214,148 @@ def stream(pipeline, chunks: Iterable, sess_name: Optional[str] = None, **kw) ->
         if ann is not None:
             yield sess.seconds, ann
     yield sess.seconds, sess.finish()
+
+
+# ----------------------------------------------------------------------------- sessions with a committed prefix
+class StreamRows:
+    """Growable host rows of a CommittedStream, one named array per output: rows below `frontier` are final, rows below
+    `covered` valid (the provisional tail lies between the two).  Needs no device."""
+
+    def __init__(self, **arrays):
+        """name = (dtype, trailing shape) per array"""
+        self.frontier = 0                                               # rows committed
+        self.covered = 0                                                # rows computed (committed + provisional tail)
+        self._rows = {k: np.zeros((1024,) + tuple(shape), dtype=dtype) for k, (dtype, shape) in arrays.items()}
+
+    def span(self, upto: int, frontier: int) -> Tuple[int, int, int]:
+        """the next step computes rows [t0, t1) = [self.frontier, upto) and commits the rows below `frontier`:
+        -> (t0, t1, frontier) with t1 >= t0 and t0 <= frontier <= t1"""
+        t0, t1 = self.frontier, max(int(upto), self.frontier)
+        return t0, t1, min(max(int(frontier), t0), t1)
+
+    def write(self, t0: int, t1: int, frontier: int, **arrays) -> None:
+        """rows [t0, t1) of the named arrays (none when the span is empty), then the new frontier; capacity doubles"""
+        for k, a in self._rows.items():
+            if t1 > len(a):
+                grown = np.zeros((max(t1, 2 * len(a)),) + a.shape[1:], dtype=a.dtype)
+                grown[:len(a)] = a
+                self._rows[k] = grown
+        for k, v in arrays.items():
+            self._rows[k][t0:t1] = v
+        self.frontier, self.covered = frontier, t1
+
+    def committed(self, name: str) -> np.ndarray:
+        """the rows below the frontier (a copy)"""
+        return self._rows[name][:self.frontier].copy()
+
+    def valid(self, name: str) -> np.ndarray:
+        """the rows below `covered` (a view)"""
+        return self._rows[name][:self.covered]
+
+
+class CommittedStream(WindowStream):
+    """A session whose output has a COMMITTED PREFIX: the windows' u8 decisions are kept in one device buffer [cmax, L, S],
+    and per feed one range call computes the frames [previous frontier, frames covered so far).
+
+    A frame's result depends only on the windows that cover it, and window start frames do not depend on how many windows
+    exist.  With windows 0 .. C - 1 computed, every frame before the start frame of window C (the FRONTIER,
+    postprocess.committed_frames) is therefore final: the committed rows are the offline bits and only ever grow.  The frames
+    from the frontier to the end of window C - 1 are the provisional tail, which the next window revises — nothing that is
+    already final is derived again.
+
+    The subclass gives `_range(t0, t1, frontier)` -> {row name: device tensor [t1 - t0, ...]} and `_annotate()`; it may extend
+    `_windows` and `_final_frames`."""
+
+    def __init__(self, pipeline, name: Optional[str], rows: Dict[str, tuple], max_seconds: float = 4 * 3600.0,
+                 slot_seconds: float = 10.0, slots: int = 4):
+        """rows: the host arrays the range call fills, name -> (dtype, trailing shape) (StreamRows)"""
+        dz_dist.require_single_rank(type(self).__name__)
+        super().__init__(pipeline, name, max_seconds, slot_seconds, slots)
+        self.chunks, self.frames = pipeline.chunks_window(), receptive_field(self.sr)
+        cmax, L, S = self.ingest.views.shape[0], self.runner.num_frames, pipeline.engine.seg.max_speakers_per_chunk
+        self.grid, starts, _ = _frame_grid(cmax, L, self.chunks, self.frames)
+        with torch.cuda.device(self.device):
+            self.seg = torch.zeros((cmax, L, S), device=self.device, dtype=torch.uint8)     # decisions of every window so far
+            self.d_start = torch.from_numpy(starts).to(self.device)
+        self.rows = StreamRows(**rows)
+        self._last = None
+        self.stats["range_calls"] = 0
+
+    @property
+    def frontier(self) -> int:
+        """frames committed"""
+        return self.rows.frontier
+
+    @property
+    def covered(self) -> int:
+        """frames computed (committed + provisional tail)"""
+        return self.rows.covered
+
+    @property
+    def committed_seconds(self) -> float:
+        """start time of the first frame that may still change"""
+        return self.grid.start + self.frontier * self.grid.step
+
+    def _windows(self, res, lo: int, hi: int) -> None:
+        self.seg[lo:hi] = res.segmentations
+
+    def _advance(self, upto_frames: int, frontier: int) -> None:
+        """one range call over [self.frontier, upto_frames); frames below `frontier` are committed"""
+        t0, t1, frontier = self.rows.span(upto_frames, frontier)
+        out = {}
+        if t1 > t0:
+            out = self._range(t0, t1, frontier)
+            self.stats["range_calls"] += 1
+        self.rows.write(t0, t1, frontier, **{k: v.cpu().numpy() for k, v in out.items()})
+
+    def _range(self, t0: int, t1: int, frontier: int) -> dict:
+        raise NotImplementedError
+
+    def _annotate(self) -> Annotation:
+        raise NotImplementedError
+
+    def _final_frames(self, T: int, has_last: bool) -> int:
+        """the length of the final output, given the T frames the windows cover"""
+        return T
+
+    def feed(self, samples) -> Optional[Annotation]:
+        """append float32 samples (mono, the pipeline's rate).  -> None while no window is complete, else the Annotation over
+        every frame computed so far (final before `committed_seconds`, provisional after)"""
+        with torch.cuda.device(self.device):
+            taken = self._append(samples)
+            upto = complete_windows(self.n, self.runner.window, self.runner.step)
+            if taken and upto > self.done:
+                self._compute(upto)
+                self._advance(covered_frames(self.done, self.chunks, self.frames, self.grid),
+                              committed_frames(self.done, self.chunks, self.frames, self.grid))
+                self._last = self._annotate()
+        return self._last
+
+    def finish(self, annotate: Optional[Callable[[], Annotation]] = None) -> Annotation:
+        """end of stream: the zero-padded last window if the reference would run one, every frame of the final length
+        committed -> `annotate()` (default: `_annotate`), written as RTTM where the subclass's `_write_rttm` says so"""
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        total, has_last = self._final_windows()
+        self.finished = True
+        if self.n == 0:
+            return Annotation(uri=self.name)
+        with torch.cuda.device(self.device):
+            self._compute(total)
+            T = self._final_frames(covered_frames(self.done, self.chunks, self.frames, self.grid), has_last)
+            assert self.frontier <= T, "committed frames beyond the offline output"
+            self._advance(T, T)
+        ann = self._last = (annotate or self._annotate)()
+        self._write_rttm(ann)
+        return ann
+
+
+def stream_committed(sess: CommittedStream, chunks: Iterable, **finish_kw) -> Iterator[Tuple[float, float, Annotation]]:
+    """generator form of a CommittedStream: chunks of float32 samples at the pipeline's rate -> (seconds received, committed
+    seconds, Annotation) for every feed that produced an annotation, then the final triple"""
+    for c in chunks:
+        ann = sess.feed(c)
+        if ann is not None:
+            yield sess.seconds, sess.committed_seconds, ann
+    ann = sess.finish(**finish_kw)
+    yield sess.seconds, sess.committed_seconds, ann

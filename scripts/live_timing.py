@@ -45,7 +45,7 @@ class Clock:
 
 def live_pass(pipe, chunks):
     sess = pipe.open_live(sess_name="timing", delta_new=0.2, max_seconds=60.0)
-    clocks = {"compute": Clock(sess, "_compute"), "assign": Clock(sess.speakers, "assign"), "range": Clock(sess, "_diarize")}
+    clocks = {"compute": Clock(sess, "_compute"), "assign": Clock(sess.speakers, "assign"), "range": Clock(sess, "_advance")}
     rows = []
     for c in chunks:
         before = {k: v.total for k, v in clocks.items()}

@@ -3,35 +3,13 @@ in 0.37 s chunks.  After every feed the committed activity and scores only grow 
 bit, every window is computed once, and the final annotation is the offline pipelines' RTTM text — for a recording on the
 step grid, one with a zero-padded last window and one shorter than a window."""
 import copy
-import io
-import os
-import wave as _wave
 
 import numpy as np
 import pytest
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-WAV = os.path.join(GOLD, "EN2002a_30s.wav")
-WINDOW, STEP, FEED = 128000, 12800, 5920            # 8 s windows at a 0.8 s step; 0.37 s per feed
-RECORDINGS = {"grid": WINDOW + 10 * STEP,           # 16 s: the last window ends with the recording, no padded window
-              "padded": 480000,                     # 30 s: 28 windows and a zero-padded 29th
-              "short": 80000}                       # 5 s: one zero-padded window, nothing is committed before finish()
+from _stream_cases import RECORDINGS, STEP, WINDOW, feeds, samples
 
 pytestmark = pytest.mark.gpu
-
-
-def blob(n):
-    """the first n samples of the fixture as an in-memory 16-bit WAV"""
-    with _wave.open(WAV, "rb") as r:
-        assert r.getframerate() == 16000 and r.getnchannels() == 1 and r.getsampwidth() == 2 and r.getnframes() >= n
-        pcm = r.readframes(n)
-    buf = io.BytesIO()
-    with _wave.open(buf, "wb") as w:
-        w.setnchannels(1)
-        w.setsampwidth(2)
-        w.setframerate(16000)
-        w.writeframes(pcm)
-    return buf.getvalue()
 
 
 @pytest.fixture(scope="module")
@@ -56,13 +34,10 @@ def offline(detectors, gpu, name):
     """per recording, once: (samples, WAV bytes, offline activity [T, 2], scores [T, 2], VAD RTTM, OSD RTTM)"""
     if name not in _OFFLINE:
         import torch
-        from diarizen_amd.audio import first_channel_16k
         from diarizen_amd.inference import window_plan
         from diarizen_amd.postprocess import _frame_grid, crop_end, detect_device, receptive_field
         vad, osd = detectors
-        data = blob(RECORDINGS[name])
-        x = first_channel_16k(data)
-        assert len(x) == RECORDINGS[name]
+        x, data = samples(RECORDINGS[name])
         res = vad._runner.run(torch.from_numpy(x).to(gpu), with_embeddings=False)
         Cn, L, _ = res.segmentations.shape
         grid, _, T = _frame_grid(Cn, L, vad.chunks_window(), receptive_field())
@@ -76,10 +51,6 @@ def offline(detectors, gpu, name):
         sc.setflags(write=False)
         _OFFLINE[name] = (x, data, act, sc, vad(file).to_rttm(), osd(file).to_rttm())
     return _OFFLINE[name]
-
-
-def feeds(x):
-    return [x[i:i + FEED] for i in range(0, len(x), FEED)]
 
 
 def lines(rttm, label):

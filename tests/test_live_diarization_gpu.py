@@ -4,42 +4,18 @@ a replay (offline device stage -> online.OnlineSpeakers over its windows on the 
 bit, whatever the chunking; a label keeps its committed frames from one provisional annotation to the next; finish(
 recluster=True) gives the offline turns under the live labels."""
 import copy
-import io
-import os
-import wave as _wave
 
 import numpy as np
 import pytest
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-WAV = os.path.join(GOLD, "EN2002a_30s.wav")
-WINDOW, STEP = 128000, 12800                        # 8 s windows at a 0.8 s step
-FEED, FEED_LONG = 5920, 46400                       # 0.37 s and 2.9 s per feed
-RECORDINGS = {"grid": WINDOW + 10 * STEP,           # 16 s: the last window ends with the recording, no padded window
-              "padded": 480000,                     # 30 s: 28 windows and a zero-padded 29th
-              "short": 80000}                       # 5 s: one zero-padded window, nothing is committed before finish()
+from _stream_cases import FEED, RECORDINGS, STEP, WINDOW, feeds, samples
+
+FEED_LONG = 46400                                   # 2.9 s per feed (FEED: 0.37 s)
 WINDOWS = {"grid": 11, "padded": 29, "short": 1}
 DELTA = 0.2                                         # the seeded embedding weights: 3 speakers at 0.2 (16 at the config's 0.1)
 KW = dict(delta_new=DELTA, max_seconds=60.0, slot_seconds=2.5, slots=3)
 
 pytestmark = pytest.mark.gpu
-
-
-def samples(n):
-    """the first n samples of the fixture: (float32 array, in-memory 16-bit WAV)"""
-    from diarizen_amd.audio import first_channel_16k
-    with _wave.open(WAV, "rb") as r:
-        assert r.getframerate() == 16000 and r.getnchannels() == 1 and r.getsampwidth() == 2 and r.getnframes() >= n
-        pcm = r.readframes(n)
-    buf = io.BytesIO()
-    with _wave.open(buf, "wb") as w:
-        w.setnchannels(1)
-        w.setsampwidth(2)
-        w.setframerate(16000)
-        w.writeframes(pcm)
-    x = first_channel_16k(buf.getvalue())
-    assert len(x) == n
-    return x, buf.getvalue()
 
 
 @pytest.fixture(scope="module")
@@ -54,10 +30,6 @@ def pipe(built_lib, gpu):
         "wavlm_large_s80_md"), 0), emb_state=emb_state_dict(0))
     yield p
     p.close()
-
-
-def feeds(x, size=FEED):
-    return [x[i:i + size] for i in range(0, len(x), size)]
 
 
 _REPLAY = {}
