@@ -65,18 +65,29 @@ struct LNp {
   int C = 0;
 };
 
+// A LayerNorm that feeds a linear, loaded by norm_lin() and run by norm_lin_desc(): the one place that decides, and the one
+// that acts on, whether the norm is folded into the weights.  ln.C == 0: no norm in front (post-norm encoder layers).
+struct NormLin {
+  LNp ln;
+  Lin lin;
+  bool folded = false;   // gamma / beta are inside lin.W / lin.b and lin.csum is set (make_lin_ln): the contraction reads RAW rows
+};
+
 struct EncLayer {
   bool attn = false, ffn = false;
+  bool pre_norm = false;   // layer_norm_first: ln1 / ln2 stand in front of qkv / f1 (and live in them); else they follow the sub-blocks
   int h = 0, F = 0, Fp = 0;
   LNp ln1, ln2;
-  Lin qkv, out, f1, f2;
+  NormLin qkv, f1;
+  Lin out, f2;
   float *Wg = nullptr, *bg = nullptr, *cst = nullptr;
   int32_t* head_idx = nullptr;
 };
 
 struct ConfLayer {
-  LNp ffn1_ln, ffn2_ln, mha_ln, conv_ln, out_ln;
-  Lin ffn1_w1, ffn1_w2, ffn2_w1, ffn2_w2, qkv, o, pw1, pw2;
+  NormLin ffn1_w1, ffn2_w1, qkv, pw1;   // each with the ln_norm of its sub-block
+  Lin ffn1_w2, ffn2_w2, o, pw2;
+  LNp out_ln;
   float *dw = nullptr, *dwb = nullptr;
 };
 
@@ -93,14 +104,73 @@ struct ResBlock {
 
 std::string last_create_error;
 
-// contraction classes of the segmentation model, by the name their call site passes to gemm(): bit index of the
-// DZN_F16_KEEP2 mask (DZN_PREC_F16: classes whose bit is set keep two fp16 terms per operand)
-const char* const F16_CLASSES[] = {"conv gemm", "feature projection", "pos conv", "qkv", "out_proj", "ffn1", "ffn2", "proj",
-                                   "conf ffn w1", "conf ffn w2", "conf qkv", "conf out", "conf pw1", "conf pw2"};
-int f16_class(const char* what) {
-  for (int i = 0; i < (int)(sizeof(F16_CLASSES) / sizeof(F16_CLASSES[0])); ++i)
-    if (!strcmp(what, F16_CLASSES[i])) return i;
-  return -1;
+// contraction classes: the value is the bit index of the DZN_F16_KEEP2 / DZN_F16_MX masks (DZN_PREC_F16: classes whose bit
+// is set keep two fp16 terms per operand / run the fp8 cross terms).  0-13 are the segmentation model's, 14 the ResNet trunk.
+enum F16Class { CLS_CONV, CLS_FEATPROJ, CLS_POSCONV, CLS_QKV, CLS_OUT, CLS_FFN1, CLS_FFN2, CLS_PROJ, CLS_CONF_W1, CLS_CONF_W2,
+                CLS_CONF_QKV, CLS_CONF_OUT, CLS_CONF_PW1, CLS_CONF_PW2, CLS_RESNET };
+// what a failed launch of a segmentation class is called in the error message
+const char* const F16_CLASSES[CLS_RESNET] = {"conv gemm", "feature projection", "pos conv", "qkv", "out_proj", "ffn1", "ffn2",
+                                             "proj", "conf ffn w1", "conf ffn w2", "conf qkv", "conf out", "conf pw1", "conf pw2"};
+
+// Every DZN_* environment switch the engine reads.  All of them are read once, by read_switches() at dzn_create: a switch
+// belongs to the handle that was created under it.
+struct Switches {
+  bool fold_ln = true;          // fp32 engine modes: LayerNorms that feed only linears are folded (make_lin_ln)
+  bool conv0_quad_stats = true;
+  bool fuse_conv01 = true;
+  bool conv01_ln = true;
+  // (r4) pre-norm encoders: every layer writes its output rows into ITS OWN buffer (xl + layer * rows * D) and the
+  // layer-weighted sum (model_wavlm_conformer.py:236,253-254) is ONE pass over those buffers after the last layer, instead of
+  // a read-modify-write of `ws` in every FFN-output epilogue: 25 reads + 1 write of [rows, D] where there were 25 reads and
+  // 25 writes.  Off: the fused read-modify-write (also taken by post-norm encoders and when there is not enough free memory).
+  bool ws_defer = true;
+  bool att_planes = true;
+  bool epilogue_stats = true;
+  bool emb_skip = true;
+  bool fuse_resblock = true;    // (r4) stride-1 BasicBlocks in the two-term fp16 modes: both convolutions in one kernel
+  bool fuse_shortcut = true;    // off: the shortcut of a down-sampling block stays its own launch
+  int resblock_ws = 2;          // bit mask: 1 = 32-plane blocks, 2 = 64-plane blocks on the producer / consumer form
+  // DZN_PREC_F16 (reduced precision): which contraction classes keep two fp16 terms (F16Class bit mask; bit 14 = the
+  // ResNet stages 2-4), and whether LayerNorm-folded single-term contractions subtract the row mean BEFORE rounding
+  // defaults from profiles/r4_f16_sensitivity.json (64 non-degenerate windows vs the f32h engine): the error of the
+  // single-term mode is NOT localised — no one class brings max |dlogp| under SURVEY 8d's 5e-2, only two terms everywhere
+  // (= f32h) does; the conv stack alone carries ~70 % of the error variance for 4 % of the flops, so it keeps two terms
+  // (0.247 -> 0.133, flips 0.52 % -> 0.33 %); centring the LayerNorm-folded split changes nothing (0.228 vs 0.247: the
+  // error is plain operand rounding, not the mean * colsum cancellation) and stays off.
+  // (r5, ADVICE r4) bit 14 governs the whole trunk: the stride-2 / shortcut / stage 3-4 contractions (gemm_split.hip NP = 1)
+  // AND the fused stride-1 BasicBlocks of stages 1-2 (resblock_fused.hip / resblock_ws.hip, which have a single-term form
+  // since r5; in r4 they were two-term whatever the bit said).
+  // (r5) with the cross terms in fp8 everywhere else, the Conformer head (bits 8-13, 8 % of the segmentation flops) keeps two
+  // fp16 terms as well: max |dlogp| does not move (1.01e-2 vs 1.03e-2) but the decisions next to the classifier do — DER of the
+  // mode's RTTM against the fp32 RTTM on the 30 s fixture 0.05 % (one 20 ms frame) instead of 0.17 % (three), inside SURVEY 8d's
+  // 0.1 abs; device step 1872 -> 1856 audio-s/s on one box (profiles/r5_reduced_mode_keep2_probe.txt)
+  unsigned f16_keep2 = 0x3f01;
+  // (r5) DZN_PREC_F16: the classes whose bit is set run fp16 hi*hi + the two cross terms in fp8 (gemm_mx.hip) — every linear
+  // contraction of the segmentation model: the class sweep of profiles/r4_reduced_mode_emulation.txt shows that any one of them
+  // at a single fp16 term costs 0.04-0.21 of max |dlogp| against SURVEY 8d's 5e-2, only the positional conv (bit 2) can stay at
+  // one term.  Bit 0 (the conv stack) keeps two fp16 terms (f16_keep2).  0 = r4's single-term mode.
+  unsigned f16_mx = 0x3ffa;
+  bool debug_taps = false;
+};
+
+Switches read_switches() {
+  Switches s;
+  s.fold_ln = !getenv("DZN_NO_LN_FOLD");                    // =1: every LayerNorm runs stand-alone, in the reference's order
+  s.conv0_quad_stats = !getenv("DZN_CONV0_WAVE_STATS");      // =1: conv0's LayerNorm statistics from its outputs, not the quadratic form
+  s.fuse_conv01 = !getenv("DZN_NO_CONV01_FUSION");          // =1: conv0 and conv1 as separate kernels (f32h)
+  s.conv01_ln = !getenv("DZN_CONV01_NO_LN");                // =1: the fused conv0 -> conv1 kernel leaves conv1's LayerNorm + GELU to the row pass
+  s.ws_defer = !getenv("DZN_NO_WS_DEFER");                  // =1: layer-weighted sum as a read-modify-write in every FFN-output epilogue
+  s.att_planes = !getenv("DZN_NO_ATT_PLANES");              // =1: fp32 K / V and the in-kernel split of attention_split.hip (f32h)
+  s.epilogue_stats = !getenv("DZN_NO_EPILOGUE_STATS");      // =1: the FFN's LayerNorm statistics by row_stats, not from the out_proj epilogue
+  s.emb_skip = !getenv("DZN_EMB_NO_SKIP");                  // =1: windows without an active speaker go through the trunk too
+  s.fuse_resblock = !getenv("DZN_NO_RESBLOCK_FUSION");      // =1: the per-conv kernels for the stride-1 BasicBlocks
+  s.fuse_shortcut = !getenv("DZN_NO_SHORTCUT_FUSION");      // =1: the 1x1 shortcut of a down-sampling block as its own launch
+  if (const char* e = getenv("DZN_RESBLOCK_WS")) s.resblock_ws = atoi(e);                      // which fused blocks take the producer / consumer form
+  if (const char* e = getenv("DZN_F16_KEEP2")) s.f16_keep2 = (unsigned)strtoul(e, nullptr, 0); // reduced mode: classes with two fp16 terms
+  if (const char* e = getenv("DZN_F16_MX")) s.f16_mx = (unsigned)strtoul(e, nullptr, 0);       // reduced mode: classes with fp8 cross terms
+  const char* dbg = getenv("DZN_DEBUG_TAPS");               // =1: every stage's output is copied to the host for dzn_debug_fetch
+  s.debug_taps = dbg && dbg[0] == '1';
+  return s;
 }
 
 }  // namespace
@@ -113,7 +183,7 @@ struct dzn_handle {
   std::set<std::string> used;
   int ignored = 0;
   bool finalized = false;
-  bool debug = false;
+  Switches sw;
   std::vector<void*> allocs;
   int64_t bytes = 0;
   std::map<std::string, std::vector<float>> taps;
@@ -130,8 +200,9 @@ struct dzn_handle {
   LNp conv_ln[DZN_MAX_CONV];
   Lin conv[DZN_MAX_CONV];
   float* dummy_w = nullptr;
-  LNp fp_ln, enc_ln;
-  Lin fp, posconv;
+  LNp enc_ln;
+  NormLin fp;
+  Lin posconv;
   int pos_rowD = 0;               // row width the row-offset table of the positional conv was built for
   int pos_cgp = 0;                // channels per positional-conv group in the pre-split planes (cg rounded up to 32)
   std::vector<EncLayer> layers;
@@ -162,11 +233,7 @@ struct dzn_handle {
   float* kvs = nullptr;
   int64_t kvp_rows = 0;
   int kvp_ldmax = 0;
-  // (r4) pre-norm encoders: every layer writes its output rows into ITS OWN buffer (xl + layer * rows * D) and the
-  // layer-weighted sum (model_wavlm_conformer.py:236,253-254) is ONE pass over those buffers after the last layer, instead of
-  // a read-modify-write of `ws` in every FFN-output epilogue: 25 reads + 1 write of [rows, D] where there were 25 reads and
-  // 25 writes.  nullptr: the fused read-modify-write (post-norm encoders, DZN_NO_WS_DEFER, not enough free memory).
-  float* xl = nullptr;
+  float* xl = nullptr;      // per-layer output buffers of the deferred layer-weighted sum (Switches::ws_defer); nullptr: not deferred
   int64_t xl_elems = 0;     // size xl would have (0: not applicable to this model / switched off)
   float* spart = nullptr;   // [max_batch * maxL][32][2] per-row partial sums left by a producing epilogue (stat_partial)
   float* rstat = nullptr;   // [max_batch * maxL][2] (mean, rstd) of the LayerNorm folded into the next contraction
@@ -176,7 +243,6 @@ struct dzn_handle {
   enum { AM_CONVA, AM_CONVB, AM_X, AM_XPAD, AM_Y, AM_MID, AM_QKV, AM_HZ, AM_HMID, AM_IMG0, AM_COUNT = AM_IMG0 + 12 };
   float conv0_bound = 0.f;  // sqrt(C0) max|gamma| + max|beta| >= |GELU(LN(conv0))|: static |max| of conv0's output
   float* amax = nullptr;
-  bool fold_ln = false;     // fp32 engine modes: LayerNorms that feed only linears are folded (make_lin_ln)
 
   // ---- embedding ----
   bool has_emb = false;
@@ -203,30 +269,6 @@ struct dzn_handle {
   int *win_flag = nullptr, *win_idx = nullptr, *win_cnt = nullptr;
   long long* emb_totals = nullptr;
   long long emb_dense_windows = 0;   // windows that went through the trunk on the dense path (no subset: nothing to skip)
-  bool emb_skip = true;       // DZN_EMB_NO_SKIP (read once, at dzn_create) switches the subset off
-  // DZN_PREC_F16 (reduced precision): which contraction classes keep two fp16 terms (F16_CLASSES bit mask; bit 14 = the
-  // ResNet stages 2-4), and whether LayerNorm-folded single-term contractions subtract the row mean BEFORE rounding
-  // defaults from profiles/r4_f16_sensitivity.json (64 non-degenerate windows vs the f32h engine): the error of the
-  // single-term mode is NOT localised — no one class brings max |dlogp| under SURVEY 8d's 5e-2, only two terms everywhere
-  // (= f32h) does; the conv stack alone carries ~70 % of the error variance for 4 % of the flops, so it keeps two terms
-  // (0.247 -> 0.133, flips 0.52 % -> 0.33 %); centring the LayerNorm-folded split changes nothing (0.228 vs 0.247: the
-  // error is plain operand rounding, not the mean * colsum cancellation) and stays off.
-  // (r5, ADVICE r4) bit 14 governs the whole trunk: the stride-2 / shortcut / stage 3-4 contractions (gemm_split.hip NP = 1)
-  // AND the fused stride-1 BasicBlocks of stages 1-2 (resblock_fused.hip / resblock_ws.hip, which have a single-term form
-  // since r5; in r4 they were two-term whatever the bit said).
-  bool fuse_resblock = true;  // DZN_NO_RESBLOCK_FUSION (read once, at dzn_create)
-  bool fuse_shortcut = true;  // DZN_NO_SHORTCUT_FUSION (read once, at dzn_create): keep the shortcut of a down-sampling block as its own launch
-  int resblock_ws = 2;        // DZN_RESBLOCK_WS bit mask: 1 = 32-plane blocks, 2 = 64-plane blocks on the producer / consumer form
-  // (r5) with the cross terms in fp8 everywhere else, the Conformer head (bits 8-13, 8 % of the segmentation flops) keeps two
-  // fp16 terms as well: max |dlogp| does not move (1.01e-2 vs 1.03e-2) but the decisions next to the classifier do — DER of the
-  // mode's RTTM against the fp32 RTTM on the 30 s fixture 0.05 % (one 20 ms frame) instead of 0.17 % (three), inside SURVEY 8d's
-  // 0.1 abs; device step 1872 -> 1856 audio-s/s on one box (profiles/r5_reduced_mode_keep2_probe.txt)
-  unsigned f16_keep2 = 0x3f01;
-  // (r5) DZN_PREC_F16: the classes whose bit is set run fp16 hi*hi + the two cross terms in fp8 (gemm_mx.hip) — every linear
-  // contraction of the segmentation model: the class sweep of profiles/r4_reduced_mode_emulation.txt shows that any one of them
-  // at a single fp16 term costs 0.04-0.21 of max |dlogp| against SURVEY 8d's 5e-2, only the positional conv (bit 2) can stay at
-  // one term.  Bit 0 (the conv stack) keeps two fp16 terms (f16_keep2).  DZN_F16_MX overrides (0 = r4's single-term mode).
-  unsigned f16_mx = 0x3ffa;
   bool mx_pack = false;   // make_lin also packs the MX planes (set while the segmentation weights are finalized)
 };
 
@@ -289,7 +331,7 @@ Lin make_lin(H* h, const std::vector<float>& W, const float* bias, int N, int K,
       if (launch_split_weights_h2(l.W, Np, Kp, Kp, l.W2h, l.wsc, nullptr) != DZN_OK)
         throw EngineError(DZN_E_HIP, "split_weights_h2 launch failed");
     }
-    if (h->cfg.precision == DZN_PREC_F16 && h->mx_pack && h->f16_mx) {
+    if (h->cfg.precision == DZN_PREC_F16 && h->mx_pack && h->sw.f16_mx) {
       l.Wmx = dalloc<unsigned char>(h, (int64_t)4 * Np * Kp, false);
       l.wsc_mx = dalloc<float>(h, Np, false);
       if (launch_split_weights_mx(l.W, Np, Kp, Kp, l.Wmx, l.wsc_mx, nullptr) != DZN_OK)
@@ -341,18 +383,6 @@ Lin make_lin_ln(H* h, const std::vector<float>& W, const float* bias, const std:
   return l;
 }
 
-Lin linear_ln_from_sd(H* h, const std::string& prefix, const std::string& ln_prefix, int N, int K, int Np, int Kp) {
-  const HostT& w = need(h, prefix + ".weight");
-  const HostT& bt = need(h, prefix + ".bias");
-  const HostT& g = need(h, ln_prefix + ".weight");
-  const HostT& b = need(h, ln_prefix + ".bias");
-  expect_numel(w, (int64_t)N * K, prefix + ".weight");
-  expect_numel(bt, N, prefix + ".bias");
-  expect_numel(g, K, ln_prefix + ".weight");
-  expect_numel(b, K, ln_prefix + ".bias");
-  return make_lin_ln(h, w.v, bt.v.data(), g.v, b.v, N, K, Np, Kp);
-}
-
 LNp ln_from_sd(H* h, const std::string& prefix, int Cn) {
   const HostT& g = need(h, prefix + ".weight");
   const HostT& b = need(h, prefix + ".bias");
@@ -363,6 +393,45 @@ LNp ln_from_sd(H* h, const std::string& prefix, int Cn) {
   l.g = upload(h, g.v);
   l.b = upload(h, b.v);
   return l;
+}
+
+// The one loader of a NormLin: W [N][K] / bias as host vectors, the norm over K at ln_prefix ("" = no norm in front), and the
+// fold decision.  `loaded`: the norm's device copy where the caller has uploaded it already.
+NormLin norm_lin(H* h, const std::vector<float>& W, const float* bias, const std::string& ln_prefix, bool fold, int N, int K,
+                 int Np, int Kp, const LNp* loaded = nullptr) {
+  NormLin nl;
+  if (!ln_prefix.empty()) nl.ln = loaded ? *loaded : ln_from_sd(h, ln_prefix, K);
+  nl.folded = fold && nl.ln.C > 0;
+  nl.lin = nl.folded ? make_lin_ln(h, W, bias, need(h, ln_prefix + ".weight").v, need(h, ln_prefix + ".bias").v, N, K, Np, Kp)
+                     : make_lin(h, W, bias, N, K, Np, Kp);
+  return nl;
+}
+
+NormLin norm_lin_from_sd(H* h, const std::string& prefix, const std::string& ln_prefix, bool fold, int N, int K, int Np, int Kp,
+                         const LNp* loaded = nullptr) {
+  LNp ln;
+  if (!ln_prefix.empty()) ln = loaded ? *loaded : ln_from_sd(h, ln_prefix, K);
+  const HostT& w = need(h, prefix + ".weight");
+  const HostT& bt = need(h, prefix + ".bias");
+  expect_numel(w, (int64_t)N * K, prefix + ".weight");
+  expect_numel(bt, N, prefix + ".bias");
+  return norm_lin(h, w.v, bt.v.data(), ln_prefix, fold, N, K, Np, Kp, &ln);
+}
+
+// q/k/v as one contraction: the three [rows, K] weights stacked to [3 rows, K], the biases to [3 rows]
+std::pair<std::vector<float>, std::vector<float>> stack_qkv(H* h, const std::string& q, const std::string& k, const std::string& v,
+                                                            int rows, int K) {
+  std::vector<float> W((size_t)3 * rows * K), bias((size_t)3 * rows);
+  const std::string* names[3] = {&q, &k, &v};
+  for (int t = 0; t < 3; ++t) {
+    const HostT& w = need(h, *names[t] + ".weight");
+    const HostT& b = need(h, *names[t] + ".bias");
+    expect_numel(w, (int64_t)rows * K, *names[t] + ".weight");
+    expect_numel(b, rows, *names[t] + ".bias");
+    std::copy(w.v.begin(), w.v.end(), W.begin() + (size_t)t * rows * K);
+    std::copy(b.v.begin(), b.v.end(), bias.begin() + (size_t)t * rows);
+  }
+  return {std::move(W), std::move(bias)};
 }
 
 int conv_out(int n, int k, int s) { return n < k ? 0 : (n - k) / s + 1; }
@@ -386,7 +455,7 @@ int relpos_bucket(int rel, int num_buckets, int max_distance) {
 void finalize_seg(H* h) {
   const dzn_config& c = h->cfg;
   const std::string P = "wavlm_model.";
-  h->fold_ln = !getenv("DZN_NO_LN_FOLD");
+  const bool fold = h->sw.fold_ln;
   h->nconv = c.n_conv;
   h->D = c.embed_dim;
   h->H = c.total_heads;
@@ -410,7 +479,7 @@ void finalize_seg(H* h) {
     expect_numel(w, (int64_t)h->C[0] * c.conv_k[0], pre + ".conv.weight");
     h->conv0_w = upload(h, w.v);
     h->conv_ln[0] = ln_from_sd(h, pre + ".layer_norm", h->C[0]);
-    if (c.extractor_layer_norm && c.conv_k[0] <= 10 && !getenv("DZN_CONV0_WAVE_STATS")) {
+    if (c.extractor_layer_norm && c.conv_k[0] <= 10 && h->sw.conv0_quad_stats) {
       // LayerNorm statistics of conv0's frames as a quadratic form of the input samples (frontend.hip)
       const int C0 = h->C[0], k0 = c.conv_k[0];
       std::vector<double> wb(10, 0.0), Q(100, 0.0);
@@ -485,7 +554,7 @@ void finalize_seg(H* h) {
     if (c.extractor_layer_norm) h->conv_ln[i] = ln_from_sd(h, pre + ".layer_norm", co);
     if (i == 1 && prec_is_h2(c.precision) && c.extractor_layer_norm && h->conv0_lnq && c.conv_k[0] == 10 &&
         c.conv_s[0] == 5 && k == 3 && c.conv_s[1] == 2 && h->C[0] % 64 == 0 && h->C[0] >= 128 &&
-        h->Cp[0] == h->C[0] && h->Cp[1] == 160 && !getenv("DZN_NO_CONV01_FUSION")) {
+        h->Cp[0] == h->C[0] && h->Cp[1] == 160 && h->sw.fuse_conv01) {
       // (C[0] >= 128: with a single 64-channel slab the kernel's epilogue statistics would race, frontend_fused.hip)
       h->conv1_W2f = dalloc<u16>(h, (int64_t)2 * h->Cp[1] * k * cip, false);
       h->conv1_wscf = dalloc<float>(h, h->Cp[1], false);
@@ -501,13 +570,8 @@ void finalize_seg(H* h) {
     h->dummy_w = upload(h, dw.v);
   }
   const int D = h->D;
-  h->fp_ln = ln_from_sd(h, P + "encoder.feature_projection.layer_norm", h->C[last]);
-  if (h->fold_ln)
-    h->fp = linear_ln_from_sd(h, P + "encoder.feature_projection.projection",
-                              P + "encoder.feature_projection.layer_norm", D, h->C[last], D, h->Cp[last]);
-  else
-    h->fp = linear_from_sd(h, P + "encoder.feature_projection.projection", D, h->C[last], D,
-                           h->Cp[last]);
+  h->fp = norm_lin_from_sd(h, P + "encoder.feature_projection.projection", P + "encoder.feature_projection.layer_norm", fold,
+                           D, h->C[last], D, h->Cp[last]);
   // positional conv: fold weight norm  W = g * v / ||v||_{dims 0,1}   (components.py:344)
   {
     const std::string pc = P + "encoder.transformer.pos_conv_embed.conv";
@@ -548,27 +612,15 @@ void finalize_seg(H* h) {
     const std::string lp = P + "encoder.transformer.layers." + std::to_string(i);
     L.attn = c.use_attention[i] && c.n_heads[i] > 0;
     L.ffn = c.use_ffn[i] != 0;
+    L.pre_norm = c.layer_norm_first != 0;
     L.ln1 = ln_from_sd(h, lp + ".layer_norm", D);
     L.ln2 = ln_from_sd(h, lp + ".final_layer_norm", D);
     if (L.attn) {
       L.h = c.n_heads[i];
       const int hd = L.h * 64;
       maxQ = std::max(maxQ, hd);
-      std::vector<float> wq((size_t)3 * hd * D), bq((size_t)3 * hd);
-      const char* names[3] = {".attention.q_proj", ".attention.k_proj", ".attention.v_proj"};
-      for (int t = 0; t < 3; ++t) {
-        const HostT& w = need(h, lp + names[t] + ".weight");
-        const HostT& b = need(h, lp + names[t] + ".bias");
-        expect_numel(w, (int64_t)hd * D, lp + names[t] + ".weight");
-        expect_numel(b, hd, lp + names[t] + ".bias");
-        std::copy(w.v.begin(), w.v.end(), wq.begin() + (size_t)t * hd * D);
-        std::copy(b.v.begin(), b.v.end(), bq.begin() + (size_t)t * hd);
-      }
-      if (h->fold_ln && c.layer_norm_first)
-        L.qkv = make_lin_ln(h, wq, bq.data(), need(h, lp + ".layer_norm.weight").v,
-                            need(h, lp + ".layer_norm.bias").v, 3 * hd, D, 3 * hd, D);
-      else
-        L.qkv = make_lin(h, wq, bq.data(), 3 * hd, D, 3 * hd, D);
+      const auto wb = stack_qkv(h, lp + ".attention.q_proj", lp + ".attention.k_proj", lp + ".attention.v_proj", hd, D);
+      L.qkv = norm_lin(h, wb.first, wb.second.data(), L.pre_norm ? lp + ".layer_norm" : "", fold, 3 * hd, D, 3 * hd, D, &L.ln1);
       L.out = linear_from_sd(h, lp + ".attention.out_proj", D, hd, D, hd);
       const HostT& wg = need(h, lp + ".attention.gru_rel_pos_linear.weight");
       const HostT& bg = need(h, lp + ".attention.gru_rel_pos_linear.bias");
@@ -594,11 +646,8 @@ void finalize_seg(H* h) {
       L.F = c.ffn_dim[i];
       L.Fp = pad32(L.F);
       maxF = std::max(maxF, L.Fp);
-      if (h->fold_ln && c.layer_norm_first)
-        L.f1 = linear_ln_from_sd(h, lp + ".feed_forward.intermediate_dense", lp + ".final_layer_norm", L.F, D,
-                                 L.Fp, D);
-      else
-        L.f1 = linear_from_sd(h, lp + ".feed_forward.intermediate_dense", L.F, D, L.Fp, D);
+      L.f1 = norm_lin_from_sd(h, lp + ".feed_forward.intermediate_dense", L.pre_norm ? lp + ".final_layer_norm" : "", fold, L.F, D,
+                              L.Fp, D, &L.ln2);
       L.f2 = linear_from_sd(h, lp + ".feed_forward.output_dense", D, L.F, D, L.Fp);
     }
   }
@@ -616,36 +665,17 @@ void finalize_seg(H* h) {
   for (int i = 0; i < c.conf_layers; ++i) {
     ConfLayer& L = h->conf[i];
     const std::string cp = "conformer.conformer_layer." + std::to_string(i);
-    L.ffn1_ln = ln_from_sd(h, cp + ".ffn1.ln_norm", A);
-    L.ffn1_w1 = h->fold_ln ? linear_ln_from_sd(h, cp + ".ffn1.w_1", cp + ".ffn1.ln_norm", Fh, A, Fh, A)
-                           : linear_from_sd(h, cp + ".ffn1.w_1", Fh, A, Fh, A);
+    L.ffn1_w1 = norm_lin_from_sd(h, cp + ".ffn1.w_1", cp + ".ffn1.ln_norm", fold, Fh, A, Fh, A);
     L.ffn1_w2 = linear_from_sd(h, cp + ".ffn1.w_2", A, Fh, A, Fh);
-    L.ffn2_ln = ln_from_sd(h, cp + ".ffn2.ln_norm", A);
-    L.ffn2_w1 = h->fold_ln ? linear_ln_from_sd(h, cp + ".ffn2.w_1", cp + ".ffn2.ln_norm", Fh, A, Fh, A)
-                           : linear_from_sd(h, cp + ".ffn2.w_1", Fh, A, Fh, A);
+    L.ffn2_w1 = norm_lin_from_sd(h, cp + ".ffn2.w_1", cp + ".ffn2.ln_norm", fold, Fh, A, Fh, A);
     L.ffn2_w2 = linear_from_sd(h, cp + ".ffn2.w_2", A, Fh, A, Fh);
-    L.mha_ln = ln_from_sd(h, cp + ".mha.ln_norm", A);
     {
-      std::vector<float> wq((size_t)3 * A * A), bq((size_t)3 * A);
-      const char* names[3] = {".mha.mha.linearQ", ".mha.mha.linearK", ".mha.mha.linearV"};
-      for (int t = 0; t < 3; ++t) {
-        const HostT& w = need(h, cp + names[t] + ".weight");
-        const HostT& b = need(h, cp + names[t] + ".bias");
-        expect_numel(w, (int64_t)A * A, cp + names[t] + ".weight");
-        expect_numel(b, A, cp + names[t] + ".bias");
-        std::copy(w.v.begin(), w.v.end(), wq.begin() + (size_t)t * A * A);
-        std::copy(b.v.begin(), b.v.end(), bq.begin() + (size_t)t * A);
-      }
-      if (h->fold_ln)
-        L.qkv = make_lin_ln(h, wq, bq.data(), need(h, cp + ".mha.ln_norm.weight").v,
-                            need(h, cp + ".mha.ln_norm.bias").v, 3 * A, A, 3 * A, A);
-      else
-        L.qkv = make_lin(h, wq, bq.data(), 3 * A, A, 3 * A, A);
+      const LNp ln = ln_from_sd(h, cp + ".mha.ln_norm", A);
+      const auto wb = stack_qkv(h, cp + ".mha.mha.linearQ", cp + ".mha.mha.linearK", cp + ".mha.mha.linearV", A, A);
+      L.qkv = norm_lin(h, wb.first, wb.second.data(), cp + ".mha.ln_norm", fold, 3 * A, A, 3 * A, A, &ln);
     }
     L.o = linear_from_sd(h, cp + ".mha.mha.linearO", A, A, A, A);
-    L.conv_ln = ln_from_sd(h, cp + ".conv.ln_norm", A);
-    L.pw1 = h->fold_ln ? linear_ln_from_sd(h, cp + ".conv.pointwise_conv1", cp + ".conv.ln_norm", 2 * A, A, 2 * A, A)
-                       : linear_from_sd(h, cp + ".conv.pointwise_conv1", 2 * A, A, 2 * A, A);
+    L.pw1 = norm_lin_from_sd(h, cp + ".conv.pointwise_conv1", cp + ".conv.ln_norm", fold, 2 * A, A, 2 * A, A);
     L.pw2 = linear_from_sd(h, cp + ".conv.pointwise_conv2", A, A, A, A);
     {
       // fold eval BatchNorm1d into the depthwise taps (conformer.py:205)
@@ -729,10 +759,10 @@ void finalize_seg(H* h) {
   h->y = dalloc<float>(h, ML * D);
   h->ws = dalloc<float>(h, ML * D);
   // the per-layer buffers of the deferred layer-weighted sum are OPTIONAL: they are taken last, by alloc_optional_workspace()
-  h->xl_elems = (c.layer_norm_first && h->fold_ln && c.n_layers > 0 && c.n_layers < WS_SUM_MAX && D % 4 == 0 &&
-                 !getenv("DZN_NO_WS_DEFER")) ? (int64_t)c.n_layers * ML * D : 0;
+  h->xl_elems = (c.layer_norm_first && fold && c.n_layers > 0 && c.n_layers < WS_SUM_MAX && D % 4 == 0 &&
+                 h->sw.ws_defer) ? (int64_t)c.n_layers * ML * D : 0;
   h->qkv = dalloc<float>(h, ML * 3 * maxQ);
-  if (c.precision == DZN_PREC_F32_H2 && maxQ > 0 && !getenv("DZN_NO_ATT_PLANES")) {
+  if (c.precision == DZN_PREC_F32_H2 && maxQ > 0 && h->sw.att_planes) {
     // two fp16 planes of [rows + 64][2 * maxQ] (the bytes of the fp32 K / V they replace) and the slot scales; zero-filled once:
     // the 64 rows past a batch are only ever read for keys that are masked, but they must be finite
     h->kvp_rows = ML + 64;
@@ -915,7 +945,7 @@ void finalize_emb(H* h) {
       const int stride = (j == 0 && s > 0) ? 2 : 1;
       rb.c1 = make_resconv(h, bp + ".conv1", bp + ".bn1", cin, cout, 3, stride);
       rb.has_sc = (stride != 1 || cin != cout);
-      if (rb.has_sc && h->fuse_shortcut) {
+      if (rb.has_sc && h->sw.fuse_shortcut) {
         rb.c2 = make_resconv_shortcut(h, bp + ".conv2", bp + ".bn2", bp + ".shortcut.0", bp + ".shortcut.1", cin, cout);
       } else {
         rb.c2 = make_resconv(h, bp + ".conv2", bp + ".bn2", cout, cout, 3, 1);
@@ -1001,7 +1031,7 @@ void chk(int rc, const char* what) {
 }
 
 void tap(H* h, const char* name, const float* p, int64_t rows, int cols, int64_t ld, hipStream_t st) {
-  if (!h->debug) return;
+  if (!h->sw.debug_taps) return;
   HIPCHK(hipStreamSynchronize(st));
   std::vector<float>& v = h->taps[name];
   v.resize((size_t)rows * cols);
@@ -1073,53 +1103,87 @@ void ensure_table(H* h, int L, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ segmentation forward
-void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* d_ml, float* d_soft, hipStream_t st) {
-  const dzn_config& c = h->cfg;
-  const bool lnx = c.extractor_layer_norm != 0;
-  int T[DZN_MAX_CONV];
-  {
-    int n = N;
-    for (int i = 0; i < c.n_conv; ++i) {
-      n = conv_out(n, c.conv_k[i], c.conv_s[i]);
-      T[i] = n;
-    }
+// What the stages of one seg_forward call share.
+struct SegCall {
+  H* h;
+  hipStream_t st;
+  int B, L;
+  int64_t ML;   // B * L: rows of every [B*L, .] tensor
+  // DZN_PREC_F32_H2: |max| trackers (see dzn_handle::amax).  am(slot) is NULL in the other modes, which makes
+  // every contraction take its bf16 three-term / fp32 kernel.  slot < 0: a tensor without a tracker.
+  float* am(int slot) const {
+    return slot >= 0 && prec_is_h2(h->cfg.precision) ? h->amax + slot * (int64_t)h->cfg.max_batch : nullptr;
   }
-  const int L = T[c.n_conv - 1];
-  if (L < 1) throw EngineError(DZN_E_INVALID, "window too short");
-  const int D = h->D, A = h->A, Fh = h->Fh;
-  const int64_t ML = (int64_t)B * L;
-  // DZN_PREC_F16: contraction classes that keep BOTH fp16 terms (three products) — f16_keep2 is a bit mask over
-  // F16_CLASSES below (dzn_handle::f16_keep2, default chosen from the measured sensitivity: profiles/r4_f16_sensitivity*)
-  auto gemm = [&](dzn_gemm_desc& d, const char* what) {
-    if (c.precision == DZN_PREC_F16) {
-      const int cls = f16_class(what);
-      const bool mx = cls >= 0 && ((h->f16_mx >> cls) & 1) && d.Wmx;
-      if (!mx) d.Wmx = nullptr;     // single-term fp16 (or two terms, next line)
-      if (cls >= 0 && ((h->f16_keep2 >> cls) & 1)) d.precision = DZN_PREC_F32_H2;
+  int conv_slot(const float* buf) const { return buf == h->bufA ? dzn_handle::AM_CONVA : dzn_handle::AM_CONVB; }
+  void gemm(dzn_gemm_desc& d, F16Class cls) const {
+    // DZN_PREC_F16: contraction classes that keep BOTH fp16 terms (three products) — Switches::f16_keep2 is a bit mask over
+    // F16Class (default chosen from the measured sensitivity: profiles/r4_f16_sensitivity*)
+    if (h->cfg.precision == DZN_PREC_F16) {
+      if (!((h->sw.f16_mx >> cls) & 1)) d.Wmx = nullptr;     // single-term fp16 (or two terms, next line)
+      if ((h->sw.f16_keep2 >> cls) & 1) d.precision = DZN_PREC_F32_H2;
     }
     // |max| trackers are per window: rows of a [B*L, .] tensor belong to window m / L; z-batched launches
     // (conv stack: z = window) use the z index
     // (r4 fix: a conv-stack launch with B == 1 also has nz == 1, but its rows are T_i frames of window 0, not B * L rows —
     // with unit = L its tracker index m / L ran past the one-window tracker array and scaled by whatever lay behind it)
     if ((d.nz == 1 && d.M == (int)ML) || (d.a_rowoff && d.a_rowoff == h->pos_rowoff)) d.amax_unit = L;
-    chk(launch_gemm(d, st), what);
-  };
-  // DZN_PREC_F32_H2: |max| trackers (see dzn_handle::amax).  am(slot) is NULL in the other modes, which makes
-  // every contraction take its bf16 three-term / fp32 kernel.
-  const bool h2 = prec_is_h2(c.precision);
-  const int64_t MB = c.max_batch;
-  if (h2) {
-    chk(launch_fill_u32(h->amax, 0u, dzn_handle::AM_IMG0 * MB, st), "tracker reset");
-    if (lnx && h->conv0_bound > 0.f) {   // conv0 (LN + GELU) writes bufA: static bound instead of a tracker
-      uint32_t bits;
-      memcpy(&bits, &h->conv0_bound, 4);
-      chk(launch_fill_u32(h->amax + dzn_handle::AM_CONVA * MB, bits, B, st), "conv0 bound");
-    }
+    chk(launch_gemm(d, st), F16_CLASSES[cls]);
   }
-  auto am = [&](int slot) -> float* { return h2 ? h->amax + slot * MB : nullptr; };
-  auto conv_slot = [&](const float* buf) { return buf == h->bufA ? dzn_handle::AM_CONVA : dzn_handle::AM_CONVB; };
+};
 
-  // ---- conv feature extractor ----
+// The contraction of a NormLin over the rows `in` [ML, nl.lin.K] (tracker slot in_slot) into C, ready but for what follows
+// the product: the caller adds the activation, c_amax and the residual, and launches it.
+//   folded    the contraction reads `in` and finishes the norm in its epilogue from (mean, rstd) per row in rstat — left there
+//             by row_stats here, unless a producer has left them already (have_stats)
+//   unfolded  the stand-alone LayerNorm writes `scratch` (tracker slot scratch_slot), which the contraction reads
+//   no norm   the contraction reads `in`
+dzn_gemm_desc norm_lin_desc(const SegCall& s, const NormLin& nl, const float* in, int in_slot, float* scratch, int scratch_slot,
+                            float* C, int64_t ldc, bool have_stats = false) {
+  H* h = s.h;
+  const int ld = nl.lin.K;
+  if (nl.folded) {
+    if (!have_stats) chk(launch_row_stats(in, ld, s.ML, nl.ln.C, 1e-5f, h->rstat, s.st), "row_stats");
+  } else if (nl.ln.C > 0) {
+    ln_t(in, ld, scratch, ld, nl.ln, s.ML, ld, 0, s.st, nullptr, s.am(scratch_slot), scratch_slot < 0 ? 0 : s.L);
+    in = scratch;
+    in_slot = scratch_slot;
+  }
+  dzn_gemm_desc d = gd(h, in, nl.lin, C, s.ML, ld, ldc);
+  if (nl.folded) {
+    d.ln_stats = h->rstat;
+    d.ln_colsum = nl.lin.csum;
+  }
+  d.a_amax = s.am(in_slot);
+  return d;
+}
+
+// Multi-head attention over packed q/k/v rows [ML, 3 * heads * 64] (tracker slot `slot`): on the fp16 K / V planes if the
+// q/k/v contraction wrote them, else the split kernel in the split modes, else fp32.  Ly: the encoder layer whose gated
+// relative-position bias applies; nullptr = the Conformer's plain MHSA.
+void attention(const SegCall& s, const EncLayer* Ly, const float* qkv, int slot, bool planes, float* out) {
+  H* h = s.h;
+  const float* gate = Ly ? h->gate : nullptr;
+  const float* table = Ly ? h->table : nullptr;
+  const int32_t* head_idx = Ly ? Ly->head_idx : nullptr;
+  const int nh = Ly ? Ly->h : h->cfg.conf_heads, Hn = Ly ? h->H : 0, hd = nh * 64;
+  const char* what = Ly ? "attention" : "conf attention";
+  if (planes)
+    chk(launch_attention_planes(qkv, h->kvp, (s.ML + 64) * (int64_t)(2 * hd), h->kvs, 2 * hd, out, gate, table, head_idx, s.B, s.L,
+                                nh, Hn, 3 * hd, hd, 0.125f, s.st, s.am(slot)),
+        what);
+  else if (prec_is_split(h->cfg.precision))
+    chk(launch_attention_split(qkv, out, gate, table, head_idx, s.B, s.L, nh, Hn, 3 * hd, hd, 0.125f, s.st, s.am(slot)), what);
+  else
+    chk(launch_attention_t(qkv, out, gate, table, head_idx, s.B, s.L, nh, Hn, 3 * hd, hd, 0.125f, s.st), what);
+}
+
+// ---- conv feature extractor: T[i] frames after conv i; returns the buffer its last layer wrote ----
+float* seg_conv_stack(const SegCall& s, const float* wave, int N, const int* T) {
+  H* h = s.h;
+  const dzn_config& c = h->cfg;
+  hipStream_t st = s.st;
+  const int B = s.B;
+  const bool lnx = c.extractor_layer_norm != 0;
   const float* stats = nullptr;
   if (c.normalize_waveform) {
     chk(launch_wave_stats(wave, B, N, 1e-5f, h->stats, st), "wave_stats");
@@ -1127,7 +1191,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
   }
   // DZN_PREC_F32_H2: conv0 + LN + GELU + conv1 in one kernel (frontend_fused.hip): conv0's 52 MB / window never
   // reach HBM.  (debug taps need the intermediate -> unfused)
-  const bool fuse01 = prec_is_h2(c.precision) && lnx && h->conv1_W2f && !h->debug && c.n_conv > 1 && T[1] > 0;
+  const bool fuse01 = prec_is_h2(c.precision) && lnx && h->conv1_W2f && !h->sw.debug_taps && c.n_conv > 1 && T[1] > 0;
   if (lnx && fuse01) {
   } else if (lnx) {
     chk(launch_conv0(wave, B, N, stats, h->conv0_w, h->conv_ln[0].g, h->conv_ln[0].b, h->C[0], h->Cp[0],
@@ -1138,7 +1202,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
                      c.conv_s[0], T[0], 0, 1e-5f, h->bufA, st),
         "conv0");
     chk(launch_groupnorm_gelu(h->bufA, h->bufA, B, T[0], h->C[0], h->Cp[0], h->Cp[0], h->conv_ln[0].g,
-                              h->conv_ln[0].b, 1e-5f, h->gn_stats, st, am(conv_slot(h->bufA))),
+                              h->conv_ln[0].b, 1e-5f, h->gn_stats, st, s.am(s.conv_slot(h->bufA))),
         "groupnorm");
   }
   tap(h, "conv0", h->bufA, (int64_t)B * T[0], h->C[0], h->Cp[0], st);
@@ -1152,105 +1216,272 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
     d.a_z0 = (int64_t)T[i - 1] * h->Cp[i - 1];
     d.c_z0 = (int64_t)T[i] * h->Cp[i];
     if (!lnx) d.act = DZN_ACT_GELU;
-    d.a_amax = am(conv_slot(cur));   // (r3: the group-norm element pass tracks its |max| too, so conv1 takes the fp16 split)
-    if (!lnx) d.c_amax = am(conv_slot(nxt));
+    d.a_amax = s.am(s.conv_slot(cur));   // (r3: the group-norm element pass tracks its |max| too, so conv1 takes the fp16 split)
+    if (!lnx) d.c_amax = s.am(s.conv_slot(nxt));
     // (r3) the fused front end also finishes conv1's own LayerNorm + GELU in its epilogue (its tile holds whole rows)
-    const bool ln_in_01 = i == 1 && fuse01 && lnx && i != last && !getenv("DZN_CONV01_NO_LN");
+    const bool ln_in_01 = i == 1 && fuse01 && lnx && i != last && h->sw.conv01_ln;
     if (i == 1 && fuse01)
       chk(launch_conv01_fused(wave, B, N, stats, h->conv0_w, h->conv_ln[0].g, h->conv_ln[0].b, h->conv0_lnq, h->C[0],
                               T[0], T[1], h->conv1_W2f, h->conv1_wscf, h->Cp[1], h->conv0_bound, 1e-5f, nxt,
                               st, ln_in_01 ? h->conv_ln[1].g : nullptr, ln_in_01 ? h->conv_ln[1].b : nullptr, h->C[1],
-                              ln_in_01 ? am(conv_slot(nxt)) : nullptr),
+                              ln_in_01 ? s.am(s.conv_slot(nxt)) : nullptr),
           "conv01 fused");
     else
-      gemm(d, "conv gemm");
+      s.gemm(d, CLS_CONV);
     if (lnx && !ln_in_01)  // channel LayerNorm + GELU (+ dummy_weight after the last conv, components.py:208)
       ln_t(nxt, h->Cp[i], nxt, h->Cp[i], h->conv_ln[i], (int64_t)B * T[i], h->Cp[i], 1, st,
-           i == last ? h->dummy_w : nullptr, am(conv_slot(nxt)), T[i]);
+           i == last ? h->dummy_w : nullptr, s.am(s.conv_slot(nxt)), T[i]);
     std::swap(cur, nxt);
   }
   if (!lnx || c.n_conv == 1)
-    chk(launch_col_scale(cur, ML, h->C[last], h->Cp[last], h->dummy_w, st), "dummy_weight");
-  tap(h, "features", cur, ML, h->C[last], h->Cp[last], st);
+    chk(launch_col_scale(cur, s.ML, h->C[last], h->Cp[last], h->dummy_w, st), "dummy_weight");
+  tap(h, "features", cur, s.ML, h->C[last], h->Cp[last], st);
+  return cur;
+}
 
-  // ---- feature projection (components.py:305-306) ----
-  const bool fold = h->fold_ln;   // LayerNorms feeding only linears are folded into those contractions
-  auto folded = [&](dzn_gemm_desc& d, const Lin& l) {
-    d.ln_stats = h->rstat;
-    d.ln_colsum = l.csum;
-  };
-  if (fold) {
-    chk(launch_row_stats(cur, h->Cp[last], ML, h->C[last], 1e-5f, h->rstat, st), "row_stats");
-    dzn_gemm_desc d = gd(h, cur, h->fp, h->x, ML, h->Cp[last], D);
-    folded(d, h->fp);
+// ---- feature projection (components.py:305-306) + positional conv: x = x + gelu(conv_pos(x))  (components.py:980-987,
+// 366-380); `feat`: the conv stack's output, in bufA or bufB ----
+void seg_project(const SegCall& s, float* feat) {
+  H* h = s.h;
+  const dzn_config& c = h->cfg;
+  hipStream_t st = s.st;
+  const int B = s.B, L = s.L, D = h->D;
+  const int64_t ML = s.ML;
+  {
     // (col_scale of the base model multiplies conv6's output AFTER its tracker: |dummy_weight| ~ 1, and the
     // tracker only needs to bound the magnitude within the 2^15 / 65504 headroom -> skip the fp16 path there)
-    if (lnx && c.n_conv > 1) d.a_amax = am(conv_slot(cur));
-    d.c_amax = am(dzn_handle::AM_X);
-    gemm(d, "feature projection");
-  } else {
-    ln_t(cur, h->Cp[last], nxt, h->Cp[last], h->fp_ln, ML, h->Cp[last], 0, st);
-    dzn_gemm_desc d = gd(h, nxt, h->fp, h->x, ML, h->Cp[last], D);
-    d.c_amax = am(dzn_handle::AM_X);
-    gemm(d, "feature projection");
+    const bool tracked = c.extractor_layer_norm && c.n_conv > 1;
+    dzn_gemm_desc d = norm_lin_desc(s, h->fp, feat, tracked ? s.conv_slot(feat) : -1, feat == h->bufA ? h->bufB : h->bufA, -1,
+                                    h->x, D);
+    d.c_amax = s.am(dzn_handle::AM_X);
+    s.gemm(d, CLS_FEATPROJ);
   }
   tap(h, "featproj", h->x, ML, D, D, st);
 
-  // ---- positional conv: x = x + gelu(conv_pos(x))  (components.py:980-987, 366-380) ----
-  {
-    const int Kc = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G, Lp = L + Kc;
-    // f32s: every element of the padded copy feeds 128 taps — split it ONCE here (three bf16 planes) and
-    // let the contraction read the planes (gemm_split_pre.hip) instead of re-splitting it per K tile
-    const int cgp = h->pos_cgp > 0 ? h->pos_cgp : cg, Dp = G * cgp;     // plane rows: G groups of cgp channels
-    const bool pre3 = h->xpad3 != nullptr && (int64_t)c.max_batch * Lp * Dp < (int64_t)1 << 31;
-    const bool pre2 = pre3 && h2 && h->posconv.W2h;   // two fp16 planes, scaled by the |max| of x (snapshotted)
-    if (pre2)
-      chk(launch_pad_rows_split2(h->x, h->xpad3, h->xpad3_plane, B, L, Lp, Kc / 2, Dp, am(dzn_handle::AM_X),
-                                 am(dzn_handle::AM_XPAD), st, cg, cgp),
-          "pad_rows_split2");
-    else if (pre3)
-      chk(launch_pad_rows_split3(h->x, h->xpad3, h->xpad3_plane, B, L, Lp, Kc / 2, Dp, st, cg, cgp), "pad_rows_split3");
-    else
-      chk(launch_pad_rows(h->x, h->xpad, B, L, Lp, Kc / 2, D, st), "pad_rows");
-    // the un-split copy (fp32 mode) keeps cg channels per group; the planes have cgp
-    const int ca = pre3 ? cgp : cg, Da = pre3 ? Dp : D;
-    if (!pre3 && cgp != cg) throw EngineError(DZN_E_INVALID, "padded positional-conv groups need the pre-split planes");
-    // one contraction per channel group over ALL B*L rows (row-offset table into the padded copy), so
-    // the 128-row tiles are not padded per window (L = 399 would waste 22 % of every window's last tile)
-    const bool tabled = (int64_t)c.max_batch * Lp * Da < (int64_t)1 << 31;
-    if (tabled) ensure_pos_rowoff(h, L, Lp, Da, st);
-    dzn_gemm_desc d = gd(h, h->xpad, h->posconv, h->x, tabled ? ML : L, Da, D);
-    d.N = cg;
-    d.kc = ca;
-    d.ldk = Da;
-    d.act = DZN_ACT_GELU;
-    d.R = h->x;
-    d.a_z1 = ca;
-    d.w_z1 = (int64_t)cg * h->posconv.K;
-    d.c_z1 = cg;
-    d.b_z1 = cg;
-    if (tabled) {
-      d.a_rowoff = h->pos_rowoff;
-      d.nz = G;
-      d.zdiv = G;
-      d.alg_flops = 2.0 * (double)ML * cg * h->posconv.Kt;
-    } else {
-      d.nz = B * G;
-      d.zdiv = G;
-      d.a_z0 = (int64_t)Lp * Da;
-      d.c_z0 = (int64_t)L * D;
-      d.alg_flops = 2.0 * (double)L * cg * h->posconv.Kt;
-    }
-    if (pre3) {
-      d.A = reinterpret_cast<const float*>(h->xpad3);
-      d.a_split3 = pre2 ? 2 : 1;
-      d.a_plane = h->xpad3_plane;
-      if (pre2) d.a_amax = am(dzn_handle::AM_XPAD);
-    }
-    d.c_amax = am(dzn_handle::AM_X);
-    gemm(d, "pos conv");
+  const bool h2 = prec_is_h2(c.precision);
+  const int Kc = c.pos_conv_kernel, G = c.pos_conv_groups, cg = D / G, Lp = L + Kc;
+  // f32s: every element of the padded copy feeds 128 taps — split it ONCE here (three bf16 planes) and
+  // let the contraction read the planes (gemm_split_pre.hip) instead of re-splitting it per K tile
+  const int cgp = h->pos_cgp > 0 ? h->pos_cgp : cg, Dp = G * cgp;     // plane rows: G groups of cgp channels
+  const bool pre3 = h->xpad3 != nullptr && (int64_t)c.max_batch * Lp * Dp < (int64_t)1 << 31;
+  const bool pre2 = pre3 && h2 && h->posconv.W2h;   // two fp16 planes, scaled by the |max| of x (snapshotted)
+  if (pre2)
+    chk(launch_pad_rows_split2(h->x, h->xpad3, h->xpad3_plane, B, L, Lp, Kc / 2, Dp, s.am(dzn_handle::AM_X),
+                               s.am(dzn_handle::AM_XPAD), st, cg, cgp),
+        "pad_rows_split2");
+  else if (pre3)
+    chk(launch_pad_rows_split3(h->x, h->xpad3, h->xpad3_plane, B, L, Lp, Kc / 2, Dp, st, cg, cgp), "pad_rows_split3");
+  else
+    chk(launch_pad_rows(h->x, h->xpad, B, L, Lp, Kc / 2, D, st), "pad_rows");
+  // the un-split copy (fp32 mode) keeps cg channels per group; the planes have cgp
+  const int ca = pre3 ? cgp : cg, Da = pre3 ? Dp : D;
+  if (!pre3 && cgp != cg) throw EngineError(DZN_E_INVALID, "padded positional-conv groups need the pre-split planes");
+  // one contraction per channel group over ALL B*L rows (row-offset table into the padded copy), so
+  // the 128-row tiles are not padded per window (L = 399 would waste 22 % of every window's last tile)
+  const bool tabled = (int64_t)c.max_batch * Lp * Da < (int64_t)1 << 31;
+  if (tabled) ensure_pos_rowoff(h, L, Lp, Da, st);
+  dzn_gemm_desc d = gd(h, h->xpad, h->posconv, h->x, tabled ? ML : L, Da, D);
+  d.N = cg;
+  d.kc = ca;
+  d.ldk = Da;
+  d.act = DZN_ACT_GELU;
+  d.R = h->x;
+  d.a_z1 = ca;
+  d.w_z1 = (int64_t)cg * h->posconv.K;
+  d.c_z1 = cg;
+  d.b_z1 = cg;
+  if (tabled) {
+    d.a_rowoff = h->pos_rowoff;
+    d.nz = G;
+    d.zdiv = G;
+    d.alg_flops = 2.0 * (double)ML * cg * h->posconv.Kt;
+  } else {
+    d.nz = B * G;
+    d.zdiv = G;
+    d.a_z0 = (int64_t)Lp * Da;
+    d.c_z0 = (int64_t)L * D;
+    d.alg_flops = 2.0 * (double)L * cg * h->posconv.Kt;
   }
-  if (!c.layer_norm_first) ln_t(h->x, D, h->x, D, h->enc_ln, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
+  if (pre3) {
+    d.A = reinterpret_cast<const float*>(h->xpad3);
+    d.a_split3 = pre2 ? 2 : 1;
+    d.a_plane = h->xpad3_plane;
+    if (pre2) d.a_amax = s.am(dzn_handle::AM_XPAD);
+  }
+  d.c_amax = s.am(dzn_handle::AM_X);
+  s.gemm(d, CLS_POSCONV);
+  if (!c.layer_norm_first) ln_t(h->x, D, h->x, D, h->enc_ln, ML, D, 0, st, nullptr, s.am(dzn_handle::AM_X), L);
+}
+
+// ---- transformer layer i (components.py:920-942) over the residual stream xr; returns where its output rows live.
+// `wsum`: the deferred layer-weighted sum (h->xl), which notes (rows, weight) per layer; else the layer adds its rows to `ws` ----
+float* seg_encoder_layer(const SegCall& s, int i, float* xr, WsSumArgs& wsum) {
+  H* h = s.h;
+  hipStream_t st = s.st;
+  const int L = s.L, D = h->D;
+  const int64_t ML = s.ML;
+  const EncLayer& Ly = h->layers[i];
+  const bool defer = h->xl != nullptr;
+  const float wl = h->wsum_w[i + 1];
+  float* const own = defer ? h->xl + (int64_t)i * ML * D : xr;   // where this layer's output rows live
+  bool have_stats = false;   // LN2's statistics already left in rstat by the out_proj epilogue
+  if (Ly.attn) {
+    const int hd = Ly.h * 64;
+    // folded LN1: one pass over x gives the LN statistics for the q/k/v contraction + the gate on LN(x) (never written);
+    // else the gate reads what the contraction reads
+    const bool gs = Ly.qkv.folded;
+    if (gs)
+      chk(launch_gate_stats(xr, D, Ly.ln1.g, Ly.ln1.b, Ly.Wg, Ly.bg, Ly.cst, h->gate, h->rstat, ML, h->H, 1e-5f, st),
+          "gate_stats");
+    dzn_gemm_desc d = norm_lin_desc(s, Ly.qkv, xr, dzn_handle::AM_X, h->y, dzn_handle::AM_Y, h->qkv, 3 * hd, gs);
+    if (!gs) chk(launch_gate(d.A, D, Ly.Wg, Ly.bg, Ly.cst, h->gate, ML, h->H, st), "gate");
+    d.c_amax = s.am(dzn_handle::AM_QKV);
+    const bool planes = h->kvp != nullptr && d.W2h && d.col_scale && d.a_amax;     // the f32h contraction writes them
+    if (planes) {
+      d.kv_planes = h->kvp;
+      d.kv_plane_stride = (ML + 64) * (int64_t)(2 * hd);
+      d.kv_scale = h->kvs;
+      d.kv_ld = 2 * hd;
+      d.kv_col0 = hd;
+    }
+    s.gemm(d, CLS_QKV);
+    attention(s, &Ly, h->qkv, dzn_handle::AM_QKV, planes, h->ao);
+    dzn_gemm_desc o = gd(h, h->ao, Ly.out, own, ML, hd, D);
+    o.R = xr;
+    o.a_amax = s.am(dzn_handle::AM_QKV);   // rows of ao are convex combinations of v rows: |ao| <= max |qkv|
+    o.c_amax = s.am(dzn_handle::AM_X);
+    if (Ly.ffn && Ly.f1.folded && h->sw.epilogue_stats) {
+      // the rows it writes are exactly what the FFN's (folded) LayerNorm normalises: leave their statistics
+      o.stat_partial = h->spart;
+      o.stat_final = h->rstat;
+      o.stat_C = D;
+      o.stat_eps = 1e-5f;
+      have_stats = true;
+    }
+    s.gemm(o, CLS_OUT);
+    xr = own;
+  }
+  if (!Ly.pre_norm) ln_t(xr, D, xr, D, Ly.ln1, ML, D, 0, st, nullptr, s.am(dzn_handle::AM_X), L);
+  if (Ly.ffn) {
+    dzn_gemm_desc f1 = norm_lin_desc(s, Ly.f1, xr, dzn_handle::AM_X, h->y, dzn_handle::AM_Y, h->mid, Ly.Fp, have_stats);
+    f1.act = DZN_ACT_GELU;
+    f1.c_amax = s.am(dzn_handle::AM_MID);
+    s.gemm(f1, CLS_FFN1);
+    dzn_gemm_desc f2 = gd(h, h->mid, Ly.f2, own, ML, Ly.Fp, D);
+    f2.R = xr;
+    if (Ly.pre_norm && !defer) {
+      f2.WS = h->ws;
+      f2.ldws = D;
+      f2.ws_w = wl;
+    }
+    f2.a_amax = s.am(dzn_handle::AM_MID);
+    f2.c_amax = s.am(dzn_handle::AM_X);
+    s.gemm(f2, CLS_FFN2);
+    xr = own;
+  } else if (Ly.pre_norm && !defer) {
+    chk(launch_ws_accum(xr, h->ws, wl, 0, ML * D, st), "ws_accum");
+  }
+  if (!Ly.pre_norm) {
+    ln_t(xr, D, xr, D, Ly.ln2, ML, D, 0, st, nullptr, s.am(dzn_handle::AM_X), L);
+    chk(launch_ws_accum(xr, h->ws, wl, 0, ML * D, st), "ws_accum");
+  } else if (defer) {   // a layer pruned to nothing leaves xr where it was: the same rows enter the sum again with this weight
+    wsum.x[wsum.n] = xr;
+    wsum.w[wsum.n++] = wl;
+  }
+  if (h->sw.debug_taps) {
+    const std::string nm = "layer" + std::to_string(i);
+    tap(h, nm.c_str(), xr, ML, D, D, st);
+  }
+  return xr;
+}
+
+// ---- head: proj + LN (model_wavlm_conformer.py:256-257) ----
+void seg_head_proj(const SegCall& s) {
+  H* h = s.h;
+  const int A = h->A;
+  dzn_gemm_desc d = gd(h, h->ws, h->proj, h->hz, s.ML, h->D, A);
+  s.gemm(d, CLS_PROJ);   // (ws has no tracker: bf16 split)
+  ln_t(h->hz, A, h->hz, A, h->lnorm, s.ML, A, 0, s.st, nullptr, s.am(dzn_handle::AM_HZ), s.L);
+  tap(h, "head_in", h->hz, s.ML, A, A, s.st);
+}
+
+// half-step feed-forward of a Conformer layer: hz += 0.5 w2(swish(w1(LN(hz))))
+void conf_half_ffn(const SegCall& s, const NormLin& w1, const Lin& w2) {
+  H* h = s.h;
+  dzn_gemm_desc a = norm_lin_desc(s, w1, h->hz, dzn_handle::AM_HZ, h->ht, -1, h->hmid, h->Fh);
+  a.act = DZN_ACT_SWISH;
+  a.c_amax = s.am(dzn_handle::AM_HMID);
+  s.gemm(a, CLS_CONF_W1);
+  dzn_gemm_desc b = gd(h, h->hmid, w2, h->hz, s.ML, h->Fh, h->A);
+  b.alpha = 0.5f;
+  b.R = h->hz;
+  b.a_amax = s.am(dzn_handle::AM_HMID);
+  b.c_amax = s.am(dzn_handle::AM_HZ);
+  s.gemm(b, CLS_CONF_W2);
+}
+
+// ---- Conformer layer i over hz (conformer.py:136-214) ----
+void seg_conformer_layer(const SegCall& s, int i) {
+  H* h = s.h;
+  const dzn_config& c = h->cfg;
+  const int A = h->A;
+  const int64_t ML = s.ML;
+  const ConfLayer& Cl = h->conf[i];
+  conf_half_ffn(s, Cl.ffn1_w1, Cl.ffn1_w2);
+  {   // MHSA
+    dzn_gemm_desc q = norm_lin_desc(s, Cl.qkv, h->hz, dzn_handle::AM_HZ, h->ht, -1, h->hmid, 3 * A);
+    q.c_amax = s.am(dzn_handle::AM_HMID);
+    s.gemm(q, CLS_CONF_QKV);
+    attention(s, nullptr, h->hmid, dzn_handle::AM_HMID, false, h->hv);
+    dzn_gemm_desc o = gd(h, h->hv, Cl.o, h->hz, ML, A, A);
+    o.R = h->hz;
+    o.a_amax = s.am(dzn_handle::AM_HMID);   // attention output <= max |q/k/v| (convex combinations of v)
+    o.c_amax = s.am(dzn_handle::AM_HZ);
+    s.gemm(o, CLS_CONF_OUT);
+  }
+  {   // conv module
+    dzn_gemm_desc p1 = norm_lin_desc(s, Cl.pw1, h->hz, dzn_handle::AM_HZ, h->ht, -1, h->hmid, 2 * A);
+    p1.c_amax = s.am(dzn_handle::AM_HMID);
+    s.gemm(p1, CLS_CONF_PW1);
+    chk(launch_glu_dwconv(h->hmid, 2 * A, Cl.dw, Cl.dwb, h->hv, A, s.B, s.L, A, c.conf_kernel, s.st), "glu_dwconv");
+    dzn_gemm_desc p2 = gd(h, h->hv, Cl.pw2, h->hz, ML, A, A);
+    p2.R = h->hz;
+    p2.c_amax = s.am(dzn_handle::AM_HZ);    // (glu_dwconv output has no tracker: bf16 split)
+    s.gemm(p2, CLS_CONF_PW2);
+  }
+  conf_half_ffn(s, Cl.ffn2_w1, Cl.ffn2_w2);
+  ln_t(h->hz, A, h->hz, A, Cl.out_ln, ML, A, 0, s.st, nullptr, s.am(dzn_handle::AM_HZ), s.L);
+  if (h->sw.debug_taps) {
+    const std::string nm = "conf" + std::to_string(i);
+    tap(h, nm.c_str(), h->hz, ML, A, A, s.st);
+  }
+}
+
+// the forward of model_wavlm_conformer.py:236-262
+void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* d_ml, float* d_soft, hipStream_t st) {
+  const dzn_config& c = h->cfg;
+  int T[DZN_MAX_CONV];
+  {
+    int n = N;
+    for (int i = 0; i < c.n_conv; ++i) {
+      n = conv_out(n, c.conv_k[i], c.conv_s[i]);
+      T[i] = n;
+    }
+  }
+  const int L = T[c.n_conv - 1];
+  if (L < 1) throw EngineError(DZN_E_INVALID, "window too short");
+  const int D = h->D, A = h->A;
+  const int64_t ML = (int64_t)B * L, MB = c.max_batch;
+  const SegCall s{h, st, B, L, ML};
+  if (prec_is_h2(c.precision)) {
+    chk(launch_fill_u32(h->amax, 0u, dzn_handle::AM_IMG0 * MB, st), "tracker reset");
+    if (c.extractor_layer_norm && h->conv0_bound > 0.f) {   // conv0 (LN + GELU) writes bufA: static bound instead of a tracker
+      uint32_t bits;
+      memcpy(&bits, &h->conv0_bound, 4);
+      chk(launch_fill_u32(h->amax + dzn_handle::AM_CONVA * MB, bits, B, st), "conv0 bound");
+    }
+  }
+  seg_project(s, seg_conv_stack(s, wave, N, T));
   // the residual stream: `xr` = rows of the representation the next operation reads.  With the deferred layer-weighted sum
   // every layer moves it into its own buffer (the first residual update of layer i reads xr and writes xl[i], the second
   // one works in place there) and (xr, weight) is noted per layer; else xr == h->x throughout.
@@ -1264,209 +1495,12 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
     chk(launch_ws_accum(h->x, h->ws, h->wsum_w[0], 1, ML * D, st), "ws_accum");
   }
   tap(h, "rep0", h->x, ML, D, D, st);
-
-  // ---- transformer layers (components.py:920-942) ----
-  static const bool stats_from_epilogue = getenv("DZN_NO_EPILOGUE_STATS") == nullptr;
   ensure_table(h, L, st);
-  for (int i = 0; i < c.n_layers; ++i) {
-    EncLayer& Ly = h->layers[i];
-    const float wl = h->wsum_w[i + 1];
-    float* const own = defer ? h->xl + (int64_t)i * ML * D : xr;   // where this layer's output rows live
-    bool have_stats = false;   // LN2's statistics already left in rstat by the out_proj epilogue
-    if (Ly.attn) {
-      const float* yin = xr;
-      const bool fold1 = fold && c.layer_norm_first;
-      if (fold1) {
-        // one pass over x: LN statistics for the folded q/k/v contraction + the gate on LN(x) (never written)
-        chk(launch_gate_stats(xr, D, Ly.ln1.g, Ly.ln1.b, Ly.Wg, Ly.bg, Ly.cst, h->gate, h->rstat, ML, h->H, 1e-5f,
-                              st),
-            "gate_stats");
-      } else if (c.layer_norm_first) {
-        ln_t(xr, D, h->y, D, Ly.ln1, ML, D, 0, st, nullptr, am(dzn_handle::AM_Y), L);
-        yin = h->y;
-      }
-      if (!fold1) chk(launch_gate(yin, D, Ly.Wg, Ly.bg, Ly.cst, h->gate, ML, h->H, st), "gate");
-      const int hd = Ly.h * 64;
-      dzn_gemm_desc d = gd(h, yin, Ly.qkv, h->qkv, ML, D, 3 * hd);
-      if (fold1) folded(d, Ly.qkv);
-      d.a_amax = am(yin == xr ? dzn_handle::AM_X : dzn_handle::AM_Y);
-      d.c_amax = am(dzn_handle::AM_QKV);
-      const bool planes = h->kvp != nullptr && d.W2h && d.col_scale && d.a_amax;     // the f32h contraction writes them
-      const int64_t pstride = (ML + 64) * (int64_t)(2 * hd);
-      if (planes) {
-        d.kv_planes = h->kvp;
-        d.kv_plane_stride = pstride;
-        d.kv_scale = h->kvs;
-        d.kv_ld = 2 * hd;
-        d.kv_col0 = hd;
-      }
-      gemm(d, "qkv");
-      if (planes)
-        chk(launch_attention_planes(h->qkv, h->kvp, pstride, h->kvs, 2 * hd, h->ao, h->gate, h->table, Ly.head_idx, B, L, Ly.h, h->H,
-                                    3 * hd, hd, 0.125f, st, am(dzn_handle::AM_QKV)),
-            "attention");
-      else if (prec_is_split(c.precision))
-        chk(launch_attention_split(h->qkv, h->ao, h->gate, h->table, Ly.head_idx, B, L, Ly.h, h->H, 3 * hd, hd,
-                                   0.125f, st, am(dzn_handle::AM_QKV)),
-            "attention");
-      else
-        chk(launch_attention_t(h->qkv, h->ao, h->gate, h->table, Ly.head_idx, B, L, Ly.h, h->H, 3 * hd,
-                               hd, 0.125f, st),
-            "attention");
-      dzn_gemm_desc o = gd(h, h->ao, Ly.out, own, ML, hd, D);
-      o.R = xr;
-      o.a_amax = am(dzn_handle::AM_QKV);   // rows of ao are convex combinations of v rows: |ao| <= max |qkv|
-      o.c_amax = am(dzn_handle::AM_X);
-      if (fold && c.layer_norm_first && Ly.ffn && stats_from_epilogue) {
-        // the rows it writes are exactly what the FFN's (folded) LayerNorm normalises: leave their statistics
-        o.stat_partial = h->spart;
-        o.stat_final = h->rstat;
-        o.stat_C = D;
-        o.stat_eps = 1e-5f;
-        have_stats = true;
-      }
-      gemm(o, "out_proj");
-      xr = own;
-    }
-    if (c.layer_norm_first) {
-      if (Ly.ffn) {
-        const float* fin = h->y;
-        if (fold) {
-          if (!have_stats) chk(launch_row_stats(xr, D, ML, D, 1e-5f, h->rstat, st), "row_stats");
-          fin = xr;
-        } else {
-          ln_t(xr, D, h->y, D, Ly.ln2, ML, D, 0, st, nullptr, am(dzn_handle::AM_Y), L);
-        }
-        dzn_gemm_desc f1 = gd(h, fin, Ly.f1, h->mid, ML, D, Ly.Fp);
-        if (fold) folded(f1, Ly.f1);
-        f1.act = DZN_ACT_GELU;
-        f1.a_amax = am(fin == xr ? dzn_handle::AM_X : dzn_handle::AM_Y);
-        f1.c_amax = am(dzn_handle::AM_MID);
-        gemm(f1, "ffn1");
-        dzn_gemm_desc f2 = gd(h, h->mid, Ly.f2, own, ML, Ly.Fp, D);
-        f2.R = xr;
-        if (!defer) {
-          f2.WS = h->ws;
-          f2.ldws = D;
-          f2.ws_w = wl;
-        }
-        f2.a_amax = am(dzn_handle::AM_MID);
-        f2.c_amax = am(dzn_handle::AM_X);
-        gemm(f2, "ffn2");
-        xr = own;
-      } else if (!defer) {
-        chk(launch_ws_accum(xr, h->ws, wl, 0, ML * D, st), "ws_accum");
-      }
-      if (defer) {   // a layer pruned to nothing leaves xr where it was: the same rows enter the sum again with this weight
-        wsum.x[wsum.n] = xr;
-        wsum.w[wsum.n++] = wl;
-      }
-    } else {
-      ln_t(xr, D, xr, D, Ly.ln1, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
-      if (Ly.ffn) {
-        dzn_gemm_desc f1 = gd(h, xr, Ly.f1, h->mid, ML, D, Ly.Fp);
-        f1.act = DZN_ACT_GELU;
-        f1.a_amax = am(dzn_handle::AM_X);
-        f1.c_amax = am(dzn_handle::AM_MID);
-        gemm(f1, "ffn1");
-        dzn_gemm_desc f2 = gd(h, h->mid, Ly.f2, xr, ML, Ly.Fp, D);
-        f2.R = xr;
-        f2.a_amax = am(dzn_handle::AM_MID);
-        f2.c_amax = am(dzn_handle::AM_X);
-        gemm(f2, "ffn2");
-      }
-      ln_t(xr, D, xr, D, Ly.ln2, ML, D, 0, st, nullptr, am(dzn_handle::AM_X), L);
-      chk(launch_ws_accum(xr, h->ws, wl, 0, ML * D, st), "ws_accum");
-    }
-    if (h->debug) {
-      const std::string nm = "layer" + std::to_string(i);
-      tap(h, nm.c_str(), xr, ML, D, D, st);
-    }
-  }
+  for (int i = 0; i < c.n_layers; ++i) xr = seg_encoder_layer(s, i, xr, wsum);
   if (defer) chk(launch_ws_sum(wsum, h->ws, ML * D, st), "ws_sum");
   tap(h, "wsum", h->ws, ML, D, D, st);
-
-  // ---- head: proj + LN, Conformer x conf_layers, classifier (model_wavlm_conformer.py:256-262) ----
-  {
-    dzn_gemm_desc d = gd(h, h->ws, h->proj, h->hz, ML, D, A);
-    gemm(d, "proj");   // (ws has no tracker: bf16 split)
-    ln_t(h->hz, A, h->hz, A, h->lnorm, ML, A, 0, st, nullptr, am(dzn_handle::AM_HZ), L);
-  }
-  tap(h, "head_in", h->hz, ML, A, A, st);
-  for (int i = 0; i < c.conf_layers; ++i) {
-    ConfLayer& Cl = h->conf[i];
-    auto half_ffn = [&](const LNp& ln, const Lin& w1, const Lin& w2) {
-      const float* in = h->ht;
-      if (fold) {
-        chk(launch_row_stats(h->hz, A, ML, A, 1e-5f, h->rstat, st), "row_stats");
-        in = h->hz;
-      } else {
-        ln_t(h->hz, A, h->ht, A, ln, ML, A, 0, st);
-      }
-      dzn_gemm_desc a = gd(h, in, w1, h->hmid, ML, A, Fh);
-      if (fold) folded(a, w1);
-      a.act = DZN_ACT_SWISH;
-      if (in == h->hz) a.a_amax = am(dzn_handle::AM_HZ);
-      a.c_amax = am(dzn_handle::AM_HMID);
-      gemm(a, "conf ffn w1");
-      dzn_gemm_desc b = gd(h, h->hmid, w2, h->hz, ML, Fh, A);
-      b.alpha = 0.5f;
-      b.R = h->hz;
-      b.a_amax = am(dzn_handle::AM_HMID);
-      b.c_amax = am(dzn_handle::AM_HZ);
-      gemm(b, "conf ffn w2");
-    };
-    half_ffn(Cl.ffn1_ln, Cl.ffn1_w1, Cl.ffn1_w2);
-    // MHSA
-    if (fold) chk(launch_row_stats(h->hz, A, ML, A, 1e-5f, h->rstat, st), "row_stats");
-    else ln_t(h->hz, A, h->ht, A, Cl.mha_ln, ML, A, 0, st);
-    {
-      dzn_gemm_desc q = gd(h, fold ? h->hz : h->ht, Cl.qkv, h->hmid, ML, A, 3 * A);
-      if (fold) {
-        folded(q, Cl.qkv);
-        q.a_amax = am(dzn_handle::AM_HZ);
-      }
-      q.c_amax = am(dzn_handle::AM_HMID);
-      gemm(q, "conf qkv");
-      if (prec_is_split(c.precision))
-        chk(launch_attention_split(h->hmid, h->hv, nullptr, nullptr, nullptr, B, L, c.conf_heads, 0, 3 * A, A,
-                                   0.125f, st, am(dzn_handle::AM_HMID)),
-            "conf attention");
-      else
-        chk(launch_attention_t(h->hmid, h->hv, nullptr, nullptr, nullptr, B, L, c.conf_heads, 0, 3 * A, A,
-                               0.125f, st),
-            "conf attention");
-      dzn_gemm_desc o = gd(h, h->hv, Cl.o, h->hz, ML, A, A);
-      o.R = h->hz;
-      o.a_amax = am(dzn_handle::AM_HMID);   // attention output <= max |q/k/v| (convex combinations of v)
-      o.c_amax = am(dzn_handle::AM_HZ);
-      gemm(o, "conf out");
-    }
-    // conv module
-    if (fold) chk(launch_row_stats(h->hz, A, ML, A, 1e-5f, h->rstat, st), "row_stats");
-    else ln_t(h->hz, A, h->ht, A, Cl.conv_ln, ML, A, 0, st);
-    {
-      dzn_gemm_desc p1 = gd(h, fold ? h->hz : h->ht, Cl.pw1, h->hmid, ML, A, 2 * A);
-      if (fold) {
-        folded(p1, Cl.pw1);
-        p1.a_amax = am(dzn_handle::AM_HZ);
-      }
-      p1.c_amax = am(dzn_handle::AM_HMID);
-      gemm(p1, "conf pw1");
-      chk(launch_glu_dwconv(h->hmid, 2 * A, Cl.dw, Cl.dwb, h->hv, A, B, L, A, c.conf_kernel, st),
-          "glu_dwconv");
-      dzn_gemm_desc p2 = gd(h, h->hv, Cl.pw2, h->hz, ML, A, A);
-      p2.R = h->hz;
-      p2.c_amax = am(dzn_handle::AM_HZ);    // (glu_dwconv output has no tracker: bf16 split)
-      gemm(p2, "conf pw2");
-    }
-    half_ffn(Cl.ffn2_ln, Cl.ffn2_w1, Cl.ffn2_w2);
-    ln_t(h->hz, A, h->hz, A, Cl.out_ln, ML, A, 0, st, nullptr, am(dzn_handle::AM_HZ), L);
-    if (h->debug) {
-      const std::string nm = "conf" + std::to_string(i);
-      tap(h, nm.c_str(), h->hz, ML, A, A, st);
-    }
-  }
+  seg_head_proj(s);
+  for (int i = 0; i < c.conf_layers; ++i) seg_conformer_layer(s, i);
   chk(launch_classify(h->hz, A, h->cls_w, h->cls_b, h->mapping, ML, A, c.n_classes,
                       c.max_speakers_per_chunk, d_logp, d_ml, d_soft, st),
       "classify");
@@ -1487,7 +1521,7 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
   if (T > h->maxTf) throw EngineError(DZN_E_INVALID, "N exceeds max_samples");
   if (S < 1 || S > 8) throw EngineError(DZN_E_INVALID, "S must be in [1, 8]");
   emb_set_geometry(h, T, st);
-  const bool subset = h->emb_skip && !h->debug && h->seg1.b != nullptr;
+  const bool subset = h->sw.emb_skip && !h->sw.debug_taps && h->seg1.b != nullptr;
   const int *zc = nullptr, *zl = nullptr, *zflag = nullptr;
   if (subset) {
     chk(launch_window_active(masks, B, S * L, h->win_flag, st), "window_active");
@@ -1534,6 +1568,29 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
     const int64_t img = h->simg[s];
     const int64_t interior = ((int64_t)(Ws + 2) + 1) * Cc;
     const int M = Hs * Ws;
+    // the contraction of one ResNet conv over a whole image per window, written to the interior of `out` in this stage
+    // (tab1): a 3x3 reads patch rows, two-level K = (dh | dw*C + ci); a stride-2 conv reads the previous stage's image (tab2),
+    // the 1x1 one its centre pixels; windows from the active list; DZN_PREC_F16: two fp16 terms if the trunk's bit asks
+    auto img_desc = [&](const float* in, const ResConv& rc, float* out) {
+      const bool down = rc.stride == 2;
+      const int Win = down ? h->sW[s - 1] : Ws;
+      dzn_gemm_desc d = gd(h, rc.ksz == 1 ? in + ((int64_t)(Win + 2) + 1) * rc.cin : in, rc.l, out + interior, M, 0, 0);
+      d.a_rowoff = down ? h->tab2[s] : h->tab1[s];
+      d.c_rowoff = h->tab1[s];
+      if (rc.ksz == 3) {
+        d.kc = 3 * rc.cin;
+        d.ldk = (int64_t)(Win + 2) * rc.cin;
+      }
+      d.nz = B;
+      d.a_z0 = down ? h->simg[s - 1] : img;
+      d.c_z0 = img;
+      d.a_amax = img_am(in);
+      d.c_amax = img_am(out);
+      d.z_count = zc;
+      d.z_list = zl;
+      if (c.precision == DZN_PREC_F16 && ((h->sw.f16_keep2 >> CLS_RESNET) & 1)) d.precision = DZN_PREC_F32_H2;
+      return d;
+    };
     // x2 (rc.k2 > 0): the previous stage's image, whose centre pixels are the second A segment (the folded shortcut)
     auto conv3 = [&](const float* in, const ResConv& rc, float* out, const float* R, int act,
                      int post_relu, const float* x2 = nullptr) {
@@ -1545,22 +1602,10 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
             "resnet conv3x3 c32");
         return;
       }
-      // stride-1 3x3 inside stage s: patch rows via tab1, two-level K = (dh | dw*C + ci)
-      dzn_gemm_desc d = gd(h, in, rc.l, out + interior, M, 0, 0);
-      d.a_rowoff = h->tab1[s];
-      d.c_rowoff = h->tab1[s];
-      d.kc = 3 * rc.cin;
-      d.ldk = (int64_t)(Ws + 2) * rc.cin;
+      dzn_gemm_desc d = img_desc(in, rc, out);   // stride-1 3x3 inside stage s
       d.act = act;
       d.R = R ? R + interior : nullptr;
       d.post_relu = post_relu;
-      d.nz = B;
-      d.a_z0 = img;
-      d.c_z0 = img;
-      d.a_amax = img_am(in);
-      d.c_amax = img_am(out);
-      d.z_count = zc;
-      d.z_list = zl;
       if (rc.k2 > 0) {
         d.A2 = x2 + ((int64_t)(h->sW[s - 1] + 2) + 1) * rc.k2;   // pixel (2y, 2x) = centre of conv1's stride-2 patch
         d.a2_rowoff = h->tab2[s];
@@ -1569,32 +1614,17 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
         d.k1 = 9 * rc.cin;
         d.k2 = rc.k2;
       }
-      if (c.precision == DZN_PREC_F16 && ((h->f16_keep2 >> 14) & 1)) d.precision = DZN_PREC_F32_H2;
       chk(launch_gemm(d, st), "resnet conv3x3");
     };
     for (size_t j = 0; j < h->stages[s].size(); ++j) {
       ResBlock& rb = h->stages[s][j];
       if (rb.has_sc) {
         // down-sampling block: reads the previous stage's image with stride 2 (tab2)
-        const int Wp = h->sW[s - 1], Cpv = h->sC[s - 1];
-        const int64_t pimg = h->simg[s - 1];
         float* midb = h->sbuf[s][0];
         float* outb = h->sbuf[s][1];
         float* scb = h->sbuf[s][2];
-        dzn_gemm_desc d = gd(h, prev, rb.c1.l, midb + interior, M, 0, 0);
-        d.a_rowoff = h->tab2[s];
-        d.c_rowoff = h->tab1[s];
-        d.kc = 3 * Cpv;
-        d.ldk = (int64_t)(Wp + 2) * Cpv;
+        dzn_gemm_desc d = img_desc(prev, rb.c1, midb);
         d.act = DZN_ACT_RELU;
-        d.nz = B;
-        d.a_z0 = pimg;
-        d.c_z0 = img;
-        d.a_amax = img_am(prev);
-        d.c_amax = img_am(midb);
-        d.z_count = zc;
-        d.z_list = zl;
-        if (c.precision == DZN_PREC_F16 && ((h->f16_keep2 >> 14) & 1)) d.precision = DZN_PREC_F32_H2;
         chk(launch_gemm(d, st), "resnet conv3x3 s2");
         if (rb.c2.k2 > 0) {
           // the 1x1 shortcut is k2 more K columns of conv2 (make_resconv_shortcut): no shortcut image, no residual read
@@ -1602,18 +1632,7 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
           cur = 1;
           continue;
         }
-        dzn_gemm_desc e = gd(h, prev + ((int64_t)(Wp + 2) + 1) * Cpv, rb.sc.l,
-                             scb + interior, M, 0, 0);
-        e.a_rowoff = h->tab2[s];
-        e.c_rowoff = h->tab1[s];
-        e.nz = B;
-        e.a_z0 = pimg;
-        e.c_z0 = img;
-        e.a_amax = img_am(prev);
-        e.c_amax = img_am(scb);
-        e.z_count = zc;
-        e.z_list = zl;
-        if (c.precision == DZN_PREC_F16 && ((h->f16_keep2 >> 14) & 1)) e.precision = DZN_PREC_F32_H2;
+        dzn_gemm_desc e = img_desc(prev, rb.sc, scb);
         chk(launch_gemm(e, st), "resnet shortcut");
         conv3(midb, rb.c2, outb, scb, DZN_ACT_NONE, 1);
         cur = 1;
@@ -1622,17 +1641,17 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
         float* midb = h->sbuf[s][(cur + 1) % 3];
         float* outb = h->sbuf[s][(cur + 2) % 3];
         // (r4) 32-channel blocks in the two-term fp16 modes: both convolutions in one kernel, the intermediate image
-        // stays in LDS (resblock_fused.hip); DZN_NO_RESBLOCK_FUSION=1 (read at dzn_create) keeps the per-conv kernels
-        const bool fusable = h->fuse_resblock && prec_is_h2(c.precision) && rb.c1.cin == rb.c1.cout && rb.c1.l.W2h &&
+        // stays in LDS (resblock_fused.hip); DZN_NO_RESBLOCK_FUSION=1 keeps the per-conv kernels
+        const bool fusable = h->sw.fuse_resblock && prec_is_h2(c.precision) && rb.c1.cin == rb.c1.cout && rb.c1.l.W2h &&
                              rb.c2.l.W2h && img_am(inb) != nullptr;
         // (r5) DZN_PREC_F16: the fused blocks keep ONE fp16 term unless bit 14 of DZN_F16_KEEP2 asks for two (the embedding
         // trunk is three orders of magnitude inside its cosine bar with one term: profiles/r4_reduced_mode_emulation.txt)
-        const int rb_np = (c.precision == DZN_PREC_F16 && !((h->f16_keep2 >> 14) & 1)) ? 1 : 2;
-        if (fusable && rb.c1.cin == 32 && !(h->resblock_ws & 1)) {
+        const int rb_np = (c.precision == DZN_PREC_F16 && !((h->sw.f16_keep2 >> CLS_RESNET) & 1)) ? 1 : 2;
+        if (fusable && rb.c1.cin == 32 && !(h->sw.resblock_ws & 1)) {
           chk(launch_resblock32_fused(inb, outb, rb.c1.l.W2h, rb.c1.l.wsc, rb.c1.l.b, rb.c2.l.W2h, rb.c2.l.wsc, rb.c2.l.b,
                                       img_am(inb), img_am(outb), rb.c1.l1max, rb.c1.bmax, B, Hs, Ws, rb_np, st, zc, zl),
               "resblock32 fused");
-        } else if (fusable && ((rb.c1.cin == 32 && (h->resblock_ws & 1)) || (rb.c1.cin == 64 && (h->resblock_ws & 2)))) {
+        } else if (fusable && ((rb.c1.cin == 32 && (h->sw.resblock_ws & 1)) || (rb.c1.cin == 64 && (h->sw.resblock_ws & 2)))) {
           // producer / consumer wavefronts (resblock_ws.hip): the only fused form for the 64-plane stage
           chk(launch_resblock_ws(inb, outb, rb.c1.l.W2h, rb.c1.l.wsc, rb.c1.l.b, rb.c2.l.W2h, rb.c2.l.wsc, rb.c2.l.b, img_am(inb),
                                  img_am(outb), rb.c1.l1max, rb.c1.bmax, B, Hs, Ws, rb.c1.cin, st, zc, zl, rb_np),
@@ -1705,14 +1724,7 @@ int dzn_create(const dzn_config* cfg, dzn_handle** out) {
   if (!h) return DZN_E_NOMEM;
   h->cfg = *cfg;
   if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-  h->emb_skip = getenv("DZN_EMB_NO_SKIP") == nullptr;
-  h->fuse_resblock = getenv("DZN_NO_RESBLOCK_FUSION") == nullptr;
-  h->fuse_shortcut = getenv("DZN_NO_SHORTCUT_FUSION") == nullptr;
-  if (const char* e = getenv("DZN_RESBLOCK_WS")) h->resblock_ws = atoi(e);
-  if (const char* e = getenv("DZN_F16_KEEP2")) h->f16_keep2 = (unsigned)strtoul(e, nullptr, 0);
-  if (const char* e = getenv("DZN_F16_MX")) h->f16_mx = (unsigned)strtoul(e, nullptr, 0);
-  const char* dbg = getenv("DZN_DEBUG_TAPS");
-  h->debug = dbg && dbg[0] == '1';
+  h->sw = read_switches();
   *out = h;
   return DZN_OK;
 }

@@ -82,6 +82,24 @@ def test_seg_fp32_matches_reference_golden(built_lib, gpu, name, precision):
     assert eng.num_ignored_keys <= cfg.conf_layers + 2
 
 
+@pytest.mark.parametrize("precision", ["f32", "f32h"])
+@pytest.mark.parametrize("name", ["tiny_ln", "tiny_gn"])
+def test_seg_matches_reference_golden_without_the_layernorm_fold(built_lib, gpu, monkeypatch, name, precision):
+    """DZN_NO_LN_FOLD=1 (read at dzn_create): every LayerNorm that feeds a linear runs stand-alone and its contraction reads
+    the normalised rows — the reference's own order of operations, reachable only under this switch.  tiny_ln is pre-norm
+    (every fold site takes its unfolded branch), tiny_gn a post-norm encoder.  Same strict bar as the folded engine."""
+    monkeypatch.setenv("DZN_NO_LN_FOLD", "1")
+    cfg, sd, wave, g, eng, logp, ml = _run_case(name, gpu, precision)
+    ref = torch.from_numpy(g["logp"])
+    err = (logp - ref).abs().max().item()
+    print(f"{name} {precision} without the fold: max |dlogp| = {err:.3e}")
+    assert err <= 1e-3, f"max |dlogp| = {err}"
+    assert torch.equal(logp.argmax(-1), ref.argmax(-1))
+    from oracle import seg_model
+    exp_ml = seg_model.to_multilabel(ref, cfg).to(torch.uint8)
+    assert torch.equal(ml, exp_ml)
+
+
 @pytest.mark.parametrize("precision", ["f32", "f32s", "f32h"])
 @pytest.mark.parametrize("name", ["tiny_ln", "tiny_gn", "wavlm_large_s80_md", "wavlm_base_s80_md"])
 def test_seg_fp32_matches_reference_golden_turn_taking(built_lib, gpu, name, precision):
@@ -435,13 +453,14 @@ def test_conv01_fusion_matches_unfused(built_lib, gpu, monkeypatch):
         monkeypatch.setenv("DZN_NO_CONV01_FUSION", "1")
         plain = Engine(cfg, sd, max_batch=3, max_samples=N, precision="f32h", device=gpu)
         monkeypatch.delenv("DZN_NO_CONV01_FUSION")
+        # (r3) the fused kernel also finishes conv1's LayerNorm + GELU in its epilogue; an engine created under
+        # DZN_CONV01_NO_LN=1 (read at dzn_create) sends the raw conv1 output through the stand-alone row pass instead
+        monkeypatch.setenv("DZN_CONV01_NO_LN", "1")
+        fused_no_ln = Engine(cfg, sd, max_batch=3, max_samples=N, precision="f32h", device=gpu)
+        monkeypatch.delenv("DZN_CONV01_NO_LN")
         lf, mf = fused.segment(wave.to(gpu))
         lp_, mp = plain.segment(wave.to(gpu))
-        # (r3) the fused kernel also finishes conv1's LayerNorm + GELU in its epilogue; DZN_CONV01_NO_LN=1 (read per call)
-        # sends the raw conv1 output through the stand-alone row pass instead
-        monkeypatch.setenv("DZN_CONV01_NO_LN", "1")
-        l2, m2 = fused.segment(wave.to(gpu))
-        monkeypatch.delenv("DZN_CONV01_NO_LN")
+        l2, m2 = fused_no_ln.segment(wave.to(gpu))
         torch.cuda.synchronize()
         d = (lf - lp_).abs().max().item()
         d2 = (lf - l2).abs().max().item()
@@ -452,6 +471,7 @@ def test_conv01_fusion_matches_unfused(built_lib, gpu, monkeypatch):
         assert (lf.cpu() - ref).abs().max().item() <= 1e-3
         fused.close()
         plain.close()
+        fused_no_ln.close()
 
 
 def _segment_profiled(eng, wave):
