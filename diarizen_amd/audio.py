@@ -1,16 +1,21 @@
 """Audio ingest for the pipeline (replaces `torchaudio.load` at diarizen/pipelines/inference.py:127
-and the `Audio` helper of PA/core/io.py for what the hot path needs: WAV or (r5) FLAC in, first channel kept —
-"force to use the SDM data", inference.py:128 — resampled to 16 kHz when the file is at another
-rate, as `Audio.downmix_and_resample` does with `torchaudio.functional.resample`, PA/core/io.py:214-218).
-torchaudio is not available in this image: RIFF/WAVE (PCM 8/16/24/32, float 32/64, WAVE_FORMAT_EXTENSIBLE) is parsed
-directly with numpy, and the resampler restates torchaudio's default algorithm
+and the `Audio` helper of PA/core/io.py for what the hot path needs: WAV, (r5) FLAC or NIST SPHERE in, ONE channel kept —
+channel 0 by default, "force to use the SDM data", inference.py:128; `channel=` selects another one or "downmix", the
+per-file "channel" key and mono="downmix" of PA/core/io.py:53-54, 205-212, 300-303 — resampled to 16 kHz when the file is at
+another rate, as `Audio.downmix_and_resample` does with `torchaudio.functional.resample`, PA/core/io.py:214-218).
+torchaudio is not available in this image: RIFF/WAVE (PCM 8/16/24/32, float 32/64, G.711 A-law / mu-law,
+WAVE_FORMAT_EXTENSIBLE) and SPHERE (`NIST_1A` header; 16-bit PCM of either byte order, mu-law, A-law; not shorten-compressed:
+`load_sphere`, `SphereSource`) are parsed directly with numpy.  G.711 is expanded by the integer tables of ITU-T G.711
+(`ulaw_table`, `alaw_table`: pinned to `audioop`; parity of SPHERE / G.711 decoding with torchaudio / sox is UNPINNED here),
+and the resampler restates torchaudio's default algorithm
 (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99; torchaudio==2.1.1 functional/functional.py
 `_get_sinc_resample_kernel` / `_apply_sinc_resample_kernel`).  Parity of the resampler is UNPINNED
 (no torchaudio here, no fixture in the reference); tests pin its properties instead.
 
 The resampler exists twice over ONE filter bank (`resample_bank`): `resample`, a strided convolution on the host (the default
 everywhere), and `resample_device` (csrc/resample.hip, `dzn_resample`), which turns a span of input samples — float32, or the
-int16 interleaved frames of a PCM16 file as stored (`WavSource.read_raw`) — into a range of output samples on the GPU, with
+interleaved frames of a file as stored (`read_stored` of a source: 8 / 16 / 24 / 32-bit PCM, float32, mu-law, A-law; the
+kernel decodes them and selects the channel or downmixes) — into a range of output samples on the GPU, with
 the bits of the same slice of a whole-recording call (`resample_input_span` says which input a range reads).
 `ResampledSource` wraps a file at another rate on top of it; `pipeline.open_recording(resample="device")` returns one.
 """
@@ -25,11 +30,140 @@ import numpy as np
 _PCM_GUID_TAIL = bytes.fromhex("000000001000800000aa00389b71")   # KSDATAFORMAT_SUBTYPE_*: tag + this tail
 
 
+# src_format codes of dzn_resample (include/dzn.h DZN_SRC_*), by the names resample_device takes
+SRC_FORMATS = {"f32": 0, "s16": 1, "u8": 2, "s24": 3, "s32": 4, "f32i": 5, "ulaw": 6, "alaw": 7}
+_SRC_DTYPES = {0: "float32", 1: "int16", 2: "uint8", 3: "uint8", 4: "int32", 5: "float32", 6: "uint8", 7: "uint8"}
+_SRC_BYTES = {0: 4, 1: 2, 2: 1, 3: 3, 4: 4, 5: 4, 6: 1, 7: 1}
+
+
+def ulaw_table() -> np.ndarray:
+    """int16 [256]: the linear value of every G.711 mu-law code byte (ITU-T G.711; == audioop.ulaw2lin).  Range +-32124;
+    0x7F and 0xFF both decode to 0.  The float sample is value * 2^-15, exact."""
+    u = ~np.arange(256, dtype=np.int32) & 0xFF
+    t = (((u & 0x0F) << 3) + 0x84) << ((u >> 4) & 7)
+    return np.where(u & 0x80, 0x84 - t, t - 0x84).astype(np.int16)
+
+
+def alaw_table() -> np.ndarray:
+    """int16 [256]: the linear value of every G.711 A-law code byte (ITU-T G.711; == audioop.alaw2lin).  Range +-32256.
+    The float sample is value * 2^-15, exact."""
+    a = np.arange(256, dtype=np.int32) ^ 0x55
+    e, m = (a >> 4) & 7, a & 0x0F
+    t = np.where(e == 0, (m << 4) + 8, ((m << 4) + 0x108) << np.maximum(e - 1, 0))
+    return np.where(a & 0x80, t, -t).astype(np.int16)
+
+
+_G711_F32 = {"ulaw": ulaw_table().astype(np.float32) * np.float32(2.0 ** -15),
+             "alaw": alaw_table().astype(np.float32) * np.float32(2.0 ** -15)}
+
+
+def downmix(x: np.ndarray) -> np.ndarray:
+    """float32 [C, N] -> [N], the mean over the channels, DEFINED as a float32 running sum over the channels in ascending
+    order, starting from channel 0, then ONE float32 division by float32(C) (C = 1: the channel itself).  The device resampler
+    (csrc/resample.hip, channel -1) computes exactly this.  It is bit-identical to `torch.mean(dim=0)` for C = 2, 3, 4; for
+    C >= 5 torch sums in another order and a few samples per 100 k differ in the last bit (multiplying by the reciprocal
+    instead of dividing would differ from torch in a third of the samples at C = 3)."""
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim == 1:
+        return np.ascontiguousarray(x)
+    s = np.array(x[0], dtype=np.float32)
+    for c in range(1, x.shape[0]):
+        s += x[c]
+    if x.shape[0] > 1:
+        s /= np.float32(x.shape[0])
+    return s
+
+
+def check_channel(channel):
+    """a channel choice is an int >= 0 or "downmix" (returned as is); anything else, a bool included, is a ValueError"""
+    if isinstance(channel, str) and channel == "downmix":
+        return channel
+    if isinstance(channel, (int, np.integer)) and not isinstance(channel, (bool, np.bool_)) and channel >= 0:
+        return int(channel)
+    raise ValueError(f'channel is an int >= 0 or "downmix", not {channel!r}')
+
+
+def _check_channel_of(channel, channels: int):
+    channel = check_channel(channel)
+    if channel != "downmix" and channel >= channels:
+        raise ValueError(f"channel {channel} of a source with {channels} channel(s)")
+    return channel
+
+
+def select_channel(x: np.ndarray, channel=0) -> np.ndarray:
+    """float32 [C, N] -> [N]: channel `channel` of a decoded file, or its `downmix`; an index >= C is a ValueError"""
+    channel = _check_channel_of(channel, x.shape[0])
+    return downmix(x) if channel == "downmix" else np.ascontiguousarray(x[channel])
+
+
+_CODEC_DTYPES = {"u8": np.uint8, "s16": "<i2", "s16be": ">i2", "s32": "<i4", "f32": "<f4", "f64": "<f8", "ulaw": np.uint8,
+                 "alaw": np.uint8}
+_CODEC_BYTES = {"u8": 1, "s16": 2, "s16be": 2, "s24": 3, "s32": 4, "f32": 4, "f64": 8, "ulaw": 1, "alaw": 1}
+# the stored form the device resampler takes (None: it goes through `read`)
+_CODEC_SRC_FORMAT = {"u8": 2, "s16": 1, "s24": 3, "s32": 4, "f32": 5, "ulaw": 6, "alaw": 7}
+
+
+def _decode_frames(body, codec: str, nch: int, channel=None) -> np.ndarray:
+    """float32 of the interleaved frames in `body` with load_wav's conversions: [m, nch] (channel None), [m] of one channel
+    (only that channel is converted), or the `downmix` of the frame"""
+    sel = channel if isinstance(channel, int) else slice(None)
+    if codec == "s24":
+        b3 = np.frombuffer(body, dtype=np.uint8).reshape(-1, nch, 3)[:, sel].astype(np.int32)
+        v = b3[..., 0] | (b3[..., 1] << 8) | (b3[..., 2] << 16)
+        v = np.where(v & 0x800000, v - 0x1000000, v)
+        x = v.astype(np.float32) / 8388608.0
+    else:
+        raw = np.frombuffer(body, dtype=_CODEC_DTYPES[codec]).reshape(-1, nch)[:, sel]
+        if codec == "u8":
+            x = (raw.astype(np.float32) - 128.0) / 128.0
+        elif codec in ("s16", "s16be"):
+            x = raw.astype(np.float32) / 32768.0
+        elif codec == "s32":
+            x = raw.astype(np.float32) / 2147483648.0
+        elif codec in ("ulaw", "alaw"):
+            x = _G711_F32[codec][raw]
+        else:
+            x = raw.astype(np.float32)
+    if channel == "downmix":
+        x = downmix(x.T)
+    return np.ascontiguousarray(x)
+
+
+class _FrameSource:
+    """what WavSource and SphereSource share: ONE channel choice of a file of fixed-size interleaved frames behind a header
+    (path, _data_off, _frame bytes per frame, _codec, channels, num_samples, _channel)"""
+
+    def _frames(self, start: int, n: int):
+        start = max(0, min(int(start), self.num_samples))
+        n = max(0, min(int(n), self.num_samples - start))
+        with open(self.path, "rb") as f:
+            f.seek(self._data_off + start * self._frame)
+            return f.read(n * self._frame)
+
+    def read(self, start: int, n: int) -> np.ndarray:
+        """float32 [m] = samples start .. start + n of the channel choice (m < n at the end of the file)"""
+        return _decode_frames(self._frames(start, n), self._codec, self.channels, self._channel)
+
+    def read_stored(self, start: int, n: int):
+        """(array [m, ...], src_format) = the interleaved frames start .. start + n exactly as they lie in the file, not
+        converted, with the format code resample_device / dzn_resample decode them by (m < n at the end of the file): int16
+        / int32 / float32 [m, channels], uint8 [m, channels] (8-bit PCM, mu-law, A-law) or uint8 [m, 3 channels] (24-bit).
+        None where the device cannot take the format (float64, big-endian PCM16): those go through `read`."""
+        fmt = _CODEC_SRC_FORMAT.get(self._codec)
+        if fmt is None:
+            return None
+        if fmt == 5 and self.channels == 1:
+            fmt = 0
+        dt = np.uint8 if self._codec == "s24" else _CODEC_DTYPES[self._codec]
+        return np.frombuffer(self._frames(start, n), dtype=dt).reshape(-1, self._frame // np.dtype(dt).itemsize), fmt
+
+
 def load_wav(src: Union[str, bytes, BinaryIO, io.BytesIO]) -> Tuple[np.ndarray, int]:
     """-> (float32 [channels, samples] in [-1, 1), sample_rate)  (torchaudio.load semantics).
-    RIFF/WAVE is parsed directly: PCM 8 / 16 / 24 / 32 bit, IEEE float 32 / 64, and WAVE_FORMAT_EXTENSIBLE
-    (tag 0xFFFE: the real format is the first two bytes of the SubFormat GUID) — everything `torchaudio.load`
-    reads from a .wav; the standard `wave` module refuses 24-bit extensible and float files."""
+    RIFF/WAVE is parsed directly: PCM 8 / 16 / 24 / 32 bit, IEEE float 32 / 64, G.711 A-law / mu-law (tags 6 / 7, one byte
+    per sample, expanded by alaw_table / ulaw_table) and WAVE_FORMAT_EXTENSIBLE (tag 0xFFFE: the real format is the first
+    two bytes of the SubFormat GUID) — everything `torchaudio.load` reads from a .wav; the standard `wave` module refuses
+    24-bit extensible, float and G.711 files."""
     if isinstance(src, (bytes, bytearray)):
         data = src
     elif hasattr(src, "read"):
@@ -89,6 +223,8 @@ def load_wav(src: Union[str, bytes, BinaryIO, io.BytesIO]) -> Tuple[np.ndarray, 
             x = np.frombuffer(body, dtype="<f8").astype(np.float32)
         else:
             raise ValueError(f"unsupported float width {width}")
+    elif tag in (6, 7) and width == 1:                       # G.711 A-law / mu-law
+        x = _G711_F32["alaw" if tag == 6 else "ulaw"][np.frombuffer(body, dtype=np.uint8)]
     else:
         raise ValueError(f"unsupported WAVE format tag {tag} ({bits} bit)")
     if nch == 1:
@@ -96,15 +232,20 @@ def load_wav(src: Union[str, bytes, BinaryIO, io.BytesIO]) -> Tuple[np.ndarray, 
     return x.reshape(-1, nch).T.copy(), sr
 
 
-class WavSource:
-    """Lazy reader of ONE channel of a RIFF/WAVE file: parses the header, then decodes only the byte range a caller
+_WAV_CODECS = {(1, 1): "u8", (1, 2): "s16", (1, 3): "s24", (1, 4): "s32", (3, 4): "f32", (3, 8): "f64", (6, 1): "alaw",
+               (7, 1): "ulaw"}
+
+
+class WavSource(_FrameSource):
+    """Lazy reader of ONE channel (an index, or "downmix": audio.downmix of the frame) of a RIFF/WAVE file: parses the header, then decodes only the byte range a caller
     asks for — with N ranks sharding one recording (pipeline.device_stage) every rank reads 1/N of the file (+ one
     window of halo) instead of decoding all of it.  Same formats and the same float conversion as
     load_wav(); a source at another rate is decoded whole and resampled on the host unless the caller asks for the device
     resampler (ResampledSource, which reads only the input span of a range)."""
 
-    def __init__(self, path, channel: int = 0):
+    def __init__(self, path, channel=0):
         self.path = str(path)
+        channel = check_channel(channel)
         with open(self.path, "rb") as f:
             head = f.read(12)
             if head[:4] not in (b"RIFF", b"RF64") or head[8:12] != b"WAVE":
@@ -138,11 +279,12 @@ class WavSource:
             if len(fmt) < 40 or fmt[26:40] != _PCM_GUID_TAIL:
                 raise ValueError("unsupported WAVE_FORMAT_EXTENSIBLE sub-format")
             tag = int.from_bytes(fmt[24:26], "little")
-        if self.channels < 1 or self.sample_rate < 1 or channel >= self.channels:
+        if self.channels < 1 or self.sample_rate < 1:
             raise ValueError("malformed WAVE fmt chunk")
         self._width = block // self.channels if block else (bits + 7) // 8
-        self._tag, self._channel = tag, channel
-        if (tag, self._width) not in ((1, 1), (1, 2), (1, 3), (1, 4), (3, 4), (3, 8)):
+        self._tag, self._channel = tag, _check_channel_of(channel, self.channels)
+        self._codec = _WAV_CODECS.get((tag, self._width))
+        if self._codec is None:
             raise ValueError(f"unsupported WAVE format tag {tag} ({bits} bit)")
         self._frame = self._width * self.channels
         self.num_samples = self._data_len // self._frame
@@ -158,27 +300,98 @@ class WavSource:
             f.seek(self._data_off + start * self._frame)
             return np.fromfile(f, dtype="<i2", count=n * self.channels).reshape(-1, self.channels)
 
-    def read(self, start: int, n: int) -> np.ndarray:
-        """float32 [m] = samples start .. start + n of the channel (m < n at the end of the file)"""
-        start = max(0, min(int(start), self.num_samples))
-        n = max(0, min(int(n), self.num_samples - start))
+
+def _sphere_header(head: bytes, avail=None):
+    """-> (data offset, codec, channels, sample_rate, sample_count or None) of a NIST SPHERE header: `NIST_1A`, the header
+    size on the second line, then `name -type value` lines (-i integer, -r real, -sN a string of N characters) up to
+    `end_head`.  `head` holds at least the header (the caller reads 8 bytes more than the first 16 say when it is longer)."""
+    def bad(why):
+        return ValueError(f"malformed NIST SPHERE header: {why}")
+    lines = bytes(head[:16]).split(b"\n")
+    if len(lines) < 3 or lines[0] != b"NIST_1A" or not lines[1].strip().isdigit():
+        raise bad("no header size on the second line")
+    size = int(lines[1])
+    if size < 16 or size > len(head):
+        raise bad(f"a header of {size} bytes in {len(head)}")
+    fields, ended = {}, False
+    for line in bytes(head[16:size]).split(b"\n"):
+        line = line.strip()
+        if line == b"end_head":
+            ended = True
+            break
+        if not line or line.startswith(b";"):
+            continue
+        parts = line.decode("latin-1").split(None, 2)
+        if len(parts) < 3 or not parts[1].startswith("-"):
+            raise bad(f"field line {line[:40]!r}")
+        fields[parts[0]] = parts[2].strip()
+    if not ended:
+        raise bad("no end_head")
+    try:
+        sr, nch = int(fields["sample_rate"]), int(fields["channel_count"])
+        width = int(fields["sample_n_bytes"])
+        count = int(fields["sample_count"]) if "sample_count" in fields else None
+    except (KeyError, ValueError) as e:
+        raise bad(f"field {e}") from None
+    if sr < 1 or nch < 1 or width < 1 or (count is not None and count < 0):
+        raise bad("sample_rate / channel_count / sample_n_bytes / sample_count out of range")
+    coding = fields.get("sample_coding", "pcm").lower()
+    base, _, suffix = coding.partition(",")
+    if suffix.startswith("embedded-shorten"):
+        raise ValueError(f"unsupported NIST SPHERE sample_coding {coding!r}: shorten-compressed SPHERE files are not decoded "
+                         "(expand them first, e.g. sph2pipe -f wav)")
+    order = fields.get("sample_byte_format", "")
+    if suffix == "" and base == "pcm" and width == 2 and order in ("01", "10"):
+        codec = "s16" if order == "01" else "s16be"
+    elif suffix == "" and base in ("ulaw", "mu-law") and width == 1:
+        codec = "ulaw"
+    elif suffix == "" and base == "alaw" and width == 1:
+        codec = "alaw"
+    else:
+        raise ValueError(f"unsupported NIST SPHERE file: sample_coding {coding!r}, sample_n_bytes {width}, "
+                         f"sample_byte_format {order!r} (read: 16-bit pcm 01 / 10, ulaw, alaw)")
+    return size, codec, nch, sr, count
+
+
+def _sphere_header_bytes(first: bytes) -> int:
+    """how many bytes the header takes, from the first 16 (1024 when they do not say: _sphere_header then refuses)"""
+    lines = bytes(first[:16]).split(b"\n")
+    return int(lines[1]) if len(lines) >= 2 and lines[1].strip().isdigit() else 1024
+
+
+def load_sphere(src: Union[str, bytes, BinaryIO, io.BytesIO]) -> Tuple[np.ndarray, int]:
+    """-> (float32 [channels, samples] in [-1, 1), sample_rate) of a NIST SPHERE file (what the LDC telephone corpora ship:
+    usually mu-law, 8 kHz, one side of the call per channel).  16-bit PCM of either byte order, mu-law and A-law, channels
+    interleaved; a sample_count beyond the data present is cut to the data; shorten-compressed files are refused."""
+    data = _read_all(src)
+    off, codec, nch, sr, count = _sphere_header(bytes(data[:max(16, _sphere_header_bytes(data[:16]))]))
+    frame = _CODEC_BYTES[codec] * nch
+    frames = (len(data) - off) // frame
+    frames = frames if count is None else min(frames, count)
+    x = _decode_frames(memoryview(data)[off:off + frames * frame], codec, nch)
+    return np.ascontiguousarray(x.T), sr
+
+
+class SphereSource(_FrameSource):
+    """Lazy reader of ONE channel (an index, or "downmix") of a NIST SPHERE file, with WavSource's interface (.sample_rate,
+    .channels, .num_samples, .read, .read_stored): the header is parsed, then only the byte range asked for is read.  Same
+    formats and conversions as load_sphere()."""
+
+    def __init__(self, path, channel=0):
+        self.path = str(path)
+        channel = check_channel(channel)
         with open(self.path, "rb") as f:
-            f.seek(self._data_off + start * self._frame)
-            body = f.read(n * self._frame)
-        w, c, nch = self._width, self._channel, self.channels
-        if self._tag == 1:
-            if w == 1:
-                return (np.frombuffer(body, dtype=np.uint8).reshape(-1, nch)[:, c].astype(np.float32) - 128.0) / 128.0
-            if w == 2:
-                return np.frombuffer(body, dtype="<i2").reshape(-1, nch)[:, c].astype(np.float32) / 32768.0
-            if w == 3:
-                b3 = np.frombuffer(body, dtype=np.uint8).reshape(-1, nch, 3)[:, c].astype(np.int32)
-                v = b3[:, 0] | (b3[:, 1] << 8) | (b3[:, 2] << 16)
-                v = np.where(v & 0x800000, v - 0x1000000, v)
-                return v.astype(np.float32) / 8388608.0
-            return np.frombuffer(body, dtype="<i4").reshape(-1, nch)[:, c].astype(np.float32) / 2147483648.0
-        dt = "<f4" if w == 4 else "<f8"
-        return np.ascontiguousarray(np.frombuffer(body, dtype=dt).reshape(-1, nch)[:, c].astype(np.float32))
+            first = f.read(16)
+            if not first.startswith(b"NIST_1A"):
+                raise ValueError("not a NIST SPHERE file")
+            head = first + f.read(max(0, _sphere_header_bytes(first) - 16))
+            f.seek(0, 2)
+            size = f.tell()
+        self._data_off, self._codec, self.channels, self.sample_rate, count = _sphere_header(head)
+        self._channel = _check_channel_of(channel, self.channels)
+        self._frame = _CODEC_BYTES[self._codec] * self.channels
+        frames = max(0, size - self._data_off) // self._frame
+        self.num_samples = frames if count is None else min(frames, count)
 
 
 def resample_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
@@ -263,58 +476,82 @@ def resample_tile() -> int:
 
 
 def resample_device(x, orig_freq: int, new_freq: int, *, device, out_range=None, total=None, first_index: int = 0,
-                    channels: int = 1, channel: int = 0):
+                    channels: int = 1, channel=0, src_format=None):
     """`resample` on the device (csrc/resample.hip, one launch on the current stream) -> float32 device tensor [m1 - m0].
-    x: a host array or a device tensor, float32 mono, or int16 frames interleaved over `channels` (flat or
-    [frames, channels]; sample * 2^-15 of `channel` is what load_wav makes of it).  x holds the input samples
-    first_index .. first_index + frames of a recording of `total` samples (default: x is the whole recording);
+    x: a host array or a device tensor holding the frames as a file stores them, interleaved over `channels` (flat or
+    [frames, ...]); the kernel decodes them and reads `channel` — an index, or "downmix" (audio.downmix of every frame).
+    src_format names the stored form (SRC_FORMATS): "f32" (mono, or interleaved when channels > 1: "f32i"), "s16" (sample * 2^-15: what load_wav
+    makes of it), "u8" (offset binary), "s24" (uint8 input, 3 bytes per sample, little-endian), "s32", "ulaw", "alaw"
+    (uint8 input, G.711) — or the integer code of include/dzn.h.  It is inferred for float32 mono and int16 input and
+    required for uint8 input, which is ambiguous.  x holds the frames first_index .. first_index + frames of a recording of `total` samples (default: x is the whole recording);
     out_range = (m0, m1) selects the output samples (default: all ceil(n total / o)); x must cover
     resample_input_span(m0, m1, ...) inside [0, total) (the library refuses otherwise).  A range call returns the bits of the
-    same slice of a whole-recording call.  The result differs from the host `resample` in the last bits (another order of
-    the same float32 sums)."""
+    same slice of a whole-recording call, and a stored-format call the bits of the float32 call on the host-decoded channel
+    (or host downmix).  The result differs from the host `resample` in the last bits (another order of the same float32
+    sums)."""
     import ctypes as C
     import torch
     from . import _lib
     device = torch.device(device)
+    channels = int(channels)
     if isinstance(x, torch.Tensor):
         xd = x.to(device)
     else:
         x = np.ascontiguousarray(x)
         xd = torch.from_numpy(x if x.flags.writeable else x.copy()).to(device)      # (torch refuses read-only arrays)
-    if xd.dtype == torch.int16:
-        fmt = 1
-    elif xd.dtype == torch.float32:
-        fmt = 0
-        if channels != 1:
-            raise ValueError("resample_device: float32 input is mono (select the channel on the host)")
+    dtype = str(xd.dtype).replace("torch.", "")
+    if src_format is None:
+        if dtype == "int16":
+            fmt = 1
+        elif dtype == "float32":
+            fmt = 0
+            if channels != 1:
+                raise ValueError('resample_device: float32 input is mono (interleaved float32 frames: src_format="f32")')
+        elif dtype == "uint8":
+            raise ValueError('resample_device: uint8 input needs src_format ("u8", "s24", "ulaw" or "alaw")')
+        else:
+            raise ValueError(f"resample_device: float32 or int16 input, or a src_format, not {xd.dtype}")
+    elif isinstance(src_format, str):
+        if src_format not in SRC_FORMATS:
+            raise ValueError(f"resample_device: src_format is one of {sorted(SRC_FORMATS)}, not {src_format!r}")
+        fmt = SRC_FORMATS[src_format]
+        if fmt == 0 and channels != 1:
+            fmt = 5
     else:
-        raise ValueError(f"resample_device: float32 or int16 input, not {xd.dtype}")
+        fmt = int(src_format)                              # a code of dzn.h; the library refuses what it does not know
+    if fmt in _SRC_DTYPES and dtype != _SRC_DTYPES[fmt]:
+        raise ValueError(f"resample_device: src_format {src_format!r} is stored as {_SRC_DTYPES[fmt]}, not {xd.dtype}")
+    # "downmix" is the library's channel -1; an integer goes to the library as it is, which refuses one out of range
+    channel = -1 if isinstance(channel, (str, bool)) and check_channel(channel) == "downmix" else int(channel)
     xd = xd.contiguous().reshape(-1)
-    if xd.numel() % max(1, int(channels)):
+    per_frame = max(1, channels) * (_SRC_BYTES.get(fmt, xd.element_size()) // xd.element_size())
+    if xd.numel() % per_frame:
         raise ValueError("resample_device: the input is not a whole number of frames")
-    frames = xd.numel() // max(1, int(channels))
+    frames = xd.numel() // per_frame
     total = frames + int(first_index) if total is None else int(total)
     bank, o, n, width = _device_bank(orig_freq, new_freq, device)
     m0, m1 = (0, resampled_length(total, o, n)) if out_range is None else (int(out_range[0]), int(out_range[1]))
     out = torch.empty(max(0, m1 - m0), device=device, dtype=torch.float32)
     st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     dev = device.index if device.index is not None else -1
-    _lib.check(_lib.load().dzn_resample(dev, C.c_void_p(xd.data_ptr()), fmt, int(channels), int(channel), int(first_index),
+    _lib.check(_lib.load().dzn_resample(dev, C.c_void_p(xd.data_ptr()), fmt, channels, channel, int(first_index),
                                         frames, total, C.c_void_p(bank.data_ptr()), o, n, width, m0, m1,
                                         C.c_void_p(out.data_ptr()), st), None, "dzn_resample")
     return out
 
 
 class ResampledSource:
-    """A recording at another rate, resampled on the device range by range: wraps a WavSource (PCM16 files are uploaded as
-    their raw interleaved frames, the kernel selects the channel and converts) or a decoded one-channel float32 array
-    (`orig_rate` says its rate).  `.sample_rate` is the new rate, `.num_samples` = ceil(n T / o) as `resample` gives, and
+    """A recording at another rate, resampled on the device range by range: wraps a WavSource or SphereSource (the frames are
+    uploaded as the file stores them — `read_stored`: PCM of 8 / 16 / 24 / 32 bit, float32, mu-law, A-law — and the kernel
+    decodes them and applies the source's channel choice; float64 and big-endian files are decoded by `.read` on the host) or
+    a decoded one-channel float32 array (`orig_rate` says its rate).  `.sample_rate` is the new rate, `.num_samples` =
+    ceil(n T / o) as `resample` gives, and
     `.read_device(start, n)` reads only resample_input_span of the range, uploads it and resamples it: the bits of the same
     slice of read_device(0, num_samples), so every rank of a sharded run touches only the span of its windows."""
 
     def __init__(self, src, new_rate: int, device, orig_rate: Optional[int] = None):
         self.src, self.device = src, "cuda" if device is None else device      # None: the current HIP device
-        self._array = not isinstance(src, WavSource)
+        self._array = not hasattr(src, "read_stored")
         if self._array:
             if orig_rate is None:
                 raise ValueError("ResampledSource: a decoded array needs orig_rate")
@@ -338,10 +575,10 @@ class ResampledSource:
         kw = dict(device=self.device, out_range=(m0, m1), total=self._total, first_index=lo)
         if self._array:
             return resample_device(self.src[lo:hi], self.orig_rate, self.sample_rate, **kw)
-        raw = self.src.read_raw(lo, hi - lo)
-        if raw is not None:
-            return resample_device(raw, self.orig_rate, self.sample_rate, channels=self.src.channels,
-                                   channel=self.src._channel, **kw)
+        stored = self.src.read_stored(lo, hi - lo)
+        if stored is not None:
+            return resample_device(stored[0], self.orig_rate, self.sample_rate, channels=self.src.channels,
+                                   channel=self.src._channel, src_format=stored[1], **kw)
         return resample_device(self.src.read(lo, hi - lo), self.orig_rate, self.sample_rate, **kw)
 
 
@@ -405,12 +642,12 @@ def load_flac(src: Union[str, bytes, BinaryIO, io.BytesIO], verify_md5: bool = T
 
 
 _FORMATS = ((b"fLaC", "FLAC"), (b"OggS", "Ogg (Vorbis / Opus / FLAC-in-Ogg)"), (b"ID3", "MP3 (ID3 tag)"), (b"\xff\xfb", "MP3"),
-            (b"\xff\xf3", "MP3"), (b"\xff\xf2", "MP3"), (b"FORM", "AIFF"), (b".snd", "Sun AU"), (b"\x1aE\xdf\xa3", "Matroska / WebM"),
-            (b"NIST_1A", "NIST SPHERE"))
+            (b"\xff\xf3", "MP3"), (b"\xff\xf2", "MP3"), (b"FORM", "AIFF"), (b".snd", "Sun AU"), (b"\x1aE\xdf\xa3", "Matroska / WebM"))
 
 
 def load_audio(src) -> Tuple[np.ndarray, int]:
-    """`torchaudio.load` for what this image can decode natively: RIFF/WAVE (load_wav) and FLAC (load_flac).  Anything else is
+    """`torchaudio.load` for what this image can decode natively: RIFF/WAVE (load_wav), FLAC (load_flac) and NIST SPHERE
+    (load_sphere).  Anything else is
     refused BY NAME (the reference accepts whatever torchaudio's backend reads, diarizen/pipelines/inference.py:127; here an
     unsupported container must not surface as "not a RIFF/WAVE file")."""
     data = _read_all(src)
@@ -419,18 +656,21 @@ def load_audio(src) -> Tuple[np.ndarray, int]:
         return load_wav(data)
     if head[:4] == b"fLaC":
         return load_flac(data)
+    if head.startswith(b"NIST_1A"):
+        return load_sphere(data)
     if len(head) >= 8 and head[4:8] == b"ftyp":
-        raise ValueError("unsupported audio container: MP4 / M4A (AAC) — decodable formats: WAV, FLAC")
+        raise ValueError("unsupported audio container: MP4 / M4A (AAC) — decodable formats: WAV, FLAC, SPHERE")
     for magic, name in _FORMATS:
         if head.startswith(magic):
-            raise ValueError(f"unsupported audio format: {name} — decodable formats: WAV (PCM / float), FLAC")
-    raise ValueError("unrecognised audio file (decodable formats: WAV (PCM / float), FLAC)")
+            raise ValueError(f"unsupported audio format: {name} — decodable formats: WAV (PCM / float / G.711), FLAC, SPHERE")
+    raise ValueError("unrecognised audio file (decodable formats: WAV (PCM / float / G.711), FLAC, SPHERE)")
 
 
-def first_channel_16k(src, expected_sr: int = 16000) -> np.ndarray:
-    """-> float32 [N] at `expected_sr`: channel 0 of the file (inference.py:128), resampled if needed."""
+def first_channel_16k(src, expected_sr: int = 16000, channel=0) -> np.ndarray:
+    """-> float32 [N] at `expected_sr`: channel 0 of the file (inference.py:128) — or channel `channel`, or the `downmix` of
+    its channels (PA/core/io.py:205-212) — resampled if needed."""
     x, sr = load_audio(src)
-    x0 = np.ascontiguousarray(x[0])
+    x0 = select_channel(x, channel)
     if sr != expected_sr:
         x0 = resample(x0, sr, expected_sr)
     return x0

@@ -214,7 +214,7 @@ int launch_prepare_masks(const uint8_t* ml, int B, int L, int S, int median, int
 
 // resample.hip: y[m0 .. m1) of the polyphase resampler (dzn_resample validates; bank is tap-major [K][n])
 size_t resample_lds_bytes(int o, int n, int width);   // 0: the input of one tile does not fit in LDS
-int launch_resample(const void* src, int i16, int channels, int channel, int64_t src_first, int64_t src_len, int64_t T,
+int launch_resample(const void* src, int format, int channels, int channel, int64_t src_first, int64_t src_len, int64_t T,
                     const float* bank, int o, int n, int width, int64_t m0, int64_t m1, float* dst, hipStream_t st);
 
 // prof.cpp

@@ -1906,11 +1906,16 @@ int dzn_resample(int32_t device, const void* d_src, int32_t src_format, int32_t 
   };
   if (o < 1 || n < 1 || width < 0 || total_len < 0 || src_len < 0 || m0 < 0 || m1 < m0 || !d_bank)
     return refuse("bad o / n / width / lengths / range");
-  if ((src_format != 0 && src_format != 1) || channels < 1 || (src_format == 0 && channels != 1))
-    return refuse("src_format is 0 (float32 mono) or 1 (int16 interleaved over channels >= 1)");
-  if (channel < 0 || channel >= channels)
+  if (src_format < 0 || src_format >= DZN_SRC_FORMATS || channels < 1)
+    return refuse("src_format " + std::to_string(src_format) + " with " + std::to_string(channels) +
+                  " channel(s): the formats are 0 (float32 mono) .. 7 (DZN_SRC_* of dzn.h), interleaved over channels >= 1");
+  if (src_format == DZN_SRC_F32 && channels != 1)
+    return refuse("src_format 0 is float32 mono, not " + std::to_string(channels) +
+                  " channels (5 is float32 interleaved over channels)");
+  if (channel < DZN_CHANNEL_DOWNMIX || channel >= channels)
     return refuse("channel " + std::to_string(channel) + " of a source with " + std::to_string(channels) + " channel(s)");
   if (total_len > INT64_MAX / n) return refuse("total_len * n overflows");
+  if (src_len > INT64_MAX / 4 / channels) return refuse("src_len * channels * bytes per sample overflows");
   const int64_t out_len = (total_len * n + o - 1) / o;
   if (m1 > out_len)
     return refuse("m1 = " + std::to_string(m1) + " is beyond the output length " + std::to_string(out_len));

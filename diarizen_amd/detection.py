@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import dist as dz_dist
+from .audio import check_channel
 from .core import SlidingWindow, SlidingWindowFeature
 from .engine import Engine
 from .inference import WindowRunner, window_plan
@@ -53,12 +54,15 @@ class _Detection:
     LABEL = ""
 
     def __init__(self, segmentation, *, rttm_out_dir: Optional[str] = None, device: Optional[torch.device] = None,
-                 precision: str = "f32h", batch_size: Optional[int] = None, resample: Optional[str] = None):
+                 precision: str = "f32h", batch_size: Optional[int] = None, resample: Optional[str] = None,
+                 channel=None):
         """segmentation: a DiariZen hub directory (config.toml + pytorch_model.bin; a segmentation-only engine is created,
         without the ResNet34 embedding model) or a `DiariZenPipeline`, whose engine handle(s) are reused (no second copy of
         the weights; its device and precision apply).  batch_size: windows per launch (default: the hub's
         [inference.args] batch_size, capped by the engine's max_batch).  resample: "host" | "device", where a recording at
-        another rate is resampled (pipeline.open_recording; default: the DiariZenPipeline's setting, else "host")."""
+        another rate is resampled (pipeline.open_recording; default: the DiariZenPipeline's setting, else "host").  channel: the
+        channel of a recording that is read, an index or "downmix" (default: the DiariZenPipeline's setting, else 0); a file
+        mapping's "channel" key overrides it."""
         from .pipeline import DiariZenPipeline, _load_checkpoint, load_hub_config
         extra = ()
         self._owned: Optional[Engine] = None
@@ -67,6 +71,9 @@ class _Detection:
         if resample not in ("host", "device"):
             raise ValueError(f'resample is "host" or "device", not {resample!r}')
         self.resample = resample
+        if channel is None:
+            channel = segmentation.channel if isinstance(segmentation, DiariZenPipeline) else 0
+        self.channel = check_channel(channel)
         if isinstance(segmentation, DiariZenPipeline):
             pipe = segmentation
             self.device = pipe.device
@@ -154,7 +161,7 @@ class _Detection:
             uri = Path(audio).stem
         want_scores = hook is not None
         hook = functools.partial(hook or _noop, file=file)            # Pipeline.setup_hook (PA/core/pipeline.py:267-271)
-        x = open_recording(audio, self.sample_rate, resample=self.resample, device=self.device)
+        x = open_recording(file, self.sample_rate, resample=self.resample, device=self.device, channel=self.channel)
         n = int(x.num_samples) if hasattr(x, "num_samples") else len(x)
         with torch.cuda.device(self.device):
             wave = recording_on_device(x, self.device)

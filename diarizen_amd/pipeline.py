@@ -141,35 +141,45 @@ def resolve_hub(repo_id: str, cache_dir: Optional[str] = None) -> Path:
                                   local_files_only=cache_dir is not None)).expanduser().absolute()
 
 
-def open_recording(in_wav, sample_rate: int, lazy: bool = False, resample: str = "host", device=None):
-    """what `DiariZenPipeline.__call__` accepts (path, BytesIO, bytes or a ProtocolFile mapping with "audio") -> first channel
-    at `sample_rate`, float32.  lazy=True (sharded runs): a WAV file at that rate is opened as an audio.WavSource, so that
-    every rank decodes only the byte range of its windows (other files need the resampler's context and are decoded whole).
+def open_recording(in_wav, sample_rate: int, lazy: bool = False, resample: str = "host", device=None, channel=0):
+    """what `DiariZenPipeline.__call__` accepts (path, BytesIO, bytes or a ProtocolFile mapping with "audio") -> ONE channel
+    at `sample_rate`, float32.  channel: an index (default 0, the first channel) or "downmix" (audio.downmix: the mean of the
+    channels); a mapping's own "channel" key (PA/core/io.py:300-303) overrides it, and an index the file does not have is a
+    ValueError.  lazy=True (sharded runs): a WAV or SPHERE file at that rate is opened as an audio.WavSource /
+    audio.SphereSource, so that every rank decodes only the byte range of its windows (other files need the resampler's
+    context and are decoded whole).
     resample="device": a file at ANOTHER rate comes back as an audio.ResampledSource on `device` — nothing is resampled on the
     host, `read_device(start, n)` reads, uploads and resamples (csrc/resample.hip) only the input span of the range, so the
-    ranks of a sharded run do that for their own windows only; a WAV file is not decoded here at all.  Files at `sample_rate`
+    ranks of a sharded run do that for their own windows only; a WAV or SPHERE file is not decoded here at all (the kernel
+    decodes the stored frames, G.711 included, and applies the channel choice).  Files at `sample_rate`
     are returned as with "host", which is the default: the device resampler differs from the host one in the last bits."""
     if resample not in ("host", "device"):
         raise ValueError(f'resample is "host" or "device", not {resample!r}')
     if isinstance(in_wav, Mapping):                    # pyannote ProtocolFile (a Mapping, not a dict)
+        if in_wav.get("channel") is not None:          # (None, as in PA/core/io.py:300: no choice of the file's own)
+            channel = in_wav["channel"]
         in_wav = in_wav["audio"]
+    channel = audio_io.check_channel(channel)
     assert isinstance(in_wav, (str, os.PathLike, BytesIO, bytes)), \
         f"input must be either a str, BytesIO or a ProtocolFile; there was {type(in_wav)}"
     if (lazy or resample == "device") and isinstance(in_wav, (str, os.PathLike)):
+        with open(in_wav, "rb") as f:
+            magic = f.read(8)
+        opener = audio_io.SphereSource if magic.startswith(b"NIST_1A") else audio_io.WavSource
         try:
-            src = audio_io.WavSource(in_wav)
+            src = opener(in_wav, channel)
             if src.sample_rate == sample_rate:
                 if lazy:
                     return src
             elif resample == "device":
                 return audio_io.ResampledSource(src, sample_rate, device)
         except ValueError:
-            pass
+            pass                                       # not that container, or a form of it only the whole-file decoders read (or refuse)
     if resample == "device":
         x, sr = audio_io.load_audio(in_wav)
-        x0 = np.ascontiguousarray(x[0])                # channel 0, as first_channel_16k
+        x0 = audio_io.select_channel(x, channel)       # as first_channel_16k
         return x0 if sr == sample_rate else audio_io.ResampledSource(x0, sample_rate, device, orig_rate=sr)
-    return audio_io.first_channel_16k(in_wav, sample_rate)
+    return audio_io.first_channel_16k(in_wav, sample_rate, channel)
 
 
 def recording_on_device(waveform, device, lo: int = 0, n: Optional[int] = None, zero_extend: bool = False) -> torch.Tensor:
@@ -201,13 +211,16 @@ class DiariZenPipeline:
                  rttm_out_dir: Optional[str] = None, *, device: Optional[torch.device] = None,
                  precision: str = "f32h", seg_state: Optional[Mapping[str, torch.Tensor]] = None,
                  emb_state: Optional[Mapping[str, torch.Tensor]] = None,
-                 config: Optional[Dict[str, Any]] = None, num_streams: int = 2, resample: str = "host"):
+                 config: Optional[Dict[str, Any]] = None, num_streams: int = 2, resample: str = "host",
+                 channel=0):
         """diarizen_hub: directory with config.toml / pytorch_model.bin / plda ; embedding_model: path of
         the WeSpeaker checkpoint.  `seg_state` / `emb_state` / `config` let callers (tests, bench)
         inject in-memory weights instead of files.
         resample: where a recording at another rate than the model's is resampled — "host" (audio.resample, the default) or
         "device" (audio.ResampledSource: the file's samples are uploaded as stored and resampled by csrc/resample.hip, in a
         sharded run every rank only its windows' span; the waveform differs from the host one in its last bits).
+        channel: which channel of a recording is diarized — an index (default 0, inference.py:128) or "downmix", the mean of
+        the channels (audio.downmix; both sides of a two-channel telephone call); a file mapping's "channel" key overrides it.
         num_streams (r4): engine handles that consecutive batches of windows alternate over, each on its own HIP stream
         (inference.WindowRunner): independent batches overlap on the device — +2.6 % on the 30-min workload,
         +44 % at 32-window batches (profiles/r4_*), same bits.  Each extra handle costs one more copy of the weights and a
@@ -224,6 +237,7 @@ class DiariZenPipeline:
         if resample not in ("host", "device"):
             raise ValueError(f'resample is "host" or "device", not {resample!r}')
         self.resample = resample
+        self.channel = audio_io.check_channel(channel)
         inf, clu = config["inference"]["args"], config["clustering"]["args"]
         if not torch.cuda.is_available():
             raise RuntimeError("DiariZenPipeline (diarizen_amd) needs a HIP device; no CPU fallback")
@@ -380,7 +394,8 @@ class DiariZenPipeline:
         file = file if isinstance(file, Mapping) else {"audio": file}
         if hook is not None:
             hook = functools.partial(hook, "segmentation", None, file=file)
-        x = open_recording(file["audio"], self.segmentation_model.sample_rate, resample=self.resample, device=self.device)
+        x = open_recording(file, self.segmentation_model.sample_rate, resample=self.resample, device=self.device,
+                           channel=self.channel)
         # the raw decisions: a runner without the median filter on this pipeline's engine handle(s), as detection._Detection
         raw = WindowRunner(self.engine, self.seg_duration, self.segmentation_step, self.batch_size, median_size=0,
                            exclude_overlap=False, sample_rate=self.segmentation_model.sample_rate,
@@ -492,7 +507,7 @@ class DiariZenPipeline:
         """decode (or, in a sharded run, lazily open) one recording: the first lines of `__call__`"""
         from . import dist as dz_dist
         return open_recording(in_wav, self.segmentation_model.sample_rate, lazy=dz_dist.world_size() > 1,
-                              resample=self.resample, device=self.device)
+                              resample=self.resample, device=self.device, channel=self.channel)
 
     # ------------------------------------------------------------------ __call__
     def __call__(self, in_wav, sess_name: Optional[str] = None, hook=None, return_scores: bool = False):
@@ -513,13 +528,11 @@ class DiariZenPipeline:
         file = in_wav if isinstance(in_wav, Mapping) else {"audio": in_wav}
         if hook is not None:
             hook = functools.partial(hook, file=file)       # Pipeline.setup_hook (PA/core/pipeline.py:267-271)
-        if isinstance(in_wav, Mapping):                    # pyannote ProtocolFile (a Mapping, not a dict)
-            in_wav = in_wav["audio"]
         t0 = time.perf_counter()
         from . import dist as dz_dist
         if return_scores and dz_dist.world_size() > 1:
             raise RuntimeError(self._ONE_DEVICE % ("return_scores=True", dz_dist.world_size()))
-        waveform = self._open(in_wav)
+        waveform = self._open(in_wav)                      # (a mapping's "channel" key is read there)
         num_samples = int(waveform.num_samples) if hasattr(waveform, "num_samples") else len(waveform)
         t1 = time.perf_counter()
         soft = None

@@ -381,13 +381,37 @@ int dzn_flac_decode(const uint8_t* data, size_t n, int32_t* out, int64_t capacit
  * in float32: one accumulator, acc = fmaf(bank[p][j], x[..], acc) for j = 0 .. K-1.  That order depends on m alone, so a call
  * for a range of a recording returns the bits of the same slice of a call for all of it.  One launch, enqueue-only, on
  * `hip_stream` of `device` (< 0 = current) writes d_dst f32 [m1 - m0] = y[m0 .. m1).
- *   d_src            device samples src_first_index .. src_first_index + src_len of the recording:
- *                    src_format 0: float32 mono (channels = 1); 1: int16 frames interleaved over `channels`, of which
- *                    `channel` is read as sample * 2^-15 (exact: what audio.load_wav makes of a PCM16 file)
+ *   d_src            device frames src_first_index .. src_first_index + src_len of the recording, as the file stores them
+ *                    (src_len counts frames: src_len * channels samples); the staging loop decodes what it reads, every
+ *                    conversion is exact in float32 except the int32 one, which rounds to nearest even as numpy's astype:
+ *                      DZN_SRC_F32   0  float32 mono (channels = 1)            as is
+ *                      DZN_SRC_S16   1  int16, interleaved over `channels`     v * 2^-15 (audio.load_wav of a PCM16 file)
+ *                      DZN_SRC_U8    2  uint8 offset-binary, interleaved       (v - 128) * 2^-7
+ *                      DZN_SRC_S24   3  24-bit packed little-endian            sign-extended v * 2^-23
+ *                      DZN_SRC_S32   4  int32, interleaved                     (float)v * 2^-31
+ *                      DZN_SRC_F32I  5  float32, interleaved over `channels`   as is
+ *                      DZN_SRC_ULAW  6  G.711 mu-law byte, interleaved         audio.ulaw_table()[v] * 2^-15
+ *                      DZN_SRC_ALAW  7  G.711 A-law byte, interleaved          audio.alaw_table()[v] * 2^-15
+ *   channel          0 .. channels - 1: that channel of every frame; DZN_CHANNEL_DOWNMIX (-1): audio.downmix of the frame,
+ *                    i.e. a float32 running sum over the decoded channels 0, 1, .. then ONE IEEE float32 division by
+ *                    (float)channels (the channel itself when channels = 1)
  *   d_bank           device f32 [K][n], TAP-major: d_bank[j * n + p] = bank[p][j] (audio.resample_bank, transposed)
- * Returns DZN_E_INVALID with a dzn_last_error(NULL) message, and launches nothing, when the span given does not cover what
- * [m0, m1) reads inside [0, T), when channel >= channels, when m1 > ceil(n T / o), or when o / n is so large that the input
- * of one tile does not fit in 64 KiB of LDS.  dzn_resample_tile: output samples per workgroup (tests place ranges on it). */
+ * The taps walk the decoded samples in the same order for every format, so a stored-format call returns the bits of the
+ * float32 call on the host-decoded channel.
+ * Returns DZN_E_INVALID with a dzn_last_error(NULL) message, and launches nothing, when src_format is none of the above or is
+ * DZN_SRC_F32 with channels != 1, when channel < -1 or channel >= channels, when the span given does not cover what [m0, m1)
+ * reads inside [0, T), when m1 > ceil(n T / o), or when o / n is so large that the input of one tile does not fit in 64 KiB
+ * of LDS.  dzn_resample_tile: output samples per workgroup (tests place ranges on it). */
+#define DZN_SRC_F32 0
+#define DZN_SRC_S16 1
+#define DZN_SRC_U8 2
+#define DZN_SRC_S24 3
+#define DZN_SRC_S32 4
+#define DZN_SRC_F32I 5
+#define DZN_SRC_ULAW 6
+#define DZN_SRC_ALAW 7
+#define DZN_SRC_FORMATS 8          /* codes 0 .. 7 */
+#define DZN_CHANNEL_DOWNMIX (-1)
 int dzn_resample(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int32_t channel,
                  int64_t src_first_index, int64_t src_len, int64_t total_len, const float* d_bank, int32_t o, int32_t n,
                  int32_t width, int64_t m0, int64_t m1, float* d_dst, void* hip_stream);

@@ -8,7 +8,7 @@ python -m pytest tests/test_ops_gpu.py tests/test_seg_gpu.py tests/test_emb_gpu.
 # the per-speaker score kernels (post.hip, ids 0x81x): a session of its own, its status line joins the first one's below
 python -m pytest tests/test_scores_gpu.py -m gpu -q -x 2>&1 | tail -3
 # the device resampler (resample.hip, ids 0x82x): likewise
-python -m pytest tests/test_resample_gpu.py -m gpu -q -x 2>&1 | tail -3
+python -m pytest tests/test_resample_gpu.py tests/test_telephony_gpu.py -m gpu -q -x 2>&1 | tail -3
 # detection: whole-recording and range form, and the stream on top of it (post.hip, ids 0x80x): likewise
 python -m pytest tests/test_detection_gpu.py tests/test_detection_stream_op_gpu.py tests/test_detection_stream_gpu.py tests/test_diarize_range_gpu.py -m gpu -q -x 2>&1 | tail -3
 # the contraction tile matrix (gemm*.hip, ids 0x10x / 0x20x / 0x30x: scale-unit indices against amax_count, ring stages): likewise
