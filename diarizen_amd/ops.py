@@ -128,17 +128,32 @@ def gemm(A, W, *, M=None, N=None, K=None, bias=None, R=None, C_out=None, WS=None
     return (C_out, stats) if want_row_stats else C_out
 
 
-def attention_planes(qkv, B, L, h, gate=None, table=None, head_idx=None, Htot=0, scale=0.125):
+def _window_amax(qkv, B, L, ncols):
+    """per-window |max| of the logical [B * L, ncols] part of qkv (which may be a strided view)"""
+    return qkv[:B * L, :ncols].reshape(B, -1).abs().amax(dim=1).float().contiguous()
+
+
+def attention_planes(qkv, B, L, h, gate=None, table=None, head_idx=None, Htot=0, scale=0.125, *, out=None, ldqkv=None, ldo=None,
+                     amax=None, planes=None, kvs=None):
     """(r6) csrc/attention_planes.hip through its test entry point: the K / V slots of `qkv` are packed into fp16 two-term planes
-    with per-(row, head) power-of-two scales (as the q/k/v contraction's epilogue does) and the planes kernel runs on them."""
+    with per-(row, head) power-of-two scales (as the q/k/v contraction's epilogue does) and the planes kernel runs on them.
+    out / amax / planes / kvs: caller-owned buffers (out f32 with row stride ldo >= h * 64, amax f32 [B], planes int16 viewed as
+    [2, B * L + 64, 2 * h * 64] and kvs f32 [B * L + 64, 2 * h], both zero-filled by the caller); ldqkv / ldo: the row strides, by
+    default those of the tensors."""
     lib = _lib.load()
     assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.shape == (B * L, 3 * h * 64)
-    out = torch.empty((B * L, h * 64), device=qkv.device, dtype=torch.float32)
-    am = qkv.reshape(B, -1).abs().amax(dim=1).float().contiguous()
-    planes = torch.zeros((2, B * L + 64, 2 * h * 64), device=qkv.device, dtype=torch.int16)
-    kvs = torch.zeros((B * L + 64, 2 * h), device=qkv.device, dtype=torch.float32)
-    check(lib.dzn_op_attention_planes(_p(qkv), _p(out), _p(gate), _p(table), _p(head_idx), B, L, h, Htot, qkv.stride(0),
-                                      out.stride(0), scale, _p(am), _p(planes), _p(kvs), _stream()), what="dzn_op_attention_planes")
+    ldqkv = qkv.stride(0) if ldqkv is None else int(ldqkv)
+    if out is None:
+        assert ldo is None
+        out = torch.empty((B * L, h * 64), device=qkv.device, dtype=torch.float32)
+    ldo = out.stride(0) if ldo is None else int(ldo)
+    am = _window_amax(qkv, B, L, 3 * h * 64) if amax is None else amax
+    if planes is None:
+        planes = torch.zeros((2, B * L + 64, 2 * h * 64), device=qkv.device, dtype=torch.int16)
+    if kvs is None:
+        kvs = torch.zeros((B * L + 64, 2 * h), device=qkv.device, dtype=torch.float32)
+    check(lib.dzn_op_attention_planes(_p(qkv), _p(out), _p(gate), _p(table), _p(head_idx), B, L, h, Htot, ldqkv,
+                                      ldo, scale, _p(am), _p(planes), _p(kvs), _stream()), what="dzn_op_attention_planes")
     return out
 
 
@@ -352,37 +367,47 @@ def row_stats(x, C_true=None, eps=1e-5):
     return out
 
 
-def gate_stats(x, gamma, beta, Wg, bg, cst, eps=1e-5):
-    """one pass over raw rows x [rows, Htot*64]: (gate [rows, Htot] on LayerNorm(x), stats [rows, 2])"""
+def gate_stats(x, gamma, beta, Wg, bg, cst, eps=1e-5, out=None):
+    """one pass over raw rows x [rows, Htot*64]: (gate [rows, Htot] on LayerNorm(x), stats [rows, 2]); out = caller-owned
+    (gate, stats), both contiguous"""
     lib = _lib.load()
     rows, Htot = x.shape[0], cst.numel()
-    gate_ = torch.empty((rows, Htot), device=x.device, dtype=torch.float32)
-    stats = torch.empty((rows, 2), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = (torch.empty((rows, Htot), device=x.device, dtype=torch.float32),
+               torch.empty((rows, 2), device=x.device, dtype=torch.float32))
+    gate_, stats = out
     check(lib.dzn_op_gate_stats(_p(x), x.stride(0), _p(gamma), _p(beta), _p(Wg), _p(bg), _p(cst), _p(gate_), _p(stats),
                                 rows, Htot, eps, _stream()), what="dzn_op_gate_stats")
     return gate_, stats
 
 
-def gate(y, Wg, bg, cst):
+def gate(y, Wg, bg, cst, out=None):
     lib = _lib.load()
     rows = y.shape[0]
     Htot = cst.numel()
-    out = torch.empty((rows, Htot), device=y.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((rows, Htot), device=y.device, dtype=torch.float32)
     check(lib.dzn_op_gate(_p(y), y.stride(0), _p(Wg), _p(bg), _p(cst), _p(out), rows, Htot,
                           _stream()), what="dzn_op_gate")
     return out
 
 
 def attention(qkv, B, L, h, *, gate=None, table=None, head_idx=None, Htot=0, scale=0.125,
-              precision=0):
+              precision=0, out=None, ldqkv=None, ldo=None, amax=None):
+    """out / amax: caller-owned buffers (out f32 with row stride ldo >= h * 64; amax f32 [B], the per-window |max| the fp16
+    two-term variant scales by); ldqkv / ldo: the row strides, by default those of the tensors (qkv may be a strided view)"""
     lib = _lib.load()
-    out = torch.empty((B * L, h * 64), device=qkv.device, dtype=torch.float32)
+    ldqkv = qkv.stride(0) if ldqkv is None else int(ldqkv)
+    if out is None:
+        assert ldo is None
+        out = torch.empty((B * L, h * 64), device=qkv.device, dtype=torch.float32)
+    ldo = out.stride(0) if ldo is None else int(ldo)
     if precision == _lib.DZN_PREC_F32_H2:      # fp16 two-term variant: per-window |max| of qkv
-        am = qkv.reshape(B, -1).abs().amax(dim=1).float().contiguous()
+        am = _window_amax(qkv, B, L, 3 * h * 64) if amax is None else amax
         check(lib.dzn_op_attention_h2(_p(qkv), _p(out), _p(gate), _p(table), _p(head_idx), B, L, h, Htot,
-                                      qkv.stride(0), out.stride(0), scale, _p(am), _stream()), what="dzn_op_attention_h2")
+                                      ldqkv, ldo, scale, _p(am), _stream()), what="dzn_op_attention_h2")
         return out
     check(lib.dzn_op_attention(_p(qkv), _p(out), _p(gate), _p(table), _p(head_idx), B, L, h,
-                               Htot, qkv.stride(0), out.stride(0), scale, precision, _stream()),
+                               Htot, ldqkv, ldo, scale, precision, _stream()),
           what="dzn_op_attention")
     return out

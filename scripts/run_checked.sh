@@ -13,5 +13,7 @@ python -m pytest tests/test_resample_gpu.py tests/test_telephony_gpu.py -m gpu -
 python -m pytest tests/test_detection_gpu.py tests/test_detection_stream_op_gpu.py tests/test_detection_stream_gpu.py tests/test_diarize_range_gpu.py -m gpu -q -x 2>&1 | tail -3
 # the contraction tile matrix (gemm*.hip, ids 0x10x / 0x20x / 0x30x: scale-unit indices against amax_count, ring stages): likewise
 python -m pytest tests/test_gemm_tiles_gpu.py -m gpu -q -x 2>&1 | tail -3
+# the attention matrix (attention_split.hip, attention_planes.hip, ids 0x60x / 0x61x: staged tiles inside their planes): likewise
+python -m pytest tests/test_attention_matrix_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
