@@ -18,6 +18,11 @@ interleaved frames of a file as stored (`read_stored` of a source: 8 / 16 / 24 /
 kernel decodes them and selects the channel or downmixes) — into a range of output samples on the GPU, with
 the bits of the same slice of a whole-recording call (`resample_input_span` says which input a range reads).
 `ResampledSource` wraps a file at another rate on top of it; `pipeline.open_recording(resample="device")` returns one.
+
+Live sources deliver the same stored forms in packets: `FeedFormat` names what a session is fed (`feed_format=`), `feed_ready`
+says which output samples are final after R frames, `FeedPlanner` turns chunks of bytes into device calls whose ranges tile
+the output (streaming.WaveIngest runs them), and `decode_device` (`dzn_decode`) is the decode without the resampler, for feeds
+already at the model's rate.
 """
 from __future__ import annotations
 
@@ -414,6 +419,14 @@ def resample_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, 
     return kernels.to(torch.float32)[:, 0].numpy(), o, n, width             # [n, 2 width + o]
 
 
+def resample_ratio(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """-> (o, n, width) of resample_bank, without building the bank (n K float64 values: 2 GB for 15999 Hz -> 16 kHz)"""
+    import math
+    g = math.gcd(int(orig_freq), int(new_freq))
+    o, n = int(orig_freq) // g, int(new_freq) // g
+    return o, n, math.ceil(lowpass_filter_width * o / (min(o, n) * rolloff))
+
+
 def resample_input_span(m0: int, m1: int, o: int, n: int, width: int):
     """-> (lo, hi): the half-open range of input indices that the output samples [m0, m1) read (see resample_bank); it may
     extend below 0 or beyond the recording, where the input counts as zero.  An empty output range reads nothing."""
@@ -421,6 +434,23 @@ def resample_input_span(m0: int, m1: int, o: int, n: int, width: int):
     if m1 <= m0:
         return 0, 0
     return (m0 // n) * o - width, ((m1 - 1) // n) * o + width + o
+
+
+def feed_ready(frames: int, o: int, n: int, width: int) -> int:
+    """the feed schedule of a live source: with `frames` = R input frames of a recording received so far (its end unknown),
+    the output samples [0, ready) are FINAL — every tap of theirs lies in [0, R), so they are the samples of the
+    whole-recording resample whatever follows — and sample `ready` reads a frame that has not arrived:
+
+        ready(R) = max(0, (R - width) // o) * n
+
+    (resample_input_span(0, ready)[1] <= R < resample_input_span(ready, ready + 1)[1]).  Output lags the feed by at most
+    width + o - 1 frames, and a later call still needs fewer than K = 2 width + o of the frames received (`feed_history`)."""
+    return max(0, (int(frames) - width) // o) * n
+
+
+def feed_history(ready: int, o: int, n: int, width: int) -> int:
+    """the first input frame that output samples >= `ready` (a value of feed_ready) still read: frames before it can go"""
+    return max(0, (int(ready) // n) * o - width)
 
 
 def resample(x: np.ndarray, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
@@ -475,6 +505,34 @@ def resample_tile() -> int:
     return int(_lib.load().dzn_resample_tile())
 
 
+def _src_format_code(torch_dtype, src_format, channels: int, what: str) -> int:
+    """the DZN_SRC_* code of `src_format` (a name of SRC_FORMATS, a code, or None: inferred for float32 mono and int16) for
+    input of `torch_dtype`; `what` names the caller in the refusals"""
+    dtype = str(torch_dtype).replace("torch.", "")
+    if src_format is None:
+        if dtype == "int16":
+            fmt = 1
+        elif dtype == "float32":
+            fmt = 0
+            if channels != 1:
+                raise ValueError(f'{what}: float32 input is mono (interleaved float32 frames: src_format="f32")')
+        elif dtype == "uint8":
+            raise ValueError(f'{what}: uint8 input needs src_format ("u8", "s24", "ulaw" or "alaw")')
+        else:
+            raise ValueError(f"{what}: float32 or int16 input, or a src_format, not {torch_dtype}")
+    elif isinstance(src_format, str):
+        if src_format not in SRC_FORMATS:
+            raise ValueError(f"{what}: src_format is one of {sorted(SRC_FORMATS)}, not {src_format!r}")
+        fmt = SRC_FORMATS[src_format]
+        if fmt == 0 and channels != 1:
+            fmt = 5
+    else:
+        fmt = int(src_format)                              # a code of dzn.h; the library refuses what it does not know
+    if fmt in _SRC_DTYPES and dtype != _SRC_DTYPES[fmt]:
+        raise ValueError(f"{what}: src_format {src_format!r} is stored as {_SRC_DTYPES[fmt]}, not {torch_dtype}")
+    return fmt
+
+
 def resample_device(x, orig_freq: int, new_freq: int, *, device, out_range=None, total=None, first_index: int = 0,
                     channels: int = 1, channel=0, src_format=None):
     """`resample` on the device (csrc/resample.hip, one launch on the current stream) -> float32 device tensor [m1 - m0].
@@ -499,28 +557,7 @@ def resample_device(x, orig_freq: int, new_freq: int, *, device, out_range=None,
     else:
         x = np.ascontiguousarray(x)
         xd = torch.from_numpy(x if x.flags.writeable else x.copy()).to(device)      # (torch refuses read-only arrays)
-    dtype = str(xd.dtype).replace("torch.", "")
-    if src_format is None:
-        if dtype == "int16":
-            fmt = 1
-        elif dtype == "float32":
-            fmt = 0
-            if channels != 1:
-                raise ValueError('resample_device: float32 input is mono (interleaved float32 frames: src_format="f32")')
-        elif dtype == "uint8":
-            raise ValueError('resample_device: uint8 input needs src_format ("u8", "s24", "ulaw" or "alaw")')
-        else:
-            raise ValueError(f"resample_device: float32 or int16 input, or a src_format, not {xd.dtype}")
-    elif isinstance(src_format, str):
-        if src_format not in SRC_FORMATS:
-            raise ValueError(f"resample_device: src_format is one of {sorted(SRC_FORMATS)}, not {src_format!r}")
-        fmt = SRC_FORMATS[src_format]
-        if fmt == 0 and channels != 1:
-            fmt = 5
-    else:
-        fmt = int(src_format)                              # a code of dzn.h; the library refuses what it does not know
-    if fmt in _SRC_DTYPES and dtype != _SRC_DTYPES[fmt]:
-        raise ValueError(f"resample_device: src_format {src_format!r} is stored as {_SRC_DTYPES[fmt]}, not {xd.dtype}")
+    fmt = _src_format_code(xd.dtype, src_format, channels, "resample_device")
     # "downmix" is the library's channel -1; an integer goes to the library as it is, which refuses one out of range
     channel = -1 if isinstance(channel, (str, bool)) and check_channel(channel) == "downmix" else int(channel)
     xd = xd.contiguous().reshape(-1)
@@ -580,6 +617,168 @@ class ResampledSource:
             return resample_device(stored[0], self.orig_rate, self.sample_rate, channels=self.src.channels,
                                    channel=self.src._channel, src_format=stored[1], **kw)
         return resample_device(self.src.read(lo, hi - lo), self.orig_rate, self.sample_rate, **kw)
+
+
+def decode_device(x, *, device, channels: int = 1, channel=0, src_format=None):
+    """the decode half of `resample_device` on its own (csrc/resample.hip, `dzn_decode`: one launch on the current stream) ->
+    float32 device tensor [frames]: channel `channel` (an index, or "downmix") of the frames in x, a host array or device
+    tensor holding them as a file stores them, at the rate they have.  src_format as resample_device takes it.  The result is
+    the bits of the host decode (`_decode_frames`, then `select_channel` or `downmix`)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    device = torch.device(device)
+    channels = int(channels)
+    if isinstance(x, torch.Tensor):
+        xd = x.to(device)
+    else:
+        x = np.ascontiguousarray(x)
+        xd = torch.from_numpy(x if x.flags.writeable else x.copy()).to(device)
+    fmt = _src_format_code(xd.dtype, src_format, channels, "decode_device")
+    channel = -1 if isinstance(channel, (str, bool)) and check_channel(channel) == "downmix" else int(channel)
+    xd = xd.contiguous().reshape(-1)
+    per_frame = max(1, channels) * (_SRC_BYTES.get(fmt, xd.element_size()) // xd.element_size())
+    if xd.numel() % per_frame:
+        raise ValueError("decode_device: the input is not a whole number of frames")
+    frames = xd.numel() // per_frame
+    out = torch.empty(frames, device=device, dtype=torch.float32)
+    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    dev = device.index if device.index is not None else -1
+    _lib.check(_lib.load().dzn_decode(dev, C.c_void_p(xd.data_ptr()), fmt, channels, channel, frames,
+                                      C.c_void_p(out.data_ptr()), st), None, "dzn_decode")
+    return out
+
+
+# ----------------------------------------------------------------------------- live feeds in a stored format
+class FeedFormat:
+    """What a live source delivers to a session (`feed_format=` of pipeline.stream / open_live / stream_live and of the
+    detection pipelines' open_stream / stream): interleaved frames of `channels` samples at `rate` Hz, little-endian, in
+    `encoding` — a key of SRC_FORMATS: "f32", "s16", "u8", "s24", "s32", "ulaw", "alaw" (G.711, one byte per sample).
+    `channel` is the channel the session hears: an index, "downmix" (audio.downmix of every frame), or None for the
+    pipeline's own `channel`.  A phone call is FeedFormat(8000, "ulaw", channels=2, channel=...), a microphone
+    FeedFormat(48000, "s16").  A bad encoding or a channel the frames do not have is refused here."""
+
+    def __init__(self, rate: int, encoding: str, channels: int = 1, channel=None):
+        if not isinstance(encoding, str) or encoding not in SRC_FORMATS:
+            raise ValueError(f"FeedFormat: encoding is one of {sorted(SRC_FORMATS)}, not {encoding!r}")
+        if isinstance(rate, bool) or int(rate) != rate or rate < 1:
+            raise ValueError(f"FeedFormat: rate is a positive integer, not {rate!r}")
+        if isinstance(channels, bool) or int(channels) != channels or channels < 1:
+            raise ValueError(f"FeedFormat: channels is a positive integer, not {channels!r}")
+        self.rate, self.encoding, self.channels = int(rate), encoding, int(channels)
+        self.channel = None if channel is None else _check_channel_of(channel, self.channels)
+        code = SRC_FORMATS[encoding]
+        self.src_format = 5 if code == 0 and self.channels != 1 else code       # float32 frames of several channels: "f32i"
+        self.dtype = np.dtype(_SRC_DTYPES[code])                                # of an array fed to the session
+        self.frame_bytes = _SRC_BYTES[code] * self.channels
+
+    def with_channel(self, channel) -> "FeedFormat":
+        """this format with its channel choice settled: its own, or `channel` where it has none"""
+        return FeedFormat(self.rate, self.encoding, self.channels, channel if self.channel is None else self.channel)
+
+    def channel_code(self) -> int:
+        """the channel as dzn_resample / dzn_decode take it (-1: downmix)"""
+        return -1 if self.channel == "downmix" else int(self.channel)
+
+    def __repr__(self):
+        return f"FeedFormat({self.rate}, {self.encoding!r}, channels={self.channels}, channel={self.channel!r})"
+
+
+def resample_tile_fits(o: int, n: int, width: int, tile: int) -> bool:
+    """whether the input of one tile of `tile` output samples fits the 64 KiB of LDS the device resampler stages it in
+    (dzn_resample refuses the ratio otherwise; even o: one pad word per 32)"""
+    span = ((tile - 1) // n + 1) * o + 2 * width + o
+    floats = span if o & 1 else span + (span >> 5) + 1
+    return 4 * floats <= 64 * 1024
+
+
+class FeedCall:
+    """one planned device call of a live feed: `data` = the stored frames first .. first + frames of the recording (the
+    history a range still reads, then new frames), `total` = frames received when the call is made (its total_len), and
+    [m0, m1) the output samples it makes — by dzn_resample, or by dzn_decode when the feed is at the model's rate (then
+    first = m0 and frames = m1 - m0)"""
+    __slots__ = ("data", "first", "frames", "total", "m0", "m1")
+
+    def __init__(self, data, first: int, frames: int, total: int, m0: int, m1: int):
+        self.data, self.first, self.frames, self.total, self.m0, self.m1 = data, first, frames, total, m0, m1
+
+
+class FeedPlanner:
+    """The host half of a stored-format feed (streaming.WaveIngest runs its calls; needs no device): turns chunks of bytes of
+    any length into FeedCalls whose ranges tile the output [0, ceil(n T / o)) exactly once and in order.
+
+    After R frames the samples below feed_ready(R) are final.  A chunk may end inside a frame (the remainder is carried and
+    dropped at the end of the stream, as the file readers do with size // frame); the frames a later range still reads —
+    fewer than K = 2 width + o, from feed_history(ready) on — are kept here as raw bytes and go in front of the next upload,
+    so nothing survives a call on the device.  A chunk of more than `slot_frames` new frames is split; an upload is at most
+    K - 1 + slot_frames frames.  `finish()` is the one call with the true length: [ready, ceil(n R / o)), zero tail on the
+    right.  A feed at the model's rate is decoded, not resampled: ready = R, no history."""
+
+    def __init__(self, fmt: FeedFormat, model_rate: int, slot_frames: int):
+        self.fmt, self.model_rate = fmt, int(model_rate)
+        self.same_rate = fmt.rate == self.model_rate
+        if self.same_rate:
+            self.o, self.n, self.width = 1, 1, 0
+        else:
+            self.o, self.n, self.width = resample_ratio(fmt.rate, self.model_rate)
+        self.K = 2 * self.width + self.o
+        self.slot_frames = int(slot_frames)
+        if self.slot_frames < 1:
+            raise ValueError("FeedPlanner: a slot holds at least one frame")
+        self.max_upload_frames = self.slot_frames + (0 if self.same_rate else self.K - 1)
+        self.frames = 0                                                 # R: whole frames received
+        self.ready = 0                                                  # output samples planned so far: [0, ready) is final
+        self.finished = False
+        self._partial = b""                                             # the bytes of a frame that has not ended
+        self._hist = b""                                                # frames _hist_first .. R as stored
+        self._hist_first = 0
+
+    def length_after(self, nbytes: int) -> int:
+        """the output length if the stream ended after `nbytes` more bytes"""
+        return resampled_length(self.frames + (len(self._partial) + nbytes) // self.fmt.frame_bytes, self.o, self.n)
+
+    def append(self, data) -> list:
+        """data: bytes-like, or an array of the format's stored dtype -> the calls that the new frames make possible"""
+        if self.finished:
+            raise RuntimeError("feed already finished")
+        fb = self.fmt.frame_bytes
+        buf = self._partial + _feed_bytes(data, self.fmt)
+        whole = len(buf) // fb
+        self._partial = buf[whole * fb:]
+        calls = []
+        for f0 in range(0, whole, self.slot_frames):
+            k = min(self.slot_frames, whole - f0)
+            self._hist += buf[f0 * fb:(f0 + k) * fb]
+            self.frames += k
+            ready = feed_ready(self.frames, self.o, self.n, self.width)
+            if ready > self.ready:
+                calls.append(self._call(ready))
+        return calls
+
+    def finish(self) -> list:
+        """end of stream: a trailing partial frame is dropped; -> the call for [ready, ceil(n R / o)), if any"""
+        if self.finished:
+            return []
+        self.finished, self._partial = True, b""
+        total = resampled_length(self.frames, self.o, self.n)
+        return [self._call(total)] if total > self.ready else []
+
+    def _call(self, ready: int) -> FeedCall:
+        call = FeedCall(self._hist, self._hist_first, self.frames - self._hist_first, self.frames, self.ready, ready)
+        self.ready = ready
+        keep = self.frames if self.same_rate else feed_history(ready, self.o, self.n, self.width)
+        self._hist = self._hist[(keep - self._hist_first) * self.fmt.frame_bytes:]
+        self._hist_first = keep
+        return call
+
+
+def _feed_bytes(data, fmt: FeedFormat) -> bytes:
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return bytes(data)
+    a = np.asarray(data)
+    if a.dtype != fmt.dtype:
+        raise ValueError(f"a {fmt.encoding} feed takes bytes or {fmt.dtype} arrays, not {a.dtype}")
+    return np.ascontiguousarray(a).tobytes()
 
 
 def _read_all(src) -> bytes:

@@ -216,6 +216,8 @@ int launch_prepare_masks(const uint8_t* ml, int B, int L, int S, int median, int
 size_t resample_lds_bytes(int o, int n, int width);   // 0: the input of one tile does not fit in LDS
 int launch_resample(const void* src, int format, int channels, int channel, int64_t src_first, int64_t src_len, int64_t T,
                     const float* bank, int o, int n, int width, int64_t m0, int64_t m1, float* dst, hipStream_t st);
+// dst[frames] = the channel choice of the stored frames, decoded, at the rate they have (dzn_decode validates)
+int launch_decode(const void* src, int format, int channels, int channel, int64_t frames, float* dst, hipStream_t st);
 
 // prof.cpp
 bool prof_enabled();

@@ -1936,6 +1936,34 @@ int dzn_resample(int32_t device, const void* d_src, int32_t src_format, int32_t 
                          m1, d_dst, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
+int dzn_decode(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int32_t channel, int64_t frames,
+               float* d_dst, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_decode: " + why;
+    return DZN_E_INVALID;
+  };
+  if (frames < 0) return refuse("bad frames");
+  if (src_format < 0 || src_format >= DZN_SRC_FORMATS || channels < 1)
+    return refuse("src_format " + std::to_string(src_format) + " with " + std::to_string(channels) +
+                  " channel(s): the formats are 0 (float32 mono) .. 7 (DZN_SRC_* of dzn.h), interleaved over channels >= 1");
+  if (src_format == DZN_SRC_F32 && channels != 1)
+    return refuse("src_format 0 is float32 mono, not " + std::to_string(channels) +
+                  " channels (5 is float32 interleaved over channels)");
+  if (channel < DZN_CHANNEL_DOWNMIX || channel >= channels)
+    return refuse("channel " + std::to_string(channel) + " of a source with " + std::to_string(channels) + " channel(s)");
+  if (frames > INT64_MAX / 4 / channels) return refuse("frames * channels * bytes per sample overflows");
+  if (frames == 0) return DZN_OK;
+  if (!d_dst || !d_src) return refuse("null pointer");
+  const uintptr_t align = src_format == DZN_SRC_S16 ? 2 : (src_format == DZN_SRC_S32 || src_format == DZN_SRC_F32 ||
+                                                           src_format == DZN_SRC_F32I) ? 4 : 1;
+  if (reinterpret_cast<uintptr_t>(d_src) % align)
+    return refuse("d_src is not aligned to the " + std::to_string(align) + "-byte samples of src_format " +
+                  std::to_string(src_format));
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  return launch_decode(d_src, src_format, channels, channel, frames, d_dst, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
 const char* dzn_version(void) {
 #ifdef DZN_CHECKED
   return "dzn-hip 0.3.0 (gfx950, MFMA f32 / fp16x2 / bf16x3 / fp16 + MX fp8) [checked build: device-side bounds assertions]";

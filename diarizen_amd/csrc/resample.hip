@@ -118,7 +118,58 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const void* __restri
   }
 }
 
+// dzn_decode: the staging loop of resample_kernel on its own, for a source that is already at the model's rate (the bank for
+// equal rates is a low-pass, not the identity, so the resampler cannot serve it).  One stored frame per lane, consecutive
+// lanes on consecutive frames; the downmix is the same running sum and ONE division.  No LDS, nothing tuned: a live chunk is
+// a few KB and the call is launch-bound.
+template <int FMT>
+__global__ __launch_bounds__(kThreads) void decode_kernel(const void* __restrict__ src, int channels, int channel,
+                                                          int64_t frames, float* __restrict__ dst) {
+  const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (r >= frames) return;
+  const int64_t s0 = r * channels;                   // first sample of the frame
+  DZN_CHECK(channel >= DZN_CHANNEL_DOWNMIX && channel < channels && (FMT != DZN_SRC_F32 || channels == 1), 0x826, channel);
+  float v;
+  if (FMT == DZN_SRC_F32) {
+    v = static_cast<const float*>(src)[r];
+  } else if (channel >= 0) {                         // (wave-uniform)
+    DZN_CHECK(s0 + channel < frames * channels, 0x827, threadIdx.x);
+    v = stored_sample<FMT>(src, s0 + channel);
+  } else {                                           // downmix: running sum over the channels, one IEEE division
+    DZN_CHECK(s0 + channels <= frames * channels, 0x827, threadIdx.x);
+    v = stored_sample<FMT>(src, s0);
+    for (int c = 1; c < channels; ++c) v += stored_sample<FMT>(src, s0 + c);
+    v /= (float)channels;
+  }
+  dst[r] = v;
+}
+
 }  // namespace
+
+int launch_decode(const void* src, int format, int channels, int channel, int64_t frames, float* dst, hipStream_t st) {
+  if (frames < 0 || format < 0 || format >= DZN_SRC_FORMATS) return DZN_E_INVALID;
+  if (frames == 0) return DZN_OK;
+  const int64_t blocks = cdiv64(frames, kThreads);
+  if (blocks > 0x7fffffff) return DZN_E_INVALID;
+  ProfScope prof_scope_(st, "decode", 0.0, (double)frames * (kFormatBytes[format] * channels + 4.0));
+  const dim3 grid((unsigned)blocks), block(kThreads);
+#define DZN_DECODE_FORMAT(FMT)                                                                            \
+  case FMT:                                                                                               \
+    hipLaunchKernelGGL((decode_kernel<FMT>), grid, block, 0, st, src, channels, channel, frames, dst);    \
+    break
+  switch (format) {
+    DZN_DECODE_FORMAT(DZN_SRC_F32);
+    DZN_DECODE_FORMAT(DZN_SRC_S16);
+    DZN_DECODE_FORMAT(DZN_SRC_U8);
+    DZN_DECODE_FORMAT(DZN_SRC_S24);
+    DZN_DECODE_FORMAT(DZN_SRC_S32);
+    DZN_DECODE_FORMAT(DZN_SRC_F32I);
+    DZN_DECODE_FORMAT(DZN_SRC_ULAW);
+    DZN_DECODE_FORMAT(DZN_SRC_ALAW);
+  }
+#undef DZN_DECODE_FORMAT
+  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
 
 extern "C" int32_t dzn_resample_tile(void) { return kResampleTile; }
 

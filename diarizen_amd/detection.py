@@ -207,11 +207,12 @@ class _Detection:
         """push form for audio that is still arriving: `DetectionStream.feed(samples)` / `.finish()`.  tasks: the dzn_detect
         bitmask (DETECT_SPEECH | DETECT_OVERLAP gives both detections from one pass over the windows, one label per column;
         default: this pipeline's own task).  scores: also keep the aggregated scores (`committed_scores`).  Further keywords:
-        max_seconds, slot_seconds, slots (the ingest ring, streaming.WaveIngest)."""
+        max_seconds, slot_seconds, slots (the ingest ring, streaming.WaveIngest) and feed_format (an audio.FeedFormat: the
+        feeds are the source's own bytes, G.711 or PCM frames at its rate, decoded and resampled on the device)."""
         return DetectionStream(self, uri=uri, tasks=tasks, scores=scores, **kw)
 
     def stream(self, chunks: Iterable, uri: Optional[str] = None, **kw) -> Iterator[Tuple[float, float, Any]]:
-        """generator form: chunks of float32 samples at the pipeline's rate -> (seconds received, committed seconds,
+        """generator form: chunks of float32 samples at the pipeline's rate (feed_format=: of the source's own bytes) -> (seconds received, committed seconds,
         Annotation) for every feed that produced an annotation, then the final triple (the offline result)"""
         yield from stream_committed(self.open_stream(uri=uri, **kw), chunks)
 
@@ -251,7 +252,7 @@ class DetectionStream(CommittedStream):
     EMBEDDINGS = False
 
     def __init__(self, detection: _Detection, uri: Optional[str] = None, tasks: Optional[int] = None, scores: bool = False,
-                 max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0, slots: int = 4):
+                 max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0, slots: int = 4, feed_format=None):
         self.tasks = int(detection.TASK if tasks is None else tasks)
         if self.tasks & ~3 or not self.tasks & 3:
             raise ValueError(f"tasks is a bitmask of DETECT_SPEECH (1) and DETECT_OVERLAP (2), not {tasks!r}")
@@ -261,7 +262,7 @@ class DetectionStream(CommittedStream):
         rows = {"act": (np.uint8, (K,))}
         if self.want_scores:
             rows["sc"] = (np.float32, (K,))
-        super().__init__(detection, uri, rows, max_seconds, slot_seconds, slots)
+        super().__init__(detection, uri, rows, max_seconds, slot_seconds, slots, feed_format)
         self.det = detection
         self.d_weight = torch.from_numpy(detection_weights(self.runner.num_frames, self.chunks.duration)).to(self.device)
         self._entry = None                                              # device u8 [K]: activity of frame frontier - 1

@@ -45,17 +45,18 @@ from .streaming import CommittedStream, stream_committed
 class LiveDiarization(CommittedStream):
     def __init__(self, pipeline, sess_name: Optional[str] = None, delta_new: Optional[float] = None,
                  max_speakers: Optional[int] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
-                 slots: int = 4):
+                 slots: int = 4, feed_format=None):
         """delta_new: the distance beyond which a clean local speaker opens a new label (default: the pipeline's
         ahc_threshold); max_speakers: the cap on labels (default: the pipeline's, at most 32); max_seconds, slot_seconds,
-        slots: the ingest ring (streaming.WaveIngest)."""
+        slots: the ingest ring (streaming.WaveIngest); feed_format: an audio.FeedFormat when the feeds are the source's own
+        bytes."""
         self.K = min(int(max_speakers or pipeline.max_speakers), 32)
         if self.K < 1:
             raise ValueError(f"max_speakers must be at least 1, not {max_speakers!r}")
         if delta_new is None:
             delta_new = pipeline.config["clustering"]["args"]["ahc_threshold"]
         super().__init__(pipeline, sess_name, {"act": (np.uint8, (self.K,)), "cnt": (np.uint8, ())}, max_seconds, slot_seconds,
-                         slots)
+                         slots, feed_format)
         S = self.seg.shape[2]
         self.hard = torch.full((len(self.seg), S), -2, device=self.device, dtype=torch.int8)       # the windows' global labels
         self.speakers = OnlineSpeakers(delta_new, self.K, pipeline.engine.emb.embed_dim)
@@ -136,6 +137,6 @@ class LiveDiarization(CommittedStream):
 
 def stream_live(pipeline, chunks: Iterable, sess_name: Optional[str] = None, recluster: bool = False, **kw
                 ) -> Iterator[Tuple[float, float, Annotation]]:
-    """generator form: chunks of float32 samples at the pipeline's rate -> (seconds received, committed seconds, Annotation)
+    """generator form: chunks of float32 samples at the pipeline's rate (feed_format=: of the source's own bytes) -> (seconds received, committed seconds, Annotation)
     for every feed that produced an annotation, then the final triple"""
     yield from stream_committed(LiveDiarization(pipeline, sess_name, **kw), chunks, recluster=recluster)

@@ -409,21 +409,24 @@ class DiariZenPipeline:
     def stream(self, chunks, sess_name: Optional[str] = None, **kw):
         """windows scheduled as the audio arrives (pinned ring + copy stream): yields (seconds received, provisional
         Annotation) at every refresh and finally (total seconds, final Annotation == __call__ on the whole file).
-        See streaming.StreamingSession for the push form (feed / finish)."""
+        See streaming.StreamingSession for the push form (feed / finish).  feed_format=audio.FeedFormat(8000, "ulaw",
+        channels=2): the chunks are the source's own bytes (G.711 / PCM frames at 8 .. 48 kHz, any chunk length), decoded,
+        channel-selected and resampled on the device; the result is that of the file at that rate with resample="device"."""
         from .streaming import stream as _stream
         return _stream(self, chunks, sess_name, **kw)
 
     def open_live(self, sess_name: Optional[str] = None, delta_new: Optional[float] = None,
                   max_speakers: Optional[int] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
-                  slots: int = 4):
+                  slots: int = 4, feed_format=None):
         """live diarization with stable labels and a committed prefix: a live.LiveDiarization to `feed(samples)` /
         `finish()`.  delta_new: the centroid distance beyond which a clean local speaker opens a new label (default: the
         config's ahc_threshold); max_speakers: the cap on labels (default: the config's, at most 32); the other keywords size
-        the ingest ring (streaming.WaveIngest).  `stream` / StreamingSession stay what they are: provisional re-clusterings
+        the ingest ring (streaming.WaveIngest); feed_format: an audio.FeedFormat when the feeds are the source's own bytes
+        (refused here when it cannot be served).  `stream` / StreamingSession stay what they are: provisional re-clusterings
         whose last annotation is the offline result."""
         from .live import LiveDiarization
         return LiveDiarization(self, sess_name, delta_new=delta_new, max_speakers=max_speakers, max_seconds=max_seconds,
-                               slot_seconds=slot_seconds, slots=slots)
+                               slot_seconds=slot_seconds, slots=slots, feed_format=feed_format)
 
     def stream_live(self, chunks, sess_name: Optional[str] = None, **kw):
         """generator form of open_live: yields (seconds received, committed seconds, Annotation) for every feed that has an

@@ -9,6 +9,10 @@ Design (MI355X-first, same kernels as the offline path):
   * ingest: every chunk lands in a slot of a PINNED host ring and is copied to the device on a dedicated copy stream
     (`non_blocking` H2D, one event per slot); the compute stream only waits for the event of the newest slot a window
     needs, so upload and compute overlap and the caller's buffer is free as soon as feed() returns;
+  * a session opened with `feed_format=audio.FeedFormat(8000, "ulaw", channels=2)` is fed the source's own bytes instead —
+    G.711 / PCM frames at 8 .. 48 kHz in packets of any length: the ring then holds stored frames, each slot has a device
+    twin, and dzn_resample (dzn_decode at the model's rate) writes the samples that have become final (audio.feed_ready)
+    straight into the device buffer, on the copy stream; the waveform is resample_device of the whole recording bit for bit;
   * the device holds the recording so far in ONE pre-zeroed buffer (4 h of 16 kHz mono = 0.92 GB of the 288 GB); windows are
     rows of a strided view over it, exactly as offline (inference.WindowRunner), so a window is computed once, when its last
     sample has arrived, and never again.  Samples past the end read as zeros: the reference's zero-padded last window
@@ -28,6 +32,8 @@ from typing import Callable, Dict, Iterable, Iterator, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _lib
+from . import audio as audio_io
 from . import dist as dz_dist
 from .core import Annotation
 from .inference import window_plan
@@ -43,10 +49,23 @@ class WaveIngest:
     """The ingest half of a streaming session (WindowStream): a PINNED host ring,
     a dedicated copy stream and ONE pre-zeroed device buffer that holds the recording so far; `views` are its windows as rows
     of a strided view.  append() stages a chunk slot by slot and queues the H2D copies; wait() makes the current stream wait
-    for the newest one."""
+    for the newest one.
+
+    With a `feed_format` (audio.FeedFormat, its channel settled) append() takes the source's own bytes — G.711 or PCM frames
+    at 8 .. 48 kHz — instead of float32 samples.  audio.FeedPlanner says what each chunk makes final; per planned call the
+    slot holds [history | new frames] as stored, is copied to its DEVICE TWIN on copy_stream, and on the same stream ONE
+    dzn_resample call (dzn_decode for a feed at the model's rate) writes the output samples [ready before, ready after)
+    straight into dev_wave.  The slot's event is recorded after the kernel, so reusing a slot waits for the kernel that read
+    its twin.  `n` counts the model-rate samples that are final, `frames` the source frames received; flush() makes the tail
+    once the stream has ended.  dev_wave[:n] is then resample_device of the whole recording, bit for bit."""
 
     def __init__(self, device, sample_rate: int, window: int, step: int, max_seconds: float = 4 * 3600.0,
-                 slot_seconds: float = 10.0, slots: int = 4):
+                 slot_seconds: float = 10.0, slots: int = 4, feed_format=None, slot_frames: Optional[int] = None):
+        """feed_format: an audio.FeedFormat with a channel; slot_frames: new source frames per slot (default: slot_seconds of
+        the feed)"""
+        self.plan = None
+        if feed_format is not None:
+            self._open_format(feed_format, sample_rate, slot_seconds, slot_frames)      # refusals before any allocation
         self.device = device
         self.sr = sample_rate
         self.window = window
@@ -54,7 +73,15 @@ class WaveIngest:
         self.dev_wave = torch.zeros(self.capacity, device=device, dtype=torch.float32)
         self.views = torch.as_strided(self.dev_wave, ((self.capacity - window) // step + 1, window), (step, 1))
         self.slot_samples = int(slot_seconds * self.sr)
-        self.ring = [torch.empty(self.slot_samples, dtype=torch.float32).pin_memory() for _ in range(slots)]
+        if self.plan is None:
+            self.ring = [torch.empty(self.slot_samples, dtype=torch.float32).pin_memory() for _ in range(slots)]
+        else:
+            nbytes = self.plan.max_upload_frames * self.plan.fmt.frame_bytes
+            self.ring = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+            self.ring_np = [r.numpy() for r in self.ring]               # views of the pinned slots
+            self.twins = [torch.empty(nbytes, device=device, dtype=torch.uint8) for _ in range(slots)]
+            if not self.plan.same_rate:
+                self.bank = audio_io._device_bank(self.plan.fmt.rate, self.sr, device)[0]
         self.slot_free = [None] * slots                                 # event: the slot's H2D copy has completed
         self.next_slot = 0
         self.copy_stream = torch.cuda.Stream(device=device)
@@ -63,12 +90,32 @@ class WaveIngest:
         # must not recycle dev_wave while copies on the other stream are pending.
         self.copy_stream.wait_stream(torch.cuda.current_stream(device))
         self.dev_wave.record_stream(self.copy_stream)
-        self.n = 0                                                      # samples received
+        if self.plan is not None:
+            for t in self.twins:
+                t.record_stream(self.copy_stream)
+        self.n = 0                                                      # samples received (a stored feed: samples that are final)
+        self.frames = 0                                                 # source frames received (== n without a feed_format)
         self.uploads = 0
         self.last_copy = None
 
+    def _open_format(self, fmt, sample_rate: int, slot_seconds: float, slot_frames: Optional[int]) -> None:
+        if not isinstance(fmt, audio_io.FeedFormat) or fmt.channel is None:
+            raise ValueError(f"feed_format is an audio.FeedFormat with a channel choice, not {fmt!r}")
+        plan = audio_io.FeedPlanner(fmt, sample_rate, int(slot_seconds * fmt.rate) if slot_frames is None else slot_frames)
+        if not plan.same_rate and not audio_io.resample_tile_fits(plan.o, plan.n, plan.width, audio_io.resample_tile()):
+            raise ValueError(f"feed_format: {fmt.rate} Hz -> {sample_rate} Hz (o / n = {plan.o} / {plan.n}): the input of one "
+                             "tile of the device resampler does not fit in LDS")
+        self.plan = plan
+
     def append(self, samples) -> int:
-        """stage float32 samples and queue their copies behind the recording so far; -> number of samples taken"""
+        """stage float32 samples and queue their copies behind the recording so far; -> number of samples taken.  With a
+        feed_format: bytes (or an array of the stored dtype) of any length, also ending inside a frame; -> the number of
+        samples that became final"""
+        if self.plan is not None:
+            data = audio_io._feed_bytes(samples, self.plan.fmt)
+            if self.plan.length_after(len(data)) + self.window > self.capacity:
+                raise MemoryError(f"stream longer than max_seconds = {(self.capacity - self.window) / self.sr:.0f} s")
+            return self._run(self.plan.append(data))
         x = np.ascontiguousarray(np.asarray(samples, dtype=np.float32).reshape(-1))
         if self.n + len(x) + self.window > self.capacity:
             raise MemoryError(f"stream longer than max_seconds = {(self.capacity - self.window) / self.sr:.0f} s")
@@ -89,7 +136,48 @@ class WaveIngest:
             self.uploads += 1
             off += k
         self.n += len(x)
+        self.frames = self.n
         return len(x)
+
+    def flush(self) -> int:
+        """end of stream.  A stored feed: the samples [n, resampled_length(frames)) that waited for frames which will not come (a
+        trailing partial frame is dropped); -> the number of samples added (0 without a feed_format)"""
+        return 0 if self.plan is None else self._run(self.plan.finish())
+
+    def _run(self, calls) -> int:
+        """upload and launch the planned calls on copy_stream; -> output samples made"""
+        import ctypes as C
+        lib, fmt, plan = _lib.load(), self.plan.fmt, self.plan
+        device = torch.device(self.device)
+        dev = device.index if device.index is not None else -1
+        n0 = self.n
+        for c in calls:
+            nb = len(c.data)
+            assert c.m0 == self.n and nb == c.frames * fmt.frame_bytes <= len(self.ring[0]) and c.m1 + self.window <= self.capacity
+            i = self.next_slot
+            if self.slot_free[i] is not None:
+                self.slot_free[i].synchronize()                         # ring full: wait for the oldest copy and its kernel
+            self.ring_np[i][:nb] = np.frombuffer(c.data, dtype=np.uint8)
+            with torch.cuda.stream(self.copy_stream):
+                self.twins[i][:nb].copy_(self.ring[i][:nb], non_blocking=True)
+                st = C.c_void_p(self.copy_stream.cuda_stream)
+                src, dst = C.c_void_p(self.twins[i].data_ptr()), C.c_void_p(self.dev_wave.data_ptr() + 4 * c.m0)
+                if plan.same_rate:
+                    _lib.check(lib.dzn_decode(dev, src, fmt.src_format, fmt.channels, fmt.channel_code(), c.frames, dst, st),
+                               None, "dzn_decode")
+                else:
+                    _lib.check(lib.dzn_resample(dev, src, fmt.src_format, fmt.channels, fmt.channel_code(), c.first, c.frames,
+                                                c.total, C.c_void_p(self.bank.data_ptr()), plan.o, plan.n, plan.width, c.m0,
+                                                c.m1, dst, st), None, "dzn_resample")
+                ev = torch.cuda.Event()
+                ev.record(self.copy_stream)
+            self.slot_free[i] = ev
+            self.last_copy = ev
+            self.next_slot = (i + 1) % len(self.ring)
+            self.uploads += 1
+            self.n = c.m1
+        self.frames = plan.frames
+        return self.n - n0
 
     def wait(self) -> None:
         """the current (compute) stream runs behind the newest upload"""
@@ -103,32 +191,41 @@ class WindowStream:
     EMBEDDINGS = True                                                   # run_views(with_embeddings=...)
 
     def __init__(self, pipeline, name: Optional[str] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
-                 slots: int = 4):
+                 slots: int = 4, feed_format=None):
         """pipeline: a DiariZenPipeline or a detection pipeline (its _runner, device and rttm_out_dir are used); name: the
-        session name / uri of the annotations and of the RTTM file"""
+        session name / uri of the annotations and of the RTTM file; feed_format: an audio.FeedFormat when the feeds are the
+        source's own bytes (G.711 / PCM frames at its rate; a format without a channel takes the pipeline's) — refused here,
+        not at the first feed, when it cannot be served"""
         self.pipe = pipeline
         self.name = name
         self.runner = r = pipeline._runner
         self.sr = r.sample_rate
         self.device = pipeline.device
         with torch.cuda.device(self.device):
-            self.ingest = WaveIngest(self.device, self.sr, r.window, r.step, max_seconds, slot_seconds, slots)
+            if feed_format is not None:
+                if not isinstance(feed_format, audio_io.FeedFormat):
+                    raise ValueError(f"feed_format is an audio.FeedFormat, not {feed_format!r}")
+                feed_format = feed_format.with_channel(getattr(pipeline, "channel", 0))
+            self.feed_format = feed_format
+            self.ingest = WaveIngest(self.device, self.sr, r.window, r.step, max_seconds, slot_seconds, slots, feed_format)
         self.done = 0                                                   # windows computed
         self.finished = False
         self.stats = {"uploads": 0, "windows": 0, "launches": 0}
 
     @property
     def n(self) -> int:
-        """samples received"""
+        """samples received (with a feed_format: model-rate samples that are final)"""
         return self.ingest.n
 
     @property
     def seconds(self) -> float:
-        """seconds of audio received"""
+        """seconds of audio received (with a feed_format: of model-rate audio that is final; the feed is at most
+        width + o - 1 source frames ahead, audio.feed_ready)"""
         return self.ingest.n / self.sr
 
     def _append(self, samples) -> int:
-        """stage float32 samples (mono, the runner's rate) -> number of samples taken"""
+        """stage float32 samples (mono, the runner's rate), or bytes / stored-dtype arrays of the session's feed_format
+        -> number of samples taken (that became final)"""
         if self.finished:
             raise RuntimeError("stream already finished")
         taken = self.ingest.append(samples)
@@ -150,6 +247,11 @@ class WindowStream:
         """keep the results of windows lo .. hi - 1"""
         raise NotImplementedError
 
+    def _flush(self) -> None:
+        """end of stream: the samples of a stored feed that waited for frames which will not come"""
+        self.ingest.flush()
+        self.stats["uploads"] = self.ingest.uploads
+
     def _final_windows(self) -> Tuple[int, bool]:
         """(windows of the whole recording, the last of them is zero-padded): the reference's rule, PA/core/inference.py:293-299"""
         n_full, has_last = window_plan(self.n, self.runner.window, self.runner.step)
@@ -164,8 +266,8 @@ class WindowStream:
 
 class StreamingSession(WindowStream):
     def __init__(self, pipeline, sess_name: Optional[str] = None, max_seconds: float = 4 * 3600.0, refresh_s: Optional[float] = 8.0,
-                 slot_seconds: float = 10.0, slots: int = 4):
-        super().__init__(pipeline, sess_name, max_seconds, slot_seconds, slots)
+                 slot_seconds: float = 10.0, slots: int = 4, feed_format=None):
+        super().__init__(pipeline, sess_name, max_seconds, slot_seconds, slots, feed_format)
         self.refresh_s = refresh_s
         self.seg = []                                                   # per batch: u8 [c, L, S] host arrays
         self.emb = []
@@ -177,8 +279,8 @@ class StreamingSession(WindowStream):
         self.emb.append(res.embeddings.cpu().numpy())
 
     def feed(self, samples) -> Optional[Annotation]:
-        """append float32 samples (16 kHz mono, the pipeline's rate); returns a provisional annotation when a refresh is
-        due, else None"""
+        """append float32 samples (16 kHz mono, the pipeline's rate) — or, in a session with a feed_format, bytes / arrays of
+        the stored dtype in that format, of any length; returns a provisional annotation when a refresh is due, else None"""
         if self._append(samples) == 0:
             return None
         self._compute(complete_windows(self.n, self.runner.window, self.runner.step))
@@ -195,6 +297,8 @@ class StreamingSession(WindowStream):
 
     def finish(self) -> Annotation:
         """end of stream: the zero-padded tail window (if the reference would run one), then the final host stage"""
+        if not self.finished:
+            self._flush()
         if self.n > 0:
             self._compute(self._final_windows()[0])
         self.finished = True
@@ -207,13 +311,14 @@ class StreamingSession(WindowStream):
 
 def stream(pipeline, chunks: Iterable, sess_name: Optional[str] = None, **kw) -> Iterator[Tuple[float, Annotation]]:
     """generator form: yields (seconds of audio received, provisional Annotation) at every refresh and finally
-    (total seconds, final Annotation)"""
+    (total seconds, final Annotation).  feed_format=audio.FeedFormat(...): the chunks are the source's own bytes"""
     sess = StreamingSession(pipeline, sess_name, **kw)
     for c in chunks:
         ann = sess.feed(c)
         if ann is not None:
             yield sess.seconds, ann
-    yield sess.seconds, sess.finish()
+    ann = sess.finish()                                                 # (a stored feed: finish() makes the last samples final)
+    yield sess.seconds, ann
 
 
 # ----------------------------------------------------------------------------- sessions with a committed prefix
@@ -267,10 +372,10 @@ class CommittedStream(WindowStream):
     `_windows` and `_final_frames`."""
 
     def __init__(self, pipeline, name: Optional[str], rows: Dict[str, tuple], max_seconds: float = 4 * 3600.0,
-                 slot_seconds: float = 10.0, slots: int = 4):
+                 slot_seconds: float = 10.0, slots: int = 4, feed_format=None):
         """rows: the host arrays the range call fills, name -> (dtype, trailing shape) (StreamRows)"""
         dz_dist.require_single_rank(type(self).__name__)
-        super().__init__(pipeline, name, max_seconds, slot_seconds, slots)
+        super().__init__(pipeline, name, max_seconds, slot_seconds, slots, feed_format)
         self.chunks, self.frames = pipeline.chunks_window(), receptive_field(self.sr)
         cmax, L, S = self.ingest.views.shape[0], self.runner.num_frames, pipeline.engine.seg.max_speakers_per_chunk
         self.grid, starts, _ = _frame_grid(cmax, L, self.chunks, self.frames)
@@ -319,7 +424,8 @@ class CommittedStream(WindowStream):
         return T
 
     def feed(self, samples) -> Optional[Annotation]:
-        """append float32 samples (mono, the pipeline's rate).  -> None while no window is complete, else the Annotation over
+        """append float32 samples (mono, the pipeline's rate), or bytes / stored-dtype arrays in the session's feed_format.
+        -> None while no window is complete, else the Annotation over
         every frame computed so far (final before `committed_seconds`, provisional after)"""
         with torch.cuda.device(self.device):
             taken = self._append(samples)
@@ -336,6 +442,8 @@ class CommittedStream(WindowStream):
         committed -> `annotate()` (default: `_annotate`), written as RTTM where the subclass's `_write_rttm` says so"""
         if self.finished:
             raise RuntimeError("stream already finished")
+        with torch.cuda.device(self.device):
+            self._flush()
         total, has_last = self._final_windows()
         self.finished = True
         if self.n == 0:
@@ -351,7 +459,8 @@ class CommittedStream(WindowStream):
 
 
 def stream_committed(sess: CommittedStream, chunks: Iterable, **finish_kw) -> Iterator[Tuple[float, float, Annotation]]:
-    """generator form of a CommittedStream: chunks of float32 samples at the pipeline's rate -> (seconds received, committed
+    """generator form of a CommittedStream: chunks of float32 samples at the pipeline's rate (or of the session's
+    feed_format) -> (seconds received, committed
     seconds, Annotation) for every feed that produced an annotation, then the final triple"""
     for c in chunks:
         ann = sess.feed(c)

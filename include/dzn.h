@@ -417,6 +417,18 @@ int dzn_resample(int32_t device, const void* d_src, int32_t src_format, int32_t 
                  int32_t width, int64_t m0, int64_t m1, float* d_dst, void* hip_stream);
 int32_t dzn_resample_tile(void);
 
+/* The decode half of dzn_resample on its own, for frames that are already at the model's rate (the bank for equal rates is a
+ * low-pass, not the identity): d_dst f32 [frames] = the channel choice of the `frames` stored frames at d_src, with the
+ * DZN_SRC_* codes, DZN_CHANNEL_DOWNMIX and the conversions above (every one exact but int32, which rounds to nearest even;
+ * the downmix is the float32 running sum over channels 0, 1, .. then ONE IEEE division by (float)channels), i.e. the bits of
+ * the host decode (audio._decode_frames, then select_channel or downmix); DZN_SRC_F32 is a plain copy.  One launch (one
+ * stored frame per lane), enqueue-only, on `hip_stream` of `device` (< 0 = current); frames = 0 is DZN_OK and launches
+ * nothing.  Returns DZN_E_INVALID with a dzn_last_error(NULL) message, and launches nothing, for what dzn_resample refuses
+ * (src_format, DZN_SRC_F32 with channels != 1, channel) and for a d_src that is not aligned to the sample size (2 bytes for
+ * int16, 4 for int32 / float32; 8-bit, 24-bit and G.711 samples take any address). */
+int dzn_decode(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int32_t channel, int64_t frames,
+               float* d_dst, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
