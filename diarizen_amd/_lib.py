@@ -147,6 +147,7 @@ def load() -> C.CDLL:
     sig("dzn_segment_forward", i32, [vp, vp, i32, i32, vp, vp, vp])
     sig("dzn_segment_forward_soft", i32, [vp, vp, i32, i32, vp, vp, vp, vp])
     sig("dzn_embed_forward", i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp])
+    sig("dzn_embed_forward_strided", i32, [vp, vp, i64, vp, i32, i32, i32, i32, vp, vp])
     sig("dzn_prepare_masks", i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp])
     sig("dzn_speaker_count", i32, [vp, i32, i32, i32, vp, i32, vp, vp, vp])
     sig("dzn_cluster_activations", i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp])
@@ -209,7 +210,7 @@ def load() -> C.CDLL:
 
 EXPORTED = [
     "dzn_create", "dzn_load_tensor", "dzn_finalize_weights", "dzn_num_frames",
-    "dzn_segment_forward", "dzn_segment_forward_soft", "dzn_embed_forward", "dzn_prepare_masks", "dzn_speaker_count", "dzn_cluster_activations", "dzn_detect", "dzn_detect_range", "dzn_diarize_range", "dzn_speaker_scores", "dzn_debug_fetch", "dzn_embed_skip_stats", "dzn_num_ignored",
+    "dzn_segment_forward", "dzn_segment_forward_soft", "dzn_embed_forward", "dzn_embed_forward_strided", "dzn_prepare_masks", "dzn_speaker_count", "dzn_cluster_activations", "dzn_detect", "dzn_detect_range", "dzn_diarize_range", "dzn_speaker_scores", "dzn_debug_fetch", "dzn_embed_skip_stats", "dzn_num_ignored",
     "dzn_workspace_bytes", "dzn_last_error", "dzn_destroy", "dzn_version", "dzn_linkage_centroid", "dzn_cdist_cosine", "dzn_host_workspace_release",
     "dzn_host_workspace_bytes",
     "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",

@@ -176,12 +176,15 @@ int launch_classify(const float* z, int64_t ldz, const float* W, const float* bi
                     const uint8_t* mapping, int64_t rows, int A, int NC, int S, float* logp,
                     uint8_t* multilabel, float* soft, hipStream_t st);
 // embed.hip
-int launch_frame_prep(const float* wave, int B, int N, int T, int flen, int fshift, int Kp,
+// B signals `stride` samples apart, T frames each -> frames [B * T, Kp]
+int launch_frame_prep(const float* wave, int B, int64_t stride, int T, int flen, int fshift, int Kp,
                       const float* window, float preemph, float* frames, hipStream_t st);
 int launch_power(const float* spec, int64_t rows, int nb, float* pw, hipStream_t st);
 int launch_window_active(const float* masks, int B, int per_window, int* flag, hipStream_t st);
 int launch_compact_active(const int* flag, int B, int* count, int* list, long long* totals, hipStream_t st);
 int launch_log_cmn(float* mel, int B, int T, int NB, float eps, hipStream_t st);
+// the same from a shared frame grid: window b's frame t is row b * q + t of mel [(B - 1) q + T, NB]; writes fb [B, T, NB]
+int launch_log_cmn_gather(const float* mel, int q, float* fb, int B, int T, int NB, float eps, hipStream_t st);
 int launch_stem_conv(const float* fb, int B, int T, int NB, int C, const float* w, const float* bias,
                      float* img, hipStream_t st, float* amax = nullptr, const int* z_count = nullptr,
                      const int* z_list = nullptr);   // (z_count, z_list): device-chosen subset of the B images

@@ -7,6 +7,7 @@
 //      [512, Kp] cos/sin matrix on the MFMA kernel: 400 non-zero taps only).
 //  power_kernel      : |rfft|^2 for bins 0..255 (bin 256 has zero mel weight).
 //  log_cmn_kernel    : log(max(mel, eps)) and per-window mean subtraction over frames (:103).
+//  log_cmn_gather_kernel : the same from the mel energies of a frame grid that overlapping windows share.
 //  stem_conv_kernel  : ResNet conv1 3x3 (1 -> 32) + folded BN + ReLU (resnet.py:358), writes the
 //      zero-bordered NHWC image the 3x3 contractions read.
 //  stats_pool_kernel : TSTP / StatsPool weighted mean + std for ALL speaker masks of a window
@@ -16,7 +17,7 @@
 
 namespace {
 
-__global__ __launch_bounds__(256) void frame_prep_kernel(const float* __restrict__ wave, int N,
+__global__ __launch_bounds__(256) void frame_prep_kernel(const float* __restrict__ wave, int64_t N,
                                                          int T, int flen, int fshift, int Kp,
                                                          const float* __restrict__ window,
                                                          float preemph, float* __restrict__ frames) {
@@ -81,6 +82,33 @@ __global__ __launch_bounds__(256) void log_cmn_kernel(float* __restrict__ mel, i
   if (bin < NB)
     for (int t = ph; t < T; t += 16) {
       const float v = logf(fmaxf(mp[(int64_t)t * NB + bin], eps));
+      mp[(int64_t)t * NB + bin] = v;
+      s += v;
+    }
+  red[ph][threadIdx.x & 15] = s;
+  __syncthreads();
+  float tot = 0.f;
+  for (int i = 0; i < 16; ++i) tot += red[i][threadIdx.x & 15];
+  const float mean = tot / (float)T;
+  if (bin < NB)
+    for (int t = ph; t < T; t += 16) mp[(int64_t)t * NB + bin] -= mean;
+}
+
+// log_cmn_kernel over a frame grid the windows share: window b's frame t is row b * q + t of mel (read only: rows belong
+// to several windows), the result goes to fb [B, T, NB].  The log, the order of the sum and the subtraction are
+// log_cmn_kernel's, so fb holds the bits the in-place form leaves.
+__global__ __launch_bounds__(256) void log_cmn_gather_kernel(const float* __restrict__ mel, int q, float* __restrict__ fb,
+                                                             int T, int NB, float eps) {
+  __shared__ float red[16][17];
+  const int b = blockIdx.y;
+  const int bin = blockIdx.x * 16 + (threadIdx.x & 15);
+  const int ph = threadIdx.x >> 4;
+  const float* sp = mel + (int64_t)b * q * NB;
+  float* mp = fb + (int64_t)b * T * NB;
+  float s = 0.f;
+  if (bin < NB)
+    for (int t = ph; t < T; t += 16) {
+      const float v = logf(fmaxf(sp[(int64_t)t * NB + bin], eps));
       mp[(int64_t)t * NB + bin] = v;
       s += v;
     }
@@ -263,11 +291,12 @@ inline unsigned grid_for(int64_t n, int per = 256, int cap = 8192) {
 
 }  // namespace
 
-int launch_frame_prep(const float* wave, int B, int N, int T, int flen, int fshift, int Kp,
+int launch_frame_prep(const float* wave, int B, int64_t stride, int T, int flen, int fshift, int Kp,
                       const float* window, float preemph, float* frames, hipStream_t st) {
-  ProfScope prof_scope_(st, "frame_prep", 0.0, (double)B * N * 4.0 + (double)B * T * Kp * 4.0);
-  if (flen > 512 || T <= 0) return DZN_E_INVALID;
-  hipLaunchKernelGGL(frame_prep_kernel, dim3((T + 3) / 4, B), dim3(256), 0, st, wave, N, T, flen,
+  const double span = (double)(T - 1) * fshift + flen;   // samples one signal's frames cover
+  ProfScope prof_scope_(st, "frame_prep", 0.0, (double)B * span * 4.0 + (double)B * T * Kp * 4.0);
+  if (flen > 512 || T <= 0 || B <= 0 || B > 65535) return DZN_E_INVALID;
+  hipLaunchKernelGGL(frame_prep_kernel, dim3((T + 3) / 4, B), dim3(256), 0, st, wave, stride, T, flen,
                      fshift, Kp, window, preemph, frames);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
@@ -292,6 +321,13 @@ int launch_power(const float* spec, int64_t rows, int nb, float* pw, hipStream_t
 int launch_log_cmn(float* mel, int B, int T, int NB, float eps, hipStream_t st) {
   ProfScope prof_scope_(st, "log_cmn", 0.0, (double)B * T * NB * 12.0);   // read for the mean, read + write
   hipLaunchKernelGGL(log_cmn_kernel, dim3((NB + 15) / 16, B), dim3(256), 0, st, mel, T, NB, eps);
+  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+int launch_log_cmn_gather(const float* mel, int q, float* fb, int B, int T, int NB, float eps, hipStream_t st) {
+  ProfScope prof_scope_(st, "log_cmn", 0.0, (double)B * T * NB * 12.0);   // read the grid, write, read + write
+  if (q < 0 || T <= 0 || B <= 0 || B > 65535) return DZN_E_INVALID;
+  hipLaunchKernelGGL(log_cmn_gather_kernel, dim3((NB + 15) / 16, B), dim3(256), 0, st, mel, q, fb, T, NB, eps);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 

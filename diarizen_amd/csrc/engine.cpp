@@ -264,6 +264,10 @@ struct dzn_handle {
   };
   std::map<int, EmbGeom> geoms;
   float *frames = nullptr, *spec = nullptr, *pw = nullptr, *fb = nullptr, *pool = nullptr;
+  // fbank rows per pass of frame_prep -> DFT -> power -> mel (frames / spec / pw hold that many rows: the frame grid of
+  // max_batch windows a tenth of a window apart) and the mel energies of a shared frame grid, [<= max_batch * maxTf, NB]
+  int64_t fb_rows = 0;
+  float* melg = nullptr;
   // trunk skip for windows without any active speaker (r3; r4: decided on the device): flag per window, the ascending
   // list of active windows + its length, running totals (windows seen, windows skipped) for dzn_embed_skip_stats
   int *win_flag = nullptr, *win_idx = nullptr, *win_cnt = nullptr;
@@ -962,10 +966,15 @@ void finalize_emb(H* h) {
   const int Tmax = c.max_samples < flen ? 0 : 1 + (c.max_samples - flen) / 160;
   if (Tmax < 8) throw EngineError(DZN_E_INVALID, "max_samples too short for the embedding model");
   h->maxTf = Tmax;
-  h->frames = dalloc<float>(h, B * Tmax * Kp);
-  h->spec = dalloc<float>(h, B * Tmax * 512);
-  h->pw = dalloc<float>(h, B * Tmax * 256);
+  // frames / spec / pw hold one pass of the fbank chain.  A pass is sized for the frame grid windows share when they lie
+  // a tenth of a window apart (segmentation_step = 0.1 in every pipeline configuration): G = (B - 1) q + Tmax rows with
+  // q = ceil(Tmax / 10), not B * Tmax.  Anything longer (unrelated windows, wider strides) takes several passes.
+  h->fb_rows = (B - 1) * ((Tmax + 9) / 10) + Tmax;
+  h->frames = dalloc<float>(h, h->fb_rows * Kp);
+  h->spec = dalloc<float>(h, h->fb_rows * 512);
+  h->pw = dalloc<float>(h, h->fb_rows * 256);
   h->fb = dalloc<float>(h, B * Tmax * NB);
+  h->melg = dalloc<float>(h, B * Tmax * NB);
   int Hs = NB, Ws = Tmax;
   for (int s = 0; s < 4; ++s) {
     if (s > 0) {
@@ -1512,8 +1521,17 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
 // tests/test_emb_gpu.py holds the device to that bit for bit).  The masks decide it and they only exist on the device, so
 // the subset is built there (window_active -> compact_active: ascending list + count) and every trunk kernel is launched
 // over all B grid rows with (count, list): surplus rows exit at once.  No flag is read back — the call only enqueues
-// (include/dzn.h), and it can be captured in a HIP graph.  The fbank (1 % of the stage) stays dense.
-void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int N, int L, float* d_emb, hipStream_t st) {
+// (include/dzn.h), and it can be captured in a HIP graph.  The fbank is computed for every window, silent or not.
+//
+// Window b starts at wave + b * win_stride.  Everything in front of the per-window mean is a function of ONE frame's 400
+// samples (DC removal, pre-emphasis, Hamming; the DFT, power and mel contractions are row-independent; the log is per
+// element).  When the windows are cut from one recording a whole number q of frame shifts apart (win_stride = 160 q) and
+// leave no gap in the frame grid (win_stride <= N - 400 + 160, i.e. q <= T), frame t of window b IS recording frame
+// b q + t: the chain runs once over the G = (B - 1) q + T frames of the span the windows cover and log_cmn gathers each
+// window's rows.  Any other stride (unrelated windows: win_stride = N) runs the chain per window, read at that stride.
+// Either way the chain works in passes of at most fb_rows rows; a row's result does not depend on the pass it is in.
+void emb_forward(H* h, const float* wave, int64_t win_stride, const float* masks, int B, int S, int N, int L, float* d_emb,
+                 hipStream_t st) {
   const dzn_config& c = h->cfg;
   const int flen = 400, fshift = 160, Kp = 416, NB = c.num_mel_bins;
   if (N < flen) throw EngineError(DZN_E_INVALID, "waveform shorter than one fbank frame (400 samples)");
@@ -1534,16 +1552,31 @@ void emb_forward(H* h, const float* wave, const float* masks, int B, int S, int 
   }
   const int64_t MT = (int64_t)B * T;
   // ---- kaldi fbank ----
-  chk(launch_frame_prep(wave, B, N, T, flen, fshift, Kp, h->hamming, 0.97f, h->frames, st), "frame_prep");
-  {
-    dzn_gemm_desc d = gd(h, h->frames, h->dft, h->spec, MT, Kp, 512);
+  // one pass: nsig signals `stride` samples apart, t frames each -> mel energies of their nsig * t (<= fb_rows) frames
+  auto fbank_pass = [&](const float* w, int nsig, int64_t stride, int t, float* mel_out) {
+    const int64_t rows = (int64_t)nsig * t;
+    chk(launch_frame_prep(w, nsig, stride, t, flen, fshift, Kp, h->hamming, 0.97f, h->frames, st), "frame_prep");
+    dzn_gemm_desc d = gd(h, h->frames, h->dft, h->spec, rows, Kp, 512);
     d.precision = DZN_PREC_F32;  // the spectrum spans ~9 decades: keep the transform in fp32
     chk(launch_gemm(d, st), "dft");
-    chk(launch_power(h->spec, MT, 256, h->pw, st), "power");
-    dzn_gemm_desc m = gd(h, h->pw, h->mel, h->fb, MT, 256, NB);
+    chk(launch_power(h->spec, rows, 256, h->pw, st), "power");
+    dzn_gemm_desc m = gd(h, h->pw, h->mel, mel_out, rows, 256, NB);
     m.precision = DZN_PREC_F32;
     chk(launch_gemm(m, st), "mel");
-    chk(launch_log_cmn(h->fb, B, T, NB, 1.1920928955078125e-07f, st), "log_cmn");
+  };
+  const float eps = 1.1920928955078125e-07f;
+  const bool shared = B > 1 && win_stride > 0 && win_stride % fshift == 0 && win_stride <= (int64_t)N - flen + fshift;
+  if (shared) {
+    const int q = (int)(win_stride / fshift);        // <= T, so G <= B * T rows of melg
+    const int64_t G = (int64_t)(B - 1) * q + T;
+    for (int64_t r0 = 0; r0 < G; r0 += h->fb_rows)
+      fbank_pass(wave + r0 * fshift, 1, 0, (int)std::min<int64_t>(h->fb_rows, G - r0), h->melg + r0 * NB);
+    chk(launch_log_cmn_gather(h->melg, q, h->fb, B, T, NB, eps, st), "log_cmn");
+  } else {
+    const int per = (int)std::min<int64_t>(h->fb_rows / T, B);   // fb_rows >= maxTf >= T: at least one window per pass
+    for (int b0 = 0; b0 < B; b0 += per)
+      fbank_pass(wave + b0 * win_stride, std::min(per, B - b0), win_stride, T, h->fb + (int64_t)b0 * T * NB);
+    chk(launch_log_cmn(h->fb, B, T, NB, eps, st), "log_cmn");
   }
   tap(h, "fbank", h->fb, MT, NB, NB, st);
   // ---- ResNet34 trunk ----
@@ -1815,19 +1848,25 @@ int dzn_segment_forward_soft(dzn_handle* h, const float* d_wave, int32_t B, int3
 
 int dzn_embed_forward(dzn_handle* h, const float* d_wave, const float* d_masks, int32_t B, int32_t S,
                       int32_t N, int32_t L, float* d_emb, void* hip_stream) {
+  // dense windows: a stride of N never meets the frame-grid conditions, every window runs its own fbank
+  return dzn_embed_forward_strided(h, d_wave, N, d_masks, B, S, N, L, d_emb, hip_stream);
+}
+
+int dzn_embed_forward_strided(dzn_handle* h, const float* d_rec, int64_t win_stride, const float* d_masks, int32_t B,
+                              int32_t S, int32_t N, int32_t L, float* d_emb, void* hip_stream) {
   if (!h) return DZN_E_INVALID;
   if (!h->finalized || !h->has_emb) {
     h->err = "embedding model not loaded / not finalized";
     return DZN_E_STATE;
   }
-  if (!d_wave || !d_masks || !d_emb || B < 1 || B > h->cfg.max_batch || N > h->cfg.max_samples ||
-      L < 1) {
+  if (!d_rec || !d_masks || !d_emb || B < 1 || B > h->cfg.max_batch || N > h->cfg.max_samples ||
+      L < 1 || (B > 1 && win_stride < 0)) {
     h->err = "bad arguments to dzn_embed_forward";
     return DZN_E_INVALID;
   }
   DeviceGuard dg(h->device);
   return guarded(h, [&] {
-    emb_forward(h, d_wave, d_masks, B, S, N, L, d_emb, reinterpret_cast<hipStream_t>(hip_stream));
+    emb_forward(h, d_rec, B > 1 ? win_stride : N, d_masks, B, S, N, L, d_emb, reinterpret_cast<hipStream_t>(hip_stream));
   });
 }
 

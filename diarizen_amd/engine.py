@@ -168,6 +168,24 @@ class Engine:
               self._h, "dzn_embed_forward")
         return out
 
+    def embed_strided(self, views: torch.Tensor, masks: torch.Tensor) -> torch.Tensor:
+        """embed() over rows of a strided view of ONE recording, without a dense copy: views f32 [B, N] with unit sample
+        stride and any non-negative row stride (torch.as_strided of the recording), masks f32 [B, S, L] -> f32 [B, S, dim].
+        Same bits as embed(views.contiguous(), masks); where the row stride is a whole number of fbank shifts and leaves no
+        gap in the frame grid (include/dzn.h: dzn_embed_forward_strided) the fbank is computed once per recording frame."""
+        assert views.is_cuda and views.dtype == torch.float32 and views.dim() == 2 and views.stride(1) == 1
+        assert masks.is_cuda and masks.dtype == torch.float32 and masks.dim() == 3 and masks.is_contiguous()
+        B, N = views.shape
+        stride = int(views.stride(0)) if B > 1 else N
+        assert stride >= 0 and masks.shape[0] == B
+        _, S, L = masks.shape
+        out = torch.empty((B, S, self.emb.embed_dim), device=views.device, dtype=torch.float32)
+        check(self.lib.dzn_embed_forward_strided(self._h, C.c_void_p(views.data_ptr()), stride,
+                                                 C.c_void_p(masks.data_ptr()), B, S, N, L,
+                                                 C.c_void_p(out.data_ptr()), self._stream()),
+              self._h, "dzn_embed_forward_strided")
+        return out
+
     def prepare_masks(self, multilabel: torch.Tensor, median_size: int = 11,
                       exclude_overlap: bool = True, min_num_frames: int = -1,
                       want_masks: bool = True):

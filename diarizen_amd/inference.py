@@ -37,6 +37,34 @@ def window_plan(num_samples: int, window: int, step: int) -> Tuple[int, bool]:
     return num_chunks, has_last
 
 
+FBANK_FRAME, FBANK_SHIFT = 400, 160       # kaldi fbank of the embedding model: 25 ms frames, 10 ms apart, snip_edges
+
+
+def fbank_frames(window: int) -> int:
+    """T: fbank frames of one window"""
+    return 1 + (window - FBANK_FRAME) // FBANK_SHIFT if window >= FBANK_FRAME else 0
+
+
+def fbank_is_shared(window: int, stride: int) -> bool:
+    """the two conditions of dzn_embed_forward_strided (include/dzn.h) under which windows `stride` samples apart share
+    the frames of the recording: a whole number of frame shifts, and no gap in the frame grid between neighbours"""
+    return stride % FBANK_SHIFT == 0 and 0 < stride <= window - FBANK_FRAME + FBANK_SHIFT
+
+
+def fbank_grid(num_windows: int, window: int, stride: int) -> Tuple[int, int, int]:
+    """(q, T, G) of a shared launch: window b's frame t is recording frame b * q + t, of G = (B - 1) q + T in all"""
+    assert fbank_is_shared(window, stride) and num_windows >= 1
+    q, T = stride // FBANK_SHIFT, fbank_frames(window)
+    return q, T, (num_windows - 1) * q + T
+
+
+def embed_routes(s0: int, s1: int, dense_from: int) -> Tuple[int, int]:
+    """windows s0 .. s1 - 1 of a batch -> (how many go to the strided entry, how many to the dense one): windows from
+    `dense_from` on do not lie in the recording (the zero-padded last window of window_plan)"""
+    k = min(max(dense_from - s0, 0), s1 - s0)
+    return k, (s1 - s0) - k
+
+
 @dataclass
 class SlideResult:
     segmentations: torch.Tensor            # u8 [C, L, S] (median-filtered hard decisions), device
@@ -147,12 +175,18 @@ class WindowRunner:
         soft=True: PA/core/inference.py:226, 319, 330); the median filter belongs to the hard decisions only."""
         views = self.windows_view(wave)
         c0, c1 = window_range if window_range is not None else (0, views.shape[0])
-        return self.run_views(views, c0, c1, with_embeddings=with_embeddings, hook=hook, with_scores=with_scores)
+        n_full, has_last = window_plan(wave.numel(), self.window, self.step)
+        return self.run_views(views, c0, c1, with_embeddings=with_embeddings, hook=hook, with_scores=with_scores,
+                              dense_from=n_full if has_last else None)
 
     def run_views(self, views: torch.Tensor, c0: int, c1: int, with_embeddings: bool = True, hook=None,
-                  with_scores: bool = False) -> SlideResult:
+                  with_scores: bool = False, dense_from: Optional[int] = None) -> SlideResult:
         """the batch loop of run() over rows c0 .. c1 of a [C, window] (strided) view of device samples — the streaming
-        session hands in a view of its pre-zeroed device ring, so nothing is re-concatenated as audio arrives"""
+        session hands in a view of its pre-zeroed device ring, so nothing is re-concatenated as audio arrives.
+        The embedding stage reads the windows through the view (Engine.embed_strided: windows a whole number of fbank
+        shifts apart share the frames of the recording); the segmentation stage reads the dense copy of the batch.
+        dense_from: rows from this index on are not windows of the recording (run(): the zero-padded last window) and take
+        the dense embedding entry; None when every row lies in the recording's own buffer."""
         eng = self.engine
         wave = views
         C = max(c1 - c0, 0)
@@ -192,7 +226,11 @@ class WindowRunner:
                                               want_masks=with_embeddings)
                 seg[s0 - c0:s1 - c0] = filt
                 if with_embeddings:
-                    emb[s0 - c0:s1 - c0] = e.embed(chunk, masks)
+                    ns, nd = embed_routes(s0, s1, c1 if dense_from is None else dense_from)
+                    if ns:
+                        emb[s0 - c0:s0 - c0 + ns] = e.embed_strided(views[s0:s0 + ns], masks[:ns])
+                    if nd:
+                        emb[s0 - c0 + ns:s1 - c0] = e.embed(chunk[ns:], masks[ns:])
             if hook is not None:
                 torch.cuda.current_stream(wave.device).synchronize()
                 hook(completed=s1 - c0, total=C)

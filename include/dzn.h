@@ -192,6 +192,25 @@ int dzn_embed_forward(dzn_handle* h, const float* d_wave, const float* d_masks,
                       void* hip_stream);
 
 /*
+ * The same forward over windows cut from ONE recording: window b is the N samples at d_rec + b * win_stride, all of
+ * them inside one allocation (the caller's strided view of the recording; no dense copy of the windows is needed).
+ * Same results, bit for bit, as dzn_embed_forward on the dense copy of those windows.
+ *
+ * kaldi's fbank frames are 400 samples long and 160 apart, and everything in front of the per-window mean subtraction
+ * is a function of one frame alone.  When
+ *     win_stride % 160 == 0   and   0 < win_stride <= N - 400 + 160
+ * (windows a whole number q = win_stride / 160 of frames apart, leaving no gap in the frame grid), frame t of window b
+ * is recording frame b q + t: framing, DFT, power and mel contraction then run ONCE over the (B - 1) q + T frames the
+ * windows cover instead of over B * T rows (windows a tenth of their length apart share 90 % of them).  Any other
+ * stride is served by the per-window arithmetic of dzn_embed_forward, reading the windows at their stride; it is not
+ * an error.  win_stride is ignored for B == 1.  Enqueue-only and capturable like every forward: no read-back, no
+ * allocation, no second stream.
+ */
+int dzn_embed_forward_strided(dzn_handle* h, const float* d_rec, int64_t win_stride, const float* d_masks,
+                              int32_t B, int32_t S, int32_t N, int32_t L, float* d_emb,
+                              void* hip_stream);
+
+/*
  * On-device glue between the two stages (keeps a window in HBM):
  *   median filter (odd `median_size`, 0/1 = off) along frames of d_multilabel u8 [B, L, S]
  *       <- diarizen/pipelines/inference.py:131-132 (scipy median_filter size=(1,11,1), "reflect")
