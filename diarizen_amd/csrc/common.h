@@ -150,8 +150,8 @@ int launch_conv0(const float* wave, int B, int N, const float* stats, const floa
 int launch_groupnorm_gelu(const float* x, float* y, int B, int T, int C, int Cp, int64_t ld,
                           const float* gamma, const float* beta, float eps, float* stats, hipStream_t st, float* amax = nullptr);
 int64_t gn_stats_floats(int B, int T, int C, int Cp);   // size of launch_groupnorm_gelu's `stats` (statistics + chunk partials)
-int launch_pad_rows(const float* x, float* xpad, int B, int L, int Lp, int pad, int D, hipStream_t st);
-int launch_ws_accum(const float* x, float* ws, float w, int init, int64_t n, hipStream_t st);
+int launch_pad_rows(const float* x, float* xpad, int B, int L, int Lp, int pad, int D, hipStream_t st);   // D % 4 == 0 or DZN_E_INVALID
+int launch_ws_accum(const float* x, float* ws, float w, int init, int64_t n, hipStream_t st);             // n % 4 == 0 or DZN_E_INVALID
 // ws = ((0 + w[0] x[0]) + w[1] x[1]) + ... in that order, element-wise over n floats: the layer-weighted sum in ONE pass over
 // the per-layer buffers (the same additions, in the same order, as n ws_accum / epilogue read-modify-writes)
 constexpr int WS_SUM_MAX = 40;
@@ -190,6 +190,7 @@ int launch_stem_conv(const float* fb, int B, int T, int NB, int C, const float* 
                      const int* z_list = nullptr);   // (z_count, z_list): device-chosen subset of the B images
 int launch_stats_pool(const float* img, int B, int H, int W, int C, const float* masks, int S,
                       int L, float* stats, hipStream_t st, const int* active = nullptr);   // active[b] == 0 -> zeros
+                      // S * W floats of dynamic LDS: more than 64 KiB is DZN_E_INVALID
 
 // conv_split.hip: 3x3 stride-1 conv 32 -> 32 over zero-bordered NHWC images (DZN_PREC_F32_SPLIT)
 int launch_conv3x3_c32_split(const float* in, const void* W3, const float* bias, const float* R, float* out, int B,

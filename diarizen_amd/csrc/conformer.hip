@@ -135,3 +135,18 @@ int launch_classify(const float* z, int64_t ldz, const float* W, const float* bi
                      bias, mapping, rows, A, NC, S, logp, multilabel, soft);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
+
+// ---- test entry points (include/dzn_ops.h) ----
+extern "C" int dzn_op_glu_dwconv(const float* u, int64_t ldu, const float* w, const float* bias, float* out, int64_t ldo,
+                                 int32_t B, int32_t L, int32_t A, int32_t ks, void* stream) {
+  if (!u || !w || !bias || !out || B <= 0 || L <= 0 || A <= 0 || ldu < 2 * (int64_t)A || ldo < A) return DZN_E_INVALID;
+  return launch_glu_dwconv(u, ldu, w, bias, out, ldo, B, L, A, ks, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_classify(const float* z, int64_t ldz, const float* W, const float* bias, const uint8_t* mapping,
+                               int64_t rows, int32_t A, int32_t NC, int32_t S, float* logp, uint8_t* multilabel, float* soft,
+                               void* stream) {
+  if (!z || !W || !bias || !mapping || rows <= 0 || A <= 0 || NC <= 0 || S <= 0 || ldz < A) return DZN_E_INVALID;
+  return launch_classify(z, ldz, W, bias, mapping, rows, A, NC, S, logp, multilabel, soft,
+                         reinterpret_cast<hipStream_t>(stream));
+}

@@ -284,6 +284,8 @@ __global__ __launch_bounds__(256) void compact_active_kernel(const int* __restri
   }
 }
 
+constexpr size_t STATS_POOL_MAX_LDS = 64 * 1024;   // dynamic LDS of one launch without a function attribute
+
 inline unsigned grid_for(int64_t n, int per = 256, int cap = 8192) {
   int64_t g = cdiv64(n, per);
   return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -348,7 +350,58 @@ int launch_stem_conv(const float* fb, int B, int T, int NB, int C, const float* 
 int launch_stats_pool(const float* img, int B, int H, int W, int C, const float* masks, int S,
                       int L, float* stats, hipStream_t st, const int* active) {
   ProfScope prof_scope_(st, "stats_pool", 0.0, (double)B * H * W * C * 4.0 + (double)B * S * L * 4.0);
+  if (S <= 0 || W <= 0) return DZN_E_INVALID;
   const size_t lds = (size_t)S * W * sizeof(float);
+  // the [S][W] weights live in dynamic LDS and the kernel sets no hipFuncAttributeMaxDynamicSharedMemorySize: 64 KiB is what
+  // a launch may ask for without it
+  if (lds > STATS_POOL_MAX_LDS) return DZN_E_INVALID;
   hipLaunchKernelGGL(stats_pool_kernel, dim3(H, B), dim3(256), lds, st, img, H, W, C, masks, S, L, stats, active);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+// ---- test entry points (include/dzn_ops.h) ----
+extern "C" int dzn_op_frame_prep(const float* wave, int32_t B, int64_t stride, int32_t T, int32_t flen, int32_t fshift,
+                                 int32_t Kp, const float* window, float preemph, float* frames, void* stream) {
+  if (!wave || !window || !frames || flen <= 0 || fshift <= 0 || Kp < flen || stride < 0) return DZN_E_INVALID;
+  return launch_frame_prep(wave, B, stride, T, flen, fshift, Kp, window, preemph, frames, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_power(const float* spec, int64_t rows, int32_t nb, float* pw, void* stream) {
+  if (!spec || !pw || rows <= 0 || nb <= 0) return DZN_E_INVALID;
+  return launch_power(spec, rows, nb, pw, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_log_cmn(float* mel, int32_t B, int32_t T, int32_t NB, float eps, void* stream) {
+  if (!mel || B <= 0 || B > 65535 || T <= 0 || NB <= 0) return DZN_E_INVALID;
+  return launch_log_cmn(mel, B, T, NB, eps, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_log_cmn_gather(const float* mel, int32_t q, float* fb, int32_t B, int32_t T, int32_t NB, float eps,
+                                     void* stream) {
+  if (!mel || !fb || NB <= 0) return DZN_E_INVALID;
+  return launch_log_cmn_gather(mel, q, fb, B, T, NB, eps, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_stem_conv(const float* fb, int32_t B, int32_t T, int32_t NB, int32_t C, const float* w, const float* bias,
+                                float* img, float* amax, const int32_t* z_count, const int32_t* z_list, void* stream) {
+  if (!fb || !w || !bias || !img || B <= 0 || B > 65535 || T <= 0 || NB <= 0 || C <= 0 || (!z_count != !z_list))
+    return DZN_E_INVALID;
+  return launch_stem_conv(fb, B, T, NB, C, w, bias, img, reinterpret_cast<hipStream_t>(stream), amax, z_count, z_list);
+}
+
+extern "C" int dzn_op_stats_pool(const float* img, int32_t B, int32_t H, int32_t W, int32_t C, const float* masks, int32_t S,
+                                 int32_t L, float* stats, const int32_t* active, void* stream) {
+  if (!img || !masks || !stats || B <= 0 || B > 65535 || H <= 0 || C <= 0 || L <= 0) return DZN_E_INVALID;
+  return launch_stats_pool(img, B, H, W, C, masks, S, L, stats, reinterpret_cast<hipStream_t>(stream), active);
+}
+
+extern "C" int dzn_op_window_active(const float* masks, int32_t B, int32_t per_window, int32_t* flag, void* stream) {
+  if (!masks || !flag || B <= 0 || per_window <= 0) return DZN_E_INVALID;
+  return launch_window_active(masks, B, per_window, flag, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_compact_active(const int32_t* flag, int32_t B, int32_t* count, int32_t* list, int64_t* totals,
+                                     void* stream) {
+  if (!flag || !count || !list || B <= 0) return DZN_E_INVALID;
+  return launch_compact_active(flag, B, count, list, reinterpret_cast<long long*>(totals), reinterpret_cast<hipStream_t>(stream));
 }

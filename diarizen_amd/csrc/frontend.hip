@@ -357,12 +357,14 @@ int64_t gn_stats_floats(int B, int T, int C, int Cp) {
 }
 
 int launch_pad_rows(const float* x, float* xpad, int B, int L, int Lp, int pad, int D, hipStream_t st) {
+  if (D & 3) return DZN_E_INVALID;   // float4 columns: D / 4 would drop the last D % 4 of every row and shift the rows after it
   ProfScope prof_scope_(st, "pad_rows", 0.0, (double)B * (L + Lp) * D * 4.0);
   hipLaunchKernelGGL(pad_rows_kernel, dim3(grid_for((int64_t)Lp * (D / 4)), B), dim3(256), 0, st, x, xpad, L, Lp, pad, D / 4);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
 
 int launch_ws_accum(const float* x, float* ws, float w, int init, int64_t n, hipStream_t st) {
+  if (n & 3) return DZN_E_INVALID;   // float4 elements, as launch_ws_sum: n / 4 would leave the last n % 4 floats out of the sum
   ProfScope prof_scope_(st, "ws_accum", 0.0, (double)n * (init ? 8.0 : 12.0));
   hipLaunchKernelGGL(ws_accum_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, x, ws, w, init, n / 4);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
@@ -379,4 +381,42 @@ int launch_col_scale(float* x, int64_t rows, int C, int64_t ld, const float* sca
   ProfScope prof_scope_(st, "col_scale", 0.0, (double)rows * C * 8.0);
   hipLaunchKernelGGL(col_scale_kernel, dim3(grid_for(rows * C)), dim3(256), 0, st, x, rows, C, ld, scale);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+// ---- test entry points (include/dzn_ops.h) ----
+extern "C" int dzn_op_groupnorm_gelu(const float* x, float* y, int32_t B, int32_t T, int32_t C, int32_t Cp, int64_t ld,
+                                     const float* gamma, const float* beta, float eps, float* stats, float* amax, void* stream) {
+  if (!x || !y || !gamma || !beta || !stats || B <= 0 || T <= 0 || C <= 0 || Cp < C || ld < Cp) return DZN_E_INVALID;
+  return launch_groupnorm_gelu(x, y, B, T, C, Cp, ld, gamma, beta, eps, stats, reinterpret_cast<hipStream_t>(stream), amax);
+}
+
+extern "C" int64_t dzn_op_gn_stats_floats(int32_t B, int32_t T, int32_t C, int32_t Cp) { return gn_stats_floats(B, T, C, Cp); }
+
+extern "C" int dzn_op_pad_rows(const float* x, float* xpad, int32_t B, int32_t L, int32_t Lp, int32_t pad, int32_t D,
+                               void* stream) {
+  if (!x || !xpad || B <= 0 || L <= 0 || pad < 0 || Lp < L + pad || D <= 0) return DZN_E_INVALID;
+  return launch_pad_rows(x, xpad, B, L, Lp, pad, D, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_ws_accum(const float* x, float* ws, float w, int32_t init, int64_t n, void* stream) {
+  if (!x || !ws || n <= 0) return DZN_E_INVALID;
+  return launch_ws_accum(x, ws, w, init, n, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_ws_sum(const float* const* xs, const float* weights, int32_t count, float* ws, int64_t n, void* stream) {
+  if (!xs || !weights || !ws || n <= 0 || count <= 0 || count > WS_SUM_MAX) return DZN_E_INVALID;
+  WsSumArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int k = 0; k < count; ++k) {
+    if (!xs[k]) return DZN_E_INVALID;
+    a.x[k] = xs[k];
+    a.w[k] = weights[k];
+  }
+  a.n = count;
+  return launch_ws_sum(a, ws, n, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_col_scale(float* x, int64_t rows, int32_t C, int64_t ld, const float* scale, void* stream) {
+  if (!x || !scale || rows <= 0 || C <= 0 || ld < C) return DZN_E_INVALID;
+  return launch_col_scale(x, rows, C, ld, scale, reinterpret_cast<hipStream_t>(stream));
 }

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       const int idx = lane + 64 * i;
       if (idx < C) {
         float o = (v[i] - mean) * rstd;
-        if (gamma) o = o * gamma[idx] + beta[idx];
+        if (gamma || beta) o = o * (gamma ? gamma[idx] : 1.f) + (beta ? beta[idx] : 0.f);   // either may be absent (F.layer_norm)
         if (gelu) o = gelu_erf(o);
         if (post) o *= post[idx];
         yp[idx] = o;
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* x, int64
     for (int e = 0; e < 4; ++e) {
       const bool in = c + e < C;
       gg[e] = (gamma && in) ? gamma[c + e] : 1.f;
-      bb[e] = (beta && gamma && in) ? beta[c + e] : 0.f;
+      bb[e] = (beta && in) ? beta[c + e] : 0.f;
       pp[e] = (post && in) ? post[c + e] : 1.f;
     }
     g4[k] = make_float4(gg[0], gg[1], gg[2], gg[3]);
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* x, int64
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float t = (in[e] - mean) * rstd;
-        if (gamma) t = t * gk[e] + bk[e];
+        if (gamma || beta) t = t * gk[e] + bk[e];
         if (gelu) t = gelu_erf(t);
         if (post) t *= pk[e];
         o[e] = c + e < C ? t : 0.f;
@@ -385,6 +385,20 @@ extern "C" int dzn_op_layernorm(const float* x, int64_t ldx, float* y, int64_t l
   if (!x || !y) return DZN_E_INVALID;
   return launch_layernorm(x, ldx, y, ldy, gamma, beta, rows, C, Cpad, eps, gelu,
                           reinterpret_cast<hipStream_t>(stream));
+}
+
+// the whole of launch_layernorm_t: + per-column post scale, + |max| tracker (amax[row / amax_unit], amax[0] when amax_unit == 0)
+extern "C" int dzn_op_layernorm_t(const float* x, int64_t ldx, float* y, int64_t ldy, const float* gamma, const float* beta,
+                                  const float* post, int64_t rows, int32_t C, int32_t Cpad, float eps, int32_t gelu,
+                                  float* amax, int64_t amax_unit, void* stream) {
+  if (!x || !y || amax_unit < 0) return DZN_E_INVALID;
+  return launch_layernorm_t(x, ldx, y, ldy, gamma, beta, post, rows, C, Cpad, eps, gelu,
+                            reinterpret_cast<hipStream_t>(stream), amax, amax_unit);
+}
+
+extern "C" int dzn_op_wave_stats(const float* w, int32_t B, int32_t N, float eps, float* stats, void* stream) {
+  if (!w || !stats || N <= 0) return DZN_E_INVALID;
+  return launch_wave_stats(w, B, N, eps, stats, reinterpret_cast<hipStream_t>(stream));
 }
 
 

@@ -411,3 +411,131 @@ def attention(qkv, B, L, h, *, gate=None, table=None, head_idx=None, Htot=0, sca
                                Htot, ldqkv, ldo, scale, precision, _stream()),
           what="dzn_op_attention")
     return out
+
+
+# ---- the small kernels (conformer.hip, frontend.hip, norm.hip, embed.hip): thin wrappers for tests/test_small_kernels_gpu.py.
+# Outputs and row strides are the caller's (a tensor argument may be a view into a larger, pattern-filled buffer); nothing is
+# allocated or reshaped here unless an output is omitted, and a launcher's refusal surfaces as DznError.
+
+def layernorm_t(x, gamma, beta, *, rows, C, Cpad, ldx, out, ldy, post=None, eps=1e-5, gelu=False, amax=None, amax_unit=0):
+    """launch_layernorm_t in full: out may be x (in place); post f32 [C]; amax f32 [units] with unit = row // amax_unit
+    (amax_unit == 0: one unit)"""
+    lib = _lib.load()
+    check(lib.dzn_op_layernorm_t(_p(x), int(ldx), _p(out), int(ldy), _p(gamma), _p(beta), _p(post), int(rows), int(C), int(Cpad),
+                                 eps, int(gelu), _p(amax), int(amax_unit), _stream()), what="dzn_op_layernorm_t")
+    return out
+
+
+def wave_stats(w, B, N, eps=1e-5, out=None):
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((B, 2), device=w.device, dtype=torch.float32)
+    check(lib.dzn_op_wave_stats(_p(w), int(B), int(N), eps, _p(out), _stream()), what="dzn_op_wave_stats")
+    return out
+
+
+def glu_dwconv(u, w, bias, out, *, B, L, A, ks, ldu, ldo):
+    lib = _lib.load()
+    check(lib.dzn_op_glu_dwconv(_p(u), int(ldu), _p(w), _p(bias), _p(out), int(ldo), int(B), int(L), int(A), int(ks), _stream()),
+          what="dzn_op_glu_dwconv")
+    return out
+
+
+def classify(z, W, bias, mapping, *, rows, A, NC, S, ldz, logp=None, multilabel=None, soft=None):
+    """mapping u8 [NC, S]; logp f32 [rows, NC], multilabel u8 [rows, S], soft f32 [rows, S]: each optional"""
+    lib = _lib.load()
+    check(lib.dzn_op_classify(_p(z), int(ldz), _p(W), _p(bias), _p(mapping), int(rows), int(A), int(NC), int(S), _p(logp),
+                              _p(multilabel), _p(soft), _stream()), what="dzn_op_classify")
+    return logp, multilabel, soft
+
+
+def gn_stats_floats(B, T, C, Cp) -> int:
+    return int(_lib.load().dzn_op_gn_stats_floats(int(B), int(T), int(C), int(Cp)))
+
+
+def groupnorm_gelu(x, y, gamma, beta, stats, *, B, T, C, Cp, ld, eps=1e-5, amax=None):
+    """stats: f32 scratch of gn_stats_floats(B, T, C, Cp) floats; y may be x"""
+    lib = _lib.load()
+    check(lib.dzn_op_groupnorm_gelu(_p(x), _p(y), int(B), int(T), int(C), int(Cp), int(ld), _p(gamma), _p(beta), eps, _p(stats),
+                                    _p(amax), _stream()), what="dzn_op_groupnorm_gelu")
+    return y
+
+
+def pad_rows(x, xpad, *, B, L, Lp, pad, D):
+    lib = _lib.load()
+    check(lib.dzn_op_pad_rows(_p(x), _p(xpad), int(B), int(L), int(Lp), int(pad), int(D), _stream()), what="dzn_op_pad_rows")
+    return xpad
+
+
+def ws_accum(x, ws, w, init, n):
+    lib = _lib.load()
+    check(lib.dzn_op_ws_accum(_p(x), _p(ws), float(w), int(bool(init)), int(n), _stream()), what="dzn_op_ws_accum")
+    return ws
+
+
+def ws_sum(xs, weights, ws, n):
+    """xs: list of device tensors, weights: list of floats (the launch takes them by value)"""
+    lib = _lib.load()
+    k = len(xs)
+    ptrs = (C.c_void_p * max(k, 1))(*[x.data_ptr() for x in xs])
+    wts = (C.c_float * max(k, 1))(*[float(w) for w in weights])
+    check(lib.dzn_op_ws_sum(ptrs, wts, k, _p(ws), int(n), _stream()), what="dzn_op_ws_sum")
+    return ws
+
+
+def col_scale(x, scale, *, rows, C_true, ld):
+    lib = _lib.load()
+    check(lib.dzn_op_col_scale(_p(x), int(rows), int(C_true), int(ld), _p(scale), _stream()), what="dzn_op_col_scale")
+    return x
+
+
+def frame_prep(wave, window, frames, *, B, stride, T, flen, fshift, Kp, preemph=0.97):
+    lib = _lib.load()
+    check(lib.dzn_op_frame_prep(_p(wave), int(B), int(stride), int(T), int(flen), int(fshift), int(Kp), _p(window), preemph,
+                                _p(frames), _stream()), what="dzn_op_frame_prep")
+    return frames
+
+
+def power(spec, pw, *, rows, nb):
+    lib = _lib.load()
+    check(lib.dzn_op_power(_p(spec), int(rows), int(nb), _p(pw), _stream()), what="dzn_op_power")
+    return pw
+
+
+def log_cmn(mel, *, B, T, NB, eps):
+    lib = _lib.load()
+    check(lib.dzn_op_log_cmn(_p(mel), int(B), int(T), int(NB), eps, _stream()), what="dzn_op_log_cmn")
+    return mel
+
+
+def log_cmn_gather(mel, fb, *, q, B, T, NB, eps):
+    lib = _lib.load()
+    check(lib.dzn_op_log_cmn_gather(_p(mel), int(q), _p(fb), int(B), int(T), int(NB), eps, _stream()), what="dzn_op_log_cmn_gather")
+    return fb
+
+
+def stem_conv(fb, w, bias, img, *, B, T, NB, C_out, amax=None, z_count=None, z_list=None):
+    lib = _lib.load()
+    check(lib.dzn_op_stem_conv(_p(fb), int(B), int(T), int(NB), int(C_out), _p(w), _p(bias), _p(img), _p(amax), _p(z_count),
+                               _p(z_list), _stream()), what="dzn_op_stem_conv")
+    return img
+
+
+def stats_pool(img, masks, stats, *, B, H, W, C_in, S, L, active=None):
+    lib = _lib.load()
+    check(lib.dzn_op_stats_pool(_p(img), int(B), int(H), int(W), int(C_in), _p(masks), int(S), int(L), _p(stats), _p(active),
+                                _stream()), what="dzn_op_stats_pool")
+    return stats
+
+
+def window_active(masks, flag, *, B, per_window):
+    lib = _lib.load()
+    check(lib.dzn_op_window_active(_p(masks), int(B), int(per_window), _p(flag), _stream()), what="dzn_op_window_active")
+    return flag
+
+
+def compact_active(flag, count, lst, *, B, totals=None):
+    """count i32 [1], lst i32 [>= B], totals i64 [2] or None (accumulates)"""
+    lib = _lib.load()
+    check(lib.dzn_op_compact_active(_p(flag), int(B), _p(count), _p(lst), _p(totals), _stream()), what="dzn_op_compact_active")
+    return count, lst

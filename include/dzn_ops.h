@@ -273,6 +273,66 @@ int dzn_op_attention(const float* qkv, float* out, const float* gate, const floa
                      int32_t precision, void* stream);
 
 /*
+ * The small (non-contraction) kernels, one entry point per launcher: tests/test_small_kernels_gpu.py holds each against a float64
+ * reference of the operation named here.  Outputs and row strides are the caller's, so a test can surround every buffer with a
+ * pattern band.  Arguments a launcher cannot serve return DZN_E_INVALID before anything is enqueued.
+ */
+/* csrc/conformer.hip: out[b,t,c] = swish(bias[c] + sum_j w[c,j] g[b, t + j - (ks-1)/2, c]), g = u[.., c] * sigmoid(u[.., A + c]),
+ * zero outside [0, L) of the window's own rows (GLU -> depthwise Conv1d -> folded BatchNorm -> Swish); u [B L, ldu >= 2 A],
+ * out [B L, ldo >= A], w [A, ks], ks in {7, 15, 31}. */
+int dzn_op_glu_dwconv(const float* u, int64_t ldu, const float* w, const float* bias, float* out, int64_t ldo, int32_t B,
+                      int32_t L, int32_t A, int32_t ks, void* stream);
+/* logits = z[r, :A] W^T + bias (W [NC, A], NC <= 16); logp [rows, NC] = log_softmax, multilabel u8 [rows, S] =
+ * mapping[argmax] (first maximum; mapping u8 [NC, S], S <= 64), soft [rows, S] = exp(logp) @ mapping; each output may be NULL. */
+int dzn_op_classify(const float* z, int64_t ldz, const float* W, const float* bias, const uint8_t* mapping, int64_t rows,
+                    int32_t A, int32_t NC, int32_t S, float* logp, uint8_t* multilabel, float* soft, void* stream);
+/* csrc/frontend.hip: y[b,t,c] = gelu((x[b,t,c] - mean[b,c]) * rstd[b,c] * gamma[c] + beta[c]) with the statistics over the T
+ * rows of window b (GroupNorm(C, C), biased variance), columns [C, Cp) of y zero; x, y [B T, ld] (y may be x), Cp % 4 == 0,
+ * ld % 4 == 0, Cp <= 1024; stats = scratch of dzn_op_gn_stats_floats() floats; amax f32 [B] or NULL: max'ed with |y|. */
+int dzn_op_groupnorm_gelu(const float* x, float* y, int32_t B, int32_t T, int32_t C, int32_t Cp, int64_t ld, const float* gamma,
+                          const float* beta, float eps, float* stats, float* amax, void* stream);
+int64_t dzn_op_gn_stats_floats(int32_t B, int32_t T, int32_t C, int32_t Cp);
+/* xpad[b, t + pad, :] = x[b, t, :], every other row of xpad [B, Lp, D] zero; D % 4 == 0 */
+int dzn_op_pad_rows(const float* x, float* xpad, int32_t B, int32_t L, int32_t Lp, int32_t pad, int32_t D, void* stream);
+/* ws = (init ? 0 : ws) + w * x over n floats (n % 4 == 0) */
+int dzn_op_ws_accum(const float* x, float* ws, float w, int32_t init, int64_t n, void* stream);
+/* ws = ((0 + w[0] x[0]) + w[1] x[1]) + ...: xs = HOST array of `count` device pointers, weights = HOST array (count <= 40) */
+int dzn_op_ws_sum(const float* const* xs, const float* weights, int32_t count, float* ws, int64_t n, void* stream);
+/* x[r, c] *= scale[c] for c < C; columns [C, ld) untouched */
+int dzn_op_col_scale(float* x, int64_t rows, int32_t C, int64_t ld, const float* scale, void* stream);
+/* csrc/norm.hip: dzn_op_layernorm + post (f32 [C] or NULL: multiplied in after the GELU) + amax (f32 [units] or NULL: entry
+ * row / amax_unit, or entry 0 when amax_unit == 0, is max'ed with |y|); gamma and beta may each be NULL. */
+int dzn_op_layernorm_t(const float* x, int64_t ldx, float* y, int64_t ldy, const float* gamma, const float* beta,
+                       const float* post, int64_t rows, int32_t C, int32_t Cpad, float eps, int32_t gelu, float* amax,
+                       int64_t amax_unit, void* stream);
+/* stats[b] = (mean, 1 / sqrt(var + eps)) of the N samples of window b (biased variance) */
+int dzn_op_wave_stats(const float* w, int32_t B, int32_t N, float eps, float* stats, void* stream);
+/* csrc/embed.hip: Kaldi framing.  frames[b T + t, :flen] = window * pre-emphasis(x - mean(x)), x = 2^15 * wave[b stride + t fshift
+ * + (0 .. flen)], previous sample of the first = itself; columns [flen, Kp) zero; flen <= 512. */
+int dzn_op_frame_prep(const float* wave, int32_t B, int64_t stride, int32_t T, int32_t flen, int32_t fshift, int32_t Kp,
+                      const float* window, float preemph, float* frames, void* stream);
+/* pw[r, f] = |spec[r, f] + i spec[r, nb + f]|^2, spec [rows, 2 nb] */
+int dzn_op_power(const float* spec, int64_t rows, int32_t nb, float* pw, void* stream);
+/* mel [B, T, NB] in place: log(max(mel, eps)) minus its mean over the T frames of the window */
+int dzn_op_log_cmn(float* mel, int32_t B, int32_t T, int32_t NB, float eps, void* stream);
+/* the same out of place from a shared frame grid: window b's frame t = row b q + t of mel; fb [B, T, NB] */
+int dzn_op_log_cmn_gather(const float* mel, int32_t q, float* fb, int32_t B, int32_t T, int32_t NB, float eps, void* stream);
+/* img[b, 1 + h, 1 + t, c] = relu(bias[c] + sum_{dh,dw} w[c, 3 dh + dw] fb[b, t + dw - 1, h + dh - 1]) (zero outside), fb [B, T, NB],
+ * img [B, NB + 2, T + 2, C] whose border is not written; C % 4 == 0 and 256 % (C / 4) == 0; amax f32 [B] or NULL;
+ * (z_count, z_list): both or neither, the images to compute, chosen on the device (dzn_gemm_desc.z_list) */
+int dzn_op_stem_conv(const float* fb, int32_t B, int32_t T, int32_t NB, int32_t C, const float* w, const float* bias, float* img,
+                     float* amax, const int32_t* z_count, const int32_t* z_list, void* stream);
+/* weighted mean / std over the W interior columns of img [B, H + 2, W + 2, C] for each of S masks [B, S, L], the mask
+ * interpolated to W frames as F.interpolate(mode="nearest") does; stats [B, S, 2 C H], feature c H + h; active i32 [B] or
+ * NULL: windows with active[b] == 0 get zeros and their image is not read.  S W floats of LDS: above 64 KiB is refused. */
+int dzn_op_stats_pool(const float* img, int32_t B, int32_t H, int32_t W, int32_t C, const float* masks, int32_t S, int32_t L,
+                      float* stats, const int32_t* active, void* stream);
+/* flag[b] = any of the per_window mask values of window b is non-zero */
+int dzn_op_window_active(const float* masks, int32_t B, int32_t per_window, int32_t* flag, void* stream);
+/* list[0 .. count[0]) = the b with flag[b] != 0, ascending; totals (i64 [2] or NULL) += (B, B - count[0]) */
+int dzn_op_compact_active(const int32_t* flag, int32_t B, int32_t* count, int32_t* list, int64_t* totals, void* stream);
+
+/*
  * In-situ kernel timing (HIP events on the launch stream).  Enable, run forwards, then collect:
  * one entry per kernel class with the number of launches, the summed event time and the summed
  * ALGORITHMIC flops / HBM bytes declared by the launch sites (un-padded reference shapes).

@@ -15,5 +15,7 @@ python -m pytest tests/test_detection_gpu.py tests/test_detection_stream_op_gpu.
 python -m pytest tests/test_gemm_tiles_gpu.py -m gpu -q -x 2>&1 | tail -3
 # the attention matrix (attention_split.hip, attention_planes.hip, ids 0x60x / 0x61x: staged tiles inside their planes): likewise
 python -m pytest tests/test_attention_matrix_gpu.py -m gpu -q -x 2>&1 | tail -3
+# the small-kernel matrix (conformer.hip, frontend.hip, norm.hip, embed.hip through their dzn_op_* entry points): likewise
+python -m pytest tests/test_small_kernels_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
