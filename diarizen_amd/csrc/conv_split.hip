@@ -230,8 +230,8 @@ int launch_conv3x3_c32_split(const float* in, const void* W3, const float* bias,
                              int Hs, int Ws, int relu, int post_relu, hipStream_t s, float* amax, const void* W2h,
                              const float* col_scale, const float* amax_in, const int* z_count, const int* z_list) {
   if (B <= 0 || Hs <= 0 || Ws <= 0) return DZN_OK;
-  if (!in || !W3 || !bias || !out) return DZN_E_INVALID;
   const bool h2 = W2h && col_scale && amax_in;
+  if (!in || !(h2 ? W2h : W3) || !bias || !out) return DZN_E_INVALID;   // the two-term form never reads W3
   static unsigned long long attr_mask = 0;  // one bit per HIP device: function attributes are per device
   const size_t lds = (h2 ? 2 : 3) * CS_PLANE;
   if (first_use_on_device(attr_mask)) {
@@ -264,4 +264,17 @@ extern "C" int dzn_op_conv3x3_c32_h2(const float* in, const void* W3, const void
   if (!W2h || !col_scale || !amax_in) return DZN_E_INVALID;
   return launch_conv3x3_c32_split(in, W3, bias, R, out, B, Hs, Ws, relu, post_relu,
                                   reinterpret_cast<hipStream_t>(stream), nullptr, W2h, col_scale, amax_in);
+}
+
+// the engine's launch form (tests): nothing fixed.  W2h / col_scale / amax_in all given -> two-term form (W3 may be NULL), none of
+// them -> three-term form; amax_out f32 [B] tracker or NULL; z_count [1] / z_list: device-chosen subset of the B images, both or
+// neither (one without the other = all images).  `out` is the caller's: nothing is filled or allocated here.
+extern "C" int dzn_op_conv3x3_c32_ex(const float* in, const void* W3, const void* W2h, const float* col_scale,
+                                     const float* amax_in, const float* bias, const float* R, float* out, int32_t B,
+                                     int32_t Hs, int32_t Ws, int32_t relu, int32_t post_relu, float* amax_out,
+                                     const int32_t* z_count, const int32_t* z_list, void* stream) {
+  const int given = (W2h != nullptr) + (col_scale != nullptr) + (amax_in != nullptr);
+  if (given != 0 && given != 3) return DZN_E_INVALID;
+  return launch_conv3x3_c32_split(in, W3, bias, R, out, B, Hs, Ws, relu, post_relu, reinterpret_cast<hipStream_t>(stream),
+                                  amax_out, W2h, col_scale, amax_in, z_count, z_list);
 }

@@ -309,3 +309,13 @@ extern "C" int dzn_op_resblock32_fused(const float* in, float* out, const void* 
   return launch_resblock32_fused(in, out, W1, cs1, b1, W2, cs2, b2, amax_in, nullptr, l1max1, bmax1, B, Hs, Ws, g_op_resblock_np,
                                  reinterpret_cast<hipStream_t>(stream), nullptr, nullptr);
 }
+
+// the engine's launch form (tests): amax_out f32 [B] tracker or NULL, an explicit np (2 or 1), z_count [1] / z_list a device-chosen
+// subset of the B images (one without the other = all images).  `out` is the caller's: nothing is filled or allocated here.
+extern "C" int dzn_op_resblock32_fused_ex(const float* in, float* out, const void* W1, const float* cs1, const float* b1,
+                                          const void* W2, const float* cs2, const float* b2, const float* amax_in,
+                                          float* amax_out, float l1max1, float bmax1, int32_t B, int32_t Hs, int32_t Ws,
+                                          int32_t np, const int32_t* z_count, const int32_t* z_list, void* stream) {
+  return launch_resblock32_fused(in, out, W1, cs1, b1, W2, cs2, b2, amax_in, amax_out, l1max1, bmax1, B, Hs, Ws, np,
+                                 reinterpret_cast<hipStream_t>(stream), z_count, z_list);
+}

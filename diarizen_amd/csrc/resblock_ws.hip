@@ -312,3 +312,12 @@ extern "C" int dzn_op_resblock_ws(const float* in, float* out, const void* W1, c
   return launch_resblock_ws(in, out, W1, cs1, b1, W2, cs2, b2, amax_in, nullptr, l1max1, bmax1, B, Hs, Ws, C,
                             reinterpret_cast<hipStream_t>(stream), nullptr, nullptr, op_resblock_np());
 }
+
+// the engine's launch form (tests): as dzn_op_resblock32_fused_ex, C = 32 or 64
+extern "C" int dzn_op_resblock_ws_ex(const float* in, float* out, const void* W1, const float* cs1, const float* b1,
+                                     const void* W2, const float* cs2, const float* b2, const float* amax_in, float* amax_out,
+                                     float l1max1, float bmax1, int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t np,
+                                     const int32_t* z_count, const int32_t* z_list, void* stream) {
+  return launch_resblock_ws(in, out, W1, cs1, b1, W2, cs2, b2, amax_in, amax_out, l1max1, bmax1, B, Hs, Ws, C,
+                            reinterpret_cast<hipStream_t>(stream), z_count, z_list, np);
+}

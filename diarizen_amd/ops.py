@@ -264,6 +264,60 @@ def resblock_ws(img, h2_w1, b1, h2_w2, b2, l1max1: float, bmax1: float, out=None
     return out
 
 
+def _image_ex_args(img, out, amax_in, amax_out, z_count, z_list, channels):
+    assert img.is_cuda and img.dtype == torch.float32 and img.is_contiguous() and img.dim() == 4 and img.shape[-1] in channels
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == img.shape
+    B = img.shape[0]
+    for t, dt in ((amax_in, torch.float32), (amax_out, torch.float32), (z_count, torch.int32), (z_list, torch.int32)):
+        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous())
+    assert amax_in is None or amax_in.numel() >= B
+    assert amax_out is None or amax_out.numel() >= B
+    assert z_count is None or z_count.numel() >= 1
+    assert z_list is None or z_list.numel() <= B
+    return B, img.shape[1] - 2, img.shape[2] - 2
+
+
+def conv3x3_c32_ex(img, bias, out, *, W3=None, h2_weights=None, amax_in=None, R=None, relu=False, post_relu=False, amax_out=None,
+                   z_count=None, z_list=None):
+    """csrc/conv_split.hip in the launch form of the engine (dzn_op_conv3x3_c32_ex): `out` and every tracker are the caller's,
+    nothing is filled or allocated.  h2_weights = (W2h, col_scale) with amax_in f32 [B] -> two-term form (W3 may be None), else
+    the three-term form on W3.  amax_out f32 [B]: per-image |max| tracker of `out`; z_count int32 [1] / z_list int32 [<= B]: the
+    images the launch works on."""
+    lib = _lib.load()
+    B, H, W = _image_ex_args(img, out, amax_in, amax_out, z_count, z_list, (32,))
+    W2h, cs = h2_weights if h2_weights is not None else (None, None)
+    check(lib.dzn_op_conv3x3_c32_ex(_p(img), _p(W3), _p(W2h), _p(cs), _p(amax_in), _p(bias), _p(R), _p(out), B, H, W, int(relu),
+                                    int(post_relu), _p(amax_out), _p(z_count), _p(z_list), _stream()), what="dzn_op_conv3x3_c32_ex")
+    return out
+
+
+def resblock32_fused_ex(img, h2_w1, b1, h2_w2, b2, l1max1: float, bmax1: float, out, *, amax_in, np=2, amax_out=None, z_count=None,
+                        z_list=None):
+    """csrc/resblock_fused.hip in the launch form of the engine (dzn_op_resblock32_fused_ex): caller-owned `out`, amax_in f32 [B],
+    optional tracker and image list, np = terms per operand (2 or 1)."""
+    lib = _lib.load()
+    B, H, W = _image_ex_args(img, out, amax_in, amax_out, z_count, z_list, (32,))
+    (W1, cs1), (W2, cs2) = h2_w1, h2_w2
+    check(lib.dzn_op_resblock32_fused_ex(_p(img), _p(out), _p(W1), _p(cs1), _p(b1), _p(W2), _p(cs2), _p(b2), _p(amax_in), _p(amax_out),
+                                         float(l1max1), float(bmax1), B, H, W, int(np), _p(z_count), _p(z_list), _stream()),
+          what="dzn_op_resblock32_fused_ex")
+    return out
+
+
+def resblock_ws_ex(img, h2_w1, b1, h2_w2, b2, l1max1: float, bmax1: float, out, *, amax_in, np=2, amax_out=None, z_count=None,
+                   z_list=None, C_planes=None):
+    """csrc/resblock_ws.hip in the launch form of the engine (dzn_op_resblock_ws_ex); C_planes: the channel count handed to the
+    library, by default the images' (a test of the refusal passes another)."""
+    lib = _lib.load()
+    B, H, W = _image_ex_args(img, out, amax_in, amax_out, z_count, z_list, (32, 64))
+    (W1, cs1), (W2, cs2) = h2_w1, h2_w2
+    Cn = img.shape[-1] if C_planes is None else int(C_planes)
+    check(lib.dzn_op_resblock_ws_ex(_p(img), _p(out), _p(W1), _p(cs1), _p(b1), _p(W2), _p(cs2), _p(b2), _p(amax_in), _p(amax_out),
+                                    float(l1max1), float(bmax1), B, H, W, Cn, int(np), _p(z_count), _p(z_list), _stream()),
+          what="dzn_op_resblock_ws_ex")
+    return out
+
+
 def linkage_centroid(emb, device: int = -1):
     """scipy.cluster.hierarchy.linkage(emb, "centroid", "euclidean") on the device (csrc/linkage.hip):
     emb = host float32 [n, dim] (numpy), returns the dendrogram float64 [n - 1, 4]."""

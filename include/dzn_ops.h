@@ -216,6 +216,25 @@ int dzn_op_conv3x3_c32_h2(const float* in, const void* W3, const void* W2h, cons
                           const float* bias, const float* R, float* out, int32_t B, int32_t Hs, int32_t Ws,
                           int32_t relu, int32_t post_relu, void* stream);
 
+/* The three image kernels in the launch form the engine uses (tests: nothing fixed, nothing filled, nothing allocated).
+ *   amax_out  f32 [B] or NULL: amax_out[b] = max(amax_out[b], max |out[b]|) for every image the launch works on
+ *   z_count / z_list  int32 [1] / int32 [<= B] or NULL: the launch works on images z_list[0 .. z_count[0]) only; one of the two
+ *                     without the other means all B images
+ *   np        (blocks) terms per operand: 2 (DZN_PREC_F32_H2) or 1 (DZN_PREC_F16); anything else is DZN_E_INVALID
+ * conv: W2h, col_scale and amax_in all given -> the fp16 two-term form (W3 may be NULL), none of them -> the bf16 three-term
+ * form (W3 required); some but not all -> DZN_E_INVALID.  dzn_op_resblock_ws_ex: C other than 32 / 64 is DZN_E_INVALID. */
+int dzn_op_conv3x3_c32_ex(const float* in, const void* W3, const void* W2h, const float* col_scale, const float* amax_in,
+                          const float* bias, const float* R, float* out, int32_t B, int32_t Hs, int32_t Ws, int32_t relu,
+                          int32_t post_relu, float* amax_out, const int32_t* z_count, const int32_t* z_list, void* stream);
+int dzn_op_resblock32_fused_ex(const float* in, float* out, const void* W1, const float* cs1, const float* b1, const void* W2,
+                               const float* cs2, const float* b2, const float* amax_in, float* amax_out, float l1max1,
+                               float bmax1, int32_t B, int32_t Hs, int32_t Ws, int32_t np, const int32_t* z_count,
+                               const int32_t* z_list, void* stream);
+int dzn_op_resblock_ws_ex(const float* in, float* out, const void* W1, const float* cs1, const float* b1, const void* W2,
+                          const float* cs2, const float* b2, const float* amax_in, float* amax_out, float l1max1, float bmax1,
+                          int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t np, const int32_t* z_count,
+                          const int32_t* z_list, void* stream);
+
 /* y[r,:] = LayerNorm(x[r,:C]) * gamma + beta (eps), optional fused erf-GELU; row strides
  * ldx / ldy; columns [C, Cpad) of y are written as zero.  torch F.layer_norm. */
 int dzn_op_layernorm(const float* x, int64_t ldx, float* y, int64_t ldy, const float* gamma,
