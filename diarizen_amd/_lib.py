@@ -103,6 +103,23 @@ class DznGemmDesc(C.Structure):
     ]
 
 
+class DznIngestDesc(C.Structure):
+    """dzn_ingest_desc of include/dzn.h: 96 bytes, no padding (`ingest_desc_dtype()` is the same layout as a numpy record)"""
+    _fields_ = [("src_offset", C.c_int64), ("src_first_index", C.c_int64), ("src_len", C.c_int64), ("total_len", C.c_int64),
+                ("m0", C.c_int64), ("m1", C.c_int64), ("bank_offset", C.c_int64), ("dst_offset", C.c_int64),
+                ("src_format", C.c_int32), ("channels", C.c_int32), ("channel", C.c_int32), ("o", C.c_int32),
+                ("n", C.c_int32), ("width", C.c_int32), ("tile0", C.c_int32), ("reserved", C.c_int32)]
+
+
+def ingest_desc_dtype():
+    """the numpy record dtype of a dzn_ingest_desc table"""
+    import numpy as np
+    kinds = {C.c_int64: "<i8", C.c_int32: "<i4"}
+    dt = np.dtype([(name, kinds[ct]) for name, ct in DznIngestDesc._fields_])
+    assert dt.itemsize == C.sizeof(DznIngestDesc) == 96
+    return dt
+
+
 class DznProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -186,6 +203,8 @@ def load() -> C.CDLL:
     sig("dzn_resample", i32, [i32, vp, i32, i32, i32, i64, i64, i64, vp, i32, i32, i32, i64, i64, vp, vp])
     sig("dzn_resample_tile", i32, [])
     sig("dzn_decode", i32, [i32, vp, i32, i32, i32, i64, vp, vp])
+    sig("dzn_ingest_many", i32, [i32, vp, i64, vp, vp, i32, vp, i64, vp, i64, i64, vp])
+    sig("dzn_gather_windows", i32, [i32, vp, i64, vp, vp, i32, i32, vp, vp])
     sig("dzn_op_set_gemm_cfg", i32, [C.c_char_p])
     sig("dzn_op_amax", i32, [vp, i64, vp, vp])
     sig("dzn_op_split_rows", i32, [vp, vp, i64, i64, i32, vp])
@@ -235,7 +254,7 @@ EXPORTED = [
     "dzn_segment_forward", "dzn_segment_forward_soft", "dzn_embed_forward", "dzn_embed_forward_strided", "dzn_prepare_masks", "dzn_speaker_count", "dzn_cluster_activations", "dzn_detect", "dzn_detect_range", "dzn_diarize_range", "dzn_speaker_scores", "dzn_debug_fetch", "dzn_embed_skip_stats", "dzn_num_ignored",
     "dzn_workspace_bytes", "dzn_last_error", "dzn_destroy", "dzn_version", "dzn_linkage_centroid", "dzn_cdist_cosine", "dzn_host_workspace_release",
     "dzn_host_workspace_bytes",
-    "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",
+    "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_ingest_many", "dzn_gather_windows", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",
     "dzn_op_gemm", "dzn_op_split_weights", "dzn_op_split_weights_h2", "dzn_op_split_weights_mx", "dzn_op_set_gemm_mx_cfg", "dzn_checked_status", "dzn_op_set_gemm_cfg", "dzn_op_amax", "dzn_op_conv3x3_c32", "dzn_op_conv3x3_c32_h2", "dzn_op_resblock32_fused", "dzn_op_resblock_ws", "dzn_op_set_resblock_np", "dzn_op_conv3x3_c32_ex", "dzn_op_resblock32_fused_ex", "dzn_op_resblock_ws_ex", "dzn_op_set_attention_noskip", "dzn_op_split_rows", "dzn_op_layernorm", "dzn_op_row_stats", "dzn_op_gate", "dzn_op_gate_stats", "dzn_op_attention", "dzn_op_attention_h2", "dzn_op_attention_planes", "dzn_op_set_attention_qb", "dzn_op_set_attention_prefetch",
     "dzn_profile_enable", "dzn_profile_collect", "dzn_profile_reserve", "dzn_op_relpos_bucket",
     "dzn_op_glu_dwconv", "dzn_op_classify", "dzn_op_groupnorm_gelu", "dzn_op_gn_stats_floats", "dzn_op_pad_rows", "dzn_op_ws_accum",

@@ -222,6 +222,11 @@ int launch_resample(const void* src, int format, int channels, int channel, int6
                     const float* bank, int o, int n, int width, int64_t m0, int64_t m1, float* dst, hipStream_t st);
 // dst[frames] = the channel choice of the stored frames, decoded, at the rate they have (dzn_decode validates)
 int launch_decode(const void* src, int format, int channels, int channel, int64_t frames, float* dst, hipStream_t st);
+// ingest.hip: one launch over a descriptor table (dzn_ingest_many validates; `tiles` = the table's tile total, lds_bytes its
+// largest tile image) and the dense batch of windows dst[b, :] = pool[offsets[b] ..] (dzn_gather_windows validates)
+int launch_ingest_many(const void* stage, const dzn_ingest_desc* desc, int num_desc, int64_t tiles, size_t lds_bytes,
+                       double bytes_moved, const float* banks, float* pool, hipStream_t st);
+int launch_gather_windows(const float* pool, const int64_t* offsets, int B, int window, float* dst, hipStream_t st);
 
 // prof.cpp
 bool prof_enabled();

@@ -2003,6 +2003,115 @@ int dzn_decode(int32_t device, const void* d_src, int32_t src_format, int32_t ch
   return launch_decode(d_src, src_format, channels, channel, frames, d_dst, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
+static_assert(sizeof(dzn_ingest_desc) == 96, "dzn_ingest_desc is 96 bytes without padding (include/dzn.h)");
+
+int dzn_ingest_many(int32_t device, const void* d_stage, int64_t stage_bytes, const dzn_ingest_desc* h_desc,
+                    const dzn_ingest_desc* d_desc, int32_t num_desc, const float* d_banks, int64_t bank_floats, float* d_pool,
+                    int64_t pool_rows, int64_t row_floats, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_ingest_many: " + why;
+    return DZN_E_INVALID;
+  };
+  if (num_desc < 0 || stage_bytes < 0 || bank_floats < 0 || pool_rows < 0 || row_floats < 0)
+    return refuse("bad num_desc / sizes");
+  if (num_desc == 0) return DZN_OK;
+  if (!h_desc || !d_desc || !d_pool) return refuse("null pointer");
+  if (pool_rows && row_floats > INT64_MAX / pool_rows) return refuse("pool_rows * row_floats overflows");
+  static const int bytes_of[DZN_SRC_FORMATS] = {4, 2, 1, 3, 4, 4, 1, 1};
+  const int64_t tile = dzn_resample_tile();
+  int64_t tiles = 0;
+  size_t lds = 0;
+  double moved = 0.0;
+  for (int32_t i = 0; i < num_desc; ++i) {
+    const dzn_ingest_desc& d = h_desc[i];
+    auto bad = [&](const std::string& why) { return refuse("descriptor " + std::to_string(i) + ": " + why); };
+    const bool decode = d.bank_offset < 0;
+    if (d.src_format < 0 || d.src_format >= DZN_SRC_FORMATS || d.channels < 1)
+      return bad("src_format " + std::to_string(d.src_format) + " with " + std::to_string(d.channels) +
+                 " channel(s): the formats are 0 (float32 mono) .. 7 (DZN_SRC_* of dzn.h), interleaved over channels >= 1");
+    if (d.src_format == DZN_SRC_F32 && d.channels != 1)
+      return bad("src_format 0 is float32 mono, not " + std::to_string(d.channels) + " channels");
+    if (d.channel < DZN_CHANNEL_DOWNMIX || d.channel >= d.channels)
+      return bad("channel " + std::to_string(d.channel) + " of a source with " + std::to_string(d.channels) + " channel(s)");
+    if (d.m0 < 0 || d.m1 < d.m0 || d.src_len < 0 || d.src_offset < 0) return bad("bad lengths / range / offset");
+    if (d.src_len > INT64_MAX / 4 / d.channels) return bad("src_len * channels * bytes per sample overflows");
+    if (d.tile0 != tiles)
+      return bad("tile0 = " + std::to_string(d.tile0) + " is not the tile prefix " + std::to_string(tiles));
+    const int64_t count = d.m1 - d.m0;
+    // the output range inside ONE pool row
+    if (d.dst_offset < 0 || row_floats < 1 || d.dst_offset / row_floats >= pool_rows ||
+        d.dst_offset % row_floats + count > row_floats)
+      return bad("the output [" + std::to_string(d.dst_offset) + ", " + std::to_string(d.dst_offset + count) +
+                 ") reaches past its pool row of " + std::to_string(row_floats) + " floats");
+    bool reads = count > 0;
+    if (decode) {
+      if (d.src_len != count)
+        return bad("a decode descriptor holds the " + std::to_string(count) + " frames it decodes, not " +
+                   std::to_string(d.src_len));
+    } else {
+      if (d.o < 1 || d.n < 1 || d.width < 0 || d.total_len < 0) return bad("bad o / n / width / total_len");
+      if (d.total_len > INT64_MAX / d.n) return bad("total_len * n overflows");
+      const int64_t out_len = (d.total_len * d.n + d.o - 1) / d.o;
+      if (d.m1 > out_len) return bad("m1 = " + std::to_string(d.m1) + " is beyond the output length " + std::to_string(out_len));
+      if (count > 0) {
+        const size_t need = resample_lds_bytes(d.o, d.n, d.width);
+        if (!need)
+          return bad("o / n = " + std::to_string(d.o) + " / " + std::to_string(d.n) + ": the input of one tile does not fit in LDS");
+        lds = need > lds ? need : lds;
+        const int64_t K = 2 * (int64_t)d.width + d.o;
+        if (!d_banks || d.bank_offset > bank_floats || K * d.n > bank_floats - d.bank_offset)
+          return bad("the bank at float " + std::to_string(d.bank_offset) + " leaves the " + std::to_string(bank_floats) +
+                     " floats of d_banks");
+        int64_t lo = (d.m0 / d.n) * d.o - d.width, hi = ((d.m1 - 1) / d.n) * d.o + d.width + d.o;      // what [m0, m1) reads
+        lo = lo < 0 ? 0 : lo;
+        hi = hi > d.total_len ? d.total_len : hi;
+        reads = lo < hi;
+        if (reads && (d.src_first_index > lo || d.src_first_index + d.src_len < hi))
+          return bad("the span given, [" + std::to_string(d.src_first_index) + ", " + std::to_string(d.src_first_index + d.src_len) +
+                     "), does not cover the input [" + std::to_string(lo) + ", " + std::to_string(hi) + ") that the range reads");
+      }
+    }
+    if (reads) {
+      const int64_t nbytes = d.src_len * d.channels * bytes_of[d.src_format];
+      if (!d_stage || d.src_offset > stage_bytes || nbytes > stage_bytes - d.src_offset)
+        return bad("the source [" + std::to_string(d.src_offset) + ", " + std::to_string(d.src_offset + nbytes) +
+                   ") leaves the " + std::to_string(stage_bytes) + " bytes of d_stage");
+      const uintptr_t align = d.src_format == DZN_SRC_S16 ? 2 : (d.src_format == DZN_SRC_S32 || d.src_format == DZN_SRC_F32 ||
+                                                                 d.src_format == DZN_SRC_F32I) ? 4 : 1;
+      if ((reinterpret_cast<uintptr_t>(d_stage) + (uintptr_t)d.src_offset) % align)
+        return bad("the source is not aligned to the " + std::to_string(align) + "-byte samples of src_format " +
+                   std::to_string(d.src_format));
+      moved += (double)nbytes;
+    }
+    moved += 4.0 * (double)count;
+    tiles += (count + tile - 1) / tile;
+    if (tiles > 0x7fffffff) return bad("more than 2^31 - 1 tiles");
+  }
+  if (tiles == 0) return DZN_OK;
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  return launch_ingest_many(d_stage, d_desc, num_desc, tiles, lds, moved, d_banks, d_pool,
+                            reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+int dzn_gather_windows(int32_t device, const float* d_pool, int64_t pool_floats, const int64_t* h_offsets,
+                       const int64_t* d_offsets, int32_t B, int32_t window, float* d_dst, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_gather_windows: " + why;
+    return DZN_E_INVALID;
+  };
+  if (B < 0 || B > 65535 || window < 1 || pool_floats < 0) return refuse("bad B (0 .. 65535) / window / pool_floats");
+  if (B == 0) return DZN_OK;
+  if (!d_pool || !h_offsets || !d_offsets || !d_dst) return refuse("null pointer");
+  for (int32_t b = 0; b < B; ++b)
+    if (h_offsets[b] < 0 || h_offsets[b] > pool_floats - window)
+      return refuse("window " + std::to_string(b) + " at float " + std::to_string(h_offsets[b]) + " leaves the pool of " +
+                    std::to_string(pool_floats) + " floats");
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  return launch_gather_windows(d_pool, d_offsets, B, window, d_dst, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
 const char* dzn_version(void) {
 #ifdef DZN_CHECKED
   return "dzn-hip 0.3.0 (gfx950, MFMA f32 / fp16x2 / bf16x3 / fp16 + MX fp8) [checked build: device-side bounds assertions]";
@@ -2026,6 +2135,7 @@ int dzn_checked_collect_attention_planes(unsigned int*, int);
 int dzn_checked_collect_frontend_fused(unsigned int*, int);
 int dzn_checked_collect_post(unsigned int*, int);
 int dzn_checked_collect_resample(unsigned int*, int);
+int dzn_checked_collect_ingest(unsigned int*, int);
 }
 #endif
 int dzn_checked_status(uint32_t* out4, int32_t reset) {
@@ -2035,7 +2145,7 @@ int dzn_checked_status(uint32_t* out4, int32_t reset) {
                             dzn_checked_collect_resblock_fused, dzn_checked_collect_resblock_ws,
                             dzn_checked_collect_attention_split, dzn_checked_collect_attention_planes,
                             dzn_checked_collect_frontend_fused, dzn_checked_collect_post,
-                            dzn_checked_collect_resample};
+                            dzn_checked_collect_resample, dzn_checked_collect_ingest};
   unsigned int tot[4] = {0u, 0u, 0u, 0u};
   for (collect_fn f : fns) {
     unsigned int w[4] = {0u, 0u, 0u, 0u};

@@ -211,6 +211,15 @@ class _Detection:
         feeds are the source's own bytes, G.711 or PCM frames at its rate, decoded and resampled on the device)."""
         return DetectionStream(self, uri=uri, tasks=tasks, scores=scores, **kw)
 
+    def open_hub(self, max_sessions: int = 64, max_seconds: float = 600.0, slot_bytes: int = 1 << 20, slots: int = 4):
+        """many concurrent detection streams, one batched forward per tick: a hub.LiveHub whose `open(uri, ...)` takes the
+        keywords of open_stream but the ingest's and returns a DetectionStream; `feed()` is then host work only and
+        `hub.tick()` does the device work of every session at once.  max_sessions x max_seconds size ONE pooled device
+        buffer (max_sessions x (max_seconds x rate + window) x 4 B), so max_seconds is far below a solo stream's 4 h."""
+        from .hub import LiveHub
+        return LiveHub(self, lambda uri, hub, **kw: DetectionStream(self, uri=uri, hub=hub, **kw), max_sessions, max_seconds,
+                       slot_bytes, slots)
+
     def stream(self, chunks: Iterable, uri: Optional[str] = None, **kw) -> Iterator[Tuple[float, float, Any]]:
         """generator form: chunks of float32 samples at the pipeline's rate (feed_format=: of the source's own bytes) -> (seconds received, committed seconds,
         Annotation) for every feed that produced an annotation, then the final triple (the offline result)"""
@@ -252,7 +261,7 @@ class DetectionStream(CommittedStream):
     EMBEDDINGS = False
 
     def __init__(self, detection: _Detection, uri: Optional[str] = None, tasks: Optional[int] = None, scores: bool = False,
-                 max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0, slots: int = 4, feed_format=None):
+                 max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0, slots: int = 4, feed_format=None, hub=None):
         self.tasks = int(detection.TASK if tasks is None else tasks)
         if self.tasks & ~3 or not self.tasks & 3:
             raise ValueError(f"tasks is a bitmask of DETECT_SPEECH (1) and DETECT_OVERLAP (2), not {tasks!r}")
@@ -262,7 +271,7 @@ class DetectionStream(CommittedStream):
         rows = {"act": (np.uint8, (K,))}
         if self.want_scores:
             rows["sc"] = (np.float32, (K,))
-        super().__init__(detection, uri, rows, max_seconds, slot_seconds, slots, feed_format)
+        super().__init__(detection, uri, rows, max_seconds, slot_seconds, slots, feed_format, hub)
         self.det = detection
         self.d_weight = torch.from_numpy(detection_weights(self.runner.num_frames, self.chunks.duration)).to(self.device)
         self._entry = None                                              # device u8 [K]: activity of frame frontier - 1

@@ -45,18 +45,18 @@ from .streaming import CommittedStream, stream_committed
 class LiveDiarization(CommittedStream):
     def __init__(self, pipeline, sess_name: Optional[str] = None, delta_new: Optional[float] = None,
                  max_speakers: Optional[int] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
-                 slots: int = 4, feed_format=None):
+                 slots: int = 4, feed_format=None, hub=None):
         """delta_new: the distance beyond which a clean local speaker opens a new label (default: the pipeline's
         ahc_threshold); max_speakers: the cap on labels (default: the pipeline's, at most 32); max_seconds, slot_seconds,
         slots: the ingest ring (streaming.WaveIngest); feed_format: an audio.FeedFormat when the feeds are the source's own
-        bytes."""
+        bytes; hub: the hub.LiveHub whose tick() drives the session (pipeline.open_hub)."""
         self.K = min(int(max_speakers or pipeline.max_speakers), 32)
         if self.K < 1:
             raise ValueError(f"max_speakers must be at least 1, not {max_speakers!r}")
         if delta_new is None:
             delta_new = pipeline.config["clustering"]["args"]["ahc_threshold"]
         super().__init__(pipeline, sess_name, {"act": (np.uint8, (self.K,)), "cnt": (np.uint8, ())}, max_seconds, slot_seconds,
-                         slots, feed_format)
+                         slots, feed_format, hub)
         S = self.seg.shape[2]
         self.hard = torch.full((len(self.seg), S), -2, device=self.device, dtype=torch.int8)       # the windows' global labels
         self.speakers = OnlineSpeakers(delta_new, self.K, pipeline.engine.emb.embed_dim)
@@ -89,7 +89,8 @@ class LiveDiarization(CommittedStream):
     def _windows(self, res, lo: int, hi: int) -> None:
         """keep the new windows' decisions on the device, label them on the host and upload the new rows of the hard buffer"""
         super()._windows(res, lo, hi)
-        seg, emb = res.segmentations.cpu().numpy(), res.embeddings.cpu().numpy()      # the new windows only
+        host = getattr(res, "host", None)                               # a hub's tick has fetched them for all sessions at once
+        seg, emb = host if host is not None else (res.segmentations.cpu().numpy(), res.embeddings.cpu().numpy())     # the new windows only
         hard = np.stack([self.speakers.assign(seg[i], emb[i]) for i in range(hi - lo)])
         self.hard[lo:hi] = torch.from_numpy(hard).to(self.device)
         self._seg_h.append(seg)

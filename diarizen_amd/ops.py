@@ -593,3 +593,36 @@ def compact_active(flag, count, lst, *, B, totals=None):
     lib = _lib.load()
     check(lib.dzn_op_compact_active(_p(flag), int(B), _p(count), _p(lst), _p(totals), _stream()), what="dzn_op_compact_active")
     return count, lst
+
+
+def ingest_many(stage, desc, banks, pool):
+    """dzn_ingest_many on the current stream: ONE launch over the descriptor table `desc` (a numpy record array of
+    _lib.ingest_desc_dtype(), validated by the library from this host image and uploaded here), sources in `stage` (u8 device
+    tensor), banks in `banks` (f32 device tensor or None), outputs into `pool` (f32 device tensor [rows, row_floats])"""
+    import numpy as np
+    lib = _lib.load()
+    desc = np.ascontiguousarray(desc, dtype=_lib.ingest_desc_dtype()).reshape(-1)
+    assert pool.dim() == 2 and pool.is_contiguous() and pool.dtype == torch.float32 and stage.dtype == torch.uint8
+    d_desc = torch.from_numpy(desc.view(np.uint8).copy()).to(pool.device)
+    dev = pool.device.index if pool.device.index is not None else -1
+    check(lib.dzn_ingest_many(dev, _p(stage), stage.numel(), C.c_void_p(desc.ctypes.data), _p(d_desc), len(desc), _p(banks),
+                              0 if banks is None else banks.numel(), _p(pool), pool.shape[0], pool.shape[1], _stream()),
+          what="dzn_ingest_many")
+    return pool
+
+
+def gather_windows(pool, offsets, window, out=None):
+    """dzn_gather_windows on the current stream: out f32 [B, window], out[b] = pool.view(-1)[offsets[b] : offsets[b] + window]
+    (offsets: a host sequence of float offsets; the library validates them against the pool's size)"""
+    import numpy as np
+    lib = _lib.load()
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    B = len(off)
+    assert pool.is_contiguous() and pool.dtype == torch.float32
+    if out is None:
+        out = torch.empty((B, int(window)), device=pool.device, dtype=torch.float32)
+    d_off = torch.from_numpy(off.copy()).to(pool.device) if B else None
+    dev = pool.device.index if pool.device.index is not None else -1
+    check(lib.dzn_gather_windows(dev, _p(pool), pool.numel(), C.c_void_p(off.ctypes.data), _p(d_off), B, int(window), _p(out),
+                                 _stream()), what="dzn_gather_windows")
+    return out

@@ -428,6 +428,18 @@ class DiariZenPipeline:
         return LiveDiarization(self, sess_name, delta_new=delta_new, max_speakers=max_speakers, max_seconds=max_seconds,
                                slot_seconds=slot_seconds, slots=slots, feed_format=feed_format)
 
+    def open_hub(self, max_sessions: int = 64, max_seconds: float = 600.0, slot_bytes: int = 1 << 20, slots: int = 4):
+        """many concurrent live sessions, one batched forward per tick: a hub.LiveHub whose `open(name, ...)` takes the
+        keywords of open_live but the ingest's and returns a live.LiveDiarization; `feed()` is then host work only and
+        `hub.tick()` does the device work of every session at once — one staging upload, one ingest launch, ceil(ready
+        windows / batch_size) forwards — with the bits each session would have alone.  max_sessions x max_seconds size ONE
+        pooled device buffer (max_sessions x (max_seconds x rate + window) x 4 B: 2.5 GB at the defaults), so max_seconds is
+        deliberately far below a solo session's 4 h."""
+        from .hub import LiveHub
+        from .live import LiveDiarization
+        return LiveHub(self, lambda name, hub, **kw: LiveDiarization(self, name, hub=hub, **kw), max_sessions, max_seconds,
+                       slot_bytes, slots)
+
     def stream_live(self, chunks, sess_name: Optional[str] = None, **kw):
         """generator form of open_live: yields (seconds received, committed seconds, Annotation) for every feed that has an
         annotation, then the final triple.  Keywords as open_live, and recluster (live.LiveDiarization.finish)."""

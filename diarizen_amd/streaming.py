@@ -45,6 +45,19 @@ def complete_windows(num_samples: int, window: int, step: int) -> int:
     return 0 if num_samples < window else (num_samples - window) // step + 1
 
 
+def plan_feed(fmt, sample_rate: int, slot_frames: int, tile: Optional[int] = None):
+    """the audio.FeedPlanner of a stored-format feed (at most `slot_frames` new source frames per planned call), or the
+    refusal, by name and before any allocation, of a format the device ingest cannot serve (WaveIngest, hub.LiveHub);
+    tile: the device resampler's tile (default: asked of the library)"""
+    if not isinstance(fmt, audio_io.FeedFormat) or fmt.channel is None:
+        raise ValueError(f"feed_format is an audio.FeedFormat with a channel choice, not {fmt!r}")
+    plan = audio_io.FeedPlanner(fmt, sample_rate, slot_frames)
+    if not plan.same_rate and not audio_io.resample_tile_fits(plan.o, plan.n, plan.width, tile or audio_io.resample_tile()):
+        raise ValueError(f"feed_format: {fmt.rate} Hz -> {sample_rate} Hz (o / n = {plan.o} / {plan.n}): the input of one "
+                         "tile of the device resampler does not fit in LDS")
+    return plan
+
+
 class WaveIngest:
     """The ingest half of a streaming session (WindowStream): a PINNED host ring,
     a dedicated copy stream and ONE pre-zeroed device buffer that holds the recording so far; `views` are its windows as rows
@@ -99,13 +112,9 @@ class WaveIngest:
         self.last_copy = None
 
     def _open_format(self, fmt, sample_rate: int, slot_seconds: float, slot_frames: Optional[int]) -> None:
-        if not isinstance(fmt, audio_io.FeedFormat) or fmt.channel is None:
+        if not isinstance(fmt, audio_io.FeedFormat):
             raise ValueError(f"feed_format is an audio.FeedFormat with a channel choice, not {fmt!r}")
-        plan = audio_io.FeedPlanner(fmt, sample_rate, int(slot_seconds * fmt.rate) if slot_frames is None else slot_frames)
-        if not plan.same_rate and not audio_io.resample_tile_fits(plan.o, plan.n, plan.width, audio_io.resample_tile()):
-            raise ValueError(f"feed_format: {fmt.rate} Hz -> {sample_rate} Hz (o / n = {plan.o} / {plan.n}): the input of one "
-                             "tile of the device resampler does not fit in LDS")
-        self.plan = plan
+        self.plan = plan_feed(fmt, sample_rate, int(slot_seconds * fmt.rate) if slot_frames is None else slot_frames)
 
     def append(self, samples) -> int:
         """stage float32 samples and queue their copies behind the recording so far; -> number of samples taken.  With a
@@ -187,16 +196,23 @@ class WaveIngest:
 
 class WindowStream:
     """What every feed / finish session shares: the ingest, each complete window run ONCE through the runner (`_compute`; the
-    subclass takes the results in `_windows`), the feed-after-finish guard, the reference's final-window rule and the RTTM file."""
+    subclass takes the results in `_windows`), the feed-after-finish guard, the reference's final-window rule and the RTTM file.
+
+    A session opened by a hub (hub.LiveHub.open: `hub=`) is the same object with the hub's ingest — a row of the hub's pooled
+    device buffer instead of a WaveIngest of its own — and its device work is driven by the hub's tick() instead of by feed():
+    the three steps "stage" (`_append` / `_flush`: host only), "take results" (`_take`) and "advance" (`_step`) are what
+    feed() / finish() of a solo session run back to back."""
     EMBEDDINGS = True                                                   # run_views(with_embeddings=...)
 
     def __init__(self, pipeline, name: Optional[str] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
-                 slots: int = 4, feed_format=None):
+                 slots: int = 4, feed_format=None, hub=None):
         """pipeline: a DiariZenPipeline or a detection pipeline (its _runner, device and rttm_out_dir are used); name: the
         session name / uri of the annotations and of the RTTM file; feed_format: an audio.FeedFormat when the feeds are the
         source's own bytes (G.711 / PCM frames at its rate; a format without a channel takes the pipeline's) — refused here,
-        not at the first feed, when it cannot be served"""
+        not at the first feed, when it cannot be served; hub: the hub.LiveHub that owns the ingest and the device work (its
+        max_seconds and staging ring hold, not these)"""
         self.pipe = pipeline
+        self.hub = hub
         self.name = name
         self.runner = r = pipeline._runner
         self.sr = r.sample_rate
@@ -207,7 +223,10 @@ class WindowStream:
                     raise ValueError(f"feed_format is an audio.FeedFormat, not {feed_format!r}")
                 feed_format = feed_format.with_channel(getattr(pipeline, "channel", 0))
             self.feed_format = feed_format
-            self.ingest = WaveIngest(self.device, self.sr, r.window, r.step, max_seconds, slot_seconds, slots, feed_format)
+            if hub is None:
+                self.ingest = WaveIngest(self.device, self.sr, r.window, r.step, max_seconds, slot_seconds, slots, feed_format)
+            else:
+                self.ingest = hub._row_ingest(feed_format)              # refuses as WaveIngest does, then takes a pool row
         self.done = 0                                                   # windows computed
         self.finished = False
         self.stats = {"uploads": 0, "windows": 0, "launches": 0}
@@ -237,7 +256,11 @@ class WindowStream:
         if upto <= self.done:
             return
         self.ingest.wait()
-        res = self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=self.EMBEDDINGS)
+        self._take(self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=self.EMBEDDINGS), upto)
+
+    def _take(self, res, upto: int) -> None:
+        """take the results of windows done .. upto - 1 from the forward that ran them (here, or a hub's batch over many
+        sessions)"""
         self._windows(res, self.done, upto)
         self.stats["launches"] += 1
         self.stats["windows"] += upto - self.done
@@ -372,10 +395,10 @@ class CommittedStream(WindowStream):
     `_windows` and `_final_frames`."""
 
     def __init__(self, pipeline, name: Optional[str], rows: Dict[str, tuple], max_seconds: float = 4 * 3600.0,
-                 slot_seconds: float = 10.0, slots: int = 4, feed_format=None):
+                 slot_seconds: float = 10.0, slots: int = 4, feed_format=None, hub=None):
         """rows: the host arrays the range call fills, name -> (dtype, trailing shape) (StreamRows)"""
         dz_dist.require_single_rank(type(self).__name__)
-        super().__init__(pipeline, name, max_seconds, slot_seconds, slots, feed_format)
+        super().__init__(pipeline, name, max_seconds, slot_seconds, slots, feed_format, hub)
         self.chunks, self.frames = pipeline.chunks_window(), receptive_field(self.sr)
         cmax, L, S = self.ingest.views.shape[0], self.runner.num_frames, pipeline.engine.seg.max_speakers_per_chunk
         self.grid, starts, _ = _frame_grid(cmax, L, self.chunks, self.frames)
@@ -384,6 +407,8 @@ class CommittedStream(WindowStream):
             self.d_start = torch.from_numpy(starts).to(self.device)
         self.rows = StreamRows(**rows)
         self._last = None
+        self.result = None                                              # the final Annotation, once the stream has ended
+        self._finish_annotate = None
         self.stats["range_calls"] = 0
 
     @property
@@ -426,34 +451,53 @@ class CommittedStream(WindowStream):
     def feed(self, samples) -> Optional[Annotation]:
         """append float32 samples (mono, the pipeline's rate), or bytes / stored-dtype arrays in the session's feed_format.
         -> None while no window is complete, else the Annotation over
-        every frame computed so far (final before `committed_seconds`, provisional after)"""
+        every frame computed so far (final before `committed_seconds`, provisional after).
+        A hub's session: host work only — the feed is staged, the hub's next tick() runs it; -> the latest Annotation"""
         with torch.cuda.device(self.device):
             taken = self._append(samples)
+            if self.hub is not None:
+                return self._last
             upto = complete_windows(self.n, self.runner.window, self.runner.step)
             if taken and upto > self.done:
                 self._compute(upto)
-                self._advance(covered_frames(self.done, self.chunks, self.frames, self.grid),
-                              committed_frames(self.done, self.chunks, self.frames, self.grid))
-                self._last = self._annotate()
+                self._step()
+        return self._last
+
+    def _step(self) -> Annotation:
+        """the new windows are in: one range call up to the frames they cover, the frontier moves, the annotation follows"""
+        self._advance(covered_frames(self.done, self.chunks, self.frames, self.grid),
+                      committed_frames(self.done, self.chunks, self.frames, self.grid))
+        self._last = self._annotate()
         return self._last
 
     def finish(self, annotate: Optional[Callable[[], Annotation]] = None) -> Annotation:
         """end of stream: the zero-padded last window if the reference would run one, every frame of the final length
-        committed -> `annotate()` (default: `_annotate`), written as RTTM where the subclass's `_write_rttm` says so"""
+        committed -> `annotate()` (default: `_annotate`), written as RTTM where the subclass's `_write_rttm` says so.
+        A hub's session: marks the end of the stream and returns None; the hub's NEXT tick() does all of the above, its result
+        holds the final Annotation, which stays in `result`"""
         if self.finished:
             raise RuntimeError("stream already finished")
+        if self.hub is not None:
+            self.finished, self._finish_annotate = True, annotate
+            return None
         with torch.cuda.device(self.device):
             self._flush()
         total, has_last = self._final_windows()
         self.finished = True
         if self.n == 0:
-            return Annotation(uri=self.name)
+            self.result = Annotation(uri=self.name)
+            return self.result
         with torch.cuda.device(self.device):
             self._compute(total)
+        return self._finish_end(has_last, annotate)
+
+    def _finish_end(self, has_last: bool, annotate: Optional[Callable[[], Annotation]] = None) -> Annotation:
+        """every window is in: commit every frame of the final length -> the final Annotation and its RTTM file"""
+        with torch.cuda.device(self.device):
             T = self._final_frames(covered_frames(self.done, self.chunks, self.frames, self.grid), has_last)
             assert self.frontier <= T, "committed frames beyond the offline output"
             self._advance(T, T)
-        ann = self._last = (annotate or self._annotate)()
+        ann = self._last = self.result = (annotate or self._annotate)()
         self._write_rttm(ann)
         return ann
 

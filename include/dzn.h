@@ -448,6 +448,71 @@ int32_t dzn_resample_tile(void);
 int dzn_decode(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int32_t channel, int64_t frames,
                float* d_dst, void* hip_stream);
 
+/* Live hub (diarizen_amd/hub.py): the ingest of MANY sessions in one launch (csrc/ingest.hip).  A descriptor is what one
+ * dzn_resample or dzn_decode call takes; its source lies in one staging buffer, its bank in one buffer of banks, its output in
+ * one pooled buffer f32 [pool_rows][row_floats] (a row per session: the recording so far, zeros behind it).  Fixed-width
+ * fields, 96 bytes, no padding:
+ *   src_offset        byte offset of the stored frames inside d_stage (the address must be aligned to the sample size:
+ *                     2 bytes for int16, 4 for int32 / float32; the hub pads every call to 16 bytes)
+ *   src_first_index,  the frames at src_offset are frames src_first_index .. + src_len of a recording of total_len frames so
+ *   src_len,          far (dzn_resample's arguments).  A decode descriptor holds the frames it decodes and nothing else:
+ *   total_len         src_len = m1 - m0; src_first_index and total_len are not read
+ *   m0, m1            the output samples [m0, m1) it makes; m1 = m0 is legal and owns no tile
+ *   bank_offset       float offset of its bank f32 [K][n] (tap-major, as dzn_resample takes it) inside d_banks;
+ *                     negative: decode only (a feed at the model's rate; o, n, width are not read)
+ *   dst_offset        float offset of y[m0] inside d_pool; [dst_offset, dst_offset + m1 - m0) must lie in ONE row
+ *   src_format,       DZN_SRC_* / channels >= 1 / a channel index or DZN_CHANNEL_DOWNMIX, as dzn_resample takes them
+ *   channels, channel
+ *   o, n, width       the ratio and filter half-width of the bank
+ *   tile0             the tile prefix: the number of tiles owned by the descriptors before this one, where a descriptor owns
+ *                     ceil((m1 - m0) / dzn_resample_tile()) tiles (the caller writes it, the call verifies it)
+ *   reserved          0 */
+typedef struct dzn_ingest_desc {
+  int64_t src_offset;
+  int64_t src_first_index;
+  int64_t src_len;
+  int64_t total_len;
+  int64_t m0;
+  int64_t m1;
+  int64_t bank_offset;
+  int64_t dst_offset;
+  int32_t src_format;
+  int32_t channels;
+  int32_t channel;
+  int32_t o;
+  int32_t n;
+  int32_t width;
+  int32_t tile0;
+  int32_t reserved;
+} dzn_ingest_desc;
+
+/* ONE launch, enqueue-only, on `hip_stream` of `device` (< 0 = current): one workgroup per tile of dzn_resample_tile() output
+ * samples (a decode descriptor: frames) of one descriptor, found by a wave-uniform search over tile0.  The arithmetic is that
+ * of the single calls — one fp32 accumulator over j = 0 .. K-1, the downmix a running fp32 sum and one IEEE division, zeros
+ * outside [0, total_len) — so every output sample has the bits dzn_resample / dzn_decode give for the same arguments.  Dynamic
+ * LDS is the largest tile image of the table.  Pool floats outside every [dst_offset, dst_offset + m1 - m0) are not touched.
+ *   d_stage, stage_bytes   the staging buffer on the device and its size
+ *   h_desc, d_desc         the table of num_desc descriptors: h_desc is the host's image of it (validated here, it may be the
+ *                          pinned buffer the table was uploaded from), d_desc the device copy the kernel reads
+ *   d_banks, bank_floats   the buffer of banks and its size in floats
+ *   d_pool, pool_rows,     the pooled output
+ *   row_floats
+ * num_desc = 0, or a table without tiles, launches nothing and returns DZN_OK.  Anything dzn_resample / dzn_decode would
+ * refuse in a descriptor — and a source that leaves the staging buffer or is not aligned to its 2- or 4-byte samples, a bank
+ * that leaves d_banks, an output range that leaves its pool row, a tile0 that is not the prefix — makes the WHOLE call return
+ * DZN_E_INVALID with a dzn_last_error(NULL) message that names the descriptor index, and launches nothing. */
+int dzn_ingest_many(int32_t device, const void* d_stage, int64_t stage_bytes, const dzn_ingest_desc* h_desc,
+                    const dzn_ingest_desc* d_desc, int32_t num_desc, const float* d_banks, int64_t bank_floats, float* d_pool,
+                    int64_t pool_rows, int64_t row_floats, void* hip_stream);
+
+/* The dense batch of windows the forward reads: d_dst f32 [B][window], d_dst[b][:] = d_pool[offsets[b] .. offsets[b] + window).
+ * h_offsets is the host's image of d_offsets (int64 [B], in floats); every window must lie inside the pool_floats floats of
+ * d_pool (DZN_E_INVALID with a dzn_last_error(NULL) message otherwise; nothing is launched).  Rows whose source and destination
+ * are both 16-byte aligned move 16 bytes per access (live offsets are multiples of the step), the others take a scalar path.
+ * One launch, enqueue-only, on `hip_stream` of `device` (< 0 = current); B = 0 launches nothing; B <= 65535. */
+int dzn_gather_windows(int32_t device, const float* d_pool, int64_t pool_floats, const int64_t* h_offsets,
+                       const int64_t* d_offsets, int32_t B, int32_t window, float* d_dst, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
