@@ -221,6 +221,8 @@ def load() -> C.CDLL:
     sig("dzn_op_gate", i32, [vp, i64, vp, vp, vp, vp, i64, i32, vp])
     sig("dzn_op_row_stats", i32, [vp, i64, i64, i32, f32, vp, vp])
     sig("dzn_op_gate_stats", i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, vp])
+    sig("dzn_op_gate_heads", i32, [vp, i64, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, f32, vp, vp, i64, i32, vp])
+    sig("dzn_op_stats_finalize", i32, [vp, i64, i32, i32, f32, vp, vp])
     sig("dzn_op_attention_h2", i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp])
     sig("dzn_op_set_attention_qb", i32, [i32])
     sig("dzn_op_set_attention_prefetch", i32, [i32])
@@ -255,7 +257,7 @@ EXPORTED = [
     "dzn_workspace_bytes", "dzn_last_error", "dzn_destroy", "dzn_version", "dzn_linkage_centroid", "dzn_cdist_cosine", "dzn_host_workspace_release",
     "dzn_host_workspace_bytes",
     "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_ingest_many", "dzn_gather_windows", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",
-    "dzn_op_gemm", "dzn_op_split_weights", "dzn_op_split_weights_h2", "dzn_op_split_weights_mx", "dzn_op_set_gemm_mx_cfg", "dzn_checked_status", "dzn_op_set_gemm_cfg", "dzn_op_amax", "dzn_op_conv3x3_c32", "dzn_op_conv3x3_c32_h2", "dzn_op_resblock32_fused", "dzn_op_resblock_ws", "dzn_op_set_resblock_np", "dzn_op_conv3x3_c32_ex", "dzn_op_resblock32_fused_ex", "dzn_op_resblock_ws_ex", "dzn_op_set_attention_noskip", "dzn_op_split_rows", "dzn_op_layernorm", "dzn_op_row_stats", "dzn_op_gate", "dzn_op_gate_stats", "dzn_op_attention", "dzn_op_attention_h2", "dzn_op_attention_planes", "dzn_op_set_attention_qb", "dzn_op_set_attention_prefetch",
+    "dzn_op_gemm", "dzn_op_split_weights", "dzn_op_split_weights_h2", "dzn_op_split_weights_mx", "dzn_op_set_gemm_mx_cfg", "dzn_checked_status", "dzn_op_set_gemm_cfg", "dzn_op_amax", "dzn_op_conv3x3_c32", "dzn_op_conv3x3_c32_h2", "dzn_op_resblock32_fused", "dzn_op_resblock_ws", "dzn_op_set_resblock_np", "dzn_op_conv3x3_c32_ex", "dzn_op_resblock32_fused_ex", "dzn_op_resblock_ws_ex", "dzn_op_set_attention_noskip", "dzn_op_split_rows", "dzn_op_layernorm", "dzn_op_row_stats", "dzn_op_gate", "dzn_op_gate_stats", "dzn_op_gate_heads", "dzn_op_stats_finalize", "dzn_op_attention", "dzn_op_attention_h2", "dzn_op_attention_planes", "dzn_op_set_attention_qb", "dzn_op_set_attention_prefetch",
     "dzn_profile_enable", "dzn_profile_collect", "dzn_profile_reserve", "dzn_op_relpos_bucket",
     "dzn_op_glu_dwconv", "dzn_op_classify", "dzn_op_groupnorm_gelu", "dzn_op_gn_stats_floats", "dzn_op_pad_rows", "dzn_op_ws_accum",
     "dzn_op_ws_sum", "dzn_op_col_scale", "dzn_op_layernorm_t", "dzn_op_wave_stats", "dzn_op_frame_prep", "dzn_op_power",

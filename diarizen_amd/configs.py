@@ -26,7 +26,7 @@ class SegConfig:
     total_heads: int
     layer_norm_first: bool              # encoder_layer_norm_first
     remaining_heads: Tuple[Tuple[int, ...], ...]   # () => layer has no attention
-    ffn_dims: Tuple[int, ...]
+    ffn_dims: Tuple[int, ...]                      # 0 => layer has no feed-forward
     conv_kernels: Tuple[int, ...] = tuple(k for k, _ in _KS)
     conv_strides: Tuple[int, ...] = tuple(s for _, s in _KS)
     pos_conv_kernel: int = 128

@@ -332,7 +332,167 @@ __global__ __launch_bounds__(256) void gate_stats_kernel(const float* __restrict
   }
 }
 
+// gate_stats_kernel without its pass over the whole row, for a row whose producer has left the LayerNorm's partial sums
+// (dzn_gemm_desc.stat_partial: P x (sum, sum of squares) per row, from the epilogue of the contraction that wrote x):
+//   * (mean, rstd) from the partials, added in index order in double — stats_finalize_kernel's expressions
+//     (stats_from_sums), so the same bits; stored for the q/k/v contraction (ln_stats);
+//   * the gate for the h KEPT heads only (head_idx, the attention kernels' list): the gate of head H needs the 64 channels
+//     [64 H, 64 H + 64) of the row and nothing else.  A lane quad takes one (row, kept head), lane sub = lane % 4 its channels
+//     16 sub .. 16 sub + 15 straight from memory; LayerNorm, the pre-summed dot products, the quad sums and the sigmoids are
+//     gate_stats_kernel's, expression for expression.  Columns of gate that belong to other heads are not written.
+// A wavefront has 16 quads and a row needs h of them, so it takes 16 / h rows per pass (quad q: row q / h of the pass, kept
+// head q % h) and walks its passes grid-stride: with one row per pass a third of the lanes had work on the pruned large model
+// (4.5 kept heads on average) and the kernel, one dependent load -> double sum -> dot chain per wavefront at a time, ran at
+// 1.8 TB/s of its few bytes.  Every lane adds the partials of its own row (the quads of a row load the same addresses); nothing
+// crosses a quad.  VEC: x rows are 16-byte aligned (float4 loads).  PT: P at compile time (the loads of the partials go out
+// together), 0 = any P.  Held to 4 wavefronts per SIMD (128 registers): the 16 partials in flight would cost the fourth.
+template <bool VEC, int PT>
+__global__ __launch_bounds__(256, 4) void gate_heads_kernel(const float* __restrict__ x, int64_t ldx,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                         const float* __restrict__ Wg, const float* __restrict__ bg,
+                                                         const float* __restrict__ cst, const int32_t* __restrict__ head_idx,
+                                                         int h, const float2* __restrict__ part, int Prt, int C, float eps,
+                                                         float* __restrict__ gate, float* __restrict__ stats, int64_t rows,
+                                                         int Htot) {
+  __shared__ float sw[2 * 64 + 2];                   // wa[64], wb[64], ba, bb
+  if (threadIdx.x < 128) {
+    const int o0 = threadIdx.x < 64 ? 0 : 4, dch = threadIdx.x & 63;
+    sw[threadIdx.x] = (Wg[(o0 + 0) * 64 + dch] + Wg[(o0 + 1) * 64 + dch]) + (Wg[(o0 + 2) * 64 + dch] + Wg[(o0 + 3) * 64 + dch]);
+  } else if (threadIdx.x < 130) {
+    const int o0 = threadIdx.x == 128 ? 0 : 4;
+    sw[threadIdx.x] = (bg[o0] + bg[o0 + 1]) + (bg[o0 + 2] + bg[o0 + 3]);
+  }
+  __syncthreads();
+  const int P = PT > 0 ? PT : Prt;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane & 3, quad = lane >> 2;
+  float wa[16], wb[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    wa[j] = sw[sub * 16 + j];
+    wb[j] = sw[64 + sub * 16 + j];
+  }
+  const float ba = sw[128], bb = sw[129];
+  const int rpp = 16 / h;                             // rows per pass (1 <= h <= 16)
+  const int rslot = quad / h, hslot = quad - rslot * h;
+  // this lane's head, its 16 channels of gamma / beta and its constant stay in registers across the passes of the wave
+  int H = rslot < rpp ? head_idx[hslot] : -1;
+  if (H >= Htot) H = -1;                              // a list entry outside the row is a head that is not there
+  const bool kept = H >= 0;
+  const int e0 = kept ? H * 64 + sub * 16 : 0;
+  float gm[16], bt[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    gm[j] = kept ? gamma[e0 + j] : 0.f;
+    bt[j] = kept ? beta[e0 + j] : 0.f;
+  }
+  const float cH = kept ? cst[H] : 0.f;
+  const bool writes_stats = rslot < rpp && hslot == 0 && sub == 0;     // one lane per row of the pass, kept head or not
+  for (int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * rpp; row0 < rows; row0 += (int64_t)gridDim.x * 4 * rpp) {
+    const int64_t row = row0 + rslot;
+    const bool live = rslot < rpp && row < rows;
+    const bool work = live && kept;
+    // the head's channels go out first; the partials travel beside them
+    float v[16];
+    if (work) {
+      const float* xp = x + row * ldx + e0;
+      if constexpr (VEC) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float4 t = *reinterpret_cast<const float4*>(xp + 4 * j);
+          v[4 * j] = t.x; v[4 * j + 1] = t.y; v[4 * j + 2] = t.z; v[4 * j + 3] = t.w;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = xp[j];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = 0.f;
+    }
+    double s = 0.0, q = 0.0;
+    if (live) {
+      const float2* pp = part + row * P;
+      if constexpr (PT > 0) {
+        float2 t[PT];
+#pragma unroll
+        for (int p = 0; p < PT; ++p) t[p] = pp[p];
+#pragma unroll
+        for (int p = 0; p < PT; ++p) {
+          s += (double)t[p].x;
+          q += (double)t[p].y;
+        }
+      } else {
+        for (int p = 0; p < P; ++p) {
+          const float2 t = pp[p];
+          s += (double)t.x;
+          q += (double)t.y;
+        }
+      }
+    }
+    const float2 st = stats_from_sums(s, q, C, eps);
+    const float mean = st.x, rstd = st.y;
+    if (live && writes_stats) *reinterpret_cast<float2*>(stats + 2 * row) = st;
+    float ta = 0.f, tb = 0.f;
+    if (work) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const float y = (v[j] - mean) * rstd * gm[j] + bt[j];
+        ta = fmaf(y, wa[j], ta);
+        tb = fmaf(y, wb[j], tb);
+      }
+    }
+    ta = dpp_add<0xB1, 0xF>(ta);   // quad_perm [1,0,3,2]
+    ta = dpp_add<0x4E, 0xF>(ta);   // quad_perm [2,3,0,1] -> every lane of the quad holds the (row, head) sum
+    tb = dpp_add<0xB1, 0xF>(tb);
+    tb = dpp_add<0x4E, 0xF>(tb);
+    if (work && sub == 0) {
+      const float ga = 1.0f / (1.0f + expf(-(ta + ba)));
+      const float gb = 1.0f / (1.0f + expf(-(tb + bb)));
+      gate[row * Htot + H] = ga * (gb * cH - 1.0f) + 2.0f;
+    }
+  }
+}
+
 }  // namespace
+
+int launch_gate_heads(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wg, const float* bg,
+                      const float* cst, const int32_t* head_idx, int h, const float* stat_partial, int P, int C, float eps,
+                      float* gate, float* stats, int64_t rows, int Htot, hipStream_t s) {
+  if (Htot < 1 || Htot > 16 || h < 1 || h > Htot || P < 1 || P > 32 || C < Htot * 64) return DZN_E_INVALID;
+  if (rows <= 0) return DZN_OK;
+  // algorithmic bytes: the kept heads' channels, the partials, (mean, rstd) and the kept gates of every row
+  int pid = prof_enabled() ? prof_begin(s, "gate_heads", 0.0, (double)rows * (h * 64 * 4.0 + P * 8.0 + 8.0 + h * 4.0)) : -1;
+  // one wavefront per pass of 16 / h rows; at most one resident round of workgroups (4 per CU), whose waves walk their
+  // passes grid-stride: per-wave constants are loaded once
+  int64_t grid = cdiv64(cdiv64(rows, 16 / h), 4);
+  grid = grid > 256 * 4 ? 256 * 4 : grid;
+  const bool vec = ((reinterpret_cast<uintptr_t>(x) | (uintptr_t)(ldx * 4)) & 15) == 0;
+#define DZN_GH(VECV, PTV)                                                                                                   \
+  hipLaunchKernelGGL((gate_heads_kernel<VECV, PTV>), dim3((unsigned)grid), dim3(256), 0, s, x, ldx, gamma, beta, Wg, bg, cst, \
+                     head_idx, h, reinterpret_cast<const float2*>(stat_partial), P, C, eps, gate, stats, rows, Htot)
+#define DZN_GHP(PTV)   \
+  do {                 \
+    if (vec) DZN_GH(true, PTV); \
+    else DZN_GH(false, PTV);    \
+  } while (0)
+  if (P == 8) DZN_GHP(8);          // the 128-wide four-wavefront tile at N = 1024
+  else if (P == 16) DZN_GHP(16);   // the 64-wide tile at N = 1024
+  else DZN_GHP(0);
+#undef DZN_GHP
+#undef DZN_GH
+  prof_end(pid, s);
+  return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+extern "C" int dzn_op_gate_heads(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wg,
+                                 const float* bg, const float* cst, const int32_t* head_idx, int32_t h,
+                                 const float* stat_partial, int32_t P, int32_t C, float eps, float* gate, float* stats,
+                                 int64_t rows, int32_t Htot, void* stream) {
+  if (!x || !gamma || !beta || !Wg || !bg || !cst || !head_idx || !stat_partial || !gate || !stats) return DZN_E_INVALID;
+  return launch_gate_heads(x, ldx, gamma, beta, Wg, bg, cst, head_idx, h, stat_partial, P, C, eps, gate, stats, rows, Htot,
+                           reinterpret_cast<hipStream_t>(stream));
+}
 
 int launch_gate_stats(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wg,
                       const float* bg, const float* cst, float* gate, float* stats, int64_t rows, int Htot, float eps,

@@ -39,6 +39,16 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// (mean, rstd) of a row of C elements from its (sum, sum of squares), both accumulated in double from the fp32 partials a
+// contraction epilogue left (dzn_gemm_desc.stat_partial).  The one statement of it: stats_finalize_kernel and
+// gate_heads_kernel give the same bits from the same partials.
+__device__ __forceinline__ float2 stats_from_sums(double s, double q, int C, float eps) {
+  const double mean = s / C;
+  double var = q / C - mean * mean;
+  var = var > 0.0 ? var : 0.0;
+  return make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
+}
+
 // |max| tracker of an activation tensor (DZN_PREC_F32_H2: the consumer scales its fp16 split by it).  One call per
 // wavefront with the wave's partial maximum.  |x| >= 0, so the IEEE bit patterns order like unsigned integers and
 // the atomic max is order independent (deterministic).  The tracker is read first (device-scope load: the value
@@ -96,6 +106,7 @@ static inline bool prec_is_split(int p) { return p == DZN_PREC_F32_SPLIT || prec
 
 // ---- kernel launchers (implemented in the .hip files) ----
 int launch_gemm(const dzn_gemm_desc& d, hipStream_t s);
+int gemm_stat_partials_last();   // partials per row left by this thread's last launch_gemm with stat_partial set (gemm_launch.h)
 int launch_gemm_split(const dzn_gemm_desc& d, hipStream_t s); // gemm_split.hip: fp32 via 3-way bf16 split
 int launch_gemm_split_pre(const dzn_gemm_desc& d, hipStream_t s);  // gemm_split_pre.hip: A pre-split planes
 int launch_pad_rows_split3(const float* x, void* planes, int64_t plane_stride, int B, int L, int Lp, int pad, int D,
@@ -125,6 +136,10 @@ int launch_row_stats(const float* x, int64_t ldx, int64_t rows, int C, float eps
 int launch_gate_stats(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wg,
                       const float* bg, const float* cst, float* gate, float* stats, int64_t rows, int Htot, float eps,
                       hipStream_t s);
+// the gate of the h kept heads (head_idx) + (mean, rstd) from the P partial sums per row a producing epilogue left
+int launch_gate_heads(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wg, const float* bg,
+                      const float* cst, const int32_t* head_idx, int h, const float* stat_partial, int P, int C, float eps,
+                      float* gate, float* stats, int64_t rows, int Htot, hipStream_t s);
 int launch_wave_stats(const float* w, int B, int N, float eps, float* stats, hipStream_t s);
 int launch_gate(const float* y, int64_t ldy, const float* Wg, const float* bg, const float* cst,
                 float* gate, int64_t rows, int Htot, hipStream_t s);

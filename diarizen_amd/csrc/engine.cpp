@@ -82,6 +82,9 @@ struct EncLayer {
   Lin out, f2;
   float *Wg = nullptr, *bg = nullptr, *cst = nullptr;
   int32_t* head_idx = nullptr;
+  // the rows this layer's first LayerNorm reads come with their statistics: the previous layer's FFN-down epilogue leaves
+  // the partial sums (decided at finalize: Switches::epilogue_stats, pre-norm, both norms folded, a predecessor with an FFN)
+  bool stats_in = false;
 };
 
 struct ConfLayer {
@@ -161,7 +164,7 @@ Switches read_switches() {
   s.conv01_ln = !getenv("DZN_CONV01_NO_LN");                // =1: the fused conv0 -> conv1 kernel leaves conv1's LayerNorm + GELU to the row pass
   s.ws_defer = !getenv("DZN_NO_WS_DEFER");                  // =1: layer-weighted sum as a read-modify-write in every FFN-output epilogue
   s.att_planes = !getenv("DZN_NO_ATT_PLANES");              // =1: fp32 K / V and the in-kernel split of attention_split.hip (f32h)
-  s.epilogue_stats = !getenv("DZN_NO_EPILOGUE_STATS");      // =1: the FFN's LayerNorm statistics by row_stats, not from the out_proj epilogue
+  s.epilogue_stats = !getenv("DZN_NO_EPILOGUE_STATS");      // =1: every LayerNorm's statistics by a pass over its rows (gate_stats / row_stats), none from a producing epilogue
   s.emb_skip = !getenv("DZN_EMB_NO_SKIP");                  // =1: windows without an active speaker go through the trunk too
   s.fuse_resblock = !getenv("DZN_NO_RESBLOCK_FUSION");      // =1: the per-conv kernels for the stride-1 BasicBlocks
   s.fuse_shortcut = !getenv("DZN_NO_SHORTCUT_FUSION");      // =1: the 1x1 shortcut of a down-sampling block as its own launch
@@ -658,6 +661,25 @@ void finalize_seg(H* h) {
   if (h->rel_embed.empty())
     throw EngineError(DZN_E_INVALID, "layer 0 must carry attention (rel_attn_embed lives there)");
   {
+    // LayerNorm statistics from the epilogue of the contraction that writes the rows (dzn_gemm_desc.stat_partial): LN2's from
+    // out_proj, and LN1's of layer i from the FFN-down of layer i - 1.  Layer 0 (rows from the positional conv), a layer behind
+    // one without an FFN, post-norm models and unfolded norms keep the pass over the rows (gate_stats / row_stats).
+    bool any = false;
+    for (int i = 0; i < c.n_layers; ++i) {
+      EncLayer& L = h->layers[i];
+      if (!h->sw.epilogue_stats) break;
+      any = any || (L.attn && L.ffn && L.f1.folded);
+      if (i == 0 || !L.pre_norm || !h->layers[i - 1].ffn) continue;
+      L.stats_in = L.attn ? (L.qkv.folded && D == h->H * 64 && h->H <= 16) : (L.ffn && L.f1.folded);
+      any = any || L.stats_in;
+    }
+    // spart holds 32 partials per row; a contraction over N = D columns leaves one per wavefront tile, the narrowest of which
+    // (any family, any forced tile) is 32 columns wide in 64-column steps
+    if (any && 2 * ((D + 63) / 64) > 32)
+      throw EngineError(DZN_E_INVALID, "encoder_embed_dim > 1024: the epilogue's row statistics need more than 32 partials per row "
+                                       "(DZN_NO_EPILOGUE_STATS=1 runs without them)");
+  }
+  {
     const HostT& w = need(h, "weight_sum.weight");
     expect_numel(w, c.n_layers + 1, "weight_sum.weight");
     h->wsum_w = w.v;
@@ -1118,6 +1140,7 @@ struct SegCall {
   hipStream_t st;
   int B, L;
   int64_t ML;   // B * L: rows of every [B*L, .] tensor
+  int stat_P = 0;   // partials per row the last FFN-down epilogue left in spart for the next layer (EncLayer::stats_in)
   // DZN_PREC_F32_H2: |max| trackers (see dzn_handle::amax).  am(slot) is NULL in the other modes, which makes
   // every contraction take its bf16 three-term / fp32 kernel.  slot < 0: a tensor without a tracker.
   float* am(int slot) const {
@@ -1324,7 +1347,7 @@ void seg_project(const SegCall& s, float* feat) {
 
 // ---- transformer layer i (components.py:920-942) over the residual stream xr; returns where its output rows live.
 // `wsum`: the deferred layer-weighted sum (h->xl), which notes (rows, weight) per layer; else the layer adds its rows to `ws` ----
-float* seg_encoder_layer(const SegCall& s, int i, float* xr, WsSumArgs& wsum) {
+float* seg_encoder_layer(SegCall& s, int i, float* xr, WsSumArgs& wsum) {
   H* h = s.h;
   hipStream_t st = s.st;
   const int L = s.L, D = h->D;
@@ -1333,13 +1356,21 @@ float* seg_encoder_layer(const SegCall& s, int i, float* xr, WsSumArgs& wsum) {
   const bool defer = h->xl != nullptr;
   const float wl = h->wsum_w[i + 1];
   float* const own = defer ? h->xl + (int64_t)i * ML * D : xr;   // where this layer's output rows live
-  bool have_stats = false;   // LN2's statistics already left in rstat by the out_proj epilogue
+  // the statistics of the rows the next folded LayerNorm reads are already in rstat: left by the previous layer's FFN-down
+  // epilogue (an attention-less layer with stats_in), further down by this layer's out_proj epilogue
+  bool have_stats = Ly.stats_in && !Ly.attn;
   if (Ly.attn) {
     const int hd = Ly.h * 64;
-    // folded LN1: one pass over x gives the LN statistics for the q/k/v contraction + the gate on LN(x) (never written);
-    // else the gate reads what the contraction reads
+    // folded LN1: the q/k/v contraction needs the LN statistics and the attention the gate on LN(x), which is never written.
+    // stats_in: the previous layer's FFN-down left the rows' partial sums in spart -> gate_heads finishes the statistics and
+    // reads the kept heads' channels only; else one pass over the whole rows gives both (gate_stats).
+    // Unfolded: the gate reads what the contraction reads.
     const bool gs = Ly.qkv.folded;
-    if (gs)
+    if (gs && Ly.stats_in)
+      chk(launch_gate_heads(xr, D, Ly.ln1.g, Ly.ln1.b, Ly.Wg, Ly.bg, Ly.cst, Ly.head_idx, Ly.h, h->spart, s.stat_P, D, 1e-5f,
+                            h->gate, h->rstat, ML, h->H, st),
+          "gate_heads");
+    else if (gs)
       chk(launch_gate_stats(xr, D, Ly.ln1.g, Ly.ln1.b, Ly.Wg, Ly.bg, Ly.cst, h->gate, h->rstat, ML, h->H, 1e-5f, st),
           "gate_stats");
     dzn_gemm_desc d = norm_lin_desc(s, Ly.qkv, xr, dzn_handle::AM_X, h->y, dzn_handle::AM_Y, h->qkv, 3 * hd, gs);
@@ -1385,7 +1416,17 @@ float* seg_encoder_layer(const SegCall& s, int i, float* xr, WsSumArgs& wsum) {
     }
     f2.a_amax = s.am(dzn_handle::AM_MID);
     f2.c_amax = s.am(dzn_handle::AM_X);
+    const EncLayer* next = i + 1 < h->cfg.n_layers ? &h->layers[i + 1] : nullptr;
+    if (next && next->stats_in) {
+      // the rows it writes are what the next layer's first (folded) LayerNorm normalises: leave their partial sums.  Before
+      // an attention layer nothing finalizes them (stat_final stays null): its gate_heads does, from s.stat_P partials per row
+      f2.stat_partial = h->spart;
+      f2.stat_final = next->attn ? nullptr : h->rstat;
+      f2.stat_C = D;
+      f2.stat_eps = 1e-5f;
+    }
     s.gemm(f2, CLS_FFN2);
+    if (f2.stat_partial) s.stat_P = gemm_stat_partials_last();
     xr = own;
   } else if (Ly.pre_norm && !defer) {
     chk(launch_ws_accum(xr, h->ws, wl, 0, ML * D, st), "ws_accum");
@@ -1481,7 +1522,7 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
   if (L < 1) throw EngineError(DZN_E_INVALID, "window too short");
   const int D = h->D, A = h->A;
   const int64_t ML = (int64_t)B * L, MB = c.max_batch;
-  const SegCall s{h, st, B, L, ML};
+  SegCall s{h, st, B, L, ML};
   if (prec_is_h2(c.precision)) {
     chk(launch_fill_u32(h->amax, 0u, dzn_handle::AM_IMG0 * MB, st), "tracker reset");
     if (c.extractor_layer_norm && h->conv0_bound > 0.f) {   // conv0 (LN + GELU) writes bufA: static bound instead of a tracker

@@ -376,6 +376,8 @@ int launch_gemm(const dzn_gemm_desc& din, hipStream_t s) {
   return launch_f32(d, s);
 }
 
+int gemm_stat_partials_last() { return g_stat_partials_last; }
+
 extern "C" int dzn_op_set_gemm_cfg(const char* cfg) {
   g_gemm_cfg.set(cfg);
   return DZN_OK;

@@ -36,6 +36,11 @@ inline bool gemm_no_h2() {
   return v;
 }
 
+// Partials per row (column tiles x wavefront columns) that the last contraction launched by this thread with stat_partial set
+// left: what a caller that reduces the partials itself (stat_final == NULL) passes on as their count.  Known only here,
+// where the tile has been chosen.
+inline thread_local int g_stat_partials_last = 0;
+
 // profiler record of one contraction launch: class gemm_<tag>_<BM>x<BN>, by shape under DZN_PROFILE_SHAPES
 inline int gemm_prof_begin(const dzn_gemm_desc& d, hipStream_t s, const char* tag, int BM, int BN, int w_bytes_per_elem) {
   if (!prof_enabled()) return -1;
@@ -61,6 +66,7 @@ int launch_contraction(const dzn_gemm_desc& d, hipStream_t s, int threads, size_
   hipLaunchKernelGGL(KERN, dim3(tilesM * tilesN, d.nz > 0 ? d.nz : 1, 1), dim3(threads), lds, s, d, extra...);
   prof_end(pid, s);
   if (hipGetLastError() != hipSuccess) return DZN_E_HIP;
+  if (d.stat_partial) g_stat_partials_last = tilesN * WGN;
   if (d.stat_partial && d.stat_final)
     return launch_stats_finalize(d.stat_partial, d.M, tilesN * WGN, d.stat_C, d.stat_eps, d.stat_final, s);
   return DZN_OK;

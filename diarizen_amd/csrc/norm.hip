@@ -121,10 +121,7 @@ __global__ __launch_bounds__(256) void stats_finalize_kernel(const float2* __res
     s += (double)v.x;
     q += (double)v.y;
   }
-  const double mean = s / C;
-  double var = q / C - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  stats[r] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
+  stats[r] = stats_from_sums(s, q, C, eps);
 }
 
 // mean / rstd of each window's N samples (F.layer_norm(waveforms, waveforms.shape), W2V/model.py:113)
@@ -364,6 +361,12 @@ int launch_row_stats(const float* x, int64_t ldx, int64_t rows, int C, float eps
 #undef DZN_RS
   prof_end(pid, s);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+extern "C" int dzn_op_stats_finalize(const float* partial, int64_t rows, int32_t P, int32_t C, float eps, float* stats,
+                                     void* stream) {
+  if (!partial || !stats) return DZN_E_INVALID;
+  return launch_stats_finalize(partial, rows, P, C, eps, stats, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int dzn_op_row_stats(const float* x, int64_t ldx, int64_t rows, int32_t C, float eps, float* stats,

@@ -47,7 +47,7 @@ def make_dzn_config(seg: SegConfig, emb: Optional[EmbConfig], max_batch: int, ma
         c.n_heads[i] = len(heads)
         for j, hd in enumerate(heads):
             c.head_idx[i][j] = hd
-        c.use_ffn[i] = 1
+        c.use_ffn[i] = int(seg.ffn_dims[i] > 0)     # width 0: a layer pruned down to its attention
         c.ffn_dim[i] = seg.ffn_dims[i]
     c.attention_in = seg.attention_in
     c.ffn_hidden = seg.ffn_hidden

@@ -435,6 +435,36 @@ def gate_stats(x, gamma, beta, Wg, bg, cst, eps=1e-5, out=None):
     return gate_, stats
 
 
+def stats_finalize(partial, C, eps=1e-5, out=None):
+    """(mean, rstd) f32 [rows, 2] of rows of C elements from the partials f32 [rows, P, 2] (sum, sum of squares) a contraction
+    epilogue left (dzn_gemm_desc.stat_partial): what the contraction launcher runs when stat_final is set"""
+    lib = _lib.load()
+    rows, P = partial.shape[0], partial.shape[1]
+    assert partial.is_contiguous() and partial.dtype == torch.float32 and partial.shape[2] == 2
+    if out is None:
+        out = torch.empty((rows, 2), device=partial.device, dtype=torch.float32)
+    check(lib.dzn_op_stats_finalize(_p(partial), rows, P, C, eps, _p(out), _stream()), what="dzn_op_stats_finalize")
+    return out
+
+
+def gate_heads(x, gamma, beta, Wg, bg, cst, head_idx, partial, eps=1e-5, out=None, h=None, P=None):
+    """gate_stats for rows whose LayerNorm partial sums are given (partial f32 [rows, P, 2], P <= 32): stats [rows, 2] from the
+    partials, and gate[:, H] for the heads H in head_idx (int32, device) from their 64 channels of x alone; the other columns
+    of gate keep what they held.  out = caller-owned (gate [rows, Htot], stats), both contiguous; h / P override the counts
+    taken from head_idx / partial (tests of the argument checks)."""
+    lib = _lib.load()
+    rows, Htot = x.shape[0], cst.numel()
+    assert head_idx.dtype == torch.int32 and partial.dtype == torch.float32 and partial.is_contiguous()
+    if out is None:
+        out = (torch.empty((rows, Htot), device=x.device, dtype=torch.float32),
+               torch.empty((rows, 2), device=x.device, dtype=torch.float32))
+    gate_, stats = out
+    check(lib.dzn_op_gate_heads(_p(x), x.stride(0), _p(gamma), _p(beta), _p(Wg), _p(bg), _p(cst), _p(head_idx),
+                                head_idx.numel() if h is None else h, _p(partial), partial.shape[1] if P is None else P,
+                                Htot * 64, eps, _p(gate_), _p(stats), rows, Htot, _stream()), what="dzn_op_gate_heads")
+    return gate_, stats
+
+
 def gate(y, Wg, bg, cst, out=None):
     lib = _lib.load()
     rows = y.shape[0]

@@ -265,6 +265,17 @@ int dzn_op_gate(const float* y, int64_t ldy, const float* Wg, const float* bg, c
 int dzn_op_gate_stats(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wg,
                       const float* bg, const float* cst, float* gate, float* stats, int64_t rows, int32_t Htot,
                       float eps, void* stream);
+/* (mean, rstd) [rows][2] of rows of C elements from P (sum, sum of squares) pairs per row, f32 [rows][P][2], as a contraction
+ * epilogue leaves them (dzn_gemm_desc.stat_partial): the kernel dzn_op_gemm runs when stat_final is set */
+int dzn_op_stats_finalize(const float* partial, int64_t rows, int32_t P, int32_t C, float eps, float* stats, void* stream);
+/* the same for rows whose LayerNorm partial sums a producing contraction has left (dzn_gemm_desc.stat_partial, P <= 32 pairs
+ * of (sum, sum of squares) per row, over C = Htot*64 channels): stats [rows][2] = what the finalize kernel gives from the same
+ * partials, bit for bit, and gate[row, H] for the h heads H listed in head_idx (i32 [h], device) — only their 64 channels of x
+ * are read; the other columns of gate are left as they are.  DZN_E_INVALID unless 1 <= h <= Htot <= 16 and 1 <= P <= 32. */
+int dzn_op_gate_heads(const float* x, int64_t ldx, const float* gamma, const float* beta, const float* Wg,
+                      const float* bg, const float* cst, const int32_t* head_idx, int32_t h, const float* stat_partial,
+                      int32_t P, int32_t C, float eps, float* gate, float* stats, int64_t rows, int32_t Htot,
+                      void* stream);
 
 /* the same attention in the fp16 two-term arithmetic (DZN_PREC_F32_H2): amax = f32 [B], |max| of each window's qkv */
 int dzn_op_attention_h2(const float* qkv, float* out, const float* gate, const float* table, const int32_t* head_idx,
