@@ -37,11 +37,12 @@ __global__ __launch_bounds__(256) void prepare_masks_kernel(const uint8_t* __res
     if (median > 1) {
       int ones = 0;
       for (int d = -half; d <= half; ++d) {
+        // scipy 'reflect' (d c b a | a b c d | d c b a) has period 2L: a window longer than the signal reflects again
         int tt = t + d;
-        // scipy 'reflect' (d c b a | a b c d | d c b a); windows longer than the signal clamp
-        if (tt < 0) tt = -tt - 1;
-        if (tt >= L) tt = 2 * L - tt - 1;
-        tt = tt < 0 ? 0 : (tt >= L ? L - 1 : tt);
+        if (tt < 0 || tt >= L) {
+          const int m = ((tt % (2 * L)) + 2 * L) % (2 * L);
+          tt = m < L ? m : 2 * L - 1 - m;
+        }
         ones += raw[tt * S + s];
       }
       v = ones > half ? 1 : 0;
