@@ -41,4 +41,5 @@
 
 // check ids: 0x1xx gemm_split, 0x2xx gemm_mx, 0x3xx gemm_split_pre, 0x4xx resblock_fused, 0x5xx resblock_ws,
 //            0x60x attention_split, 0x61x attention_planes, 0x7xx frontend_fused, 0x80x post (detection), 0x81x post (speaker scores),
-//            0x82x resample / decode / ingest (0x828 ..), 0x83x post (diarize range)
+//            0x82x resample / decode / ingest (0x828 ..), 0x83x post (diarize range),
+//            0x84x gallery (0x840 row-tile index, 0x841 partial-list write, 0x842 survivor queue)

@@ -121,6 +121,17 @@ int launch_split_weights_h2(const float* W, int64_t rows, int K, int64_t ldw, vo
 int host_stage_stream(int device, hipStream_t* stream);
 int host_state_lease(int device, size_t bytes, hipStream_t* stream, char** base);
 void host_state_release(int device);
+// one call's hold on that context for a translation unit outside linkage.hip (gallery.hip): the context's mutex is held while
+// the object lives; `stream` is the host stage's stream and `base` at least `bytes` of its per-call arena (nullptr for 0 bytes)
+struct HostScratch {
+  int rc = 0;
+  hipStream_t stream = nullptr;
+  char* base = nullptr;
+  HostScratch(int device, size_t bytes);
+  ~HostScratch();
+  HostScratch(const HostScratch&) = delete;
+  HostScratch& operator=(const HostScratch&) = delete;
+};
 int launch_gemm_mx(const dzn_gemm_desc& d, hipStream_t s);   // gemm_mx.hip: fp16 hi*hi + fp8 cross terms (DZN_PREC_F16)
 int launch_split_weights_mx(const float* W, int64_t rows, int K, int64_t ldw, void* Wmx, float* col_scale, hipStream_t s);
 int launch_amax(const float* x, int64_t n, float* amax, hipStream_t s);

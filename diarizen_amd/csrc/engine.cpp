@@ -2177,6 +2177,7 @@ int dzn_checked_collect_frontend_fused(unsigned int*, int);
 int dzn_checked_collect_post(unsigned int*, int);
 int dzn_checked_collect_resample(unsigned int*, int);
 int dzn_checked_collect_ingest(unsigned int*, int);
+int dzn_checked_collect_gallery(unsigned int*, int);
 }
 #endif
 int dzn_checked_status(uint32_t* out4, int32_t reset) {
@@ -2186,7 +2187,7 @@ int dzn_checked_status(uint32_t* out4, int32_t reset) {
                             dzn_checked_collect_resblock_fused, dzn_checked_collect_resblock_ws,
                             dzn_checked_collect_attention_split, dzn_checked_collect_attention_planes,
                             dzn_checked_collect_frontend_fused, dzn_checked_collect_post,
-                            dzn_checked_collect_resample, dzn_checked_collect_ingest};
+                            dzn_checked_collect_resample, dzn_checked_collect_ingest, dzn_checked_collect_gallery};
   unsigned int tot[4] = {0u, 0u, 0u, 0u};
   for (collect_fn f : fns) {
     unsigned int w[4] = {0u, 0u, 0u, 0u};

@@ -567,6 +567,16 @@ int host_state_lease(int device, size_t bytes, hipStream_t* stream, char** base)
   return DZN_OK;
 }
 
+// gallery.hip: one call's hold on the context — the mutex from construction to destruction, the stream, and `bytes` of the
+// per-call arena (the same discipline as the two entry points below, for a translation unit that cannot see HostCtx)
+HostScratch::HostScratch(int device, size_t bytes) {
+  g_host_mu.lock();
+  HostCtx* c = nullptr;
+  rc = host_ctx(device, bytes, &c);
+  if (rc == DZN_OK) { stream = c->stream; base = bytes ? c->base : nullptr; }
+}
+HostScratch::~HostScratch() { g_host_mu.unlock(); }
+
 void host_state_release(int device) {
   std::lock_guard<std::mutex> lk(g_host_mu);
   int dev = device;

@@ -81,6 +81,12 @@ class LiveDiarization(CommittedStream):
         return self.speakers.num_speakers
 
     @property
+    def centroids(self) -> np.ndarray:
+        """float64 [num_speakers, dim]: the centroid of every label opened so far, row k = label k (a copy; what
+        identification.SpeakerIdentification.identify_live scores against a gallery)"""
+        return np.array(self.speakers.centroids, dtype=np.float64, copy=True)
+
+    @property
     def hard_clusters(self) -> np.ndarray:
         """int8 [done, S]: the label of every local speaker of every window so far, -2 = none (a copy)"""
         return self._hard_h.copy()

@@ -398,6 +398,65 @@ class VbxState:
             pass
 
 
+class GalleryState:
+    """a device-resident gallery of L2-normalised fp32 rows and the cosine search over it (csrc/gallery.hip): host arrays in,
+    host arrays out; see diarizen_amd/identification.py:SpeakerGallery for the bookkeeping that drives it."""
+
+    def __init__(self, dim: int, capacity: int, device: int = -1):
+        import numpy as np
+        self.np, self.lib = np, _lib.load()
+        self.dim, self.capacity = int(dim), int(capacity)
+        self.state = C.c_void_p()
+        check(self.lib.dzn_gallery_create(device, self.dim, self.capacity, C.byref(self.state)), what="dzn_gallery_create")
+        g = [C.c_int32(0) for _ in range(4)]
+        check(self.lib.dzn_gallery_geometry(self.state, *[C.byref(v) for v in g]), what="dzn_gallery_geometry")
+        self.tile_rows, self.sweep_rows, self.query_group, self.max_top_n = (v.value for v in g)
+
+    @property
+    def rows(self) -> int:
+        """highest slot ever put + 1: the width of the dense output"""
+        n = C.c_int64(0)
+        check(self.lib.dzn_gallery_rows(self.state, C.byref(n)), what="dzn_gallery_rows")
+        return n.value
+
+    def put(self, slot: int, vecs) -> None:
+        v = self.np.ascontiguousarray(vecs, dtype=self.np.float32).reshape(-1, self.dim)
+        check(self.lib.dzn_gallery_put(self.state, int(slot), v.ctypes.data_as(C.c_void_p), v.shape[0]), what="dzn_gallery_put")
+
+    def drop(self, slot: int, count: int = 1) -> None:
+        check(self.lib.dzn_gallery_drop(self.state, int(slot), int(count)), what="dzn_gallery_drop")
+
+    def search(self, queries, top_n: int, dense: bool = False):
+        """queries f32 [Q, dim] -> (scores f32 [Q, top_n], slots i64 [Q, top_n]) (+ every score f32 [Q, rows] with dense=True)"""
+        np = self.np
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        Q = q.shape[0]
+        scores = np.empty((Q, int(top_n)), dtype=np.float32)
+        slots = np.empty((Q, int(top_n)), dtype=np.int64)
+        d = np.empty((Q, self.rows), dtype=np.float32) if dense else None
+        check(self.lib.dzn_gallery_search(self.state, q.ctypes.data_as(C.c_void_p), Q, int(top_n),
+                                          scores.ctypes.data_as(C.c_void_p), slots.ctypes.data_as(C.c_void_p),
+                                          d.ctypes.data_as(C.c_void_p) if dense else None), what="dzn_gallery_search")
+        return (scores, slots, d) if dense else (scores, slots)
+
+    def last_launch_ms(self):
+        """(HIP-event time of the last search's launches, the share of its last merge), in ms"""
+        ms, merge = C.c_float(0.0), C.c_float(0.0)
+        check(self.lib.dzn_gallery_last_launch_ms(self.state, C.byref(ms), C.byref(merge)), what="dzn_gallery_last_launch_ms")
+        return ms.value, merge.value
+
+    def close(self):
+        if self.state:
+            self.lib.dzn_gallery_destroy(self.state)
+            self.state = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # pragma: no cover
+            pass
+
+
 def layernorm(x, gamma, beta, C_true=None, eps=1e-5, gelu=False, out=None):
     lib = _lib.load()
     rows, ld = x.shape[0], x.stride(0)

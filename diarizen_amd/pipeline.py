@@ -81,7 +81,7 @@ def _load_checkpoint(path: str) -> Dict[str, torch.Tensor]:
 
 def run_host_stage(seg: np.ndarray, emb: np.ndarray, *, chunks: SlidingWindow, clustering, min_speakers: int,
                    max_speakers: int, sample_rate: int = 16000, sess_name: Optional[str] = None,
-                   device=None, hook=None, soft=None, num_frames: Optional[int] = None):
+                   device=None, hook=None, soft=None, num_frames: Optional[int] = None, return_embeddings: bool = False):
     """The host half of `DiariZenPipeline.__call__` (diarizen/pipelines/inference.py:137-185): speaker
     counting -> clustering -> inactive speakers to -2 -> reconstruction -> Binarize.  Needs no device, so
     it is checked on the CPU against the oracle's loop-for-loop restatement (tests/test_host.py).
@@ -91,7 +91,10 @@ def run_host_stage(seg: np.ndarray, emb: np.ndarray, *, chunks: SlidingWindow, c
     `device` given, dzn_speaker_scores aggregates it and only [T, K] comes back) or a host array.  The return value is then
     (Annotation, per-speaker activity scores as a SlidingWindowFeature [T, K]): column k is cluster k = label k of the
     Annotation, T = num_frames (the cropped length) or every frame of the aggregation; the hook sees them as
-    "speaker_scores".  The Annotation is the one a call without `soft` returns."""
+    "speaker_scores".  The Annotation is the one a call without `soft` returns.
+    return_embeddings=True: the clustering's centroids (its third return value, unchanged) go to the hook as "centroids" and
+    are appended to the return value as float32 [K, dim], row k = cluster k: (Annotation, embeddings) or
+    (Annotation, scores, embeddings)."""
     hook = hook or (lambda *a, **k: None)
     frames = receptive_field(sample_rate)
     hard_decisions = seg.dtype == np.uint8
@@ -101,9 +104,13 @@ def run_host_stage(seg: np.ndarray, emb: np.ndarray, *, chunks: SlidingWindow, c
     count = post.speaker_count() if post is not None else speaker_count(segf, chunks, frames)
     hook("speaker_counting", count)
     # the clustering only counts frames of `segmentations`: u8 decisions are counted as bytes (clustering.py)
-    hard, _, _ = clustering(embeddings=emb.astype(np.float64) if emb.dtype != np.float32 else emb,
+    hard, _, centroids = clustering(embeddings=emb.astype(np.float64) if emb.dtype != np.float32 else emb,
                             segmentations=seg if hard_decisions else segf, min_clusters=min_speakers,
                             max_clusters=max_speakers)
+    embeddings = None
+    if return_embeddings:      # (a call without the flag keeps the reference's hook steps, and only those)
+        hook("centroids", centroids)
+        embeddings = np.asarray(centroids, dtype=np.float32)
     count.data = np.minimum(count.data, max_speakers).astype(np.int8)
     inactive = ~active_speakers(seg) if hard_decisions else np.sum(segf, axis=1) == 0
     hard = np.array(hard, copy=True)
@@ -115,7 +122,7 @@ def run_host_stage(seg: np.ndarray, emb: np.ndarray, *, chunks: SlidingWindow, c
     hook("discrete_diarization", discrete)
     result = binarize(discrete, onset=0.5, offset=0.5, uri=sess_name)
     if soft is None:
-        return result
+        return (result, embeddings) if return_embeddings else result
     if post is not None and isinstance(soft, torch.Tensor) and soft.is_cuda:
         scores = post.speaker_scores(hard, soft, num_frames)
     else:
@@ -123,7 +130,7 @@ def run_host_stage(seg: np.ndarray, emb: np.ndarray, *, chunks: SlidingWindow, c
         if num_frames is not None:
             scores.data = np.ascontiguousarray(scores.data[:int(num_frames)])
     hook("speaker_scores", scores)
-    return result, scores
+    return (result, scores, embeddings) if return_embeddings else (result, scores)
 
 
 def load_hub_config(hub: Path) -> Dict[str, Any]:
@@ -367,14 +374,15 @@ class DiariZenPipeline:
         return seg.numpy(), emb.numpy()
 
     def host_stage(self, seg: np.ndarray, emb: np.ndarray, sess_name: Optional[str] = None, hook=None, soft=None,
-                   num_frames: Optional[int] = None):
+                   num_frames: Optional[int] = None, return_embeddings: bool = False):
         """counting -> clustering -> reconstruction -> Annotation (inference.py:137-185); with `soft` (the device tensor of
-        device_stage(with_scores=True)) -> (Annotation, per-speaker activity scores [T, K]), see run_host_stage."""
+        device_stage(with_scores=True)) -> (Annotation, per-speaker activity scores [T, K]), see run_host_stage;
+        return_embeddings=True appends the cluster centroids f32 [K, 256]."""
         return run_host_stage(seg, emb, chunks=self.chunks_window(), clustering=self.clustering,
                               min_speakers=self.min_speakers, max_speakers=self.max_speakers,
                               sample_rate=self.segmentation_model.sample_rate, sess_name=sess_name,
                               device=self.device if self.device_postprocess else None, hook=hook, soft=soft,
-                              num_frames=num_frames)
+                              num_frames=num_frames, return_embeddings=return_embeddings)
 
     _ONE_DEVICE = ("%s runs on one device: the soft scores of a recording sharded over torch.distributed ranks are not "
                    "gathered (world size %d)")
@@ -525,7 +533,8 @@ class DiariZenPipeline:
                               resample=self.resample, device=self.device, channel=self.channel)
 
     # ------------------------------------------------------------------ __call__
-    def __call__(self, in_wav, sess_name: Optional[str] = None, hook=None, return_scores: bool = False):
+    def __call__(self, in_wav, sess_name: Optional[str] = None, hook=None, return_scores: bool = False,
+                 return_embeddings: bool = False):
         """`hook` (optional, not in the reference's DiariZenPipeline signature but in the pyannote pipeline it
         derives from): hook(step_name, step_artifact, file=..., total=..., completed=...) as
         PA/pipelines/utils/hook.py:36-224 expects (ProgressHook / ArtifactHook / TimingHook work unchanged).
@@ -537,7 +546,13 @@ class DiariZenPipeline:
         soft=True)) mapped to the clusters as reconstruct does and aggregated with Inference.aggregate(hamming=True,
         missing=0.0).  Column k is cluster k, the integer label k of the Annotation (K = max(hard_clusters) + 1: a cluster
         that never wins a frame keeps its column); T is cropped at the end of the audio when the last window was zero-padded.
-        The Annotation and the RTTM file are those of a call without the flag; the hook also sees "speaker_scores"."""
+        The Annotation and the RTTM file are those of a call without the flag; the hook also sees "speaker_scores".
+        return_embeddings=True (SpeakerDiarization.apply(return_embeddings=True), PA/pipelines/speaker_diarization.py:433,
+        612-636): -> (Annotation, embeddings), or (Annotation, scores, embeddings) together with return_scores.  embeddings is
+        float32 [K, 256], the clustering's centroids: row k is cluster k, the integer label k of the Annotation — the convention
+        of the return_scores columns, a cluster that wins no frame keeps its row.  One deviation from pyannote: it re-orders
+        the rows by `labels()`; our labels already are the cluster indices, so nothing is re-ordered.  The Annotation and the
+        RTTM file are those of a call without the flag; in a sharded run rank 0 has the centroids (other ranks: None)."""
         import functools
         import time
         file = in_wav if isinstance(in_wav, Mapping) else {"audio": in_wav}
@@ -560,7 +575,7 @@ class DiariZenPipeline:
             hook("segmentation", SlidingWindowFeature(seg, self.chunks_window()))
             hook("embeddings", emb)
         t2 = time.perf_counter()
-        result = scores = None
+        result = scores = embeddings = None
         if dz_dist.rank() == 0:
             if return_scores:
                 r = self._runner
@@ -568,7 +583,12 @@ class DiariZenPipeline:
                                          receptive_field(self.segmentation_model.sample_rate))
                 if window_plan(num_samples, r.window, r.step)[1]:
                     T = crop_end(T, grid, num_samples / self.segmentation_model.sample_rate)   # PA/core/inference.py:400-403
-                result, scores = self.host_stage(seg, emb, sess_name, hook=hook, soft=soft, num_frames=T)
+                out = self.host_stage(seg, emb, sess_name, hook=hook, soft=soft, num_frames=T,
+                                      return_embeddings=return_embeddings)
+                result, scores = out[0], out[1]
+                embeddings = out[2] if return_embeddings else None
+            elif return_embeddings:
+                result, embeddings = self.host_stage(seg, emb, sess_name, hook=hook, return_embeddings=True)
             else:
                 result = self.host_stage(seg, emb, sess_name, hook=hook)
             if self.rttm_out_dir is not None:
@@ -579,4 +599,18 @@ class DiariZenPipeline:
         self.streams_in_use = len(self._runner.engines)       # <= num_streams (WindowRunner.grow_declined says why when fewer)
         self.timings = {"load_s": t1 - t0, "device_s": t2 - t1, "host_s": t3 - t2,
                         "audio_s": num_samples / self.segmentation_model.sample_rate}
+        if return_embeddings:
+            return (result, scores, embeddings) if return_scores else (result, embeddings)
         return (result, scores) if return_scores else result
+
+    def voiceprint(self, in_wav, sess_name: Optional[str] = None) -> np.ndarray:
+        """the enrolment call: float32 [256], the centroid of the label with the largest total duration in the recording (ties:
+        the smaller label).  ValueError when the recording has no speech."""
+        annotation, embeddings = self(in_wav, sess_name=sess_name, return_embeddings=True)
+        duration: Dict[int, float] = {}
+        for segment, _, label in annotation.itertracks(yield_label=True):
+            duration[int(label)] = duration.get(int(label), 0.0) + segment.duration
+        if not duration:
+            raise ValueError("voiceprint: the recording has no speech")
+        best = min(duration, key=lambda k: (-duration[k], k))
+        return np.array(embeddings[best], dtype=np.float32, copy=True)

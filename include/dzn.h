@@ -382,6 +382,34 @@ int dzn_vbx_estep(void* state, const double* h_alpha, const double* h_ck, const 
 int dzn_vbx_gamma(void* state, double* h_gamma);
 int dzn_vbx_destroy(void* state);
 
+/* Speaker identification (csrc/gallery.hip): a device-resident gallery of enrolled voiceprints and one cosine
+ * search over it.  No reference counterpart: the reference ends at anonymous cluster labels.  A voiceprint is a cluster
+ * centroid of the embeddings the engine already produces, so enrolment and test live in the same space.
+ *   storage  fp32 [capacity, dim] (dim a multiple of 16, 16 .. 512), every row L2-normalised at put: norm in float64 (in-order
+ *            sum, as dzn_cdist_cosine's row norms), quotient rounded once to fp32; one validity byte per slot.  The gallery's
+ *            own allocation, made at create and freed at destroy; dzn_host_workspace_release leaves it alone.
+ *   search   queries normalised the same way; score = fp32 dot product on the f32-input MFMA (one fmaf chain of dim products,
+ *            |score - float64 cosine| <= (dim + 8) 2^-24).  Per query the top_n VALID rows by (score descending, slot
+ *            ascending): duplicated rows tie, the lower slot first; entries beyond the number of valid rows are slot -1,
+ *            score -inf.  h_dense (optional) receives every score, [Q, rows] with rows = highest slot ever put + 1
+ *            (dzn_gallery_rows): the same bits the selection saw, -inf at dropped or never-put slots.
+ * HOST pointers, blocking calls on the host stage's stream and arena (as dzn_cdist_cosine: callable from a second thread beside
+ * the engine).  DZN_E_INVALID, nothing written: null pointers, Q < 1, top_n < 1 or > max_top_n (32), a slot range outside the
+ * capacity, a put row or a query that is all zero or not finite (checked on the host before any upload).
+ *   dzn_gallery_geometry        tile_rows: rows per workgroup tile; sweep_rows: rows one pass of the launched grid covers on this
+ *                               device; query_group: queries that share one sweep (Q beyond it loops); max_top_n
+ *   dzn_gallery_last_launch_ms  HIP-event time of the last search's launches (scans + merges, without the copies);
+ *                               merge_ms (optional): the share of the last group's merge */
+int dzn_gallery_create(int32_t device, int32_t dim, int64_t capacity, void** out);
+int dzn_gallery_put(void* g, int64_t slot, const float* h_vecs, int64_t count);
+int dzn_gallery_drop(void* g, int64_t slot, int64_t count);
+int dzn_gallery_search(void* g, const float* h_queries, int32_t Q, int32_t top_n, float* h_scores, int64_t* h_slots,
+                       float* h_dense);
+int dzn_gallery_geometry(const void* g, int32_t* tile_rows, int32_t* sweep_rows, int32_t* query_group, int32_t* max_top_n);
+int dzn_gallery_rows(const void* g, int64_t* rows);
+int dzn_gallery_last_launch_ms(const void* g, float* ms, float* merge_ms);
+int dzn_gallery_destroy(void* g);
+
 /* Row f3, audio ingest: native FLAC decoder (csrc/flac.cpp, host code; the reference reads whatever torchaudio.load does,
  * diarizen/pipelines/inference.py:127 — WAV is parsed in diarizen_amd/audio.py, FLAC here).  Frame-header CRC-8 and frame
  * CRC-16 are verified while decoding; the caller checks the STREAMINFO MD5 (audio.load_flac does).
