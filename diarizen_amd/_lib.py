@@ -239,6 +239,10 @@ def load() -> C.CDLL:
     # the small kernels (conformer.hip, frontend.hip, norm.hip, embed.hip)
     sig("dzn_op_glu_dwconv", i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp])
     sig("dzn_op_classify", i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp])
+    sig("dzn_op_conv0_lnq", i32, [vp, i32, i32, vp])
+    sig("dzn_op_conv0", i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp])
+    sig("dzn_op_split_weights_h2_frag", i32, [vp, i32, i32, vp, vp, vp])
+    sig("dzn_op_conv01_fused", i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, f32, f32, vp, vp, vp, i32, vp, vp])
     sig("dzn_op_groupnorm_gelu", i32, [vp, vp, i32, i32, i32, i32, i64, vp, vp, f32, vp, vp, vp])
     sig("dzn_op_gn_stats_floats", i64, [i32, i32, i32, i32])
     sig("dzn_op_pad_rows", i32, [vp, vp, i32, i32, i32, i32, i32, vp])
@@ -273,6 +277,7 @@ EXPORTED = [
     "dzn_op_ws_sum", "dzn_op_col_scale", "dzn_op_layernorm_t", "dzn_op_wave_stats", "dzn_op_frame_prep", "dzn_op_power",
     "dzn_op_log_cmn", "dzn_op_log_cmn_gather", "dzn_op_stem_conv", "dzn_op_stats_pool", "dzn_op_window_active",
     "dzn_op_compact_active",
+    "dzn_op_conv0_lnq", "dzn_op_conv0", "dzn_op_split_weights_h2_frag", "dzn_op_conv01_fused",
 ]
 
 

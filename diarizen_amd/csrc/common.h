@@ -173,6 +173,7 @@ int launch_attention_planes(const float* qkv, const void* planes, int64_t plane_
 int launch_conv0(const float* wave, int B, int N, const float* stats, const float* w,
                  const float* gamma, const float* beta, int C0, int Cp, int k, int s, int T0,
                  int layer_norm, float eps, float* out, hipStream_t st, const float* lnq = nullptr);
+void conv0_lnq_factor(const float* w, int C0, int k0, float* lq);   // engine.cpp: lq [10 + 100] = (wbar, F) of conv0's taps, host
 int launch_groupnorm_gelu(const float* x, float* y, int B, int T, int C, int Cp, int64_t ld,
                           const float* gamma, const float* beta, float eps, float* stats, hipStream_t st, float* amax = nullptr);
 int64_t gn_stats_floats(int B, int T, int C, int Cp);   // size of launch_groupnorm_gelu's `stats` (statistics + chunk partials)

@@ -488,55 +488,8 @@ void finalize_seg(H* h) {
     h->conv_ln[0] = ln_from_sd(h, pre + ".layer_norm", h->C[0]);
     if (c.extractor_layer_norm && c.conv_k[0] <= 10 && h->sw.conv0_quad_stats) {
       // LayerNorm statistics of conv0's frames as a quadratic form of the input samples (frontend.hip)
-      const int C0 = h->C[0], k0 = c.conv_k[0];
-      std::vector<double> wb(10, 0.0), Q(100, 0.0);
-      for (int ch = 0; ch < C0; ++ch)
-        for (int i = 0; i < k0; ++i) wb[i] += w.v[(size_t)ch * k0 + i] / C0;
-      for (int ch = 0; ch < C0; ++ch)
-        for (int i = 0; i < k0; ++i)
-          for (int j = 0; j < k0; ++j)
-            Q[i * 10 + j] += (w.v[(size_t)ch * k0 + i] - wb[i]) * (w.v[(size_t)ch * k0 + j] - wb[j]) / C0;
-      // var = x^T Q x as a plain sum of products cancels when the frame lies near Q's small-eigenvalue directions (trained
-      // DC-blocking / band-pass conv0 taps on low-frequency or quiet audio: ADVICE r2).  Q is PSD: factor it once, in
-      // double, as Q = sum_e lambda_e v_e v_e^T (cyclic Jacobi) and ship F[e][j] = sqrt(lambda_e) v_e[j]; the kernels
-      // evaluate var = sum_e (F[e] . x)^2 — a sum of squares, nothing to cancel.
-      std::vector<double> Aj(Q), V(100, 0.0);
-      for (int i = 0; i < 10; ++i) V[i * 10 + i] = 1.0;
-      for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < 10; ++p)
-          for (int q = p + 1; q < 10; ++q) off += Aj[p * 10 + q] * Aj[p * 10 + q];
-        if (off < 1e-300) break;
-        for (int p = 0; p < 10; ++p)
-          for (int q = p + 1; q < 10; ++q) {
-            const double apq = Aj[p * 10 + q];
-            if (apq == 0.0) continue;
-            const double theta = (Aj[q * 10 + q] - Aj[p * 10 + p]) / (2.0 * apq);
-            const double tt = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-            const double cs = 1.0 / std::sqrt(tt * tt + 1.0), sn = tt * cs;
-            for (int r = 0; r < 10; ++r) {        // A <- A J (columns p, q)
-              const double arp = Aj[r * 10 + p], arq = Aj[r * 10 + q];
-              Aj[r * 10 + p] = cs * arp - sn * arq;
-              Aj[r * 10 + q] = sn * arp + cs * arq;
-            }
-            for (int r = 0; r < 10; ++r) {        // A <- J^T A (rows p, q)
-              const double apr = Aj[p * 10 + r], aqr = Aj[q * 10 + r];
-              Aj[p * 10 + r] = cs * apr - sn * aqr;
-              Aj[q * 10 + r] = sn * apr + cs * aqr;
-            }
-            for (int r = 0; r < 10; ++r) {        // V <- V J
-              const double vrp = V[r * 10 + p], vrq = V[r * 10 + q];
-              V[r * 10 + p] = cs * vrp - sn * vrq;
-              V[r * 10 + q] = sn * vrp + cs * vrq;
-            }
-          }
-      }
       std::vector<float> lq(110);
-      for (int i = 0; i < 10; ++i) lq[i] = (float)wb[i];
-      for (int e = 0; e < 10; ++e) {
-        const double lam = std::max(Aj[e * 10 + e], 0.0);
-        for (int j = 0; j < 10; ++j) lq[10 + e * 10 + j] = (float)(std::sqrt(lam) * V[j * 10 + e]);
-      }
+      conv0_lnq_factor(w.v.data(), h->C[0], c.conv_k[0], lq.data());
       h->conv0_lnq = upload(h, lq);
     }
     if (c.extractor_layer_norm) {   // |LN(x)_c| <= sqrt(C - 1), |GELU(t)| <= |t|
@@ -1771,6 +1724,66 @@ int guarded(H* h, F&& f) {
 }  // namespace
 
 // ====================================================================== C ABI
+// conv0's channel-LayerNorm statistics as functions of a frame's k0 samples (frontend.hip): lq[0 .. 10) = wbar = mean over the
+// C0 channels of the taps, lq[10 + 10 e + j] = F[e][j] with F^T F = Q = the covariance over channels of the taps; entries of
+// taps >= k0 are zero.  Shared by dzn_create and dzn_op_conv0_lnq.
+void conv0_lnq_factor(const float* w, int C0, int k0, float* lq) {
+  std::vector<double> wb(10, 0.0), Q(100, 0.0);
+  for (int ch = 0; ch < C0; ++ch)
+    for (int i = 0; i < k0; ++i) wb[i] += (double)w[(size_t)ch * k0 + i] / C0;   // in double: as fp32 the quotient is exact only for C0 = 2^n
+  for (int ch = 0; ch < C0; ++ch)
+    for (int i = 0; i < k0; ++i)
+      for (int j = 0; j < k0; ++j)
+        Q[i * 10 + j] += (w[(size_t)ch * k0 + i] - wb[i]) * (w[(size_t)ch * k0 + j] - wb[j]) / C0;
+  // var = x^T Q x as a plain sum of products cancels when the frame lies near Q's small-eigenvalue directions (trained
+  // DC-blocking / band-pass conv0 taps on low-frequency or quiet audio: ADVICE r2).  Q is PSD: factor it once, in
+  // double, as Q = sum_e lambda_e v_e v_e^T (cyclic Jacobi) and ship F[e][j] = sqrt(lambda_e) v_e[j]; the kernels
+  // evaluate var = sum_e (F[e] . x)^2 — a sum of squares, nothing to cancel.
+  std::vector<double> Aj(Q), V(100, 0.0);
+  for (int i = 0; i < 10; ++i) V[i * 10 + i] = 1.0;
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0.0;
+    for (int p = 0; p < 10; ++p)
+      for (int q = p + 1; q < 10; ++q) off += Aj[p * 10 + q] * Aj[p * 10 + q];
+    if (off < 1e-300) break;
+    for (int p = 0; p < 10; ++p)
+      for (int q = p + 1; q < 10; ++q) {
+        const double apq = Aj[p * 10 + q];
+        if (apq == 0.0) continue;
+        const double theta = (Aj[q * 10 + q] - Aj[p * 10 + p]) / (2.0 * apq);
+        const double tt = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double cs = 1.0 / std::sqrt(tt * tt + 1.0), sn = tt * cs;
+        for (int r = 0; r < 10; ++r) {        // A <- A J (columns p, q)
+          const double arp = Aj[r * 10 + p], arq = Aj[r * 10 + q];
+          Aj[r * 10 + p] = cs * arp - sn * arq;
+          Aj[r * 10 + q] = sn * arp + cs * arq;
+        }
+        for (int r = 0; r < 10; ++r) {        // A <- J^T A (rows p, q)
+          const double apr = Aj[p * 10 + r], aqr = Aj[q * 10 + r];
+          Aj[p * 10 + r] = cs * apr - sn * aqr;
+          Aj[q * 10 + r] = sn * apr + cs * aqr;
+        }
+        for (int r = 0; r < 10; ++r) {        // V <- V J
+          const double vrp = V[r * 10 + p], vrq = V[r * 10 + q];
+          V[r * 10 + p] = cs * vrp - sn * vrq;
+          V[r * 10 + q] = sn * vrp + cs * vrq;
+        }
+      }
+  }
+  for (int i = 0; i < 110; ++i) lq[i] = 0.f;
+  for (int i = 0; i < 10; ++i) lq[i] = (float)wb[i];
+  for (int e = 0; e < 10; ++e) {
+    const double lam = std::max(Aj[e * 10 + e], 0.0);
+    for (int j = 0; j < 10; ++j) lq[10 + e * 10 + j] = (float)(std::sqrt(lam) * V[j * 10 + e]);
+  }
+}
+
+extern "C" int dzn_op_conv0_lnq(const float* w, int32_t C0, int32_t k, float* lnq110) {
+  if (!w || !lnq110 || C0 < 1 || k < 1 || k > 10) return DZN_E_INVALID;
+  conv0_lnq_factor(w, C0, k, lnq110);
+  return DZN_OK;
+}
+
 extern "C" {
 
 int dzn_create(const dzn_config* cfg, dzn_handle** out) {

@@ -384,6 +384,16 @@ int launch_col_scale(float* x, int64_t rows, int C, int64_t ld, const float* sca
 }
 
 // ---- test entry points (include/dzn_ops.h) ----
+extern "C" int dzn_op_conv0(const float* wave, int32_t B, int32_t N, const float* stats, const float* w, const float* gamma,
+                            const float* beta, int32_t C0, int32_t Cp, int32_t k, int32_t s, int32_t T0, int32_t layer_norm, float eps,
+                            float* out, const float* lnq, void* stream) {
+  if (!wave || !w || !out || B <= 0 || N <= 0 || T0 <= 0 || C0 <= 0 || Cp < C0 || (Cp & 3) || k < 1 || s < 1) return DZN_E_INVALID;
+  if ((int64_t)(T0 - 1) * s + k > N) return DZN_E_INVALID;      // the last frame would read past its window
+  if ((layer_norm != 0 && layer_norm != 1) || (layer_norm && (!gamma || !beta))) return DZN_E_INVALID;
+  return launch_conv0(wave, B, N, stats, w, gamma, beta, C0, Cp, k, s, T0, layer_norm, eps, out, reinterpret_cast<hipStream_t>(stream),
+                      lnq);
+}
+
 extern "C" int dzn_op_groupnorm_gelu(const float* x, float* y, int32_t B, int32_t T, int32_t C, int32_t Cp, int64_t ld,
                                      const float* gamma, const float* beta, float eps, float* stats, float* amax, void* stream) {
   if (!x || !y || !gamma || !beta || !stats || B <= 0 || T <= 0 || C <= 0 || Cp < C || ld < Cp) return DZN_E_INVALID;

@@ -467,3 +467,20 @@ int launch_conv01_fused(const float* wave, int B, int N, const float* wstats, co
   prof_end(pid, st);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
 }
+
+// ---- test entry points (include/dzn_ops.h) ----
+extern "C" int dzn_op_split_weights_h2_frag(const float* W, int32_t rows, int32_t K, void* W2h, float* col_scale, void* stream) {
+  if (!W || !W2h || !col_scale) return DZN_E_INVALID;
+  return launch_split_weights_h2_frag(W, rows, K, W2h, col_scale, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int dzn_op_conv01_fused(const float* wave, int32_t B, int32_t N, const float* wstats, const float* w0, const float* gamma0,
+                                   const float* beta0, const float* lnq, int32_t C0, int32_t T0, int32_t T1, const void* W2h,
+                                   const float* col_scale, int32_t N1p, float act_bound, float eps, float* out, const float* gamma1,
+                                   const float* beta1, int32_t C1, float* amax1, void* stream) {
+  if (!wave || !w0 || !gamma0 || !beta0 || !out || B <= 0 || N <= 0 || T1 <= 0) return DZN_E_INVALID;
+  // conv0 frame T0 - 1 inside the window, conv1 frame T1 - 1 inside conv0's T0 frames
+  if (T0 < 3 || (int64_t)(T0 - 1) * 5 + 10 > N || T1 > (T0 - 3) / 2 + 1) return DZN_E_INVALID;
+  return launch_conv01_fused(wave, B, N, wstats, w0, gamma0, beta0, lnq, C0, T0, T1, W2h, col_scale, N1p, act_bound, eps, out,
+                             reinterpret_cast<hipStream_t>(stream), gamma1, beta1, C1, amax1);
+}

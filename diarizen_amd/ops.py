@@ -604,6 +604,47 @@ def groupnorm_gelu(x, y, gamma, beta, stats, *, B, T, C, Cp, ld, eps=1e-5, amax=
     return y
 
 
+def conv0_lnq(w, C0, k):
+    """HOST: w = numpy float32 [C0, k] -> numpy float32 [110]: (wbar [10], F [10, 10]) of dzn_op_conv0_lnq; no device involved"""
+    import numpy as np
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    out = np.full(110, np.nan, np.float32)
+    check(_lib.load().dzn_op_conv0_lnq(C.c_void_p(w.ctypes.data), int(C0), int(k), C.c_void_p(out.ctypes.data)), what="dzn_op_conv0_lnq")
+    return out
+
+
+def conv0(wave, w, out, *, B, N, C0, Cp, k, s, T0, layer_norm, stats=None, gamma=None, beta=None, lnq=None, eps=1e-5):
+    """out [B, T0, Cp] = conv0 of wave [B, N] (csrc/frontend.hip); layer_norm: LayerNorm over C0 + GELU, statistics from lnq or,
+    without it, from the frame's outputs"""
+    lib = _lib.load()
+    check(lib.dzn_op_conv0(_p(wave), int(B), int(N), _p(stats), _p(w), _p(gamma), _p(beta), int(C0), int(Cp), int(k), int(s), int(T0),
+                           int(layer_norm), eps, _p(out), _p(lnq), _stream()), what="dzn_op_conv0")
+    return out
+
+
+def split_weights_h2_frag(W, out=None, col_scale=None):
+    """split_weights_h2 in the fragment-major order conv01_fused reads: (planes int16 [K // 32, rows // 16, 2, 16, 32], col_scale)"""
+    lib = _lib.load()
+    assert W.is_cuda and W.dtype == torch.float32 and W.dim() == 2 and W.is_contiguous()
+    rows, K = W.shape
+    if out is None:
+        out = torch.empty((max(K // 32, 1), max(rows // 16, 1), 2, 16, 32), device=W.device, dtype=torch.int16)
+    if col_scale is None:
+        col_scale = torch.empty((rows,), device=W.device, dtype=torch.float32)
+    check(lib.dzn_op_split_weights_h2_frag(_p(W), rows, K, _p(out), _p(col_scale), _stream()), what="dzn_op_split_weights_h2_frag")
+    return out, col_scale
+
+
+def conv01_fused(wave, w0, gamma0, beta0, lnq, W2h, col_scale, out, *, B, N, C0, T0, T1, act_bound, N1p=160, wstats=None, gamma1=None,
+                 beta1=None, C1=0, amax1=None, eps=1e-5):
+    """out [B, T1, N1p] = conv1(GELU(LN(conv0(wave)))) in one kernel (csrc/frontend_fused.hip); gamma1 / beta1: + LN over C1 + GELU"""
+    lib = _lib.load()
+    check(lib.dzn_op_conv01_fused(_p(wave), int(B), int(N), _p(wstats), _p(w0), _p(gamma0), _p(beta0), _p(lnq), int(C0), int(T0), int(T1),
+                                  _p(W2h), _p(col_scale), int(N1p), float(act_bound), eps, _p(out), _p(gamma1), _p(beta1), int(C1),
+                                  _p(amax1), _stream()), what="dzn_op_conv01_fused")
+    return out
+
+
 def pad_rows(x, xpad, *, B, L, Lp, pad, D):
     lib = _lib.load()
     check(lib.dzn_op_pad_rows(_p(x), _p(xpad), int(B), int(L), int(Lp), int(pad), int(D), _stream()), what="dzn_op_pad_rows")

@@ -316,6 +316,31 @@ int dzn_op_glu_dwconv(const float* u, int64_t ldu, const float* w, const float* 
  * mapping[argmax] (first maximum; mapping u8 [NC, S], S <= 64), soft [rows, S] = exp(logp) @ mapping; each output may be NULL. */
 int dzn_op_classify(const float* z, int64_t ldz, const float* W, const float* bias, const uint8_t* mapping, int64_t rows,
                     int32_t A, int32_t NC, int32_t S, float* logp, uint8_t* multilabel, float* soft, void* stream);
+/* The front end of a segmentation forward (tests/test_frontend_kernels_gpu.py).
+ * HOST: lnq110[0 .. 10) = mean over the C0 channels of the taps w [C0, k] (k <= 10), lnq110[10 + 10 e + j] = F[e][j] with
+ * F^T F = the covariance over channels of the taps; entries of taps >= k are zero.  The statistics conv0 takes from a frame's
+ * samples x: mean_c y = wbar . x, var_c y = |F x|^2. */
+int dzn_op_conv0_lnq(const float* w, int32_t C0, int32_t k, float* lnq110);
+/* csrc/frontend.hip: out[b, f, c] = sum_t w[c, t] x[b, f s + t], x = (wave - stats[b, 0]) * stats[b, 1] (stats NULL: x = wave);
+ * layer_norm = 1: then LayerNorm over the C0 channels of the frame (gamma, beta) and erf-GELU, the statistics from lnq (above)
+ * or, lnq NULL, from the frame's outputs.  wave [B, N], out [B, T0, Cp] with columns [C0, Cp) zero; Cp % 4 == 0, k <= 10, s <= 8,
+ * C0 <= 512, (T0 - 1) s + k <= N. */
+int dzn_op_conv0(const float* wave, int32_t B, int32_t N, const float* stats, const float* w, const float* gamma, const float* beta,
+                 int32_t C0, int32_t Cp, int32_t k, int32_t s, int32_t T0, int32_t layer_norm, float eps, float* out,
+                 const float* lnq, void* stream);
+/* csrc/frontend_fused.hip: the values of dzn_op_split_weights_h2(W [rows, K] contiguous) in fragment-major order
+ * [K/32][rows/16][2][16][32] fp16, col_scale f32 [rows]; rows % 16 == 0, K % 32 == 0. */
+int dzn_op_split_weights_h2_frag(const float* W, int32_t rows, int32_t K, void* W2h, float* col_scale, void* stream);
+/* conv0 (k 10, s 5, LayerNorm from lnq, GELU) -> conv1 (k 3, s 2) in one kernel, fp16 two-term arithmetic:
+ * out[b, t, n] = sum_{j < 3, c < C0} W[n, j C0 + c] a[b, 2 t + j, c], a = dzn_op_conv0's output; gamma1 / beta1 non-NULL: then LayerNorm
+ * over the C1 real channels and GELU, and amax1 (f32 [B] or NULL) is max'ed with |out| (raw output: amax1 is not touched).
+ * W2h / col_scale = dzn_op_split_weights_h2_frag of W [N1p, 3 C0] with zero rows n >= C1; act_bound >= max |a| (static:
+ * sqrt(C0) max|gamma0| + max|beta0|).  out [B, T1, N1p].  C0 % 64 == 0, C0 >= 128, N1p == 160, 80 < C1 <= 160 with gamma1,
+ * (T0 - 1) 5 + 10 <= N, T0 >= 3, T1 <= (T0 - 3) / 2 + 1; wstats, gamma1, beta1, amax1 may be NULL. */
+int dzn_op_conv01_fused(const float* wave, int32_t B, int32_t N, const float* wstats, const float* w0, const float* gamma0,
+                        const float* beta0, const float* lnq, int32_t C0, int32_t T0, int32_t T1, const void* W2h,
+                        const float* col_scale, int32_t N1p, float act_bound, float eps, float* out, const float* gamma1,
+                        const float* beta1, int32_t C1, float* amax1, void* stream);
 /* csrc/frontend.hip: y[b,t,c] = gelu((x[b,t,c] - mean[b,c]) * rstd[b,c] * gamma[c] + beta[c]) with the statistics over the T
  * rows of window b (GroupNorm(C, C), biased variance), columns [C, Cp) of y zero; x, y [B T, ld] (y may be x), Cp % 4 == 0,
  * ld % 4 == 0, Cp <= 1024; stats = scratch of dzn_op_gn_stats_floats() floats; amax f32 [B] or NULL: max'ed with |y|. */

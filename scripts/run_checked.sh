@@ -19,5 +19,7 @@ python -m pytest tests/test_attention_matrix_gpu.py -m gpu -q -x 2>&1 | tail -3
 python -m pytest tests/test_small_kernels_gpu.py -m gpu -q -x 2>&1 | tail -3
 # the image-kernel matrix (conv_split.hip, resblock_fused.hip, resblock_ws.hip, ids 0x40x / 0x50x: image indices of the lists, ring rows): likewise
 python -m pytest tests/test_image_kernels_gpu.py -m gpu -q -x 2>&1 | tail -3
+# the front-end matrix (frontend.hip, frontend_fused.hip, ids 0x71x: plane rows, conv1 fragments, weight fragments): likewise
+python -m pytest tests/test_frontend_kernels_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
