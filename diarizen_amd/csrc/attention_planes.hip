@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256, QB == 1 ? AP_OCC : 2) void attn_planes_kernel(
   u32x4 rk[2][2], rv[2][2];                          // [plane][i]
   float sc_k = 0.f, sc_v = 0.f;                      // wave 0, lane = key: the tile's inverse scales
   auto fetch = [&](int kt) {
-    const int64_t trow = rowbase + kt * 64;          // rows past the window / the batch are readable (zero tail) and masked
+    const int64_t trow = rowbase + kt * 64;          // rows past the window / the batch are readable; the tile loop masks them
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int64_t ro = (trow + skey + 32 * i) * kv_ld;
@@ -167,6 +167,15 @@ __global__ __launch_bounds__(256, QB == 1 ? AP_OCC : 2) void attn_planes_kernel(
   for (int kt = 0; kt < nkt; ++kt) {
     if constexpr (!PF) fetch(kt);
     __syncthreads();  // previous tile fully consumed
+    if ((kt + 1) * 64 > L) {
+      // last tile (wave-uniform): the keys past L are rows of the NEXT window or, behind the batch, whatever an earlier layer
+      // or call left in the planes.  Their probabilities are exactly 0, but 0 x NaN = NaN in P'V': stage zeros for them, so
+      // that a non-finite neighbour (or its stale planes) cannot reach this window.  K needs nothing: its scores are
+      // replaced, not multiplied, below
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        if (kt * 64 + skey + 32 * i >= L) rv[0][i] = rv[1][i] = (u32x4){0u, 0u, 0u, 0u};
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int key = skey + 32 * i;
@@ -354,7 +363,8 @@ __global__ __launch_bounds__(64) void kv_pack_kernel(const float* __restrict__ q
 }  // namespace
 
 // planes = fp16 [2][rows + 64][kv_ld] written by the q/k/v contraction (dzn_gemm_desc.kv_planes), kvs = f32 [rows + 64][kv_ld / 64];
-// rows past B * L must be readable and finite (the engine zero-fills the buffers once)
+// rows past B * L must be readable: what they hold (the next window's rows, another layer's or an earlier call's planes,
+// non-finite values included) is never used
 int launch_attention_planes(const float* qkv, const void* planes, int64_t plane_stride, const float* kvs, int kv_ld, float* out,
                             const float* gate, const float* table, const int32_t* head_idx, int B, int L, int h, int Htot,
                             int ldqkv, int ldo, float scale, hipStream_t s, const float* amax) {

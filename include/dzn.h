@@ -166,6 +166,11 @@ int dzn_num_frames(const dzn_handle* h, int32_t num_samples);
  * inference.py:128 / model_wavlm_conformer.py:250).  Outputs (device, either may
  * be NULL): d_logp f32 [B, L, n_classes] log-probabilities; d_multilabel u8
  * [B, L, max_speakers_per_chunk] hard multilabel decisions.
+ *
+ * Window isolation (this call, its _soft form and both embedding forwards): a window's results depend on that window's
+ * samples and masks alone — not on B, on the window's place in the batch, on max_batch / max_samples or on what the handle
+ * ran before — also when another window of the batch or an earlier call on the handle held non-finite samples (NaN, Inf,
+ * values whose square overflows).  What the non-finite window itself returns is unspecified.
  */
 int dzn_segment_forward(dzn_handle* h, const float* d_wave, int32_t B, int32_t N,
                         float* d_logp, uint8_t* d_multilabel, void* hip_stream);
