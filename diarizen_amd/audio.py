@@ -19,6 +19,11 @@ kernel decodes them and selects the channel or downmixes) — into a range of ou
 the bits of the same slice of a whole-recording call (`resample_input_span` says which input a range reads).
 `ResampledSource` wraps a file at another rate on top of it; `pipeline.open_recording(resample="device")` returns one.
 
+Array recordings (2 - 64 microphones) have a channel choice of their own, `Beamform`: GCC-PHAT delays per block
+(`beamform_delays_device`, csrc/beamform.hip), smoothed on the host (`smooth_delays`), then the channels aligned and averaged
+(`beamform_sum_device`); `BeamformedSource` runs the three over a file span by span, and
+`pipeline.open_recording(channel=Beamform(...))` returns one.
+
 Live sources deliver the same stored forms in packets: `FeedFormat` names what a session is fed (`feed_format=`), `feed_ready`
 says which output samples are final after R frames, `FeedPlanner` turns chunks of bytes into device calls whose ranges tile
 the output (streaming.WaveIngest runs them), and `decode_device` (`dzn_decode`) is the decode without the resampler, for feeds
@@ -647,6 +652,345 @@ def decode_device(x, *, device, channels: int = 1, channel=0, src_format=None):
     _lib.check(_lib.load().dzn_decode(dev, C.c_void_p(xd.data_ptr()), fmt, channels, channel, frames,
                                       C.c_void_p(out.data_ptr()), st), None, "dzn_decode")
     return out
+
+
+# ----------------------------------------------------------------------------- array recordings: GCC-PHAT delay-and-sum
+class Beamform:
+    """A channel choice for array recordings (`channel=Beamform(...)` where an index or "downmix" is accepted on the offline
+    path): the channels are aligned to channel `reference` by per-block time differences of arrival (GCC-PHAT) and averaged
+    (csrc/beamform.hip, DESIGN.md §4.23).  max_delay: the search range in seconds (10 ms covers an aperture of about 3.4 m);
+    hop: the block hop in samples at the FILE's rate, a power of two in [256, 4096] (default: the largest one <= 0.256 s,
+    capped at 4096); min_peak: the GCC-PHAT peak below which a block's delay is not trusted (default 8 / sqrt(2 hop): for
+    unrelated channels the correlation is roughly Gaussian with sigma = 1 / sqrt(2 hop), so this is 8 sigma — a statistical
+    derivation that no real array recording has met yet).  Validated here; `plan` settles what depends on the file."""
+
+    def __init__(self, reference: int = 0, max_delay: float = 0.01, hop: Optional[int] = None,
+                 min_peak: Optional[float] = None):
+        if isinstance(reference, (bool, np.bool_)) or not isinstance(reference, (int, np.integer)) or reference < 0:
+            raise ValueError(f"Beamform: reference is a channel index >= 0, not {reference!r}")
+        if isinstance(max_delay, (bool, str)) or not np.isfinite(max_delay) or not max_delay > 0:
+            raise ValueError(f"Beamform: max_delay is a positive number of seconds, not {max_delay!r}")
+        if hop is not None and (isinstance(hop, (bool, np.bool_)) or not isinstance(hop, (int, np.integer))
+                                or hop < 256 or hop > 4096 or hop & (hop - 1)):
+            raise ValueError(f"Beamform: hop is a power of two in [256, 4096], not {hop!r}")
+        if min_peak is not None and (isinstance(min_peak, (bool, str)) or not np.isfinite(min_peak) or min_peak < 0):
+            raise ValueError(f"Beamform: min_peak is a number >= 0, not {min_peak!r}")
+        self.reference, self.max_delay = int(reference), float(max_delay)
+        self.hop = None if hop is None else int(hop)
+        self.min_peak = None if min_peak is None else float(min_peak)
+
+    def plan(self, rate: int, channels: int) -> Tuple[int, int, float]:
+        """-> (hop, max_lag, min_peak) for a file of `channels` channels at `rate` Hz; ValueError for a file with one channel,
+        with more than 64, or without the reference channel"""
+        rate, channels = int(rate), int(channels)
+        if channels < 2 or channels > 64:
+            raise ValueError(f"Beamform: a source with {channels} channel(s) (an array has 2 .. 64)")
+        if self.reference >= channels:
+            raise ValueError(f"Beamform: reference channel {self.reference} of a source with {channels} channel(s)")
+        hop = self.hop
+        if hop is None:
+            hop = 256
+            while hop < 4096 and 2 * hop <= 0.256 * rate:
+                hop *= 2
+        max_lag = min(max(1, int(round(self.max_delay * rate))), hop // 2)
+        min_peak = 8.0 / float(np.sqrt(2.0 * hop)) if self.min_peak is None else self.min_peak
+        return hop, max_lag, min_peak
+
+    def _key(self):
+        return (self.reference, self.max_delay, self.hop, self.min_peak)
+
+    def __eq__(self, other):
+        return isinstance(other, Beamform) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return (f"Beamform(reference={self.reference}, max_delay={self.max_delay}, hop={self.hop}, "
+                f"min_peak={self.min_peak})")
+
+
+def beamform_blocks(total: int, hop: int) -> int:
+    """ceil(T / hop) + 1: the blocks of a recording of T samples (centres at b hop, frames of 2 hop)"""
+    return -(-int(total) // int(hop)) + 1
+
+
+def beamform_twiddle(hop: int) -> np.ndarray:
+    """float32 [hop, 2] = (cos, -sin)(2 pi k / W) for k < W / 2 = hop: computed in float64, rounded once (what
+    dzn_beamform_delays takes as d_twiddle; its Hann window comes from the cosines)"""
+    a = 2.0 * np.pi * np.arange(int(hop), dtype=np.float64) / (2.0 * int(hop))
+    return np.stack([np.cos(a), -np.sin(a)], axis=1).astype(np.float32)
+
+
+def smooth_delays(lag, peak, total: int, hop: int, min_peak: float, reference: int = 0) -> np.ndarray:
+    """raw GCC-PHAT lags int [C, nb] and peaks float32 [C, nb] of a recording of `total` samples -> int32 [C, nb], the delays
+    the alignment pass applies.  A block is reliable when its frame holds at least `hop` samples of the recording (a ragged
+    last frame of a few samples gives high, meaningless peaks) and its peak >= float32(min_peak).  Every block takes the lag of
+    the latest reliable block at or before it, the blocks before the first reliable one take that one's, and a channel without
+    any reliable block stays 0; then a median of 5 with mirror padding that does not repeat the edge sample
+    (numpy.pad(mode="reflect")) removes isolated outliers (skipped when nb < 3).  The reference row is 0."""
+    lag = np.asarray(lag)
+    peak = np.asarray(peak, dtype=np.float32)
+    C, nb = lag.shape
+    total, hop = int(total), int(hop)
+    if nb != beamform_blocks(total, hop) or peak.shape != lag.shape:
+        raise ValueError(f"smooth_delays: [C, {beamform_blocks(total, hop)}] lags and peaks for {total} samples at hop {hop}, "
+                         f"not {lag.shape} / {peak.shape}")
+    b = np.arange(nb, dtype=np.int64)
+    support = np.minimum(total, (b + 1) * hop) - np.maximum(0, (b - 1) * hop) >= hop
+    out = np.zeros((C, nb), dtype=np.int32)
+    for c in range(C):
+        if c == reference:
+            continue
+        reliable = support & (peak[c] >= np.float32(min_peak))
+        if not reliable.any():
+            continue
+        at = np.maximum.accumulate(np.where(reliable, b, -1))
+        at[at < 0] = np.argmax(reliable)
+        held = lag[c][at].astype(np.int64)
+        if nb >= 3:
+            padded = np.pad(held, 2, mode="reflect")
+            held = np.median(np.stack([padded[k:k + nb] for k in range(5)]), axis=0)
+        out[c] = held.astype(np.int32)
+    return out
+
+
+_DEVICE_TWIDDLES: dict = {}
+
+
+def _device_twiddle(hop: int, device):
+    """beamform_twiddle(hop) on `device`, uploaded once per (hop, device)"""
+    import torch
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(hop), str(device))
+    hit = _DEVICE_TWIDDLES.get(key)
+    if hit is None:
+        hit = _DEVICE_TWIDDLES[key] = torch.from_numpy(beamform_twiddle(hop)).to(device)
+    return hit
+
+
+def beamform_tile() -> int:
+    """output samples per workgroup of the alignment pass (csrc/beamform.hip)"""
+    from . import _lib
+    return int(_lib.load().dzn_beamform_tile())
+
+
+def beamform_delays_span(b0: int, b1: int, hop: int, total: int):
+    """-> (lo, hi): the samples of the recording that the frames of blocks [b0, b1) hold"""
+    if b1 <= b0:
+        return 0, 0
+    lo, hi = max(0, (int(b0) - 1) * hop), min(int(total), int(b1) * hop)
+    return lo, max(lo, hi)
+
+
+def beamform_sum_span(delays, hop: int, n0: int, n1: int, total: int):
+    """-> (lo, hi): the hull of the samples inside [0, total) that output samples [n0, n1) read with `delays` int [C, nb]
+    (sample n of block b reads n + delay of blocks b and b + 1 in every channel); (0, 0) when they read nothing"""
+    n0, n1, hop, total = int(n0), int(n1), int(hop), int(total)
+    if n1 <= n0:
+        return 0, 0
+    d = np.asarray(delays, dtype=np.int64)
+    ba, bz = n0 // hop, (n1 - 1) // hop + 1                      # the last block used is bz
+    b = np.arange(ba, bz, dtype=np.int64)
+    s0, s1 = np.maximum(n0, b * hop), np.minimum(n1, (b + 1) * hop)
+    pair = np.stack([d[:, ba:bz], d[:, ba + 1:bz + 1]], axis=2)   # [C, blocks, 2]
+    a = np.maximum(0, s0[None, :, None] + pair)
+    z = np.minimum(total, s1[None, :, None] + pair)
+    ok = a < z
+    if not ok.any():
+        return 0, 0
+    return int(a[ok].min()), int(z[ok].max())
+
+
+def _planar_on_device(x, device):
+    """float32 [C, len] on `device`, contiguous, from a host array or a tensor"""
+    import torch
+    if isinstance(x, torch.Tensor):
+        xd = x.to(device=device, dtype=torch.float32)
+    else:
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        xd = torch.from_numpy(x if x.flags.writeable else x.copy()).to(device)
+    if xd.dim() != 2:
+        raise ValueError(f"planar float32 [channels, samples], not a tensor of shape {tuple(xd.shape)}")
+    return xd.contiguous()
+
+
+def beamform_delays_device(x, *, device, reference: int, hop: int, max_lag: int, total=None, first_index: int = 0,
+                           blocks=None):
+    """raw GCC-PHAT delays on the device (csrc/beamform.hip, `dzn_beamform_delays`: one launch on the current stream) ->
+    (lag int32 [C, b1 - b0], peak float32 [C, b1 - b0]) device tensors for blocks = (b0, b1) (default: all ceil(T / hop) + 1).
+    x: planar float32 [C, len], a host array or device tensor, holding samples first_index .. first_index + len of a recording
+    of `total` samples (default: x is the whole recording); it must cover beamform_delays_span(b0, b1, hop, total) (the
+    library refuses otherwise).  A range call returns the bits of the same columns of a whole-recording call."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    device = torch.device(device)
+    xd = _planar_on_device(x, device)
+    channels, length = int(xd.shape[0]), int(xd.shape[1])
+    total = length + int(first_index) if total is None else int(total)
+    hop = int(hop)
+    if hop < 256 or hop > 4096 or hop & (hop - 1):          # (the twiddle table is built for it before the library sees it)
+        raise ValueError(f"beamform_delays_device: hop is a power of two in [256, 4096], not {hop}")
+    b0, b1 = (0, beamform_blocks(total, hop)) if blocks is None else (int(blocks[0]), int(blocks[1]))
+    lag = torch.empty((channels, max(0, b1 - b0)), device=device, dtype=torch.int32)
+    peak = torch.empty((channels, max(0, b1 - b0)), device=device, dtype=torch.float32)
+    tw = _device_twiddle(hop, device)
+    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    dev = device.index if device.index is not None else -1
+    _lib.check(_lib.load().dzn_beamform_delays(dev, C.c_void_p(xd.data_ptr()), channels, length, int(first_index), length,
+                                               total, int(reference), int(hop), int(max_lag), C.c_void_p(tw.data_ptr()),
+                                               b0, b1, C.c_void_p(lag.data_ptr()), C.c_void_p(peak.data_ptr()), st),
+               None, "dzn_beamform_delays")
+    return lag, peak
+
+
+def beamform_sum_device(x, delays, *, device, hop: int, total=None, first_index: int = 0, out_range=None, out=None):
+    """the alignment pass on the device (csrc/beamform.hip, `dzn_beamform_sum`) -> float32 device tensor [n1 - n0] for
+    out_range = (n0, n1) (default: the whole recording).  x as beamform_delays_device takes it; it must cover
+    beamform_sum_span(delays, hop, n0, n1, total).  delays: int [C, nb] of the WHOLE recording (smooth_delays), a host array or
+    an int32 device tensor.  The call waits for the delays on the current stream (the library checks the columns it uses on the
+    host), then enqueues one launch.  The result is bit for bit the float32 restatement (testkit/beamform_ref.py: synth)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    device = torch.device(device)
+    xd = _planar_on_device(x, device)
+    channels, length = int(xd.shape[0]), int(xd.shape[1])
+    total = length + int(first_index) if total is None else int(total)
+    if isinstance(delays, torch.Tensor):
+        dd = delays.to(device=device, dtype=torch.int32).contiguous()
+    else:
+        dd = torch.from_numpy(np.ascontiguousarray(delays, dtype=np.int32)).to(device)
+    if dd.dim() != 2 or dd.shape[0] != channels:
+        raise ValueError(f"beamform_sum_device: delays [{channels}, blocks], not {tuple(dd.shape)}")
+    n0, n1 = (0, total) if out_range is None else (int(out_range[0]), int(out_range[1]))
+    if out is None:
+        out = torch.empty(max(0, n1 - n0), device=device, dtype=torch.float32)
+    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    dev = device.index if device.index is not None else -1
+    _lib.check(_lib.load().dzn_beamform_sum(dev, C.c_void_p(xd.data_ptr()), channels, length, int(first_index), length, total,
+                                            int(hop), C.c_void_p(dd.data_ptr()), int(dd.shape[1]), n0, n1,
+                                            C.c_void_p(out.data_ptr()), st), None, "dzn_beamform_sum")
+    return out
+
+
+class BeamformedSource:
+    """An array recording reduced to one channel on the device (`open_recording(..., channel=Beamform(...))`): wraps a
+    WavSource or SphereSource — the frames are uploaded as the file stores them (`read_stored`) and made planar float32 by
+    `dzn_decode`, one call per channel; forms the device does not decode go through the host decode — or a decoded float32
+    [C, T] array (`orig_rate` says its rate).  `.sample_rate` is `new_rate`, `.num_samples` the length at that rate, and
+    `.read_device(start, n)` returns the bits of the same slice of read_device(0, num_samples).
+
+    The first read estimates the delays of the whole recording: blocks go to `dzn_beamform_delays` in spans of about SPAN
+    frames plus a halo of one hop, the [C, nb] lags and peaks come back (`.lags`, `.peaks`: raw) and `smooth_delays` makes
+    `.delays` of them.  Every read then walks its range in spans of at most SPAN samples, uploads the frames a span reads
+    (beamform_sum_span: a halo of at most hop / 2) and runs `dzn_beamform_sum`, so a 4 h, 8-channel file is never on the
+    device as a whole.  A file at another rate than `new_rate` is beamformed at ITS rate and then resampled by the device
+    resampler (csrc/resample.hip), whatever `resample=` says: the samples are already on the device."""
+
+    SPAN = 1 << 22
+
+    def __init__(self, src, new_rate: int, device, beamform: Beamform, orig_rate: Optional[int] = None):
+        if not isinstance(beamform, Beamform):
+            raise ValueError(f"BeamformedSource: beamform is an audio.Beamform, not {beamform!r}")
+        self.src, self.device, self.beamform = src, "cuda" if device is None else device, beamform
+        self._array = not hasattr(src, "read_stored")
+        if self._array:
+            if orig_rate is None:
+                raise ValueError("BeamformedSource: a decoded array needs orig_rate")
+            self.src = np.asarray(src, dtype=np.float32)
+            if self.src.ndim != 2:
+                raise ValueError("BeamformedSource: a decoded array is float32 [channels, samples]")
+            self.orig_rate, self.channels, self._total = int(orig_rate), int(self.src.shape[0]), int(self.src.shape[1])
+        else:
+            self.orig_rate, self.channels, self._total = int(src.sample_rate), int(src.channels), int(src.num_samples)
+        self.hop, self.max_lag, self.min_peak = beamform.plan(self.orig_rate, self.channels)
+        self.num_blocks = beamform_blocks(self._total, self.hop)
+        self.sample_rate = int(new_rate)
+        if self.orig_rate == self.sample_rate:
+            self._o = self._n = 1
+            self._width = 0
+            self.num_samples = self._total
+        else:
+            self._o, self._n, self._width = resample_ratio(self.orig_rate, self.sample_rate)
+            self.num_samples = resampled_length(self._total, self._o, self._n)
+        self.lags = self.peaks = self.delays = None
+        self._d_delays = None
+
+    def _planar(self, lo: int, hi: int):
+        """float32 device tensor [C, hi - lo] = samples lo .. hi of every channel"""
+        import ctypes as C
+        import torch
+        from . import _lib
+        device = torch.device(self.device)
+        if self._array:
+            return _planar_on_device(self.src[:, lo:hi], device)
+        stored = self.src.read_stored(lo, hi - lo) if hi > lo else None
+        if stored is None:          # nothing to read, or a form only the host decodes (float64, big-endian PCM16)
+            x = _decode_frames(self.src._frames(lo, hi - lo), self.src._codec, self.channels)
+            return _planar_on_device(x.reshape(-1, self.channels).T, device)
+        arr, fmt = stored
+        raw = torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(device).reshape(-1)
+        frames = int(arr.shape[0])
+        out = torch.empty((self.channels, frames), device=device, dtype=torch.float32)
+        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        dev = device.index if device.index is not None else -1
+        lib = _lib.load()
+        for c in range(self.channels):
+            _lib.check(lib.dzn_decode(dev, C.c_void_p(raw.data_ptr()), fmt, self.channels, c, frames,
+                                      C.c_void_p(out[c].data_ptr()), st), None, "dzn_decode")
+        return out
+
+    def estimate(self):
+        """the delays of the whole recording (done once; the first read calls it) -> `.delays` int32 [C, nb]"""
+        import torch
+        if self.delays is not None:
+            return self.delays
+        per = max(1, self.SPAN // self.hop)
+        lags, peaks = [], []
+        for b0 in range(0, self.num_blocks, per):
+            b1 = min(self.num_blocks, b0 + per)
+            lo, hi = beamform_delays_span(b0, b1, self.hop, self._total)
+            lag, peak = beamform_delays_device(self._planar(lo, hi), device=self.device, reference=self.beamform.reference,
+                                               hop=self.hop, max_lag=self.max_lag, total=self._total, first_index=lo,
+                                               blocks=(b0, b1))
+            lags.append(lag.cpu().numpy())
+            peaks.append(peak.cpu().numpy())
+        self.lags, self.peaks = np.concatenate(lags, axis=1), np.concatenate(peaks, axis=1)
+        self.delays = smooth_delays(self.lags, self.peaks, self._total, self.hop, self.min_peak, self.beamform.reference)
+        self._d_delays = torch.from_numpy(self.delays).to(self.device)
+        return self.delays
+
+    def _beam(self, n0: int, n1: int, out=None):
+        """float32 device tensor [n1 - n0]: the beamformed samples n0 .. n1 at the file's rate"""
+        lo, hi = beamform_sum_span(self.delays, self.hop, n0, n1, self._total)
+        return beamform_sum_device(self._planar(lo, hi), self._d_delays, device=self.device, hop=self.hop, total=self._total,
+                                   first_index=lo, out_range=(n0, n1), out=out)
+
+    def read_device(self, start: int, n: int):
+        """float32 device tensor [m] = output samples start .. start + n (m < n at the end of the recording)"""
+        import torch
+        m0 = max(0, min(int(start), self.num_samples))
+        m1 = max(m0, min(m0 + int(n), self.num_samples))
+        self.estimate()
+        out = torch.empty(m1 - m0, device=self.device, dtype=torch.float32)
+        if self.orig_rate == self.sample_rate:
+            for a in range(m0, m1, self.SPAN):
+                z = min(m1, a + self.SPAN)
+                self._beam(a, z, out=out[a - m0:z - m0])
+            return out
+        step = max(1, self.SPAN * self._n // self._o)
+        for a in range(m0, m1, step):
+            z = min(m1, a + step)
+            lo, hi = resample_input_span(a, z, self._o, self._n, self._width)
+            lo, hi = max(lo, 0), max(min(hi, self._total), 0)
+            hi = max(hi, lo)
+            out[a - m0:z - m0] = resample_device(self._beam(lo, hi), self.orig_rate, self.sample_rate, device=self.device,
+                                                 out_range=(a, z), total=self._total, first_index=lo)
+        return out
 
 
 # ----------------------------------------------------------------------------- live feeds in a stored format

@@ -42,4 +42,6 @@
 // check ids: 0x1xx gemm_split, 0x2xx gemm_mx, 0x3xx gemm_split_pre, 0x4xx resblock_fused, 0x5xx resblock_ws,
 //            0x60x attention_split, 0x61x attention_planes, 0x7xx frontend_fused, 0x80x post (detection), 0x81x post (speaker scores),
 //            0x82x resample / decode / ingest (0x828 ..), 0x83x post (diarize range),
-//            0x84x gallery (0x840 row-tile index, 0x841 partial-list write, 0x842 survivor queue)
+//            0x84x gallery (0x840 row-tile index, 0x841 partial-list write, 0x842 survivor queue),
+//            0x85x beamform (0x850 frame read, 0x852 / 0x853 butterfly and twiddle index, 0x854 block, 0x855 lag read,
+//                            0x858 delay read, 0x859 shifted sample read, 0x85a output write)

@@ -254,6 +254,13 @@ int launch_decode(const void* src, int format, int channels, int channel, int64_
 int launch_ingest_many(const void* stage, const dzn_ingest_desc* desc, int num_desc, int64_t tiles, size_t lds_bytes,
                        double bytes_moved, const float* banks, float* pool, hipStream_t st);
 int launch_gather_windows(const float* pool, const int64_t* offsets, int B, int window, float* dst, hipStream_t st);
+// beamform.hip: GCC-PHAT lag / peak of blocks [b0, b1) and the delay-and-sum of samples [n0, n1) over planar float32 channels
+// (dzn_beamform_delays / dzn_beamform_sum validate)
+int launch_beamform_delays(const float* x, int channels, int64_t ch_stride, int64_t x_first, int64_t x_len, int64_t T, int ref,
+                           int hop, int max_lag, const float* twiddle, int64_t b0, int64_t b1, int* lag, float* peak,
+                           hipStream_t st);
+int launch_beamform_sum(const float* x, int channels, int64_t ch_stride, int64_t x_first, int64_t x_len, int64_t T, int hop,
+                        const int* delay, int64_t num_blocks, int64_t n0, int64_t n1, float* dst, hipStream_t st);
 
 // prof.cpp
 bool prof_enabled();

@@ -2057,6 +2057,104 @@ int dzn_decode(int32_t device, const void* d_src, int32_t src_format, int32_t ch
   return launch_decode(d_src, src_format, channels, channel, frames, d_dst, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
+// what dzn_beamform_delays and dzn_beamform_sum refuse alike; "" when the geometry is sound
+static std::string beamform_geometry(int32_t channels, int64_t ch_stride, int64_t x_first, int64_t x_len, int64_t T,
+                                     int32_t hop) {
+  if (channels < 2 || channels > 64)
+    return std::to_string(channels) + " channel(s): an array has 2 .. 64";
+  if (hop < 256 || hop > 4096 || (hop & (hop - 1)))
+    return "hop " + std::to_string(hop) + " is not a power of two in [256, 4096]";
+  if (T < 0 || x_len < 0 || x_first < 0 || ch_stride < x_len || T > INT64_MAX / 8 || ch_stride > INT64_MAX / 4 / channels)
+    return "bad T / x_first / x_len / ch_stride (ch_stride >= x_len >= 0)";
+  return "";
+}
+
+static std::string span_text(int64_t lo, int64_t hi) {
+  return "[" + std::to_string(lo) + ", " + std::to_string(hi) + ")";
+}
+
+int dzn_beamform_delays(int32_t device, const float* d_x, int32_t channels, int64_t ch_stride, int64_t x_first, int64_t x_len,
+                        int64_t T, int32_t ref, int32_t hop, int32_t max_lag, const float* d_twiddle, int64_t b0, int64_t b1,
+                        int32_t* d_lag, float* d_peak, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_beamform_delays: " + why;
+    return DZN_E_INVALID;
+  };
+  const std::string geo = beamform_geometry(channels, ch_stride, x_first, x_len, T, hop);
+  if (!geo.empty()) return refuse(geo);
+  if (ref < 0 || ref >= channels)
+    return refuse("reference channel " + std::to_string(ref) + " of a source with " + std::to_string(channels) + " channels");
+  if (max_lag < 1 || max_lag > hop / 2)
+    return refuse("max_lag " + std::to_string(max_lag) + " is outside [1, hop / 2 = " + std::to_string(hop / 2) + "]");
+  const int64_t nb = (T + hop - 1) / hop + 1;
+  if (b0 < 0 || b1 < b0 || b1 > nb)
+    return refuse("blocks " + span_text(b0, b1) + " are not inside the " + std::to_string(nb) + " blocks of the recording");
+  if (b1 == b0) return DZN_OK;
+  // what frames b0 .. b1 - 1 read inside the recording: samples (b0 - 1) hop .. b1 hop - 1
+  int64_t lo = (b0 - 1) * hop, hi = b1 * hop;
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > T ? T : hi;
+  if (lo < hi && (x_first > lo || x_first + x_len < hi))
+    return refuse("the span given, " + span_text(x_first, x_first + x_len) + ", does not cover the input " + span_text(lo, hi) +
+                  " that the blocks read");
+  if (!d_twiddle || !d_lag || !d_peak || (lo < hi && !d_x)) return refuse("null pointer");
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  return launch_beamform_delays(d_x, channels, ch_stride, x_first, x_len, T, ref, hop, max_lag, d_twiddle, b0, b1, d_lag,
+                                d_peak, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+int dzn_beamform_sum(int32_t device, const float* d_x, int32_t channels, int64_t ch_stride, int64_t x_first, int64_t x_len,
+                     int64_t T, int32_t hop, const int32_t* d_delay, int64_t num_blocks, int64_t n0, int64_t n1, float* d_dst,
+                     void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_beamform_sum: " + why;
+    return DZN_E_INVALID;
+  };
+  const std::string geo = beamform_geometry(channels, ch_stride, x_first, x_len, T, hop);
+  if (!geo.empty()) return refuse(geo);
+  const int64_t nb = (T + hop - 1) / hop + 1;
+  if (num_blocks != nb)
+    return refuse("num_blocks = " + std::to_string(num_blocks) + ", a recording of " + std::to_string(T) + " samples has " +
+                  std::to_string(nb) + " blocks of hop " + std::to_string(hop));
+  if (n0 < 0 || n1 < n0 || n1 > T)
+    return refuse("samples " + span_text(n0, n1) + " are not inside the recording of " + std::to_string(T));
+  if (n1 == n0) return DZN_OK;
+  if (!d_delay || !d_dst) return refuse("null pointer");
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  // The delays decide which samples are read, so the columns this range uses — blocks n0 / hop .. (n1 - 1) / hop + 1 of every
+  // channel, a few KB — come back to the host and are checked before anything is launched.  This is the one wait of the call:
+  // it ends when the stream has produced d_delay.
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const int64_t ba = n0 / hop, bz = (n1 - 1) / hop + 2, cols = bz - ba;
+  std::vector<int32_t> dl((size_t)(cols * channels));
+  if (hipMemcpy2DAsync(dl.data(), (size_t)cols * 4, d_delay + ba, (size_t)num_blocks * 4, (size_t)cols * 4, (size_t)channels,
+                       hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return DZN_E_HIP;
+  int64_t lo = INT64_MAX, hi = INT64_MIN;
+  for (int64_t b = ba; b + 1 < bz; ++b) {      // samples of block b read with the delays of b and b + 1
+    const int64_t s0 = n0 > b * hop ? n0 : b * hop, s1 = n1 < (b + 1) * hop ? n1 : (b + 1) * hop;
+    for (int32_t c = 0; c < channels; ++c)
+      for (int k = 0; k < 2; ++k) {
+        const int64_t d = dl[(size_t)(c * cols + (b - ba) + k)];
+        if (d < -(hop / 2) || d > hop / 2)
+          return refuse("delay " + std::to_string(d) + " of channel " + std::to_string(c) + " in block " +
+                        std::to_string(b + k) + " is beyond hop / 2 = " + std::to_string(hop / 2));
+        const int64_t a = s0 + d < 0 ? 0 : s0 + d, z = s1 + d > T ? T : s1 + d;
+        if (a < z) {
+          lo = a < lo ? a : lo;
+          hi = z > hi ? z : hi;
+        }
+      }
+  }
+  if (lo < hi && (x_first > lo || x_first + x_len < hi))
+    return refuse("the span given, " + span_text(x_first, x_first + x_len) + ", does not cover the input " + span_text(lo, hi) +
+                  " that the range reads");
+  if (lo < hi && !d_x) return refuse("null pointer");
+  return launch_beamform_sum(d_x, channels, ch_stride, x_first, x_len, T, hop, d_delay, num_blocks, n0, n1, d_dst, st);
+}
+
 static_assert(sizeof(dzn_ingest_desc) == 96, "dzn_ingest_desc is 96 bytes without padding (include/dzn.h)");
 
 int dzn_ingest_many(int32_t device, const void* d_stage, int64_t stage_bytes, const dzn_ingest_desc* h_desc,
@@ -2191,6 +2289,7 @@ int dzn_checked_collect_post(unsigned int*, int);
 int dzn_checked_collect_resample(unsigned int*, int);
 int dzn_checked_collect_ingest(unsigned int*, int);
 int dzn_checked_collect_gallery(unsigned int*, int);
+int dzn_checked_collect_beamform(unsigned int*, int);
 }
 #endif
 int dzn_checked_status(uint32_t* out4, int32_t reset) {
@@ -2200,7 +2299,8 @@ int dzn_checked_status(uint32_t* out4, int32_t reset) {
                             dzn_checked_collect_resblock_fused, dzn_checked_collect_resblock_ws,
                             dzn_checked_collect_attention_split, dzn_checked_collect_attention_planes,
                             dzn_checked_collect_frontend_fused, dzn_checked_collect_post,
-                            dzn_checked_collect_resample, dzn_checked_collect_ingest, dzn_checked_collect_gallery};
+                            dzn_checked_collect_resample, dzn_checked_collect_ingest, dzn_checked_collect_gallery,
+                            dzn_checked_collect_beamform};
   unsigned int tot[4] = {0u, 0u, 0u, 0u};
   for (collect_fn f : fns) {
     unsigned int w[4] = {0u, 0u, 0u, 0u};

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import dist as dz_dist
-from .audio import check_channel
+from .audio import Beamform, check_channel
 from .core import SlidingWindow, SlidingWindowFeature
 from .engine import Engine
 from .inference import WindowRunner, window_plan
@@ -61,8 +61,8 @@ class _Detection:
         the weights; its device and precision apply).  batch_size: windows per launch (default: the hub's
         [inference.args] batch_size, capped by the engine's max_batch).  resample: "host" | "device", where a recording at
         another rate is resampled (pipeline.open_recording; default: the DiariZenPipeline's setting, else "host").  channel: the
-        channel of a recording that is read, an index or "downmix" (default: the DiariZenPipeline's setting, else 0); a file
-        mapping's "channel" key overrides it."""
+        channel of a recording that is read, an index, "downmix" or an audio.Beamform (default: the DiariZenPipeline's setting,
+        else 0); a file mapping's "channel" key overrides it."""
         from .pipeline import DiariZenPipeline, _load_checkpoint, load_hub_config
         extra = ()
         self._owned: Optional[Engine] = None
@@ -73,7 +73,7 @@ class _Detection:
         self.resample = resample
         if channel is None:
             channel = segmentation.channel if isinstance(segmentation, DiariZenPipeline) else 0
-        self.channel = check_channel(channel)
+        self.channel = channel if isinstance(channel, Beamform) else check_channel(channel)
         if isinstance(segmentation, DiariZenPipeline):
             pipe = segmentation
             self.device = pipe.device

@@ -150,10 +150,12 @@ def resolve_hub(repo_id: str, cache_dir: Optional[str] = None) -> Path:
 
 def open_recording(in_wav, sample_rate: int, lazy: bool = False, resample: str = "host", device=None, channel=0):
     """what `DiariZenPipeline.__call__` accepts (path, BytesIO, bytes or a ProtocolFile mapping with "audio") -> ONE channel
-    at `sample_rate`, float32.  channel: an index (default 0, the first channel) or "downmix" (audio.downmix: the mean of the
-    channels); a mapping's own "channel" key (PA/core/io.py:300-303) overrides it, and an index the file does not have is a
-    ValueError.  lazy=True (sharded runs): a WAV or SPHERE file at that rate is opened as an audio.WavSource /
-    audio.SphereSource, so that every rank decodes only the byte range of its windows (other files need the resampler's
+    at `sample_rate`, float32.  channel: an index (default 0, the first channel), "downmix" (audio.downmix: the mean of the
+    channels) or an audio.Beamform (array recordings: the channels aligned by GCC-PHAT delays and averaged on `device`; the
+    result is an audio.BeamformedSource whatever `lazy` and `resample` say, a file at another rate is beamformed at its own
+    rate and resampled on the device, and a sharded run is refused); a mapping's own "channel" key (PA/core/io.py:300-303)
+    overrides it, and an index the file does not have is a ValueError.
+    lazy=True (sharded runs): a WAV or SPHERE file at that rate is opened as an audio.WavSource / audio.SphereSource, so that every rank decodes only the byte range of its windows (other files need the resampler's
     context and are decoded whole).
     resample="device": a file at ANOTHER rate comes back as an audio.ResampledSource on `device` — nothing is resampled on the
     host, `read_device(start, n)` reads, uploads and resamples (csrc/resample.hip) only the input span of the range, so the
@@ -166,9 +168,13 @@ def open_recording(in_wav, sample_rate: int, lazy: bool = False, resample: str =
         if in_wav.get("channel") is not None:          # (None, as in PA/core/io.py:300: no choice of the file's own)
             channel = in_wav["channel"]
         in_wav = in_wav["audio"]
-    channel = audio_io.check_channel(channel)
+    beamform = channel if isinstance(channel, audio_io.Beamform) else None
+    if beamform is None:
+        channel = audio_io.check_channel(channel)
     assert isinstance(in_wav, (str, os.PathLike, BytesIO, bytes)), \
         f"input must be either a str, BytesIO or a ProtocolFile; there was {type(in_wav)}"
+    if beamform is not None:
+        return _open_beamformed(in_wav, sample_rate, device, beamform)
     if (lazy or resample == "device") and isinstance(in_wav, (str, os.PathLike)):
         with open(in_wav, "rb") as f:
             magic = f.read(8)
@@ -187,6 +193,27 @@ def open_recording(in_wav, sample_rate: int, lazy: bool = False, resample: str =
         x0 = audio_io.select_channel(x, channel)       # as first_channel_16k
         return x0 if sr == sample_rate else audio_io.ResampledSource(x0, sample_rate, device, orig_rate=sr)
     return audio_io.first_channel_16k(in_wav, sample_rate, channel)
+
+
+def _open_beamformed(in_wav, sample_rate: int, device, beamform):
+    """open_recording for channel=audio.Beamform(...): an audio.BeamformedSource on `device` over the file's channels.  A WAV
+    or SPHERE file on disk is read span by span as stored; anything else is decoded whole by load_audio.  One device only."""
+    from . import dist as dz_dist
+    if dz_dist.world_size() > 1:
+        raise RuntimeError(DiariZenPipeline._ONE_DEVICE % ("channel=Beamform(...)", dz_dist.world_size()))
+    src = None
+    if isinstance(in_wav, (str, os.PathLike)):
+        with open(in_wav, "rb") as f:
+            magic = f.read(8)
+        opener = audio_io.SphereSource if magic.startswith(b"NIST_1A") else audio_io.WavSource
+        try:
+            src = opener(in_wav, 0)
+        except ValueError:
+            src = None                                 # not that container, or a form of it only the whole-file decoders read
+    if src is not None:
+        return audio_io.BeamformedSource(src, sample_rate, device, beamform)
+    x, sr = audio_io.load_audio(in_wav)
+    return audio_io.BeamformedSource(x, sample_rate, device, beamform, orig_rate=sr)
 
 
 def recording_on_device(waveform, device, lo: int = 0, n: Optional[int] = None, zero_extend: bool = False) -> torch.Tensor:
@@ -227,7 +254,9 @@ class DiariZenPipeline:
         "device" (audio.ResampledSource: the file's samples are uploaded as stored and resampled by csrc/resample.hip, in a
         sharded run every rank only its windows' span; the waveform differs from the host one in its last bits).
         channel: which channel of a recording is diarized — an index (default 0, inference.py:128) or "downmix", the mean of
-        the channels (audio.downmix; both sides of a two-channel telephone call); a file mapping's "channel" key overrides it.
+        the channels (audio.downmix; both sides of a two-channel telephone call), or an audio.Beamform for array recordings
+        (GCC-PHAT delay-and-sum on the device, offline only: live sessions and the hub refuse it); a file mapping's "channel"
+        key overrides it.
         num_streams (r4): engine handles that consecutive batches of windows alternate over, each on its own HIP stream
         (inference.WindowRunner): independent batches overlap on the device — +2.6 % on the 30-min workload,
         +44 % at 32-window batches (profiles/r4_*), same bits.  Each extra handle costs one more copy of the weights and a
@@ -244,7 +273,7 @@ class DiariZenPipeline:
         if resample not in ("host", "device"):
             raise ValueError(f'resample is "host" or "device", not {resample!r}')
         self.resample = resample
-        self.channel = audio_io.check_channel(channel)
+        self.channel = channel if isinstance(channel, audio_io.Beamform) else audio_io.check_channel(channel)
         inf, clu = config["inference"]["args"], config["clustering"]["args"]
         if not torch.cuda.is_available():
             raise RuntimeError("DiariZenPipeline (diarizen_amd) needs a HIP device; no CPU fallback")

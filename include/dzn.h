@@ -481,6 +481,44 @@ int32_t dzn_resample_tile(void);
 int dzn_decode(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int32_t channel, int64_t frames,
                float* d_dst, void* hip_stream);
 
+/* Array recordings (csrc/beamform.hip; diarizen_amd/audio.py: Beamform, BeamformedSource): GCC-PHAT
+ * delay-and-sum over C = `channels` microphones, 2 <= C <= 64, into the one channel the engine diarizes.  Both calls are
+ * stateless.  Input is PLANAR float32: d_x[c * ch_stride + (i - x_first)] is sample i of channel c for
+ * x_first <= i < x_first + x_len of a recording of T samples (x = 0 outside [0, T)); ch_stride >= x_len.
+ * With hop H a power of two in [256, 4096], W = 2 H, the recording has nb = ceil(T / H) + 1 blocks; frame b is samples
+ * (b - 1) H .. (b + 1) H - 1 times the periodic Hann window 0.5 - 0.5 cos(2 pi i / W).
+ *
+ * dzn_beamform_delays: for the blocks [b0, b1) and every channel c != ref, X = FFT_W(frame), P = X_c conj(X_ref),
+ * G = P / |P| (0 where P is 0), g[l] = (1 / W) sum_k G_k e^{+2 pi i k l / W} (circular), and
+ *     d_lag  i32 [channels][b1 - b0]   the l in [-max_lag, max_lag] with the largest g[l]; ties go to the first of
+ *                                      0, -1, +1, -2, +2, ..; with x_c[i] = s[i - d] the peak sits at l = +d
+ *     d_peak f32 [channels][b1 - b0]   g[lag]
+ * The row of `ref` is 0 / 0, and so is every block whose frames are all zero.  1 <= max_lag <= H / 2.
+ * d_twiddle f32 [W / 2][2] = (cos, -sin)(2 pi k / W), computed in float64 and rounded once (audio.beamform_twiddle).
+ * One launch, enqueue-only, on `hip_stream` of `device` (< 0 = current).
+ *
+ * dzn_beamform_sum: d_dst f32 [n1 - n0] = y[n0 .. n1) with, for n in [b H, (b + 1) H),
+ *     S_b(n) = (sum_{c = 0 .. C-1} x_c[n + delay[c][b]]) / C      float32 running sum in ascending c, ONE IEEE division
+ *     y[n]   = a + w (v - a),  a = S_b(n), v = S_{b+1}(n), w = (n - b H) / H      three separately rounded float32 operations
+ * d_delay i32 [channels][num_blocks] holds the smoothed delays of the WHOLE recording (num_blocks = nb; audio.smooth_delays),
+ * |delay| <= H / 2.  The delays decide which samples are read, so the call copies the columns its range uses back to the host
+ * (a few KB) and checks them before it launches: it waits for what `hip_stream` holds up to d_delay; the launch itself is
+ * enqueued.  dzn_beamform_tile: output samples per workgroup (tests place ranges on it).
+ *
+ * Results depend on the inputs and parameters alone, not on the range asked for: a range call returns the bits of the same
+ * slice of a whole-recording call.  Both return DZN_E_INVALID with a dzn_last_error(NULL) message, and launch nothing, for
+ * channels outside [2, 64], ref outside the channels, a hop that is not a power of two in [256, 4096], max_lag outside
+ * [1, H / 2], blocks outside [0, nb] or samples outside [0, T], num_blocks != nb, a delay beyond H / 2 in the columns used, and
+ * an x span that does not cover what the range reads inside [0, T): samples (b0 - 1) H .. b1 H - 1 for the delays, n + delay
+ * of either block for the sum. */
+int dzn_beamform_delays(int32_t device, const float* d_x, int32_t channels, int64_t ch_stride, int64_t x_first, int64_t x_len,
+                        int64_t T, int32_t ref, int32_t hop, int32_t max_lag, const float* d_twiddle, int64_t b0, int64_t b1,
+                        int32_t* d_lag, float* d_peak, void* hip_stream);
+int dzn_beamform_sum(int32_t device, const float* d_x, int32_t channels, int64_t ch_stride, int64_t x_first, int64_t x_len,
+                     int64_t T, int32_t hop, const int32_t* d_delay, int64_t num_blocks, int64_t n0, int64_t n1, float* d_dst,
+                     void* hip_stream);
+int32_t dzn_beamform_tile(void);
+
 /* Live hub (diarizen_amd/hub.py): the ingest of MANY sessions in one launch (csrc/ingest.hip).  A descriptor is what one
  * dzn_resample or dzn_decode call takes; its source lies in one staging buffer, its bank in one buffer of banks, its output in
  * one pooled buffer f32 [pool_rows][row_floats] (a row per session: the recording so far, zeros behind it).  Fixed-width

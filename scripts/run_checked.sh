@@ -24,5 +24,7 @@ python -m pytest tests/test_frontend_kernels_gpu.py -m gpu -q -x 2>&1 | tail -3
 # engine reuse (one oversize handle, many shapes: tracker indices m / L against max_batch entries, tile offsets, the last key tile
 # of the plane attention): likewise
 python -m pytest tests/test_engine_reuse_gpu.py -m gpu -q -x 2>&1 | tail -3
+# the beamformer (beamform.hip, ids 0x85x: frame and shifted sample reads against the span given, butterfly / twiddle indices): likewise
+python -m pytest tests/test_beamform_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
