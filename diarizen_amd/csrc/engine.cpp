@@ -99,10 +99,29 @@ struct ResConv {
   int cin = 0, cout = 0, ksz = 3, stride = 1;
   int k2 = 0;   // > 0: conv2 of a down-sampling block with the 1x1 shortcut folded in — k2 more K columns from the previous stage's image
   float l1max = 0.f, bmax = 0.f;   // max_oc sum_k |W[oc][k]| and max_oc |shift[oc]| of the folded conv: |out| <= amax(in) l1max + bmax
+  // decided at finalize (finalize_emb), from the arithmetic mode, the switches and the weight planes that exist
+  bool c32 = false;     // 3x3 stride 1 over 32 planes in a split mode: the first stage's dedicated kernel (conv_split.hip)
+  bool keep2 = false;   // DZN_PREC_F16: this contraction keeps two fp16 terms (bit CLS_RESNET of Switches::f16_keep2)
 };
+// A BasicBlock and the kernels it runs as (decided at finalize, finalize_emb; acted on by emb_block):
+//   PER_CONV     stride 1: conv1 and conv2 as a launch each
+//   FUSED32      stride 1, 32 planes, two-term fp16 modes: both convolutions in one kernel (resblock_fused.hip)
+//   WS           stride 1, 32 or 64 planes, two-term fp16 modes: the producer / consumer form (resblock_ws.hip)
+//   DOWN         first block of stages 2-4: stride-2 conv1, the 1x1 shortcut as its own launch (sc), conv2 adds it
+//   DOWN_FOLDED  ... the 1x1 shortcut is c2.k2 more K columns of conv2 (make_resconv_shortcut)
 struct ResBlock {
+  enum Form { PER_CONV, FUSED32, WS, DOWN, DOWN_FOLDED };
   ResConv c1, c2, sc;
-  bool has_sc = false;
+  Form form = PER_CONV;
+  int np = 2;   // fp16 terms per operand in the FUSED32 / WS kernels
+};
+// One stage of the ResNet trunk over an fbank image of given size: what a launch over its images needs (stage_geometry; the
+// tables by emb_set_geometry).
+struct EmbStage {
+  int s, Hs, Ws, Cc;       // images of Hs x Ws pixels, Cc planes innermost, stored with a one-pixel zero border
+  int64_t img, interior;   // elements of one image with its border; offset of pixel (0, 0) behind the border
+  int M;                   // Hs * Ws: rows of a contraction over one image
+  int32_t *tab1, *tab2;    // device, row y * Ws + x -> offset of its 3x3 patch here / of pixel (2y, 2x) in the previous stage
 };
 
 std::string last_create_error;
@@ -255,17 +274,14 @@ struct dzn_handle {
   std::vector<std::vector<ResBlock>> stages;
   int emb_T = -1;  // geometry currently baked into tables / borders
   int maxTf = 0;
-  int sH[4]{}, sW[4]{}, sC[4]{};
+  int sC[4]{};
   float* sbuf[4][3]{};
   int64_t sbuf_elems[4]{};  // allocation per image at the largest geometry
-  int64_t simg[4]{};        // elements per image at the current geometry
-  int32_t* tab1[4]{};   // tables of the CURRENT geometry (owned by geoms)
-  int32_t* tab2[4]{};
-  struct EmbGeom {      // per fbank-frame-count T: row-offset tables stay resident, so alternating window
-    int32_t* t1[4]{};   // lengths (full windows / a ragged tail) neither re-upload nor synchronise
-    int32_t* t2[4]{};
+  struct EmbGeom {          // per fbank-frame-count T: row-offset tables stay resident, so alternating window
+    EmbStage stage[4]{};    // lengths (full windows / a ragged tail) neither re-upload nor synchronise
   };
   std::map<int, EmbGeom> geoms;
+  const EmbStage* stage = nullptr;   // the four stages at the CURRENT geometry (emb_T; owned by geoms)
   float *frames = nullptr, *spec = nullptr, *pw = nullptr, *fb = nullptr, *pool = nullptr;
   // fbank rows per pass of frame_prep -> DFT -> power -> mel (frames / spec / pw hold that many rows: the frame grid of
   // max_batch windows a tenth of a window apart) and the mel energies of a shared frame grid, [<= max_batch * maxTf, NB]
@@ -783,6 +799,19 @@ void alloc_optional_workspace(H* h) {
 }
 
 // ------------------------------------------------------------------ embedding: finalize
+// kaldi fbank at 16 kHz: 25 ms frames every 10 ms, a frame row zero-padded to a multiple of 32 columns, a 512-point real DFT
+// of which bins 0 .. 255 are kept (the spectrum row is [cos | sin] of those bins)
+constexpr int FB_FLEN = 400, FB_SHIFT = 160, FB_KP = 416, FB_NFFT = 512, FB_BINS = 256;
+
+// The four trunk stages g[0 .. 4) over an fbank image of NB mel bins x T frames: stage 0 keeps its size, every later stage
+// halves both sides (3x3, stride 2, padding 1).  The tables are left null.
+void stage_geometry(int NB, int T, const int* C, EmbStage* g) {
+  for (int s = 0; s < 4; ++s) {
+    const int Hs = s == 0 ? NB : (g[s - 1].Hs - 1) / 2 + 1, Ws = s == 0 ? T : (g[s - 1].Ws - 1) / 2 + 1;
+    g[s] = {s, Hs, Ws, C[s], (int64_t)(Hs + 2) * (Ws + 2) * C[s], ((int64_t)(Ws + 2) + 1) * C[s], Hs * Ws, nullptr, nullptr};
+  }
+}
+
 void fold_bn(H* h, const std::string& bn, int Cn, std::vector<float>& scale, std::vector<float>& shift) {
   const HostT& g = need(h, bn + ".weight");
   const HostT& b = need(h, bn + ".bias");
@@ -797,20 +826,27 @@ void fold_bn(H* h, const std::string& bn, int Cn, std::vector<float>& scale, std
   }
 }
 
-ResConv make_resconv(H* h, const std::string& conv, const std::string& bn, int cin, int cout, int ksz,
-                     int stride) {
+// One conv of the ResNet with its BatchNorm folded: the weights OIHW [cout][cin][ksz][ksz] times the BatchNorm scale of their
+// output channel as K = ksz^2 cin columns of the contraction's rows, wp[o * ld + (dh * ksz + dw) * cin + ci]; returns the shifts.
+std::vector<float> conv_bn_columns(H* h, const std::string& conv, const std::string& bn, int cin, int cout, int ksz, float* wp,
+                                   int ld) {
   const HostT& w = need(h, conv + ".weight");
   expect_numel(w, (int64_t)cout * cin * ksz * ksz, conv + ".weight");
   std::vector<float> sc, sh;
   fold_bn(h, bn, cout, sc, sh);
-  const int K = ksz * ksz * cin;
-  std::vector<float> wp((size_t)cout * K);
   for (int o = 0; o < cout; ++o)
     for (int ci = 0; ci < cin; ++ci)
       for (int dh = 0; dh < ksz; ++dh)
         for (int dw = 0; dw < ksz; ++dw)
-          wp[(size_t)o * K + (dh * ksz + dw) * cin + ci] =
-              w.v[(((size_t)o * cin + ci) * ksz + dh) * ksz + dw] * sc[o];
+          wp[(size_t)o * ld + (dh * ksz + dw) * cin + ci] = w.v[(((size_t)o * cin + ci) * ksz + dh) * ksz + dw] * sc[o];
+  return sh;
+}
+
+ResConv make_resconv(H* h, const std::string& conv, const std::string& bn, int cin, int cout, int ksz,
+                     int stride) {
+  const int K = ksz * ksz * cin;
+  std::vector<float> wp((size_t)cout * K);
+  const std::vector<float> sh = conv_bn_columns(h, conv, bn, cin, cout, ksz, wp.data(), K);
   ResConv r;
   r.cin = cin;
   r.cout = cout;
@@ -832,24 +868,12 @@ ResConv make_resconv(H* h, const std::string& conv, const std::string& bn, int c
 // whole concatenated row (make_lin).  Built once: the weights do not change between calls.
 ResConv make_resconv_shortcut(H* h, const std::string& conv, const std::string& bn, const std::string& sconv,
                               const std::string& sbn, int cprev, int cout) {
-  const HostT& w = need(h, conv + ".weight");
-  expect_numel(w, (int64_t)cout * cout * 9, conv + ".weight");
-  const HostT& ws = need(h, sconv + ".weight");
-  expect_numel(ws, (int64_t)cout * cprev, sconv + ".weight");
-  std::vector<float> sc, sh, ssc, ssh;
-  fold_bn(h, bn, cout, sc, sh);
-  fold_bn(h, sbn, cout, ssc, ssh);
   const int K1 = 9 * cout, Kp = K1 + (cprev + 63) / 64 * 64;
+  std::vector<float> wp((size_t)cout * Kp, 0.f);
+  std::vector<float> bias = conv_bn_columns(h, conv, bn, cout, cout, 3, wp.data(), Kp);
+  const std::vector<float> ssh = conv_bn_columns(h, sconv, sbn, cprev, cout, 1, wp.data() + K1, Kp);
   if (K1 % 64 != 0 || cprev % 32 != 0) throw EngineError(DZN_E_INVALID, "shortcut fusion: channel counts");
-  std::vector<float> wp((size_t)cout * Kp, 0.f), bias(cout);
-  for (int o = 0; o < cout; ++o) {
-    for (int ci = 0; ci < cout; ++ci)
-      for (int dh = 0; dh < 3; ++dh)
-        for (int dw = 0; dw < 3; ++dw)
-          wp[(size_t)o * Kp + (dh * 3 + dw) * cout + ci] = w.v[(((size_t)o * cout + ci) * 3 + dh) * 3 + dw] * sc[o];
-    for (int ci = 0; ci < cprev; ++ci) wp[(size_t)o * Kp + K1 + ci] = ws.v[(size_t)o * cprev + ci] * ssc[o];
-    bias[o] = sh[o] + ssh[o];
-  }
+  for (int o = 0; o < cout; ++o) bias[o] += ssh[o];
   ResConv r;
   r.cin = cout;
   r.cout = cout;
@@ -864,55 +888,53 @@ void finalize_emb(H* h) {
   const std::string E = "embedding.resnet.";
   const int NB = c.num_mel_bins;
   if (NB != 80 || c.embed_out_dim <= 0) throw EngineError(DZN_E_INVALID, "embedding config");
-  const int flen = 400, NFFT = 512, Kp = 416;
   {
     // torch.hamming_window(400, periodic=False): 0.54 - 0.46 cos(2 pi n / (N-1))
-    std::vector<float> wdw(flen);
-    for (int i = 0; i < flen; ++i)
-      wdw[i] = (float)(0.54 - 0.46 * std::cos(2.0 * M_PI * (double)i / (double)(flen - 1)));
+    std::vector<float> wdw(FB_FLEN);
+    for (int i = 0; i < FB_FLEN; ++i)
+      wdw[i] = (float)(0.54 - 0.46 * std::cos(2.0 * M_PI * (double)i / (double)(FB_FLEN - 1)));
     h->hamming = upload(h, wdw);
     // real DFT as a contraction: rows 0..255 cos, 256..511 sin, bins 0..255 (bin 256 unused)
-    std::vector<float> dft((size_t)512 * Kp, 0.f);
-    for (int f = 0; f < 256; ++f)
-      for (int t = 0; t < flen; ++t) {
-        const double ang = 2.0 * M_PI * (double)((int64_t)f * t % NFFT) / (double)NFFT;
-        dft[(size_t)f * Kp + t] = (float)std::cos(ang);
-        dft[(size_t)(256 + f) * Kp + t] = (float)(-std::sin(ang));
+    std::vector<float> dft((size_t)2 * FB_BINS * FB_KP, 0.f);
+    for (int f = 0; f < FB_BINS; ++f)
+      for (int t = 0; t < FB_FLEN; ++t) {
+        const double ang = 2.0 * M_PI * (double)((int64_t)f * t % FB_NFFT) / (double)FB_NFFT;
+        dft[(size_t)f * FB_KP + t] = (float)std::cos(ang);
+        dft[(size_t)(FB_BINS + f) * FB_KP + t] = (float)(-std::sin(ang));
       }
-    h->dft = make_lin(h, dft, nullptr, 512, Kp, 512, Kp);
+    h->dft = make_lin(h, dft, nullptr, 2 * FB_BINS, FB_KP, 2 * FB_BINS, FB_KP);
     // Kaldi mel banks (torchaudio.compliance.kaldi.get_mel_banks, float32 arithmetic):
     // low 20 Hz, high = Nyquist, 80 triangles in mel(f) = 1127 ln(1 + f/700), bins 0..255
     const float mel_low = 1127.0f * logf(1.0f + 20.0f / 700.0f);
     const float mel_high = 1127.0f * logf(1.0f + 8000.0f / 700.0f);
     const float delta = (mel_high - mel_low) / (float)(NB + 1);
-    std::vector<float> mw((size_t)NB * 256, 0.f);
+    std::vector<float> mw((size_t)NB * FB_BINS, 0.f);
     for (int b = 0; b < NB; ++b) {
       const float left = mel_low + (float)b * delta;
       const float center = mel_low + ((float)b + 1.0f) * delta;
       const float right = mel_low + ((float)b + 2.0f) * delta;
-      for (int f = 0; f < 256; ++f) {
+      for (int f = 0; f < FB_BINS; ++f) {
         const float mel = 1127.0f * logf(1.0f + (31.25f * (float)f) / 700.0f);
         const float up = (mel - left) / (center - left);
         const float down = (right - mel) / (right - center);
-        mw[(size_t)b * 256 + f] = std::max(0.0f, std::min(up, down));
+        mw[(size_t)b * FB_BINS + f] = std::max(0.0f, std::min(up, down));
       }
     }
-    h->mel = make_lin(h, mw, nullptr, NB, 256, NB, 256);
+    h->mel = make_lin(h, mw, nullptr, NB, FB_BINS, NB, FB_BINS);
   }
   const int m = 32;
   {
-    const HostT& w = need(h, E + "conv1.weight");
-    expect_numel(w, (int64_t)m * 9, E + "conv1.weight");
-    std::vector<float> sc, sh;
-    fold_bn(h, E + "bn1", m, sc, sh);
-    std::vector<float> wf(w.v);
-    for (int o = 0; o < m; ++o)
-      for (int k = 0; k < 9; ++k) wf[(size_t)o * 9 + k] *= sc[o];
+    std::vector<float> wf((size_t)m * 9);
+    const std::vector<float> sh = conv_bn_columns(h, E + "conv1", E + "bn1", 1, m, 3, wf.data(), 9);
     h->stem_w = upload(h, wf);
     h->stem_b = upload(h, sh);
   }
   const int nblocks[4] = {3, 4, 6, 3};
   h->stages.resize(4);
+  // DZN_PREC_F16: bit CLS_RESNET of DZN_F16_KEEP2 governs the whole trunk — the contractions of img_desc keep two fp16 terms
+  // and so do the fused BasicBlocks; without it both run on ONE term (the embedding trunk is three orders of magnitude inside
+  // its cosine bar with one term: profiles/r4_reduced_mode_emulation.txt)
+  const bool h2 = prec_is_h2(c.precision), keep2 = c.precision == DZN_PREC_F16 && ((h->sw.f16_keep2 >> CLS_RESNET) & 1);
   int cin = m;
   for (int s = 0; s < 4; ++s) {
     const int cout = m << s;
@@ -923,12 +945,27 @@ void finalize_emb(H* h) {
       ResBlock& rb = h->stages[s][j];
       const int stride = (j == 0 && s > 0) ? 2 : 1;
       rb.c1 = make_resconv(h, bp + ".conv1", bp + ".bn1", cin, cout, 3, stride);
-      rb.has_sc = (stride != 1 || cin != cout);
-      if (rb.has_sc && h->sw.fuse_shortcut) {
+      const bool down = stride != 1 || cin != cout;   // with a 1x1 shortcut; DZN_NO_SHORTCUT_FUSION=1 keeps it its own launch
+      if (down && h->sw.fuse_shortcut) {
         rb.c2 = make_resconv_shortcut(h, bp + ".conv2", bp + ".bn2", bp + ".shortcut.0", bp + ".shortcut.1", cin, cout);
       } else {
         rb.c2 = make_resconv(h, bp + ".conv2", bp + ".bn2", cout, cout, 3, 1);
-        if (rb.has_sc) rb.sc = make_resconv(h, bp + ".shortcut.0", bp + ".shortcut.1", cin, cout, 1, stride);
+        if (down) rb.sc = make_resconv(h, bp + ".shortcut.0", bp + ".shortcut.1", cin, cout, 1, stride);
+      }
+      // (r4) stride-1 blocks of 32 and 64 planes in the two-term fp16 modes: both convolutions in one kernel, the intermediate
+      // image stays in LDS; DZN_NO_RESBLOCK_FUSION=1 keeps the per-conv kernels.  DZN_RESBLOCK_WS: which plane counts take the
+      // producer / consumer form (bit 0: 32 planes, bit 1: 64 planes — the only fused form that stage has)
+      const bool fusable = h->sw.fuse_resblock && h2 && rb.c1.l.W2h && rb.c2.l.W2h;
+      const int ws = h->sw.resblock_ws;
+      if (down) rb.form = rb.c2.k2 > 0 ? ResBlock::DOWN_FOLDED : ResBlock::DOWN;
+      else if (fusable && cin == 32 && !(ws & 1)) rb.form = ResBlock::FUSED32;
+      else if (fusable && ((cin == 32 && (ws & 1)) || (cin == 64 && (ws & 2)))) rb.form = ResBlock::WS;
+      rb.np = c.precision == DZN_PREC_F16 && !keep2 ? 1 : 2;
+      for (ResConv* rc : {&rb.c1, &rb.c2, &rb.sc}) {
+        if (rc == &rb.sc && rb.form != ResBlock::DOWN) continue;   // no shortcut conv of its own
+        // first ResNet stage: every input pixel split once instead of once per tap
+        rc->c32 = prec_is_split(c.precision) && rc->cin == 32 && rc->cout == 32 && rc->l.W3;
+        rc->keep2 = keep2;
       }
       cin = cout;
     }
@@ -938,25 +975,22 @@ void finalize_emb(H* h) {
 
   // workspace
   const int64_t B = c.max_batch;
-  const int Tmax = c.max_samples < flen ? 0 : 1 + (c.max_samples - flen) / 160;
+  const int Tmax = c.max_samples < FB_FLEN ? 0 : 1 + (c.max_samples - FB_FLEN) / FB_SHIFT;
   if (Tmax < 8) throw EngineError(DZN_E_INVALID, "max_samples too short for the embedding model");
   h->maxTf = Tmax;
   // frames / spec / pw hold one pass of the fbank chain.  A pass is sized for the frame grid windows share when they lie
   // a tenth of a window apart (segmentation_step = 0.1 in every pipeline configuration): G = (B - 1) q + Tmax rows with
   // q = ceil(Tmax / 10), not B * Tmax.  Anything longer (unrelated windows, wider strides) takes several passes.
   h->fb_rows = (B - 1) * ((Tmax + 9) / 10) + Tmax;
-  h->frames = dalloc<float>(h, h->fb_rows * Kp);
-  h->spec = dalloc<float>(h, h->fb_rows * 512);
-  h->pw = dalloc<float>(h, h->fb_rows * 256);
+  h->frames = dalloc<float>(h, h->fb_rows * FB_KP);
+  h->spec = dalloc<float>(h, h->fb_rows * 2 * FB_BINS);
+  h->pw = dalloc<float>(h, h->fb_rows * FB_BINS);
   h->fb = dalloc<float>(h, B * Tmax * NB);
   h->melg = dalloc<float>(h, B * Tmax * NB);
-  int Hs = NB, Ws = Tmax;
+  EmbStage g[4];
+  stage_geometry(NB, Tmax, h->sC, g);
   for (int s = 0; s < 4; ++s) {
-    if (s > 0) {
-      Hs = (Hs - 1) / 2 + 1;
-      Ws = (Ws - 1) / 2 + 1;
-    }
-    h->sbuf_elems[s] = (int64_t)(Hs + 2) * (Ws + 2) * h->sC[s];
+    h->sbuf_elems[s] = g[s].img;
     for (int k = 0; k < 3; ++k) h->sbuf[s][k] = dalloc<float>(h, B * h->sbuf_elems[s]);
   }
   h->pool = dalloc<float>(h, B * 8 * feat);
@@ -972,40 +1006,28 @@ void finalize_emb(H* h) {
 void emb_set_geometry(H* h, int T, hipStream_t st) {
   if (T == h->emb_T) return;
   const int64_t B = h->cfg.max_batch;
-  int Hs = h->cfg.num_mel_bins, Ws = T;
-  int Hp = 0, Wp = 0;
-  auto it = h->geoms.find(T);
-  const bool fresh = it == h->geoms.end();
+  const bool fresh = h->geoms.find(T) == h->geoms.end();
   if (fresh && h->geoms.size() >= 64) throw EngineError(DZN_E_INVALID, "too many distinct window lengths on one handle");
-  H::EmbGeom& gm = h->geoms[T];
+  EmbStage* g = h->geoms[T].stage;
+  if (fresh) stage_geometry(h->cfg.num_mel_bins, T, h->sC, g);
   for (int s = 0; s < 4; ++s) {
-    if (s > 0) {
-      Hp = Hs;
-      Wp = Ws;
-      Hs = (Hs - 1) / 2 + 1;
-      Ws = (Ws - 1) / 2 + 1;
-    }
-    h->sH[s] = Hs;
-    h->sW[s] = Ws;
-    const int Cc = h->sC[s];
-    h->simg[s] = (int64_t)(Hs + 2) * (Ws + 2) * Cc;
     if (fresh) {
+      const int Hs = g[s].Hs, Ws = g[s].Ws;
       std::vector<int32_t> t1((size_t)Hs * Ws), t2((size_t)Hs * Ws, 0);
       for (int y = 0; y < Hs; ++y)
         for (int x = 0; x < Ws; ++x) {
-          t1[(size_t)y * Ws + x] = (y * (Ws + 2) + x) * Cc;  // top-left of the 3x3 patch
-          if (s > 0) t2[(size_t)y * Ws + x] = ((2 * y) * (Wp + 2) + 2 * x) * h->sC[s - 1];
+          t1[(size_t)y * Ws + x] = (y * (Ws + 2) + x) * g[s].Cc;  // top-left of the 3x3 patch
+          if (s > 0) t2[(size_t)y * Ws + x] = ((2 * y) * (g[s - 1].Ws + 2) + 2 * x) * g[s - 1].Cc;
         }
-      gm.t1[s] = dalloc<int32_t>(h, (int64_t)Hs * Ws, false);
-      gm.t2[s] = dalloc<int32_t>(h, (int64_t)Hs * Ws, false);
-      HIPCHK(hipMemcpy(gm.t1[s], t1.data(), t1.size() * 4, hipMemcpyHostToDevice));  // synchronous, first use only
-      HIPCHK(hipMemcpy(gm.t2[s], t2.data(), t2.size() * 4, hipMemcpyHostToDevice));
+      g[s].tab1 = dalloc<int32_t>(h, (int64_t)Hs * Ws, false);
+      g[s].tab2 = dalloc<int32_t>(h, (int64_t)Hs * Ws, false);
+      HIPCHK(hipMemcpy(g[s].tab1, t1.data(), t1.size() * 4, hipMemcpyHostToDevice));  // synchronous, first use only
+      HIPCHK(hipMemcpy(g[s].tab2, t2.data(), t2.size() * 4, hipMemcpyHostToDevice));
     }
-    h->tab1[s] = gm.t1[s];
-    h->tab2[s] = gm.t2[s];
     for (int k = 0; k < 3; ++k)
       HIPCHK(hipMemsetAsync(h->sbuf[s][k], 0, B * h->sbuf_elems[s] * sizeof(float), st));
   }
+  h->stage = g;
   h->emb_T = T;
 }
 
@@ -1510,13 +1532,43 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
 }
 
 // ------------------------------------------------------------------ embedding forward
-// `subset`: windows in which no speaker is active skip the trunk.  Zero weights pool to zero
-// (PA/models/blocks/pooling.py:44-131 with its 1e-8 guards), so every one of their embeddings is seg_1's bias (SURVEY a18;
-// tests/test_emb_gpu.py holds the device to that bit for bit).  The masks decide it and they only exist on the device, so
-// the subset is built there (window_active -> compact_active: ascending list + count) and every trunk kernel is launched
-// over all B grid rows with (count, list): surplus rows exit at once.  No flag is read back — the call only enqueues
-// (include/dzn.h), and it can be captured in a HIP graph.  The fbank is computed for every window, silent or not.
-//
+// An image of the trunk with its |max| tracker (null outside the two-term fp16 modes).
+struct Img {
+  float *p, *am;
+};
+
+// What the stages of one emb_forward call share.
+struct EmbCall {
+  H* h;
+  hipStream_t st;
+  int B, T, S, L;   // windows, fbank frames per window, masks per window, frames per mask
+  // the device-side list of windows with an active speaker (count, ascending list, flag per window): every trunk kernel is
+  // launched over all B grid rows with it; all null on the dense path
+  const int *z_count, *z_list, *flag;
+  // DZN_PREC_F32_H2 / DZN_PREC_F16: one |max| tracker per image buffer (sbuf[stage][k] -> slot AM_IMG0 + 3 stage + k), running
+  // over the forward (stem kernel, stage-1 kernel and the contraction epilogues all track what they write)
+  float* am(int stage, int k) const {
+    return prec_is_h2(h->cfg.precision) ? h->amax + (dzn_handle::AM_IMG0 + 3 * stage + k) * (int64_t)h->cfg.max_batch : nullptr;
+  }
+  Img image(int stage, int k) const { return {h->sbuf[stage][k], am(stage, k)}; }
+};
+
+// one pass of the fbank chain: nsig signals `stride` samples apart, t frames each -> mel energies of their nsig * t
+// (<= fb_rows) frames
+void fbank_pass(const EmbCall& e, const float* w, int nsig, int64_t stride, int t, float* mel_out) {
+  H* h = e.h;
+  const int64_t rows = (int64_t)nsig * t;
+  chk(launch_frame_prep(w, nsig, stride, t, FB_FLEN, FB_SHIFT, FB_KP, h->hamming, 0.97f, h->frames, e.st), "frame_prep");
+  dzn_gemm_desc d = gd(h, h->frames, h->dft, h->spec, rows, FB_KP, 2 * FB_BINS);
+  d.precision = DZN_PREC_F32;  // the spectrum spans ~9 decades: keep the transform in fp32
+  chk(launch_gemm(d, e.st), "dft");
+  chk(launch_power(h->spec, rows, FB_BINS, h->pw, e.st), "power");
+  dzn_gemm_desc m = gd(h, h->pw, h->mel, mel_out, rows, FB_BINS, h->cfg.num_mel_bins);
+  m.precision = DZN_PREC_F32;
+  chk(launch_gemm(m, e.st), "mel");
+}
+
+// ---- kaldi fbank + per-window mean subtraction of B windows of N samples into h->fb [B * T, NB] ----
 // Window b starts at wave + b * win_stride.  Everything in front of the per-window mean is a function of ONE frame's 400
 // samples (DC removal, pre-emphasis, Hamming; the DFT, power and mel contractions are row-independent; the log is per
 // element).  When the windows are cut from one recording a whole number q of frame shifts apart (win_stride = 160 q) and
@@ -1524,183 +1576,171 @@ void seg_forward(H* h, const float* wave, int B, int N, float* d_logp, uint8_t* 
 // b q + t: the chain runs once over the G = (B - 1) q + T frames of the span the windows cover and log_cmn gathers each
 // window's rows.  Any other stride (unrelated windows: win_stride = N) runs the chain per window, read at that stride.
 // Either way the chain works in passes of at most fb_rows rows; a row's result does not depend on the pass it is in.
+void emb_fbank(const EmbCall& e, const float* wave, int64_t win_stride, int N) {
+  H* h = e.h;
+  const int B = e.B, T = e.T, NB = h->cfg.num_mel_bins;
+  const float eps = 1.1920928955078125e-07f;
+  const bool shared = B > 1 && win_stride > 0 && win_stride % FB_SHIFT == 0 && win_stride <= (int64_t)N - FB_FLEN + FB_SHIFT;
+  if (shared) {
+    const int q = (int)(win_stride / FB_SHIFT);        // <= T, so G <= B * T rows of melg
+    const int64_t G = (int64_t)(B - 1) * q + T;
+    for (int64_t r0 = 0; r0 < G; r0 += h->fb_rows)
+      fbank_pass(e, wave + r0 * FB_SHIFT, 1, 0, (int)std::min<int64_t>(h->fb_rows, G - r0), h->melg + r0 * NB);
+    chk(launch_log_cmn_gather(h->melg, q, h->fb, B, T, NB, eps, e.st), "log_cmn");
+  } else {
+    const int per = (int)std::min<int64_t>(h->fb_rows / T, B);   // fb_rows >= maxTf >= T: at least one window per pass
+    for (int b0 = 0; b0 < B; b0 += per)
+      fbank_pass(e, wave + b0 * win_stride, std::min(per, B - b0), win_stride, T, h->fb + (int64_t)b0 * T * NB);
+    chk(launch_log_cmn(h->fb, B, T, NB, eps, e.st), "log_cmn");
+  }
+  tap(h, "fbank", h->fb, (int64_t)B * T, NB, NB, e.st);
+}
+
+// ---- stem: conv1 + bn1 + relu of the fbank image into buffer 0 of the first stage ----
+Img emb_stem(const EmbCall& e) {
+  H* h = e.h;
+  const Img out = e.image(0, 0);
+  chk(launch_stem_conv(h->fb, e.B, e.T, h->cfg.num_mel_bins, h->sC[0], h->stem_w, h->stem_b, out.p, e.st, out.am, e.z_count,
+                       e.z_list),
+      "stem");
+  return out;
+}
+
+// the contraction of one ResNet conv over a whole image per window, written to the interior of `out` in this stage
+// (tab1): a 3x3 reads patch rows, two-level K = (dh | dw*C + ci); a stride-2 conv reads the previous stage's image (tab2),
+// the 1x1 one its centre pixels; windows from the active list; DZN_PREC_F16: two fp16 terms if the trunk's bit asks
+dzn_gemm_desc img_desc(const EmbCall& e, const EmbStage& g, const Img& in, const ResConv& rc, const Img& out) {
+  const bool down = rc.stride == 2;
+  const EmbStage& gin = down ? e.h->stage[g.s - 1] : g;   // the stage whose image it reads (rc.cin planes)
+  dzn_gemm_desc d = gd(e.h, rc.ksz == 1 ? in.p + gin.interior : in.p, rc.l, out.p + g.interior, g.M, 0, 0);
+  d.a_rowoff = down ? g.tab2 : g.tab1;
+  d.c_rowoff = g.tab1;
+  if (rc.ksz == 3) {
+    d.kc = 3 * rc.cin;
+    d.ldk = (int64_t)(gin.Ws + 2) * rc.cin;
+  }
+  d.nz = e.B;
+  d.a_z0 = gin.img;
+  d.c_z0 = g.img;
+  d.a_amax = in.am;
+  d.c_amax = out.am;
+  d.z_count = e.z_count;
+  d.z_list = e.z_list;
+  if (rc.keep2) d.precision = DZN_PREC_F32_H2;
+  return d;
+}
+
+// a stride-1 3x3 inside stage g.s: out = [relu](act(conv(in)) + R).  x2 (rc.k2 > 0): the previous stage's image, whose centre
+// pixels are the second A segment (the folded shortcut)
+void conv3(const EmbCall& e, const EmbStage& g, const Img& in, const ResConv& rc, const Img& out, const float* R, int act,
+           int post_relu, const Img* x2 = nullptr) {
+  if (rc.c32) {
+    // first ResNet stage: dedicated kernel, every input pixel split once instead of once per tap
+    chk(launch_conv3x3_c32_split(in.p, rc.l.W3, rc.l.b, R, out.p, e.B, g.Hs, g.Ws, act == DZN_ACT_RELU, post_relu, e.st, out.am,
+                                 rc.l.W2h, rc.l.wsc, in.am, e.z_count, e.z_list),
+        "resnet conv3x3 c32");
+    return;
+  }
+  dzn_gemm_desc d = img_desc(e, g, in, rc, out);
+  d.act = act;
+  d.R = R ? R + g.interior : nullptr;
+  d.post_relu = post_relu;
+  if (rc.k2 > 0) {
+    d.A2 = x2->p + e.h->stage[g.s - 1].interior;   // pixel (2y, 2x) = centre of conv1's stride-2 patch (rc.k2 planes)
+    d.a2_rowoff = g.tab2;
+    d.a2_z0 = e.h->stage[g.s - 1].img;
+    d.a2_amax = x2->am;
+    d.k1 = 9 * rc.cin;
+    d.k2 = rc.k2;
+  }
+  chk(launch_gemm(d, e.st), "resnet conv3x3");
+}
+
+// One BasicBlock in the form finalize_emb chose for it.  A stride-1 block reads buffer `cur` of its stage; a down-sampling
+// block reads `prev`, the previous stage's output.  Returns the buffer of the stage that holds the block's output.
+int emb_block(const EmbCall& e, const EmbStage& g, const ResBlock& rb, const Img& prev, int cur) {
+  const int B = e.B, s = g.s;
+  const Img in = e.image(s, cur), mid = e.image(s, (cur + 1) % 3), out = e.image(s, (cur + 2) % 3);   // of a stride-1 block
+  switch (rb.form) {
+    case ResBlock::DOWN:
+    case ResBlock::DOWN_FOLDED: {
+      // reads the previous stage's image with stride 2 (tab2); buffers 0, 1, 2 = conv1's output, the block's, the shortcut's
+      dzn_gemm_desc d = img_desc(e, g, prev, rb.c1, e.image(s, 0));
+      d.act = DZN_ACT_RELU;
+      chk(launch_gemm(d, e.st), "resnet conv3x3 s2");
+      const bool folded = rb.form == ResBlock::DOWN_FOLDED;
+      if (!folded) {
+        dzn_gemm_desc d1 = img_desc(e, g, prev, rb.sc, e.image(s, 2));
+        chk(launch_gemm(d1, e.st), "resnet shortcut");
+      }
+      // folded: the 1x1 shortcut is k2 more K columns of conv2 (make_resconv_shortcut): no shortcut image, no residual read
+      conv3(e, g, e.image(s, 0), rb.c2, e.image(s, 1), folded ? nullptr : e.h->sbuf[s][2], DZN_ACT_NONE, 1, &prev);
+      return 1;
+    }
+    case ResBlock::FUSED32:
+      chk(launch_resblock32_fused(in.p, out.p, rb.c1.l.W2h, rb.c1.l.wsc, rb.c1.l.b, rb.c2.l.W2h, rb.c2.l.wsc, rb.c2.l.b, in.am,
+                                  out.am, rb.c1.l1max, rb.c1.bmax, B, g.Hs, g.Ws, rb.np, e.st, e.z_count, e.z_list),
+          "resblock32 fused");
+      break;
+    case ResBlock::WS:
+      chk(launch_resblock_ws(in.p, out.p, rb.c1.l.W2h, rb.c1.l.wsc, rb.c1.l.b, rb.c2.l.W2h, rb.c2.l.wsc, rb.c2.l.b, in.am, out.am,
+                             rb.c1.l1max, rb.c1.bmax, B, g.Hs, g.Ws, rb.c1.cin, e.st, e.z_count, e.z_list, rb.np),
+          "resblock ws");
+      break;
+    case ResBlock::PER_CONV:
+      conv3(e, g, in, rb.c1, mid, nullptr, DZN_ACT_RELU, 0);
+      conv3(e, g, mid, rb.c2, out, in.p, DZN_ACT_NONE, 1);
+  }
+  return (cur + 2) % 3;
+}
+
+// ---- one stage of the ResNet34 trunk: `prev` = the image it reads (stage 0: the stem's, its own buffer 0; later stages: the
+// previous stage's output); returns the image its last block wrote ----
+Img emb_stage(const EmbCall& e, int s, const Img& prev) {
+  int cur = 0;
+  for (const ResBlock& rb : e.h->stages[s]) cur = emb_block(e, e.h->stage[s], rb, prev, cur);
+  return e.image(s, cur);
+}
+
+// ---- TSTP pooling of the last stage's image `x` for all S masks + seg_1 ----
+void emb_pool_head(const EmbCall& e, const Img& x, const float* masks, float* d_emb) {
+  H* h = e.h;
+  const EmbStage& g = h->stage[3];
+  const int feat = g.Cc * g.Hs;
+  chk(launch_stats_pool(x.p, e.B, g.Hs, g.Ws, g.Cc, masks, e.S, e.L, h->pool, e.st, e.flag), "stats_pool");
+  tap(h, "pool", h->pool, (int64_t)e.B * e.S, 2 * feat, 2 * feat, e.st);
+  dzn_gemm_desc d = gd(h, h->pool, h->seg1, d_emb, (int64_t)e.B * e.S, 2 * feat, h->cfg.embed_out_dim);
+  d.precision = DZN_PREC_F32;
+  chk(launch_gemm(d, e.st), "seg_1");
+}
+
+// kaldi fbank -> ResNet34 -> multi-mask TSTP -> seg_1 for B windows of N samples, window b at wave + b * win_stride.
+// `subset`: windows in which no speaker is active skip the trunk.  Zero weights pool to zero
+// (PA/models/blocks/pooling.py:44-131 with its 1e-8 guards), so every one of their embeddings is seg_1's bias (SURVEY a18;
+// tests/test_emb_gpu.py holds the device to that bit for bit).  The masks decide it and they only exist on the device, so
+// the subset is built there (window_active -> compact_active: ascending list + count) and every trunk kernel is launched
+// over all B grid rows with (count, list): surplus rows exit at once.  No flag is read back — the call only enqueues
+// (include/dzn.h), and it can be captured in a HIP graph.  The fbank is computed for every window, silent or not.
 void emb_forward(H* h, const float* wave, int64_t win_stride, const float* masks, int B, int S, int N, int L, float* d_emb,
                  hipStream_t st) {
-  const dzn_config& c = h->cfg;
-  const int flen = 400, fshift = 160, Kp = 416, NB = c.num_mel_bins;
-  if (N < flen) throw EngineError(DZN_E_INVALID, "waveform shorter than one fbank frame (400 samples)");
-  const int T = 1 + (N - flen) / fshift;
+  if (N < FB_FLEN) throw EngineError(DZN_E_INVALID, "waveform shorter than one fbank frame (400 samples)");
+  const int T = 1 + (N - FB_FLEN) / FB_SHIFT;
   if (T > h->maxTf) throw EngineError(DZN_E_INVALID, "N exceeds max_samples");
   if (S < 1 || S > 8) throw EngineError(DZN_E_INVALID, "S must be in [1, 8]");
   emb_set_geometry(h, T, st);
   const bool subset = h->sw.emb_skip && !h->sw.debug_taps && h->seg1.b != nullptr;
-  const int *zc = nullptr, *zl = nullptr, *zflag = nullptr;
+  const EmbCall e{h, st, B, T, S, L, subset ? h->win_cnt : nullptr, subset ? h->win_idx : nullptr, subset ? h->win_flag : nullptr};
   if (subset) {
     chk(launch_window_active(masks, B, S * L, h->win_flag, st), "window_active");
     chk(launch_compact_active(h->win_flag, B, h->win_cnt, h->win_idx, h->emb_totals, st), "compact_active");
-    zc = h->win_cnt;
-    zl = h->win_idx;
-    zflag = h->win_flag;
   } else {
     h->emb_dense_windows += B;   // dzn_embed_skip_stats counts every window, whichever path it took
   }
-  const int64_t MT = (int64_t)B * T;
-  // ---- kaldi fbank ----
-  // one pass: nsig signals `stride` samples apart, t frames each -> mel energies of their nsig * t (<= fb_rows) frames
-  auto fbank_pass = [&](const float* w, int nsig, int64_t stride, int t, float* mel_out) {
-    const int64_t rows = (int64_t)nsig * t;
-    chk(launch_frame_prep(w, nsig, stride, t, flen, fshift, Kp, h->hamming, 0.97f, h->frames, st), "frame_prep");
-    dzn_gemm_desc d = gd(h, h->frames, h->dft, h->spec, rows, Kp, 512);
-    d.precision = DZN_PREC_F32;  // the spectrum spans ~9 decades: keep the transform in fp32
-    chk(launch_gemm(d, st), "dft");
-    chk(launch_power(h->spec, rows, 256, h->pw, st), "power");
-    dzn_gemm_desc m = gd(h, h->pw, h->mel, mel_out, rows, 256, NB);
-    m.precision = DZN_PREC_F32;
-    chk(launch_gemm(m, st), "mel");
-  };
-  const float eps = 1.1920928955078125e-07f;
-  const bool shared = B > 1 && win_stride > 0 && win_stride % fshift == 0 && win_stride <= (int64_t)N - flen + fshift;
-  if (shared) {
-    const int q = (int)(win_stride / fshift);        // <= T, so G <= B * T rows of melg
-    const int64_t G = (int64_t)(B - 1) * q + T;
-    for (int64_t r0 = 0; r0 < G; r0 += h->fb_rows)
-      fbank_pass(wave + r0 * fshift, 1, 0, (int)std::min<int64_t>(h->fb_rows, G - r0), h->melg + r0 * NB);
-    chk(launch_log_cmn_gather(h->melg, q, h->fb, B, T, NB, eps, st), "log_cmn");
-  } else {
-    const int per = (int)std::min<int64_t>(h->fb_rows / T, B);   // fb_rows >= maxTf >= T: at least one window per pass
-    for (int b0 = 0; b0 < B; b0 += per)
-      fbank_pass(wave + b0 * win_stride, std::min(per, B - b0), win_stride, T, h->fb + (int64_t)b0 * T * NB);
-    chk(launch_log_cmn(h->fb, B, T, NB, eps, st), "log_cmn");
-  }
-  tap(h, "fbank", h->fb, MT, NB, NB, st);
-  // ---- ResNet34 trunk ----
-  const float* prev = nullptr;  // output image of the previous stage
-  int cur = 0;
-  // DZN_PREC_F32_H2: one |max| tracker per image buffer (sbuf[s][k] -> slot AM_IMG0 + 3 s + k), running over the
-  // forward (stem kernel, stage-1 kernel and the contraction epilogues all track what they write)
-  const bool h2 = prec_is_h2(c.precision);
-  const int64_t MB = c.max_batch;
-  if (h2) chk(launch_fill_u32(h->amax + dzn_handle::AM_IMG0 * MB, 0u, 12 * MB, st), "image tracker reset");
-  auto img_am = [&](const float* buf) -> float* {
-    if (!h2 || !buf) return nullptr;
-    for (int s2 = 0; s2 < 4; ++s2)
-      for (int k = 0; k < 3; ++k)
-        if (buf == h->sbuf[s2][k]) return h->amax + (dzn_handle::AM_IMG0 + 3 * s2 + k) * MB;
-    return nullptr;
-  };
-  chk(launch_stem_conv(h->fb, B, T, NB, h->sC[0], h->stem_w, h->stem_b, h->sbuf[0][0], st, img_am(h->sbuf[0][0]), zc, zl),
-      "stem");
-  for (int s = 0; s < 4; ++s) {
-    const int Hs = h->sH[s], Ws = h->sW[s], Cc = h->sC[s];
-    const int64_t img = h->simg[s];
-    const int64_t interior = ((int64_t)(Ws + 2) + 1) * Cc;
-    const int M = Hs * Ws;
-    // the contraction of one ResNet conv over a whole image per window, written to the interior of `out` in this stage
-    // (tab1): a 3x3 reads patch rows, two-level K = (dh | dw*C + ci); a stride-2 conv reads the previous stage's image (tab2),
-    // the 1x1 one its centre pixels; windows from the active list; DZN_PREC_F16: two fp16 terms if the trunk's bit asks
-    auto img_desc = [&](const float* in, const ResConv& rc, float* out) {
-      const bool down = rc.stride == 2;
-      const int Win = down ? h->sW[s - 1] : Ws;
-      dzn_gemm_desc d = gd(h, rc.ksz == 1 ? in + ((int64_t)(Win + 2) + 1) * rc.cin : in, rc.l, out + interior, M, 0, 0);
-      d.a_rowoff = down ? h->tab2[s] : h->tab1[s];
-      d.c_rowoff = h->tab1[s];
-      if (rc.ksz == 3) {
-        d.kc = 3 * rc.cin;
-        d.ldk = (int64_t)(Win + 2) * rc.cin;
-      }
-      d.nz = B;
-      d.a_z0 = down ? h->simg[s - 1] : img;
-      d.c_z0 = img;
-      d.a_amax = img_am(in);
-      d.c_amax = img_am(out);
-      d.z_count = zc;
-      d.z_list = zl;
-      if (c.precision == DZN_PREC_F16 && ((h->sw.f16_keep2 >> CLS_RESNET) & 1)) d.precision = DZN_PREC_F32_H2;
-      return d;
-    };
-    // x2 (rc.k2 > 0): the previous stage's image, whose centre pixels are the second A segment (the folded shortcut)
-    auto conv3 = [&](const float* in, const ResConv& rc, float* out, const float* R, int act,
-                     int post_relu, const float* x2 = nullptr) {
-      if (prec_is_split(c.precision) && rc.cin == 32 && rc.cout == 32 && rc.l.W3 &&
-          (act == DZN_ACT_NONE || act == DZN_ACT_RELU)) {
-        // first ResNet stage: dedicated kernel, every input pixel split once instead of once per tap
-        chk(launch_conv3x3_c32_split(in, rc.l.W3, rc.l.b, R, out, B, Hs, Ws, act == DZN_ACT_RELU, post_relu, st,
-                                     img_am(out), rc.l.W2h, rc.l.wsc, img_am(in), zc, zl),
-            "resnet conv3x3 c32");
-        return;
-      }
-      dzn_gemm_desc d = img_desc(in, rc, out);   // stride-1 3x3 inside stage s
-      d.act = act;
-      d.R = R ? R + interior : nullptr;
-      d.post_relu = post_relu;
-      if (rc.k2 > 0) {
-        d.A2 = x2 + ((int64_t)(h->sW[s - 1] + 2) + 1) * rc.k2;   // pixel (2y, 2x) = centre of conv1's stride-2 patch
-        d.a2_rowoff = h->tab2[s];
-        d.a2_z0 = h->simg[s - 1];
-        d.a2_amax = img_am(x2);
-        d.k1 = 9 * rc.cin;
-        d.k2 = rc.k2;
-      }
-      chk(launch_gemm(d, st), "resnet conv3x3");
-    };
-    for (size_t j = 0; j < h->stages[s].size(); ++j) {
-      ResBlock& rb = h->stages[s][j];
-      if (rb.has_sc) {
-        // down-sampling block: reads the previous stage's image with stride 2 (tab2)
-        float* midb = h->sbuf[s][0];
-        float* outb = h->sbuf[s][1];
-        float* scb = h->sbuf[s][2];
-        dzn_gemm_desc d = img_desc(prev, rb.c1, midb);
-        d.act = DZN_ACT_RELU;
-        chk(launch_gemm(d, st), "resnet conv3x3 s2");
-        if (rb.c2.k2 > 0) {
-          // the 1x1 shortcut is k2 more K columns of conv2 (make_resconv_shortcut): no shortcut image, no residual read
-          conv3(midb, rb.c2, outb, nullptr, DZN_ACT_NONE, 1, prev);
-          cur = 1;
-          continue;
-        }
-        dzn_gemm_desc e = img_desc(prev, rb.sc, scb);
-        chk(launch_gemm(e, st), "resnet shortcut");
-        conv3(midb, rb.c2, outb, scb, DZN_ACT_NONE, 1);
-        cur = 1;
-      } else {
-        float* inb = h->sbuf[s][cur];
-        float* midb = h->sbuf[s][(cur + 1) % 3];
-        float* outb = h->sbuf[s][(cur + 2) % 3];
-        // (r4) 32-channel blocks in the two-term fp16 modes: both convolutions in one kernel, the intermediate image
-        // stays in LDS (resblock_fused.hip); DZN_NO_RESBLOCK_FUSION=1 keeps the per-conv kernels
-        const bool fusable = h->sw.fuse_resblock && prec_is_h2(c.precision) && rb.c1.cin == rb.c1.cout && rb.c1.l.W2h &&
-                             rb.c2.l.W2h && img_am(inb) != nullptr;
-        // (r5) DZN_PREC_F16: the fused blocks keep ONE fp16 term unless bit 14 of DZN_F16_KEEP2 asks for two (the embedding
-        // trunk is three orders of magnitude inside its cosine bar with one term: profiles/r4_reduced_mode_emulation.txt)
-        const int rb_np = (c.precision == DZN_PREC_F16 && !((h->sw.f16_keep2 >> CLS_RESNET) & 1)) ? 1 : 2;
-        if (fusable && rb.c1.cin == 32 && !(h->sw.resblock_ws & 1)) {
-          chk(launch_resblock32_fused(inb, outb, rb.c1.l.W2h, rb.c1.l.wsc, rb.c1.l.b, rb.c2.l.W2h, rb.c2.l.wsc, rb.c2.l.b,
-                                      img_am(inb), img_am(outb), rb.c1.l1max, rb.c1.bmax, B, Hs, Ws, rb_np, st, zc, zl),
-              "resblock32 fused");
-        } else if (fusable && ((rb.c1.cin == 32 && (h->sw.resblock_ws & 1)) || (rb.c1.cin == 64 && (h->sw.resblock_ws & 2)))) {
-          // producer / consumer wavefronts (resblock_ws.hip): the only fused form for the 64-plane stage
-          chk(launch_resblock_ws(inb, outb, rb.c1.l.W2h, rb.c1.l.wsc, rb.c1.l.b, rb.c2.l.W2h, rb.c2.l.wsc, rb.c2.l.b, img_am(inb),
-                                 img_am(outb), rb.c1.l1max, rb.c1.bmax, B, Hs, Ws, rb.c1.cin, st, zc, zl, rb_np),
-              "resblock ws");
-        } else {
-          conv3(inb, rb.c1, midb, nullptr, DZN_ACT_RELU, 0);
-          conv3(midb, rb.c2, outb, inb, DZN_ACT_NONE, 1);
-        }
-        cur = (cur + 2) % 3;
-      }
-    }
-    prev = h->sbuf[s][cur];
-  }
-  // ---- TSTP pooling for all S masks + seg_1 ----
-  const int feat = h->sC[3] * h->sH[3];
-  chk(launch_stats_pool(prev, B, h->sH[3], h->sW[3], h->sC[3], masks, S, L, h->pool, st, zflag), "stats_pool");
-  tap(h, "pool", h->pool, (int64_t)B * S, 2 * feat, 2 * feat, st);
-  {
-    dzn_gemm_desc d = gd(h, h->pool, h->seg1, d_emb, (int64_t)B * S, 2 * feat, c.embed_out_dim);
-    d.precision = DZN_PREC_F32;
-    chk(launch_gemm(d, st), "seg_1");
-  }
+  emb_fbank(e, wave, win_stride, N);
+  if (float* am0 = e.am(0, 0)) chk(launch_fill_u32(am0, 0u, 12 * (int64_t)h->cfg.max_batch, st), "image tracker reset");
+  Img x = emb_stem(e);
+  for (int s = 0; s < 4; ++s) x = emb_stage(e, s, x);
+  emb_pool_head(e, x, masks, d_emb);
 }
 
 template <typename F>

@@ -167,6 +167,37 @@ def test_embedding_reduced_precision_engines(built_lib, gpu, precision):
     assert torch.equal(emb.cpu()[0, 2], emb_model.emb_state_dict(0)["resnet.seg_1.bias"])
 
 
+@pytest.mark.parametrize("env", [("DZN_RESBLOCK_WS", "0"), ("DZN_RESBLOCK_WS", "3"), ("DZN_NO_RESBLOCK_FUSION", "1")],
+                         ids=lambda e: f"{e[0]}={e[1]}")
+@pytest.mark.parametrize("precision", ["f32h", "f16"])
+def test_embedding_matches_reference_golden_in_every_block_form(built_lib, gpu, monkeypatch, precision, env):
+    """The form a stride-1 BasicBlock takes is fixed at dzn_create from the precision and the switches: DZN_RESBLOCK_WS=0 runs
+    the 64-plane blocks per conv and the 32-plane blocks fused, =3 the 32-plane blocks on the producer / consumer form,
+    DZN_NO_RESBLOCK_FUSION=1 every stride-1 block per conv (stage 1 on the dedicated 32-plane kernel).  Each against the
+    reference golden at the bars of the default engine: f32h rel < 1e-4 and cosine > 0.9999, f16 cosine > 0.999; the inactive
+    speaker's embedding is seg_1's bias exactly."""
+    from oracle import emb_model
+    from oracle.gen_golden import synth_wave
+    g = np.load(os.path.join(GOLD, "emb_resnet.npz"))
+    B, N = int(g["B"]), int(g["N"])
+    monkeypatch.setenv(*env)                            # read once, at dzn_create
+    eng = _engine(gpu, B, N, precision=precision)
+    monkeypatch.delenv(env[0])
+    emb = eng.embed(synth_wave(B, N, int(g["wave_seed"])).to(gpu), torch.from_numpy(g["masks"]).to(gpu))
+    torch.cuda.synchronize()
+    emb = emb.cpu()
+    ref = torch.from_numpy(g["emb"])
+    rel = (emb - ref).abs().max().item() / ref.abs().max().item()
+    cos = torch.nn.functional.cosine_similarity(emb.reshape(-1, 256), ref.reshape(-1, 256), dim=-1).min().item()
+    print(f"[emb block forms {precision} {env[0]}={env[1]}] rel err {rel:.3e} min cosine {cos:.7f}")
+    if precision == "f16":
+        assert cos > 0.999
+    else:
+        assert rel < 1e-4 and cos > 0.9999
+    assert torch.equal(emb[0, 2], emb_model.emb_state_dict(0)["resnet.seg_1.bias"])
+    eng.close()
+
+
 def test_fbank_linear_mel_error_on_real_audio_vs_float64(built_lib, gpu):
     """How close is the device fbank (fp32 MFMA direct DFT + mel contraction) to the kaldi restatement evaluated in FLOAT64,
     on real speech (tests/golden/EN2002a_30s.wav, 4 windows of 8 s)?  Reported in log-mel units (what the ResNet sees,
