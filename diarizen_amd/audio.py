@@ -22,7 +22,10 @@ the bits of the same slice of a whole-recording call (`resample_input_span` says
 Array recordings (2 - 64 microphones) have a channel choice of their own, `Beamform`: GCC-PHAT delays per block
 (`beamform_delays_device`, csrc/beamform.hip), smoothed on the host (`smooth_delays`), then the channels aligned and averaged
 (`beamform_sum_device`); `BeamformedSource` runs the three over a file span by span, and
-`pipeline.open_recording(channel=Beamform(...))` returns one.
+`pipeline.open_recording(channel=Beamform(...))` returns one.  `Beamform(causal=True)` replaces the smoothing by
+`causal_delays`, which looks at no later block: the form a LIVE array feed takes (`FeedFormat(..., channel=Beamform(causal=True))`,
+`beam_ready`, `ArrayFeedPlanner`; csrc/beamform_live.hip tracks the delays on the device), with the offline result of the same
+file bit for bit.
 
 Live sources deliver the same stored forms in packets: `FeedFormat` names what a session is fed (`feed_format=`), `feed_ready`
 says which output samples are final after R frames, `FeedPlanner` turns chunks of bytes into device calls whose ranges tile
@@ -662,10 +665,13 @@ class Beamform:
     hop: the block hop in samples at the FILE's rate, a power of two in [256, 4096] (default: the largest one <= 0.256 s,
     capped at 4096); min_peak: the GCC-PHAT peak below which a block's delay is not trusted (default 8 / sqrt(2 hop): for
     unrelated channels the correlation is roughly Gaussian with sigma = 1 / sqrt(2 hop), so this is 8 sigma — a statistical
-    derivation that no real array recording has met yet).  Validated here; `plan` settles what depends on the file."""
+    derivation that no real array recording has met yet).  causal=True replaces the smoothing of the raw delays by the rule
+    that looks at no later block (`causal_delays`, DESIGN.md §4.24: a change of delay takes effect two blocks late) — the form a
+    live feed takes (`FeedFormat(..., channel=Beamform(causal=True))`), offered offline too so that the live result equals the
+    file's.  Validated here; `plan` settles what depends on the file."""
 
     def __init__(self, reference: int = 0, max_delay: float = 0.01, hop: Optional[int] = None,
-                 min_peak: Optional[float] = None):
+                 min_peak: Optional[float] = None, causal: bool = False):
         if isinstance(reference, (bool, np.bool_)) or not isinstance(reference, (int, np.integer)) or reference < 0:
             raise ValueError(f"Beamform: reference is a channel index >= 0, not {reference!r}")
         if isinstance(max_delay, (bool, str)) or not np.isfinite(max_delay) or not max_delay > 0:
@@ -675,6 +681,9 @@ class Beamform:
             raise ValueError(f"Beamform: hop is a power of two in [256, 4096], not {hop!r}")
         if min_peak is not None and (isinstance(min_peak, (bool, str)) or not np.isfinite(min_peak) or min_peak < 0):
             raise ValueError(f"Beamform: min_peak is a number >= 0, not {min_peak!r}")
+        if not isinstance(causal, (bool, np.bool_)):
+            raise ValueError(f"Beamform: causal is True or False, not {causal!r}")
+        self.causal = bool(causal)
         self.reference, self.max_delay = int(reference), float(max_delay)
         self.hop = None if hop is None else int(hop)
         self.min_peak = None if min_peak is None else float(min_peak)
@@ -697,7 +706,7 @@ class Beamform:
         return hop, max_lag, min_peak
 
     def _key(self):
-        return (self.reference, self.max_delay, self.hop, self.min_peak)
+        return (self.reference, self.max_delay, self.hop, self.min_peak, self.causal)
 
     def __eq__(self, other):
         return isinstance(other, Beamform) and self._key() == other._key()
@@ -707,7 +716,7 @@ class Beamform:
 
     def __repr__(self):
         return (f"Beamform(reference={self.reference}, max_delay={self.max_delay}, hop={self.hop}, "
-                f"min_peak={self.min_peak})")
+                f"min_peak={self.min_peak}{', causal=True' if self.causal else ''})")
 
 
 def beamform_blocks(total: int, hop: int) -> int:
@@ -753,6 +762,41 @@ def smooth_delays(lag, peak, total: int, hop: int, min_peak: float, reference: i
             held = np.median(np.stack([padded[k:k + nb] for k in range(5)]), axis=0)
         out[c] = held.astype(np.int32)
     return out
+
+
+def causal_delays(lag, peak, total: int, hop: int, min_peak: float, reference: int = 0) -> np.ndarray:
+    """`smooth_delays` restated so that delay[c, b] depends on blocks <= b alone (what a live feed can know; the device form
+    is dzn_beamform_track, csrc/beamform_live.hip): same arguments -> int32 [C, nb].  A block is reliable as in `smooth_delays`
+    (its frame holds at least `hop` samples of the recording, its peak >= float32(min_peak)); held[b] = lag[c, b] if reliable,
+    else held[b - 1], with held[-1] = 0 — no backward fill: a channel aligns from its first reliable block on; delay[c, b] = the
+    median of held[b - 4 .. b] with held[k] = held[0] for k < 0, a trailing median of 5 whose left edge repeats the first
+    entry.  The reference row is 0.  A change of delay takes effect two blocks late."""
+    lag = np.asarray(lag)
+    peak = np.asarray(peak, dtype=np.float32)
+    C, nb = lag.shape
+    total, hop = int(total), int(hop)
+    if nb != beamform_blocks(total, hop) or peak.shape != lag.shape:
+        raise ValueError(f"causal_delays: [C, {beamform_blocks(total, hop)}] lags and peaks for {total} samples at hop {hop}, "
+                         f"not {lag.shape} / {peak.shape}")
+    b = np.arange(nb, dtype=np.int64)
+    support = np.minimum(total, (b + 1) * hop) - np.maximum(0, (b - 1) * hop) >= hop
+    out = np.zeros((C, nb), dtype=np.int32)
+    for c in range(C):
+        if c == reference:
+            continue
+        reliable = support & (peak[c] >= np.float32(min_peak))
+        at = np.maximum.accumulate(np.where(reliable, b, -1))       # the latest reliable block at or before b, -1: none yet
+        held = np.where(at >= 0, lag[c][np.maximum(at, 0)], 0).astype(np.int64)
+        padded = np.concatenate([np.full(4, held[0], dtype=np.int64), held])
+        out[c] = np.median(np.stack([padded[k:k + nb] for k in range(5)]), axis=0).astype(np.int32)
+    return out
+
+
+def beam_ready(frames: int, hop: int) -> int:
+    """the schedule of an array feed: with `frames` = R frames received (the end unknown), nc = R // hop blocks are complete
+    and the beamformed samples [0, max(0, nc - 1) hop) are FINAL — sample n of block b reads n + delay of blocks b and b + 1,
+    below (b + 2) hop.  Output lags the feed by less than 2 hop frames."""
+    return max(0, int(frames) // int(hop) - 1) * int(hop)
 
 
 _DEVICE_TWIDDLES: dict = {}
@@ -886,7 +930,7 @@ class BeamformedSource:
 
     The first read estimates the delays of the whole recording: blocks go to `dzn_beamform_delays` in spans of about SPAN
     frames plus a halo of one hop, the [C, nb] lags and peaks come back (`.lags`, `.peaks`: raw) and `smooth_delays` makes
-    `.delays` of them.  Every read then walks its range in spans of at most SPAN samples, uploads the frames a span reads
+    `.delays` of them (`causal_delays` for a Beamform(causal=True)).  Every read then walks its range in spans of at most SPAN samples, uploads the frames a span reads
     (beamform_sum_span: a halo of at most hop / 2) and runs `dzn_beamform_sum`, so a 4 h, 8-channel file is never on the
     device as a whole.  A file at another rate than `new_rate` is beamformed at ITS rate and then resampled by the device
     resampler (csrc/resample.hip), whatever `resample=` says: the samples are already on the device."""
@@ -960,7 +1004,8 @@ class BeamformedSource:
             lags.append(lag.cpu().numpy())
             peaks.append(peak.cpu().numpy())
         self.lags, self.peaks = np.concatenate(lags, axis=1), np.concatenate(peaks, axis=1)
-        self.delays = smooth_delays(self.lags, self.peaks, self._total, self.hop, self.min_peak, self.beamform.reference)
+        rule = causal_delays if self.beamform.causal else smooth_delays
+        self.delays = rule(self.lags, self.peaks, self._total, self.hop, self.min_peak, self.beamform.reference)
         self._d_delays = torch.from_numpy(self.delays).to(self.device)
         return self.delays
 
@@ -998,9 +1043,12 @@ class FeedFormat:
     """What a live source delivers to a session (`feed_format=` of pipeline.stream / open_live / stream_live and of the
     detection pipelines' open_stream / stream): interleaved frames of `channels` samples at `rate` Hz, little-endian, in
     `encoding` — a key of SRC_FORMATS: "f32", "s16", "u8", "s24", "s32", "ulaw", "alaw" (G.711, one byte per sample).
-    `channel` is the channel the session hears: an index, "downmix" (audio.downmix of every frame), or None for the
-    pipeline's own `channel`.  A phone call is FeedFormat(8000, "ulaw", channels=2, channel=...), a microphone
-    FeedFormat(48000, "s16").  A bad encoding or a channel the frames do not have is refused here."""
+    `channel` is the channel the session hears: an index, "downmix" (audio.downmix of every frame), a
+    Beamform(causal=True) for a microphone array (2 .. 64 channels: GCC-PHAT delay-and-sum inside the device ingest,
+    `ArrayFeedPlanner`), or None for the pipeline's own `channel`.  A phone call is FeedFormat(8000, "ulaw", channels=2,
+    channel=...), a microphone FeedFormat(48000, "s16"), a meeting-room array FeedFormat(16000, "s16", channels=8,
+    channel=Beamform(causal=True)).  A bad encoding, a channel the frames do not have, an array geometry Beamform.plan refuses
+    and a Beamform that is not causal are refused here."""
 
     def __init__(self, rate: int, encoding: str, channels: int = 1, channel=None):
         if not isinstance(encoding, str) or encoding not in SRC_FORMATS:
@@ -1010,7 +1058,14 @@ class FeedFormat:
         if isinstance(channels, bool) or int(channels) != channels or channels < 1:
             raise ValueError(f"FeedFormat: channels is a positive integer, not {channels!r}")
         self.rate, self.encoding, self.channels = int(rate), encoding, int(channels)
-        self.channel = None if channel is None else _check_channel_of(channel, self.channels)
+        if isinstance(channel, Beamform):
+            if not channel.causal:
+                raise ValueError(f"FeedFormat: channel={channel!r} is not causal, and a live feed cannot look at later blocks: "
+                                 "pass Beamform(causal=True)")
+            channel.plan(self.rate, self.channels)                              # refuses 1 or > 64 channels, a missing reference
+            self.channel = channel
+        else:
+            self.channel = None if channel is None else _check_channel_of(channel, self.channels)
         code = SRC_FORMATS[encoding]
         self.src_format = 5 if code == 0 and self.channels != 1 else code       # float32 frames of several channels: "f32i"
         self.dtype = np.dtype(_SRC_DTYPES[code])                                # of an array fed to the session
@@ -1021,7 +1076,9 @@ class FeedFormat:
         return FeedFormat(self.rate, self.encoding, self.channels, channel if self.channel is None else self.channel)
 
     def channel_code(self) -> int:
-        """the channel as dzn_resample / dzn_decode take it (-1: downmix)"""
+        """the channel as dzn_resample / dzn_decode take it (-1: downmix); an array feed has none"""
+        if isinstance(self.channel, Beamform):
+            raise ValueError("FeedFormat: an array feed (channel=Beamform) has no channel code")
         return -1 if self.channel == "downmix" else int(self.channel)
 
     def __repr__(self):
@@ -1111,6 +1168,106 @@ class FeedPlanner:
         call = FeedCall(self._hist, self._hist_first, self.frames - self._hist_first, self.frames, self.ready, ready)
         self.ready = ready
         keep = self.frames if self.same_rate else feed_history(ready, self.o, self.n, self.width)
+        self._hist = self._hist[(keep - self._hist_first) * self.fmt.frame_bytes:]
+        self._hist_first = keep
+        return call
+
+
+class ArrayFeedCall:
+    """one planned device call of an array feed (dzn_beamform_feed, then dzn_resample where the rates differ): `data` = the
+    stored frames first .. first + frames (history, then new frames), `total` = frames received when the call is made (the
+    true length at the end of the stream), [b0, b1) the blocks it completes, [n0, n1) the beamformed samples it makes at the
+    feed's rate, and [m0, m1) the model-rate samples — equal to [n0, n1) for a feed at the model's rate; otherwise resampled
+    from the beamformed samples s_first .. n1, of which [s_first, n0) are carried over from the call before"""
+    __slots__ = ("data", "first", "frames", "total", "b0", "b1", "n0", "n1", "s_first", "m0", "m1")
+
+    def __init__(self, data, first, frames, total, b0, b1, n0, n1, s_first, m0, m1):
+        self.data, self.first, self.frames, self.total = data, first, frames, total
+        self.b0, self.b1, self.n0, self.n1, self.s_first, self.m0, self.m1 = b0, b1, n0, n1, s_first, m0, m1
+
+
+class ArrayFeedPlanner:
+    """The host half of an array feed, `FeedFormat(..., channel=Beamform(causal=True))` (streaming.WaveIngest runs its calls;
+    needs no device): turns chunks of bytes of any length into ArrayFeedCalls whose sample ranges tile [0, T) exactly once and
+    in order at the feed's rate, and whose block ranges tile the ceil(T / hop) + 1 blocks.
+
+    After R frames nc = R // hop blocks are complete and the samples below beam_ready(R) are final; a call is planned whenever
+    nc grows.  A chunk may end inside a frame (the remainder is carried and dropped at the end of the stream).  The frames a
+    later call still reads — from max(0, (nc - 1) hop - max_lag) on — are kept here as raw bytes and go in front of the next
+    upload, so no samples survive a call on the device; a chunk of more than `slot_frames` new frames is split, and an upload is
+    at most slot_frames + 2 hop + max_lag frames.  `finish()` is the one call with the true length: the remaining blocks and
+    [ready, T).  Where the feed's rate differs from the model's, the beamformed signal is the source of the device resampler
+    with FeedPlanner's arithmetic, "frames received" replaced by `ready` (T at finish): `out_ready` model-rate samples are
+    final, and a call names the first beamformed sample (`s_first`) its resample range still reads."""
+
+    def __init__(self, fmt: FeedFormat, model_rate: int, slot_frames: int):
+        if not isinstance(fmt.channel, Beamform):
+            raise ValueError(f"ArrayFeedPlanner: a FeedFormat with channel=Beamform(causal=True), not {fmt!r}")
+        self.fmt, self.model_rate = fmt, int(model_rate)
+        self.beamform = fmt.channel
+        self.hop, self.max_lag, self.min_peak = fmt.channel.plan(fmt.rate, fmt.channels)
+        self.same_rate = fmt.rate == self.model_rate
+        if self.same_rate:
+            self.o, self.n, self.width = 1, 1, 0
+        else:
+            self.o, self.n, self.width = resample_ratio(fmt.rate, self.model_rate)
+        self.K = 2 * self.width + self.o
+        self.slot_frames = int(slot_frames)
+        if self.slot_frames < 1:
+            raise ValueError("ArrayFeedPlanner: a slot holds at least one frame")
+        H = self.hop
+        self.max_upload_frames = self.slot_frames + 2 * H + self.max_lag
+        self.max_blocks = max(2, (self.slot_frames + H - 1) // H)        # blocks one call completes at the most
+        self.max_new = self.max_blocks * H                              # beamformed samples one call makes at the most
+        self.frames = 0                                                 # R: whole frames received
+        self.blocks = 0                                                 # blocks planned so far (nc; every block once finished)
+        self.ready = 0                                                  # beamformed samples planned so far: [0, ready) is final
+        self.out_ready = 0                                              # model-rate samples planned so far
+        self.finished = False
+        self._partial = b""
+        self._hist = b""                                                # frames _hist_first .. R as stored
+        self._hist_first = 0
+
+    def length_after(self, nbytes: int) -> int:
+        """the output length if the stream ended after `nbytes` more bytes"""
+        return resampled_length(self.frames + (len(self._partial) + nbytes) // self.fmt.frame_bytes, self.o, self.n)
+
+    def append(self, data) -> list:
+        """data: bytes-like, or an array of the format's stored dtype -> the calls that the new frames make possible"""
+        if self.finished:
+            raise RuntimeError("feed already finished")
+        fb = self.fmt.frame_bytes
+        buf = self._partial + _feed_bytes(data, self.fmt)
+        whole = len(buf) // fb
+        self._partial = buf[whole * fb:]
+        calls = []
+        for f0 in range(0, whole, self.slot_frames):
+            k = min(self.slot_frames, whole - f0)
+            self._hist += buf[f0 * fb:(f0 + k) * fb]
+            self.frames += k
+            nc = self.frames // self.hop
+            if nc > self.blocks:
+                calls.append(self._call(nc, beam_ready(self.frames, self.hop), False))
+        return calls
+
+    def finish(self) -> list:
+        """end of stream: a trailing partial frame is dropped; -> the call for the remaining blocks and [ready, T)"""
+        if self.finished:
+            return []
+        self.finished, self._partial = True, b""
+        return [self._call(beamform_blocks(self.frames, self.hop), self.frames, True)]
+
+    def _call(self, blocks: int, ready: int, last: bool) -> ArrayFeedCall:
+        if self.same_rate:
+            s_first, out = self.ready, ready
+        else:
+            s_first = feed_history(self.out_ready, self.o, self.n, self.width)
+            out = resampled_length(ready, self.o, self.n) if last else feed_ready(ready, self.o, self.n, self.width)
+            out = max(out, self.out_ready)
+        call = ArrayFeedCall(self._hist, self._hist_first, self.frames - self._hist_first, self.frames, self.blocks, blocks,
+                             self.ready, ready, min(s_first, self.ready), self.out_ready, out)
+        self.blocks, self.ready, self.out_ready = blocks, ready, out
+        keep = max(self._hist_first, max(0, (blocks - 1) * self.hop - self.max_lag))
         self._hist = self._hist[(keep - self._hist_first) * self.fmt.frame_bytes:]
         self._hist_first = keep
         return call

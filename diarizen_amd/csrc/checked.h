@@ -44,4 +44,5 @@
 //            0x82x resample / decode / ingest (0x828 ..), 0x83x post (diarize range),
 //            0x84x gallery (0x840 row-tile index, 0x841 partial-list write, 0x842 survivor queue),
 //            0x85x beamform (0x850 frame read, 0x852 / 0x853 butterfly and twiddle index, 0x854 block, 0x855 lag read,
-//                            0x858 delay read, 0x859 shifted sample read, 0x85a output write)
+//                            0x858 delay read, 0x859 shifted sample read, 0x85a output write),
+//            0x86x beamform_live (0x860 planar frame read / write, 0x862 tracker column)

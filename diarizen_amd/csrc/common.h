@@ -261,6 +261,14 @@ int launch_beamform_delays(const float* x, int channels, int64_t ch_stride, int6
                            hipStream_t st);
 int launch_beamform_sum(const float* x, int channels, int64_t ch_stride, int64_t x_first, int64_t x_len, int64_t T, int hop,
                         const int* delay, int64_t num_blocks, int64_t n0, int64_t n1, float* dst, hipStream_t st);
+// beamform_live.hip: every channel of the stored frames as planar float32 [channels][ch_stride] in one pass, and the causal
+// delay rule over blocks [b0, b1) of compact lags / peaks with row stride nblk (column 0 is block b0); lags and the state are
+// clamped to [-bound, bound] (dzn_decode_planar / dzn_beamform_track / dzn_beamform_feed validate)
+int launch_decode_planar(const void* src, int format, int channels, int64_t frames, float* dst, int64_t ch_stride,
+                         hipStream_t st);
+int launch_beamform_track(const int* lag, const float* peak, int64_t nblk, int channels, int ref, int hop, int64_t T,
+                          float min_peak, int bound, int64_t b0, int64_t b1, int* state, int* delay, int64_t delay_stride,
+                          hipStream_t st);
 
 // prof.cpp
 bool prof_enabled();

@@ -2195,6 +2195,135 @@ int dzn_beamform_sum(int32_t device, const float* d_x, int32_t channels, int64_t
   return launch_beamform_sum(d_x, channels, ch_stride, x_first, x_len, T, hop, d_delay, num_blocks, n0, n1, d_dst, st);
 }
 
+// what dzn_decode_planar and dzn_beamform_feed refuse in the stored frames, in dzn_decode's words; "" when they are sound
+static std::string planar_source(int32_t src_format, int32_t channels, int64_t frames, int64_t ch_stride, const void* d_src) {
+  if (frames < 0) return "bad frames";
+  if (src_format < 0 || src_format >= DZN_SRC_FORMATS || channels < 1)
+    return "src_format " + std::to_string(src_format) + " with " + std::to_string(channels) +
+           " channel(s): the formats are 0 (float32 mono) .. 7 (DZN_SRC_* of dzn.h), interleaved over channels >= 1";
+  if (src_format == DZN_SRC_F32 && channels != 1)
+    return "src_format 0 is float32 mono, not " + std::to_string(channels) + " channels (5 is float32 interleaved over channels)";
+  if (frames > INT64_MAX / 4 / channels) return "frames * channels * bytes per sample overflows";
+  if (ch_stride < frames || ch_stride > INT64_MAX / 4 / channels)
+    return "ch_stride = " + std::to_string(ch_stride) + " for " + std::to_string(frames) + " frames (ch_stride >= frames)";
+  const uintptr_t align = src_format == DZN_SRC_S16 ? 2 : (src_format == DZN_SRC_S32 || src_format == DZN_SRC_F32 ||
+                                                           src_format == DZN_SRC_F32I) ? 4 : 1;
+  if (reinterpret_cast<uintptr_t>(d_src) % align)
+    return "d_src is not aligned to the " + std::to_string(align) + "-byte samples of src_format " + std::to_string(src_format);
+  return "";
+}
+
+int dzn_decode_planar(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int64_t frames, float* d_dst,
+                      int64_t ch_stride, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_decode_planar: " + why;
+    return DZN_E_INVALID;
+  };
+  const std::string bad = planar_source(src_format, channels, frames, ch_stride, d_src);
+  if (!bad.empty()) return refuse(bad);
+  if (frames == 0) return DZN_OK;
+  if (!d_dst || !d_src) return refuse("null pointer");
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  return launch_decode_planar(d_src, src_format, channels, frames, d_dst, ch_stride, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+// what dzn_beamform_track and dzn_beamform_feed refuse in a block range; "" when it is sound
+static std::string track_blocks(int32_t channels, int32_t ref, int32_t hop, int64_t T, int64_t nblk, int64_t b0, int64_t b1,
+                                int64_t delay_stride, const int64_t* h_seen) {
+  if (channels < 2 || channels > 64) return std::to_string(channels) + " channel(s): an array has 2 .. 64";
+  if (ref < 0 || ref >= channels)
+    return "reference channel " + std::to_string(ref) + " of a source with " + std::to_string(channels) + " channels";
+  if (hop < 256 || hop > 4096 || (hop & (hop - 1))) return "hop " + std::to_string(hop) + " is not a power of two in [256, 4096]";
+  if (T < 0 || T > INT64_MAX / 8) return "bad T";
+  if (!h_seen) return "null pointer";
+  const int64_t nb = (T + hop - 1) / hop + 1;
+  if (b0 < 0 || b1 < b0 || b1 > nb)
+    return "blocks " + span_text(b0, b1) + " are not inside the " + std::to_string(nb) + " blocks of the recording";
+  if (b1 - b0 > nblk || b1 > delay_stride)
+    return "blocks " + span_text(b0, b1) + " do not fit lag / peak rows of " + std::to_string(nblk) + " or a delay table of " +
+           std::to_string(delay_stride) + " blocks";
+  if (b0 != *h_seen)
+    return "b0 = " + std::to_string(b0) + " is out of sequence: the state has seen " + std::to_string(*h_seen) + " block(s)";
+  return "";
+}
+
+int dzn_beamform_track(int32_t device, const int32_t* d_lag, const float* d_peak, int64_t nblk, int32_t channels, int32_t ref,
+                       int32_t hop, int64_t T, float min_peak, int64_t b0, int64_t b1, int32_t* d_state, int64_t* h_seen,
+                       int32_t* d_delay, int64_t delay_stride, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_beamform_track: " + why;
+    return DZN_E_INVALID;
+  };
+  const std::string bad = track_blocks(channels, ref, hop, T, nblk, b0, b1, delay_stride, h_seen);
+  if (!bad.empty()) return refuse(bad);
+  if (b1 == b0) return DZN_OK;
+  if (!d_lag || !d_peak || !d_state || !d_delay) return refuse("null pointer");
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  const int rc = launch_beamform_track(d_lag, d_peak, nblk, channels, ref, hop, T, min_peak, hop / 2, b0, b1, d_state, d_delay,
+                                       delay_stride, reinterpret_cast<hipStream_t>(hip_stream));
+  if (rc == DZN_OK) *h_seen = b1;
+  return rc;
+}
+
+int dzn_beamform_feed(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int64_t src_first,
+                      int64_t src_frames, int64_t T, int32_t ref, int32_t hop, int32_t max_lag, float min_peak,
+                      const float* d_twiddle, float* d_planar, int64_t ch_stride, int32_t* d_lag, float* d_peak, int64_t blk_cap,
+                      int64_t b0, int64_t b1, int32_t* d_state, int64_t* h_seen, int32_t* d_delay, int64_t table_blocks,
+                      int64_t n0, int64_t n1, float* d_dst, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_beamform_feed: " + why;
+    return DZN_E_INVALID;
+  };
+  std::string bad = planar_source(src_format, channels, src_frames, ch_stride, d_src);
+  if (bad.empty()) bad = beamform_geometry(channels, ch_stride, src_first, src_frames, T, hop);
+  if (bad.empty() && (max_lag < 1 || max_lag > hop / 2))
+    bad = "max_lag " + std::to_string(max_lag) + " is outside [1, hop / 2 = " + std::to_string(hop / 2) + "]";
+  if (bad.empty()) bad = track_blocks(channels, ref, hop, T, blk_cap, b0, b1, table_blocks, h_seen);
+  if (!bad.empty()) return refuse(bad);
+  if (n0 < 0 || n1 < n0 || n1 > T)
+    return refuse("samples " + span_text(n0, n1) + " are not inside the recording of " + std::to_string(T));
+  if (n1 > n0 && (n1 - 1) / hop + 1 >= b1)
+    return refuse("samples " + span_text(n0, n1) + " use block " + std::to_string((n1 - 1) / hop + 1) + ", and only the blocks below " +
+                  std::to_string(b1) + " are tracked after this call");
+  // what the call reads inside [0, T): the frames of the blocks, and n + delay with |delay| <= max_lag (the tracker's bound)
+  const int64_t x1 = src_first + src_frames;
+  if (b1 > b0) {
+    int64_t lo = (b0 - 1) * hop, hi = b1 * hop;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > T ? T : hi;
+    if (lo < hi && (src_first > lo || x1 < hi))
+      return refuse("the span given, " + span_text(src_first, x1) + ", does not cover the input " + span_text(lo, hi) +
+                    " that the blocks read");
+  }
+  if (n1 > n0) {
+    int64_t lo = n0 - max_lag, hi = n1 + max_lag;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > T ? T : hi;
+    if (lo < hi && (src_first > lo || x1 < hi))
+      return refuse("the span given, " + span_text(src_first, x1) + ", does not cover the input " + span_text(lo, hi) +
+                    " that the samples may read");
+  }
+  if (b1 == b0 && n1 == n0) return DZN_OK;
+  if (!d_twiddle || !d_planar || !d_lag || !d_peak || !d_state || !d_delay || (n1 > n0 && !d_dst) || (src_frames > 0 && !d_src))
+    return refuse("null pointer");
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  int rc = launch_decode_planar(d_src, src_format, channels, src_frames, d_planar, ch_stride, st);
+  if (rc != DZN_OK) return rc;
+  rc = launch_beamform_delays(d_planar, channels, ch_stride, src_first, src_frames, T, ref, hop, max_lag, d_twiddle, b0, b1,
+                              d_lag, d_peak, st);
+  if (rc != DZN_OK) return rc;
+  rc = launch_beamform_track(d_lag, d_peak, b1 - b0, channels, ref, hop, T, min_peak, max_lag, b0, b1, d_state, d_delay,
+                             table_blocks, st);
+  if (rc != DZN_OK) return rc;
+  *h_seen = b1;
+  return launch_beamform_sum(d_planar, channels, ch_stride, src_first, src_frames, T, hop, d_delay, table_blocks, n0, n1, d_dst,
+                             st);
+}
+
 static_assert(sizeof(dzn_ingest_desc) == 96, "dzn_ingest_desc is 96 bytes without padding (include/dzn.h)");
 
 int dzn_ingest_many(int32_t device, const void* d_stage, int64_t stage_bytes, const dzn_ingest_desc* h_desc,
@@ -2330,6 +2459,7 @@ int dzn_checked_collect_resample(unsigned int*, int);
 int dzn_checked_collect_ingest(unsigned int*, int);
 int dzn_checked_collect_gallery(unsigned int*, int);
 int dzn_checked_collect_beamform(unsigned int*, int);
+int dzn_checked_collect_beamform_live(unsigned int*, int);
 }
 #endif
 int dzn_checked_status(uint32_t* out4, int32_t reset) {
@@ -2340,7 +2470,7 @@ int dzn_checked_status(uint32_t* out4, int32_t reset) {
                             dzn_checked_collect_attention_split, dzn_checked_collect_attention_planes,
                             dzn_checked_collect_frontend_fused, dzn_checked_collect_post,
                             dzn_checked_collect_resample, dzn_checked_collect_ingest, dzn_checked_collect_gallery,
-                            dzn_checked_collect_beamform};
+                            dzn_checked_collect_beamform, dzn_checked_collect_beamform_live};
   unsigned int tot[4] = {0u, 0u, 0u, 0u};
   for (collect_fn f : fns) {
     unsigned int w[4] = {0u, 0u, 0u, 0u};

@@ -246,6 +246,10 @@ class HubBook:
         if feed_format is not None:
             if not isinstance(feed_format, audio_io.FeedFormat) or feed_format.channel is None:
                 raise ValueError(f"feed_format is an audio.FeedFormat with a channel choice, not {feed_format!r}")
+            if isinstance(feed_format.channel, audio_io.Beamform):
+                raise ValueError(f"feed_format: {feed_format!r} is an array feed (channel=Beamform): a hub's rows share one "
+                                 "batched ingest launch, which does not beamform; open the session on its own (open_live / "
+                                 "open_stream / pipeline.stream)")
             hist = 0
             if feed_format.rate != self.sr:
                 o, _, width = audio_io.resample_ratio(feed_format.rate, self.sr)

@@ -13,6 +13,10 @@ Design (MI355X-first, same kernels as the offline path):
     G.711 / PCM frames at 8 .. 48 kHz in packets of any length: the ring then holds stored frames, each slot has a device
     twin, and dzn_resample (dzn_decode at the model's rate) writes the samples that have become final (audio.feed_ready)
     straight into the device buffer, on the copy stream; the waveform is resample_device of the whole recording bit for bit;
+  * a microphone ARRAY (`FeedFormat(16000, "s16", channels=8, channel=Beamform(causal=True))`, or a pipeline built with that
+    channel) is beamformed inside the same ingest: per planned call dzn_beamform_feed enqueues the planar decode, GCC-PHAT of the
+    newly complete blocks, the device delay tracker and delay-and-sum on the copy stream (csrc/beamform_live.hip); the waveform
+    is the offline BeamformedSource of the whole recording bit for bit;
   * the device holds the recording so far in ONE pre-zeroed buffer (4 h of 16 kHz mono = 0.92 GB of the 288 GB); windows are
     rows of a strided view over it, exactly as offline (inference.WindowRunner), so a window is computed once, when its last
     sample has arrived, and never again.  Samples past the end read as zeros: the reference's zero-padded last window
@@ -51,7 +55,10 @@ def plan_feed(fmt, sample_rate: int, slot_frames: int, tile: Optional[int] = Non
     tile: the device resampler's tile (default: asked of the library)"""
     if not isinstance(fmt, audio_io.FeedFormat) or fmt.channel is None:
         raise ValueError(f"feed_format is an audio.FeedFormat with a channel choice, not {fmt!r}")
-    plan = audio_io.FeedPlanner(fmt, sample_rate, slot_frames)
+    if isinstance(fmt.channel, audio_io.Beamform):                       # an array feed: beamformed inside the ingest
+        plan = audio_io.ArrayFeedPlanner(fmt, sample_rate, slot_frames)
+    else:
+        plan = audio_io.FeedPlanner(fmt, sample_rate, slot_frames)
     if not plan.same_rate and not audio_io.resample_tile_fits(plan.o, plan.n, plan.width, tile or audio_io.resample_tile()):
         raise ValueError(f"feed_format: {fmt.rate} Hz -> {sample_rate} Hz (o / n = {plan.o} / {plan.n}): the input of one "
                          "tile of the device resampler does not fit in LDS")
@@ -70,7 +77,15 @@ class WaveIngest:
     dzn_resample call (dzn_decode for a feed at the model's rate) writes the output samples [ready before, ready after)
     straight into dev_wave.  The slot's event is recorded after the kernel, so reusing a slot waits for the kernel that read
     its twin.  `n` counts the model-rate samples that are final, `frames` the source frames received; flush() makes the tail
-    once the stream has ended.  dev_wave[:n] is then resample_device of the whole recording, bit for bit."""
+    once the stream has ended.  dev_wave[:n] is then resample_device of the whole recording, bit for bit.
+
+    An ARRAY feed (`FeedFormat(..., channel=Beamform(causal=True))`, audio.ArrayFeedPlanner) uses the same ring, twins and slot
+    events; per planned call ONE dzn_beamform_feed enqueues, on copy_stream, the planar decode of the uploaded frames, GCC-PHAT
+    of the newly complete blocks, the delay tracker and the delay-and-sum of the samples that became final
+    (audio.beam_ready) — straight into dev_wave, or, where the rates differ, behind the carried history of one of two small
+    staging buffers that dzn_resample then reads.  The tracker state and the delay table live on the device; nothing is read
+    back (`delays()` is the one call that synchronises).  dev_wave[:n] is then BeamformedSource.read_device of the whole
+    recording with the same Beamform, bit for bit."""
 
     def __init__(self, device, sample_rate: int, window: int, step: int, max_seconds: float = 4 * 3600.0,
                  slot_seconds: float = 10.0, slots: int = 4, feed_format=None, slot_frames: Optional[int] = None):
@@ -86,6 +101,9 @@ class WaveIngest:
         self.dev_wave = torch.zeros(self.capacity, device=device, dtype=torch.float32)
         self.views = torch.as_strided(self.dev_wave, ((self.capacity - window) // step + 1, window), (step, 1))
         self.slot_samples = int(slot_seconds * self.sr)
+        self.array = isinstance(self.plan, audio_io.ArrayFeedPlanner)
+        if self.array:
+            self._open_array(max_seconds)
         if self.plan is None:
             self.ring = [torch.empty(self.slot_samples, dtype=torch.float32).pin_memory() for _ in range(slots)]
         else:
@@ -106,6 +124,9 @@ class WaveIngest:
         if self.plan is not None:
             for t in self.twins:
                 t.record_stream(self.copy_stream)
+        if self.array:
+            for t in [self._planar, self._lag, self._peak, self._state, self._delay, *self._stage]:
+                t.record_stream(self.copy_stream)
         self.n = 0                                                      # samples received (a stored feed: samples that are final)
         self.frames = 0                                                 # source frames received (== n without a feed_format)
         self.uploads = 0
@@ -115,6 +136,32 @@ class WaveIngest:
         if not isinstance(fmt, audio_io.FeedFormat):
             raise ValueError(f"feed_format is an audio.FeedFormat with a channel choice, not {fmt!r}")
         self.plan = plan_feed(fmt, sample_rate, int(slot_seconds * fmt.rate) if slot_frames is None else slot_frames)
+
+    def _open_array(self, max_seconds: float) -> None:
+        """the per-session device buffers of an array feed: planar scratch, lag / peak temporaries, tracker state (zeroed), delay
+        table, and where the rates differ two staging buffers [history | new] of beamformed samples"""
+        plan, device = self.plan, self.device
+        C = plan.fmt.channels
+        self._table_blocks = -(-(int(max_seconds * plan.fmt.rate) + 1) // plan.hop) + 2
+        self._planar = torch.empty((C, plan.max_upload_frames), device=device, dtype=torch.float32)
+        self._lag = torch.empty((C, plan.max_blocks), device=device, dtype=torch.int32)
+        self._peak = torch.empty((C, plan.max_blocks), device=device, dtype=torch.float32)
+        self._state = torch.zeros((C, 5), device=device, dtype=torch.int32)      # DZN_BEAMFORM_STATE_INTS
+        self._delay = torch.zeros((C, self._table_blocks), device=device, dtype=torch.int32)
+        self._twiddle = audio_io._device_twiddle(plan.hop, device)
+        self._stage = [] if plan.same_rate else [torch.empty(plan.K + plan.max_new, device=device, dtype=torch.float32)
+                                                 for _ in range(2)]
+        self._stage_at, self._stage_first = 0, 0        # the buffer that holds beamformed samples _stage_first .. plan.ready
+        import ctypes
+        self._seen = ctypes.c_int64(0)                  # blocks tracked: the host's count that dzn_beamform_feed checks b0 by
+
+    def delays(self) -> np.ndarray:
+        """int32 [C, blocks]: the delay table of an array feed as far as it is filled (after flush(): of the whole recording).
+        The one call of the ingest that waits for the device; append() and flush() never do."""
+        if not self.array:
+            raise ValueError("delays(): not an array feed")
+        self.copy_stream.synchronize()
+        return self._delay[:, :self.plan.blocks].cpu().numpy()
 
     def append(self, samples) -> int:
         """stage float32 samples and queue their copies behind the recording so far; -> number of samples taken.  With a
@@ -156,6 +203,8 @@ class WaveIngest:
     def _run(self, calls) -> int:
         """upload and launch the planned calls on copy_stream; -> output samples made"""
         import ctypes as C
+        if self.array:
+            return self._run_array(calls)
         lib, fmt, plan = _lib.load(), self.plan.fmt, self.plan
         device = torch.device(self.device)
         dev = device.index if device.index is not None else -1
@@ -187,6 +236,56 @@ class WaveIngest:
             self.n = c.m1
         self.frames = plan.frames
         return self.n - n0
+
+    def _run_array(self, calls) -> int:
+        """the planned calls of an array feed, enqueue-only on copy_stream: upload, dzn_beamform_feed, and where the rates
+        differ the history carried into the other staging buffer and dzn_resample; -> output samples made"""
+        import ctypes as C
+        lib, fmt, plan = _lib.load(), self.plan.fmt, self.plan
+        device = torch.device(self.device)
+        dev = device.index if device.index is not None else -1
+        vp = C.c_void_p
+        made = self.n
+        for c in calls:
+            nb = len(c.data)
+            assert (c.m0 == self.n and nb == c.frames * fmt.frame_bytes <= len(self.ring[0]) and c.m1 + self.window <= self.capacity
+                    and c.b1 <= self._table_blocks and c.b1 - c.b0 <= plan.max_blocks and c.n1 - c.n0 <= plan.max_new)
+            i = self.next_slot
+            if self.slot_free[i] is not None:
+                self.slot_free[i].synchronize()                         # ring full: wait for the oldest copy and its kernels
+            self.ring_np[i][:nb] = np.frombuffer(c.data, dtype=np.uint8)
+            with torch.cuda.stream(self.copy_stream):
+                if nb:
+                    self.twins[i][:nb].copy_(self.ring[i][:nb], non_blocking=True)
+                st = vp(self.copy_stream.cuda_stream)
+                dst, stage = self.dev_wave.data_ptr() + 4 * c.n0, None
+                if not plan.same_rate and (c.n1 > c.n0 or c.m1 > c.m0):
+                    old, stage = self._stage[self._stage_at], self._stage[self._stage_at ^ 1]
+                    hist = c.n0 - c.s_first                             # < K beamformed samples a later range still reads
+                    assert c.s_first >= self._stage_first and hist + c.n1 - c.n0 <= len(stage)
+                    if hist:
+                        stage[:hist].copy_(old[c.s_first - self._stage_first:c.n0 - self._stage_first], non_blocking=True)
+                    dst = stage.data_ptr() + 4 * hist
+                    self._stage_at, self._stage_first = self._stage_at ^ 1, c.s_first
+                _lib.check(lib.dzn_beamform_feed(
+                    dev, vp(self.twins[i].data_ptr()), fmt.src_format, fmt.channels, c.first, c.frames, c.total,
+                    plan.beamform.reference, plan.hop, plan.max_lag, plan.min_peak, vp(self._twiddle.data_ptr()),
+                    vp(self._planar.data_ptr()), self._planar.shape[1], vp(self._lag.data_ptr()), vp(self._peak.data_ptr()),
+                    plan.max_blocks, c.b0, c.b1, vp(self._state.data_ptr()), C.byref(self._seen), vp(self._delay.data_ptr()),
+                    self._table_blocks, c.n0, c.n1, vp(dst), st), None, "dzn_beamform_feed")
+                if stage is not None and c.m1 > c.m0:
+                    _lib.check(lib.dzn_resample(dev, vp(stage.data_ptr()), 0, 1, 0, c.s_first, c.n1 - c.s_first, c.n1,
+                                                vp(self.bank.data_ptr()), plan.o, plan.n, plan.width, c.m0, c.m1,
+                                                vp(self.dev_wave.data_ptr() + 4 * c.m0), st), None, "dzn_resample")
+                ev = torch.cuda.Event()
+                ev.record(self.copy_stream)
+            self.slot_free[i] = ev
+            self.last_copy = ev
+            self.next_slot = (i + 1) % len(self.ring)
+            self.uploads += 1
+            self.n = c.m1
+        self.frames = plan.frames
+        return self.n - made
 
     def wait(self) -> None:
         """the current (compute) stream runs behind the newest upload"""

@@ -519,6 +519,72 @@ int dzn_beamform_sum(int32_t device, const float* d_x, int32_t channels, int64_t
                      void* hip_stream);
 int32_t dzn_beamform_tile(void);
 
+/* Array FEEDS (csrc/beamform_live.hip; audio.Beamform(causal=True), audio.causal_delays, audio.ArrayFeedPlanner,
+ * streaming.WaveIngest): the same blocks, frames, raw lag / peak and alignment pass as above, with a delay rule
+ * that looks at no later block and is tracked on the device, so that a live session beamforms in stream order.
+ *
+ * Causal delays.  For a channel c != ref and blocks b = 0, 1, ..:
+ *     reliable[b] = frame b holds at least H samples of the recording (min(T, (b + 1) H) - max(0, (b - 1) H) >= H)
+ *                   and peak[c][b] >= min_peak (float32)
+ *     held[b]     = lag[c][b] if reliable[b], else held[b - 1]; held[-1] = 0 (no backward fill: a channel aligns from its
+ *                   first reliable block on)
+ *     delay[c][b] = the median of held[b - 4 .. b], where held[k] = held[0] for k < 0 (a TRAILING median of 5 whose left
+ *                   edge repeats the first entry)
+ * and the row of `ref` is 0.  delay[c][b] depends on blocks <= b alone and |delay| <= max_lag.  A change of delay takes effect
+ * two blocks late (the trailing median needs three of five entries): 0.5 s at the default hop.
+ *
+ * Schedule.  After R frames of a feed block b is complete when R >= (b + 1) H: nc = floor(R / H) blocks are.  A complete
+ * frame holds the same samples whatever the eventual length T, so its lag, peak and reliability are those of the
+ * whole-recording computation.  Output sample n of block b reads n + delay of blocks b and b + 1, below (b + 2) H, so the
+ * samples below beam_ready(R) = max(0, nc - 1) H are final: output lags the feed by less than 2 H frames.  At the end of the
+ * stream the blocks nc .. ceil(T / H) are evaluated with the true T (ragged frames, zero outside [0, T)) and the samples
+ * [beam_ready, T) made.
+ *
+ * dzn_decode_planar: d_dst f32 [channels][ch_stride], d_dst[c * ch_stride + r] = sample c of stored frame r for r < frames
+ * (ch_stride >= frames; the floats behind `frames` in a row are not touched), with the DZN_SRC_* codes and conversions of
+ * dzn_decode bit for bit, in ONE pass over the source (one frame per lane).  One launch, enqueue-only; frames = 0 is DZN_OK and
+ * launches nothing.  It refuses what dzn_decode refuses (src_format, DZN_SRC_F32 with channels != 1, a misaligned d_src) and
+ * ch_stride < frames.
+ *
+ * dzn_beamform_track: the causal rule over blocks [b0, b1).  d_lag i32 / d_peak f32 are compact arrays of row stride nblk
+ * whose column 0 is block b0 (what dzn_beamform_delays writes for blocks [b0, b1): nblk = b1 - b0; nblk > b1 - b0 reads the
+ * leading columns of wider rows).  d_state i32 [channels][DZN_BEAMFORM_STATE_INTS] is the tracker's state — per channel the
+ * held values of the four blocks before b0, oldest first, then the number of blocks seen — ZEROED by the caller before block
+ * 0 and otherwise only passed on.  d_delay i32 [channels][delay_stride]: columns b0 .. b1 - 1 are written.  The kernel is a
+ * function of (state, columns) alone: tracking [0, nb) at once or in any partition into consecutive calls gives the same table
+ * and the same final state.  Lags and state are clamped to [-H / 2, H / 2] as they are read.  *h_seen is the HOST's count of
+ * blocks tracked on this state (0 for a zeroed state): b0 must equal it — DZN_E_INVALID otherwise — and the call sets it to
+ * b1; device memory is never read back.  One launch of one wavefront (a lane per channel, sequential over the blocks),
+ * enqueue-only, plain loads and stores.  Refused: channels outside [2, 64], ref outside the channels, a bad hop, T < 0,
+ * b0 < 0, b1 < b0, b1 - b0 > nblk, b1 > delay_stride, b1 > ceil(T / H) + 1, b0 != *h_seen, null pointers.
+ *
+ * dzn_beamform_feed: what ONE live call enqueues on `hip_stream`, in order: dzn_decode_planar of the uploaded frames
+ * src_first .. src_first + src_frames into d_planar [channels][ch_stride]; GCC-PHAT (the kernel of dzn_beamform_delays) of
+ * blocks [b0, b1) into d_lag / d_peak [channels][b1 - b0] (temporaries of blk_cap blocks per channel); the tracker (lags
+ * clamped to max_lag) into columns [b0, b1) of d_delay i32 [channels][table_blocks]; the alignment pass (the kernel of
+ * dzn_beamform_sum) for samples [n0, n1) into d_dst f32 [n1 - n0], reading the device-resident table with num_blocks =
+ * table_blocks.  T is the number of frames received when the call is made (the true length at the end of the stream).  No
+ * synchronisation, no allocation, no read-back: every buffer is the caller's, and the call validates from its arguments alone
+ * — the tracker bounds the delays by max_lag, so the span the sum can read is [n0 - max_lag, n1 + max_lag) inside [0, T).
+ * Refused, with a dzn_last_error(NULL) message and nothing enqueued: what dzn_decode_planar, dzn_beamform_delays and
+ * dzn_beamform_track refuse; b1 - b0 > blk_cap or b1 > table_blocks; samples outside [0, T] or that use a block that is not
+ * tracked after this call ((n1 - 1) / H + 1 >= b1); an uploaded span that does not cover samples (b0 - 1) H .. b1 H - 1 of
+ * the blocks or [n0 - max_lag, n1 + max_lag) of the samples, inside [0, T).
+ * Measured on one MI355X (scripts/beamform_live_timing.py): the upload and this call for a 10 s slot of int16
+ * frames take 0.13 / 0.46 / 3.6 ms of device time for 2 / 8 / 64 channels at 16 kHz and 0.19 / 0.61 / 4.8 ms at 48 kHz
+ * (with the resampler), against 0.04 - 1.1 ms for one channel of the same frames.  No speed is promised or tested. */
+#define DZN_BEAMFORM_STATE_INTS 5
+int dzn_decode_planar(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int64_t frames, float* d_dst,
+                      int64_t ch_stride, void* hip_stream);
+int dzn_beamform_track(int32_t device, const int32_t* d_lag, const float* d_peak, int64_t nblk, int32_t channels, int32_t ref,
+                       int32_t hop, int64_t T, float min_peak, int64_t b0, int64_t b1, int32_t* d_state, int64_t* h_seen,
+                       int32_t* d_delay, int64_t delay_stride, void* hip_stream);
+int dzn_beamform_feed(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int64_t src_first,
+                      int64_t src_frames, int64_t T, int32_t ref, int32_t hop, int32_t max_lag, float min_peak,
+                      const float* d_twiddle, float* d_planar, int64_t ch_stride, int32_t* d_lag, float* d_peak, int64_t blk_cap,
+                      int64_t b0, int64_t b1, int32_t* d_state, int64_t* h_seen, int32_t* d_delay, int64_t table_blocks,
+                      int64_t n0, int64_t n1, float* d_dst, void* hip_stream);
+
 /* Live hub (diarizen_amd/hub.py): the ingest of MANY sessions in one launch (csrc/ingest.hip).  A descriptor is what one
  * dzn_resample or dzn_decode call takes; its source lies in one staging buffer, its bank in one buffer of banks, its output in
  * one pooled buffer f32 [pool_rows][row_floats] (a row per session: the recording so far, zeros behind it).  Fixed-width

@@ -26,5 +26,7 @@ python -m pytest tests/test_frontend_kernels_gpu.py -m gpu -q -x 2>&1 | tail -3
 python -m pytest tests/test_engine_reuse_gpu.py -m gpu -q -x 2>&1 | tail -3
 # the beamformer (beamform.hip, ids 0x85x: frame and shifted sample reads against the span given, butterfly / twiddle indices): likewise
 python -m pytest tests/test_beamform_gpu.py -m gpu -q -x 2>&1 | tail -3
+# live array feeds (beamform_live.hip, ids 0x86x: planar frame rows, tracker columns; beamform.hip's reads against the uploaded span): likewise
+python -m pytest tests/test_beamform_live_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
