@@ -120,6 +120,24 @@ def ingest_desc_dtype():
     return dt
 
 
+class DznBeamformDesc(C.Structure):
+    """dzn_beamform_desc of include/dzn.h: 208 bytes, no padding (`beamform_desc_dtype()` is the same layout as a numpy record)"""
+    _fields_ = ([(k, C.c_int64) for k in ("src_offset", "src_first", "src_frames", "T", "twiddle_offset", "planar_offset",
+                                          "ch_stride", "lag_offset", "blk_cap", "b0", "b1", "seen", "state_offset",
+                                          "delay_offset", "table_blocks", "n0", "n1", "s_first", "dst_offset", "carry_offset")]
+                + [(k, C.c_int32) for k in ("src_format", "channels", "ref", "hop", "max_lag")] + [("min_peak", C.c_float)]
+                + [(k, C.c_int32) for k in ("dst_space", "decode_tile0", "gcc_item0", "sum_tile0", "reserved0", "reserved1")])
+
+
+def beamform_desc_dtype():
+    """the numpy record dtype of a dzn_beamform_desc table"""
+    import numpy as np
+    kinds = {C.c_int64: "<i8", C.c_int32: "<i4", C.c_float: "<f4"}
+    dt = np.dtype([(name, kinds[ct]) for name, ct in DznBeamformDesc._fields_])
+    assert dt.itemsize == C.sizeof(DznBeamformDesc) == 208
+    return dt
+
+
 class DznProfEntry(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -219,6 +237,7 @@ def load() -> C.CDLL:
     sig("dzn_beamform_feed", i32, [i32, vp, i32, i32, i64, i64, i64, i32, i32, i32, f32, vp, vp, i64, vp, vp, i64, i64, i64, vp,
                                    C.POINTER(i64), vp, i64, i64, i64, vp, vp])
     sig("dzn_ingest_many", i32, [i32, vp, i64, vp, vp, i32, vp, i64, vp, i64, i64, vp])
+    sig("dzn_beamform_many", i32, [i32, vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp])
     sig("dzn_gather_windows", i32, [i32, vp, i64, vp, vp, i32, i32, vp, vp])
     sig("dzn_op_set_gemm_cfg", i32, [C.c_char_p])
     sig("dzn_op_amax", i32, [vp, i64, vp, vp])
@@ -275,7 +294,7 @@ EXPORTED = [
     "dzn_segment_forward", "dzn_segment_forward_soft", "dzn_embed_forward", "dzn_embed_forward_strided", "dzn_prepare_masks", "dzn_speaker_count", "dzn_cluster_activations", "dzn_detect", "dzn_detect_range", "dzn_diarize_range", "dzn_speaker_scores", "dzn_debug_fetch", "dzn_embed_skip_stats", "dzn_num_ignored",
     "dzn_workspace_bytes", "dzn_last_error", "dzn_destroy", "dzn_version", "dzn_linkage_centroid", "dzn_cdist_cosine", "dzn_host_workspace_release",
     "dzn_host_workspace_bytes",
-    "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_beamform_delays", "dzn_beamform_sum", "dzn_beamform_tile", "dzn_decode_planar", "dzn_beamform_track", "dzn_beamform_feed", "dzn_ingest_many", "dzn_gather_windows", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",
+    "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_beamform_delays", "dzn_beamform_sum", "dzn_beamform_tile", "dzn_decode_planar", "dzn_beamform_track", "dzn_beamform_feed", "dzn_ingest_many", "dzn_beamform_many", "dzn_gather_windows", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",
     "dzn_gallery_create", "dzn_gallery_put", "dzn_gallery_drop", "dzn_gallery_search", "dzn_gallery_geometry", "dzn_gallery_rows",
     "dzn_gallery_last_launch_ms", "dzn_gallery_destroy",
     "dzn_op_gemm", "dzn_op_split_weights", "dzn_op_split_weights_h2", "dzn_op_split_weights_mx", "dzn_op_set_gemm_mx_cfg", "dzn_checked_status", "dzn_op_set_gemm_cfg", "dzn_op_amax", "dzn_op_conv3x3_c32", "dzn_op_conv3x3_c32_h2", "dzn_op_resblock32_fused", "dzn_op_resblock_ws", "dzn_op_set_resblock_np", "dzn_op_conv3x3_c32_ex", "dzn_op_resblock32_fused_ex", "dzn_op_resblock_ws_ex", "dzn_op_set_attention_noskip", "dzn_op_split_rows", "dzn_op_layernorm", "dzn_op_row_stats", "dzn_op_gate", "dzn_op_gate_stats", "dzn_op_gate_heads", "dzn_op_stats_finalize", "dzn_op_attention", "dzn_op_attention_h2", "dzn_op_attention_planes", "dzn_op_set_attention_qb", "dzn_op_set_attention_prefetch",

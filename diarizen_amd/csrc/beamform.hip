@@ -31,72 +31,9 @@
 
 DZN_CHECKED_TU(beamform)
 
+#include "beamform_tile.h"      // (after DZN_CHECKED_TU: its DZN_CHECKs count in this translation unit's word)
+
 namespace {
-
-constexpr int kGccThreadsMax = 1024;
-constexpr int kSumThreads = 256;
-constexpr int kSumTile = 1024;       // output samples per workgroup of delay_sum_kernel (dzn_beamform_tile)
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) {
-  return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
-}
-
-// z[i] = hann[i] * x_c[(b - 1) hop + i], zero outside the recording
-__device__ __forceinline__ void stage_frame(float2* z, const float* __restrict__ xc, int64_t x_first, int64_t x_len, int64_t T,
-                                            int64_t first, int W, const float2* __restrict__ tw) {
-  const int half = W >> 1;
-  for (int i = threadIdx.x; i < W; i += blockDim.x) {
-    const int64_t s = first + i;
-    float v = 0.f;
-    if (s >= 0 && s < T) {
-      const int64_t at = s - x_first;
-      DZN_CHECK(at >= 0 && at < x_len, 0x850, i);
-      v = xc[at];
-    }
-    const float c = tw[i & (half - 1)].x;
-    const float w = i < half ? 0.5f - 0.5f * c : 0.5f + 0.5f * c;
-    z[i] = make_float2(v * w, 0.f);
-  }
-  __syncthreads();
-}
-
-// natural order in, bit-reversed order out
-__device__ __forceinline__ void fft_forward(float2* z, int W, const float2* __restrict__ tw) {
-  const int half = W >> 1;
-  for (int m = half, sh = 0; m >= 1; m >>= 1, ++sh) {
-    for (int j = threadIdx.x; j < half; j += blockDim.x) {
-      const int p = j & (m - 1);
-      const int i0 = ((j - p) << 1) + p, i1 = i0 + m;
-      DZN_CHECK(i1 < W && (p << sh) < half, 0x852, j);
-      const float2 a = z[i0], c = z[i1];
-      z[i0] = make_float2(a.x + c.x, a.y + c.y);
-      z[i1] = cmul(make_float2(a.x - c.x, a.y - c.y), tw[p << sh]);
-    }
-    __syncthreads();
-  }
-}
-
-// bit-reversed order in, natural order out, not scaled
-__device__ __forceinline__ void fft_inverse(float2* z, int W, int logW, const float2* __restrict__ tw) {
-  const int half = W >> 1;
-  for (int m = 1, sh = logW - 1; m <= half; m <<= 1, --sh) {
-    for (int j = threadIdx.x; j < half; j += blockDim.x) {
-      const int p = j & (m - 1);
-      const int i0 = ((j - p) << 1) + p, i1 = i0 + m;
-      DZN_CHECK(i1 < W && sh >= 0 && (p << sh) < half, 0x853, j);
-      const float2 w = tw[p << sh];
-      const float2 a = z[i0], t = cmul(z[i1], make_float2(w.x, -w.y));
-      z[i0] = make_float2(a.x + t.x, a.y + t.y);
-      z[i1] = make_float2(a.x - t.x, a.y - t.y);
-    }
-    __syncthreads();
-  }
-}
-
-// the better of two (value, visiting rank) candidates: strictly greater wins, equal values keep the earlier visit
-__device__ __forceinline__ void keep_better(float& v, int& r, float v2, int r2) {
-  if (v2 > v || (v2 == v && r2 < r)) { v = v2; r = r2; }
-}
 
 __global__ __launch_bounds__(kGccThreadsMax) void gcc_phat_kernel(const float* __restrict__ x, int channels, int64_t ch_stride,
                                                                  int64_t x_first, int64_t x_len, int64_t T, int ref, int hop,
@@ -122,72 +59,9 @@ __global__ __launch_bounds__(kGccThreadsMax) void gcc_phat_kernel(const float* _
 
   for (int c = 0; c < channels; ++c) {
     if (c == ref) continue;
-    stage_frame(Z, x + (int64_t)c * ch_stride, x_first, x_len, T, first, W, tw);
-    fft_forward(Z, W, tw);
-    // G = X_c conj(X_ref) / |.|, 0 where the product is 0; scaled by its larger component first, so that neither the squares
-    // of a faint bin underflow nor those of a loud one overflow
-    for (int k = threadIdx.x; k < W; k += blockDim.x) {
-      const float2 r = R[k], s = Z[k];
-      float pr = s.x * r.x + s.y * r.y, pi = s.y * r.x - s.x * r.y;
-      const float big = fmaxf(fabsf(pr), fabsf(pi));
-      float2 g = make_float2(0.f, 0.f);
-      if (big > 0.f && big <= 3.0e38f) {
-        pr /= big;
-        pi /= big;
-        const float n = sqrtf(pr * pr + pi * pi);
-        g = make_float2(pr / n, pi / n);
-      }
-      Z[k] = g;
-    }
-    __syncthreads();
-    fft_inverse(Z, W, logW, tw);
-
-    // argmax of Re Z[l mod W] over l in [-L, L]
-    float v = Z[0].x;
-    int rk = 0;
-    for (int i = threadIdx.x; i < 2 * max_lag + 1; i += blockDim.x) {
-      const int l = i - max_lag;
-      const int at = (l + W) & (W - 1);
-      DZN_CHECK(at >= 0 && at < W, 0x855, i);
-      keep_better(v, rk, Z[at].x, l == 0 ? 0 : (l < 0 ? -2 * l - 1 : 2 * l));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float v2 = __shfl_xor(v, o, 64);
-      const int r2 = __shfl_xor(rk, o, 64);
-      keep_better(v, rk, v2, r2);
-    }
-    const int wave = threadIdx.x / DZN_WAVE, waves = blockDim.x / DZN_WAVE;
-    if ((threadIdx.x & (DZN_WAVE - 1)) == 0) {
-      red_v[wave] = v;
-      red_r[wave] = rk;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (int w = 1; w < waves; ++w) keep_better(v, rk, red_v[w], red_r[w]);
-      lag[(int64_t)c * nblk + blockIdx.x] = (rk & 1) ? -((rk + 1) >> 1) : (rk >> 1);
-      peak[(int64_t)c * nblk + blockIdx.x] = v * (1.0f / (float)W);      // a power of two: exact
-    }
-    __syncthreads();      // red_* and Z are rewritten by the next channel
+    gcc_phat_pair(R, Z, red_v, red_r, x + (int64_t)c * ch_stride, x_first, x_len, T, first, W, logW, max_lag, tw,
+                  lag + (int64_t)c * nblk + blockIdx.x, peak + (int64_t)c * nblk + blockIdx.x);
   }
-}
-
-// S_b(n) = (sum_c x_c[n + delay[c, b]]) / C
-__device__ __forceinline__ float aligned_mean(const float* __restrict__ x, int channels, int64_t ch_stride, int64_t x_first,
-                                              int64_t x_len, int64_t T, const int* __restrict__ delay, int64_t num_blocks,
-                                              int64_t b, int64_t n) {
-  float s = 0.f;
-  for (int c = 0; c < channels; ++c) {
-    DZN_CHECK(b >= 0 && b < num_blocks, 0x858, c);
-    const int64_t at = n + delay[(int64_t)c * num_blocks + b];
-    float v = 0.f;
-    if (at >= 0 && at < T) {
-      DZN_CHECK(at - x_first >= 0 && at - x_first < x_len, 0x859, c);
-      v = x[(int64_t)c * ch_stride + (at - x_first)];
-    }
-    s = c == 0 ? v : __fadd_rn(s, v);
-  }
-  return __fdiv_rn(s, (float)channels);
 }
 
 __global__ __launch_bounds__(kSumThreads) void delay_sum_kernel(const float* __restrict__ x, int channels, int64_t ch_stride,
@@ -199,12 +73,8 @@ __global__ __launch_bounds__(kSumThreads) void delay_sum_kernel(const float* __r
   for (int k = 0; k < kSumTile / kSumThreads; ++k) {
     const int64_t n = base + k * kSumThreads + threadIdx.x;
     if (n >= n1) return;
-    const int64_t b = n >> logH;
-    const float w = (float)(n - (b << logH)) / (float)hop;      // exact: hop is a power of two
-    const float a = aligned_mean(x, channels, ch_stride, x_first, x_len, T, delay, num_blocks, b, n);
-    const float v = aligned_mean(x, channels, ch_stride, x_first, x_len, T, delay, num_blocks, b + 1, n);
     DZN_CHECK(n - n0 >= 0 && n - n0 < n1 - n0, 0x85a, threadIdx.x);
-    dst[n - n0] = __fadd_rn(a, __fmul_rn(w, __fsub_rn(v, a)));
+    dst[n - n0] = beam_sample(x, channels, ch_stride, x_first, x_len, T, hop, logH, delay, num_blocks, n);
   }
 }
 

@@ -21,7 +21,7 @@
 
 DZN_CHECKED_TU(beamform_live)
 
-#include "resample_tile.h"      // (after DZN_CHECKED_TU: its DZN_CHECKs count in this translation unit's word)
+#include "beamform_tile.h"      // (after DZN_CHECKED_TU: its DZN_CHECKs count in this translation unit's word)
 
 namespace {
 
@@ -30,29 +30,7 @@ __global__ __launch_bounds__(kThreads) void decode_planar_kernel(const void* __r
                                                                  float* __restrict__ dst, int64_t ch_stride) {
   const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (r >= frames) return;
-  const int64_t s0 = r * channels;                   // first sample of the frame
-  DZN_CHECK(r < ch_stride && s0 + channels <= frames * channels, 0x860, threadIdx.x);
-  for (int c = 0; c < channels; ++c) dst[(int64_t)c * ch_stride + r] = stored_sample<FMT>(src, s0 + c);
-}
-
-__device__ __forceinline__ int clampi(int v, int bound) { return v < -bound ? -bound : (v > bound ? bound : v); }
-
-__device__ __forceinline__ void order2(int& a, int& b) {
-  const int lo = a < b ? a : b, hi = a < b ? b : a;
-  a = lo;
-  b = hi;
-}
-
-// the median of five (a sorting network cut down to the comparisons the middle element needs)
-__device__ __forceinline__ int median5(int a, int b, int c, int d, int e) {
-  order2(a, b);
-  order2(d, e);
-  order2(a, d);      // a is the least of a, b, d, e: not the median
-  order2(b, e);      // e is the greatest of a, b, d, e: not the median
-  order2(b, c);
-  order2(c, d);
-  order2(b, c);      // the median of b, c, d
-  return c;
+  planar_frame<FMT>(src, channels, frames, r, dst, ch_stride);
 }
 
 __global__ __launch_bounds__(DZN_WAVE) void track_kernel(const int* __restrict__ lag, const float* __restrict__ peak,
@@ -61,27 +39,7 @@ __global__ __launch_bounds__(DZN_WAVE) void track_kernel(const int* __restrict__
                                                          int* __restrict__ delay, int64_t delay_stride) {
   const int c = threadIdx.x;
   if (c >= channels) return;
-  int* s = state + c * DZN_BEAMFORM_STATE_INTS;
-  int h0 = clampi(s[0], bound), h1 = clampi(s[1], bound), h2 = clampi(s[2], bound), h3 = clampi(s[3], bound);
-  int seen = s[4];
-  for (int64_t b = b0; b < b1; ++b) {
-    DZN_CHECK(b - b0 < nblk && b < delay_stride, 0x862, c);
-    const int64_t lo = (b - 1) * hop > 0 ? (b - 1) * hop : 0, hi = (b + 1) * hop < T ? (b + 1) * hop : T;
-    const bool reliable = c != ref && hi - lo >= hop && peak[(int64_t)c * nblk + (b - b0)] >= min_peak;
-    const int held = reliable ? clampi(lag[(int64_t)c * nblk + (b - b0)], bound) : (seen == 0 ? 0 : h3);
-    if (seen == 0) h0 = h1 = h2 = h3 = held;
-    delay[(int64_t)c * delay_stride + b] = c == ref ? 0 : median5(h0, h1, h2, h3, held);
-    h0 = h1;
-    h1 = h2;
-    h2 = h3;
-    h3 = held;
-    ++seen;
-  }
-  s[0] = h0;
-  s[1] = h1;
-  s[2] = h2;
-  s[3] = h3;
-  s[4] = seen;
+  track_channel(lag, peak, nblk, c, ref, hop, T, min_peak, bound, b0, b1, state, delay, delay_stride);
 }
 
 }  // namespace

@@ -45,4 +45,7 @@
 //            0x84x gallery (0x840 row-tile index, 0x841 partial-list write, 0x842 survivor queue),
 //            0x85x beamform (0x850 frame read, 0x852 / 0x853 butterfly and twiddle index, 0x854 block, 0x855 lag read,
 //                            0x858 delay read, 0x859 shifted sample read, 0x85a output write),
-//            0x86x beamform_live (0x860 planar frame read / write, 0x862 tracker column)
+//            0x86x beamform_live (0x860 planar frame read / write, 0x862 tracker column),
+//            0x87x beamform_many (0x870 decode tile of its descriptor, 0x871 format, 0x872 GCC work item and LDS image,
+//                                 0x873 channel of the item, 0x874 tracker descriptor, 0x875 sum tile, 0x876 carried sample);
+//            the 0x85x / 0x86x checks of beamform_tile.h count in the translation unit that includes it

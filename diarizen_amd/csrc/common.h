@@ -269,6 +269,12 @@ int launch_decode_planar(const void* src, int format, int channels, int64_t fram
 int launch_beamform_track(const int* lag, const float* peak, int64_t nblk, int channels, int ref, int hop, int64_t T,
                           float min_peak, int bound, int64_t b0, int64_t b1, int* state, int* delay, int64_t delay_stride,
                           hipStream_t st);
+// beamform_many.hip: the four table-driven launches of a hub's array wave (dzn_beamform_many validates; the three totals are
+// those of the table's prefixes, max_hop its largest hop, work = {decode bytes, GCC-PHAT flops, bytes, sum flops, bytes} for
+// the profiler)
+int launch_beamform_many(const void* stage, const dzn_beamform_desc* desc, int num_desc, int64_t decode_tiles, int64_t gcc_items,
+                         int64_t sum_tiles, int max_hop, const double* work, const float* twiddles, float* planar,
+                         int* lag, float* peak, int* state, int* delay, float* pool, float* beam, hipStream_t st);
 
 // prof.cpp
 bool prof_enabled();

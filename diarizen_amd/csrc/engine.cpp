@@ -21,6 +21,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <array>
 #include <vector>
 
 #include "common.h"
@@ -2267,6 +2268,43 @@ int dzn_beamform_track(int32_t device, const int32_t* d_lag, const float* d_peak
   return rc;
 }
 
+// what dzn_beamform_feed and a descriptor of dzn_beamform_many refuse in their arguments; "" when they are sound
+static std::string beamform_feed_args(const void* d_src, int32_t src_format, int32_t channels, int64_t src_first,
+                                      int64_t src_frames, int64_t T, int32_t ref, int32_t hop, int32_t max_lag, int64_t ch_stride,
+                                      int64_t blk_cap, int64_t b0, int64_t b1, const int64_t* h_seen, int64_t table_blocks,
+                                      int64_t n0, int64_t n1) {
+  std::string bad = planar_source(src_format, channels, src_frames, ch_stride, d_src);
+  if (bad.empty()) bad = beamform_geometry(channels, ch_stride, src_first, src_frames, T, hop);
+  if (bad.empty() && (max_lag < 1 || max_lag > hop / 2))
+    bad = "max_lag " + std::to_string(max_lag) + " is outside [1, hop / 2 = " + std::to_string(hop / 2) + "]";
+  if (bad.empty()) bad = track_blocks(channels, ref, hop, T, blk_cap, b0, b1, table_blocks, h_seen);
+  if (!bad.empty()) return bad;
+  if (n0 < 0 || n1 < n0 || n1 > T)
+    return "samples " + span_text(n0, n1) + " are not inside the recording of " + std::to_string(T);
+  if (n1 > n0 && (n1 - 1) / hop + 1 >= b1)
+    return "samples " + span_text(n0, n1) + " use block " + std::to_string((n1 - 1) / hop + 1) + ", and only the blocks below " +
+           std::to_string(b1) + " are tracked after this call";
+  // what the call reads inside [0, T): the frames of the blocks, and n + delay with |delay| <= max_lag (the tracker's bound)
+  const int64_t x1 = src_first + src_frames;
+  if (b1 > b0) {
+    int64_t lo = (b0 - 1) * hop, hi = b1 * hop;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > T ? T : hi;
+    if (lo < hi && (src_first > lo || x1 < hi))
+      return "the span given, " + span_text(src_first, x1) + ", does not cover the input " + span_text(lo, hi) +
+             " that the blocks read";
+  }
+  if (n1 > n0) {
+    int64_t lo = n0 - max_lag, hi = n1 + max_lag;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > T ? T : hi;
+    if (lo < hi && (src_first > lo || x1 < hi))
+      return "the span given, " + span_text(src_first, x1) + ", does not cover the input " + span_text(lo, hi) +
+             " that the samples may read";
+  }
+  return "";
+}
+
 int dzn_beamform_feed(int32_t device, const void* d_src, int32_t src_format, int32_t channels, int64_t src_first,
                       int64_t src_frames, int64_t T, int32_t ref, int32_t hop, int32_t max_lag, float min_peak,
                       const float* d_twiddle, float* d_planar, int64_t ch_stride, int32_t* d_lag, float* d_peak, int64_t blk_cap,
@@ -2276,35 +2314,9 @@ int dzn_beamform_feed(int32_t device, const void* d_src, int32_t src_format, int
     last_create_error = "dzn_beamform_feed: " + why;
     return DZN_E_INVALID;
   };
-  std::string bad = planar_source(src_format, channels, src_frames, ch_stride, d_src);
-  if (bad.empty()) bad = beamform_geometry(channels, ch_stride, src_first, src_frames, T, hop);
-  if (bad.empty() && (max_lag < 1 || max_lag > hop / 2))
-    bad = "max_lag " + std::to_string(max_lag) + " is outside [1, hop / 2 = " + std::to_string(hop / 2) + "]";
-  if (bad.empty()) bad = track_blocks(channels, ref, hop, T, blk_cap, b0, b1, table_blocks, h_seen);
+  const std::string bad = beamform_feed_args(d_src, src_format, channels, src_first, src_frames, T, ref, hop, max_lag, ch_stride,
+                                             blk_cap, b0, b1, h_seen, table_blocks, n0, n1);
   if (!bad.empty()) return refuse(bad);
-  if (n0 < 0 || n1 < n0 || n1 > T)
-    return refuse("samples " + span_text(n0, n1) + " are not inside the recording of " + std::to_string(T));
-  if (n1 > n0 && (n1 - 1) / hop + 1 >= b1)
-    return refuse("samples " + span_text(n0, n1) + " use block " + std::to_string((n1 - 1) / hop + 1) + ", and only the blocks below " +
-                  std::to_string(b1) + " are tracked after this call");
-  // what the call reads inside [0, T): the frames of the blocks, and n + delay with |delay| <= max_lag (the tracker's bound)
-  const int64_t x1 = src_first + src_frames;
-  if (b1 > b0) {
-    int64_t lo = (b0 - 1) * hop, hi = b1 * hop;
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > T ? T : hi;
-    if (lo < hi && (src_first > lo || x1 < hi))
-      return refuse("the span given, " + span_text(src_first, x1) + ", does not cover the input " + span_text(lo, hi) +
-                    " that the blocks read");
-  }
-  if (n1 > n0) {
-    int64_t lo = n0 - max_lag, hi = n1 + max_lag;
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > T ? T : hi;
-    if (lo < hi && (src_first > lo || x1 < hi))
-      return refuse("the span given, " + span_text(src_first, x1) + ", does not cover the input " + span_text(lo, hi) +
-                    " that the samples may read");
-  }
   if (b1 == b0 && n1 == n0) return DZN_OK;
   if (!d_twiddle || !d_planar || !d_lag || !d_peak || !d_state || !d_delay || (n1 > n0 && !d_dst) || (src_frames > 0 && !d_src))
     return refuse("null pointer");
@@ -2415,6 +2427,122 @@ int dzn_ingest_many(int32_t device, const void* d_stage, int64_t stage_bytes, co
                             reinterpret_cast<hipStream_t>(hip_stream));
 }
 
+static_assert(sizeof(dzn_beamform_desc) == 208, "dzn_beamform_desc is 208 bytes without padding (include/dzn.h)");
+
+int dzn_beamform_many(int32_t device, const void* d_stage, int64_t stage_bytes, const dzn_beamform_desc* h_desc,
+                      const dzn_beamform_desc* d_desc, int32_t num_desc, const float* d_twiddles, int64_t twiddle_floats,
+                      float* d_planar, int64_t planar_floats, int32_t* d_lag, float* d_peak, int64_t temp_elems,
+                      int32_t* d_state, int64_t state_ints, int32_t* d_delay, int64_t delay_ints, float* d_pool,
+                      int64_t pool_floats, float* d_beam, int64_t beam_floats, void* hip_stream) {
+  auto refuse = [](const std::string& why) {
+    last_create_error = "dzn_beamform_many: " + why;
+    return DZN_E_INVALID;
+  };
+  if (num_desc < 0 || stage_bytes < 0 || twiddle_floats < 0 || planar_floats < 0 || temp_elems < 0 || state_ints < 0 ||
+      delay_ints < 0 || pool_floats < 0 || beam_floats < 0)
+    return refuse("bad num_desc / sizes");
+  if (num_desc == 0) return DZN_OK;
+  if (!h_desc || !d_desc) return refuse("null pointer");
+  static const int bytes_of[DZN_SRC_FORMATS] = {4, 2, 1, 3, 4, 4, 1, 1};
+  const int64_t tile = dzn_beamform_tile();
+  // [lo, lo + len) lies inside a buffer of `size` elements (len >= 0)
+  auto inside = [](int64_t lo, int64_t len, int64_t size) { return lo >= 0 && len >= 0 && lo <= size && len <= size - lo; };
+  auto overlap = [](int64_t a, int64_t al, int64_t b, int64_t bl) { return al > 0 && bl > 0 && a < b + bl && b < a + al; };
+  int64_t decode_tiles = 0, gcc_items = 0, sum_tiles = 0;
+  int max_hop = 0;
+  double work[5] = {0.0, 0.0, 0.0, 0.0, 0.0};      // decode bytes, GCC-PHAT flops / bytes, sum flops / bytes
+  std::vector<std::array<int64_t, 2>> planars, temps, dsts[2];      // the regions written by the descriptors so far
+  bool need[9] = {false, false, false, false, false, false, false, false, false};
+  for (int32_t i = 0; i < num_desc; ++i) {
+    const dzn_beamform_desc& d = h_desc[i];
+    auto bad = [&](const std::string& why) { return refuse("descriptor " + std::to_string(i) + ": " + why); };
+    if (d.src_offset < 0 || d.src_offset > stage_bytes) return bad("bad src_offset");
+    const void* src = static_cast<const uint8_t*>(d_stage) + d.src_offset;
+    const std::string why = beamform_feed_args(src, d.src_format, d.channels, d.src_first, d.src_frames, d.T, d.ref, d.hop,
+                                               d.max_lag, d.ch_stride, d.blk_cap, d.b0, d.b1, &d.seen, d.table_blocks, d.n0, d.n1);
+    if (!why.empty()) return bad(why);
+    if (d.reserved[0] || d.reserved[1] || d.dst_space < 0 || d.dst_space > 1) return bad("bad dst_space / reserved");
+    if (d.decode_tile0 != decode_tiles || d.gcc_item0 != gcc_items || d.sum_tile0 != sum_tiles)
+      return bad("decode_tile0 / gcc_item0 / sum_tile0 = " + std::to_string(d.decode_tile0) + " / " + std::to_string(d.gcc_item0) +
+                 " / " + std::to_string(d.sum_tile0) + " are not the tile prefixes " + std::to_string(decode_tiles) + " / " +
+                 std::to_string(gcc_items) + " / " + std::to_string(sum_tiles));
+    const int64_t nbytes = d.src_frames * d.channels * bytes_of[d.src_format];
+    if (nbytes > 0 && (!d_stage || nbytes > stage_bytes - d.src_offset))
+      return bad("the source [" + std::to_string(d.src_offset) + ", " + std::to_string(d.src_offset + nbytes) + ") leaves the " +
+                 std::to_string(stage_bytes) + " bytes of d_stage");
+    const int64_t nblk = d.b1 - d.b0;
+    if (d.s_first < 0 || d.s_first > d.n0) return bad("s_first = " + std::to_string(d.s_first) + " is not in [0, n0]");
+    const int64_t hist = d.n0 - d.s_first, count = d.n1 - d.s_first;
+    const int64_t plen = (int64_t)d.channels * d.ch_stride, tlen = (int64_t)d.channels * d.blk_cap;
+    if (!inside(d.planar_offset, plen, planar_floats))
+      return bad("the planar decode at float " + std::to_string(d.planar_offset) + " leaves the " + std::to_string(planar_floats) +
+                 " floats of d_planar");
+    if (d.blk_cap < 0 || d.blk_cap > INT64_MAX / 64 || !inside(d.lag_offset, tlen, temp_elems))
+      return bad("the lag / peak rows at element " + std::to_string(d.lag_offset) + " leave the " + std::to_string(temp_elems) +
+                 " elements of d_lag / d_peak");
+    if (!inside(d.state_offset, (int64_t)d.channels * DZN_BEAMFORM_STATE_INTS, state_ints))
+      return bad("the state at int " + std::to_string(d.state_offset) + " leaves the " + std::to_string(state_ints) +
+                 " ints of d_state");
+    if (d.table_blocks > INT64_MAX / 4 / d.channels || !inside(d.delay_offset, (int64_t)d.channels * d.table_blocks, delay_ints))
+      return bad("the delay table at int " + std::to_string(d.delay_offset) + " leaves the " + std::to_string(delay_ints) +
+                 " ints of d_delay");
+    if (d.twiddle_offset < 0 || d.twiddle_offset % 2 || !inside(d.twiddle_offset, 2 * (int64_t)d.hop, twiddle_floats))
+      return bad("the twiddle table at float " + std::to_string(d.twiddle_offset) + " leaves the " +
+                 std::to_string(twiddle_floats) + " floats of d_twiddles");
+    if (!inside(d.dst_offset, count, d.dst_space ? beam_floats : pool_floats))
+      return bad("the output [" + std::to_string(d.dst_offset) + ", " + std::to_string(d.dst_offset + count) + ") leaves the " +
+                 std::to_string(d.dst_space ? beam_floats : pool_floats) + " floats of " + (d.dst_space ? "d_beam" : "d_pool"));
+    if (hist > 0) {
+      if (!inside(d.carry_offset, hist, beam_floats))
+        return bad("the carried samples at float " + std::to_string(d.carry_offset) + " leave the " + std::to_string(beam_floats) +
+                   " floats of d_beam");
+      if (d.dst_space == 1 && overlap(d.carry_offset, hist, d.dst_offset, count))
+        return bad("the carried samples lie in the range the call writes");
+    } else if (d.carry_offset < -1) {
+      return bad("carry_offset is a float offset or -1");
+    }
+    for (int32_t j = 0; j < i; ++j) {
+      if (h_desc[j].state_offset == d.state_offset)
+        return bad("state_offset " + std::to_string(d.state_offset) + " is that of descriptor " + std::to_string(j) +
+                   ": two calls of one session never share a table");
+      if (overlap(planars[j][0], planars[j][1], d.planar_offset, plen) || overlap(temps[j][0], temps[j][1], d.lag_offset, tlen))
+        return bad("its scratch overlaps that of descriptor " + std::to_string(j));
+    }
+    for (const auto& r : dsts[d.dst_space])
+      if (overlap(r[0], r[1], d.dst_offset, count)) return bad("its output overlaps that of an earlier descriptor");
+    if (hist > 0)
+      for (const auto& r : dsts[1])
+        if (overlap(r[0], r[1], d.carry_offset, hist)) return bad("the carried samples lie in the range an earlier descriptor writes");
+    planars.push_back({d.planar_offset, plen});
+    temps.push_back({d.lag_offset, tlen});
+    dsts[d.dst_space].push_back({d.dst_offset, count});
+    need[0] |= nbytes > 0;
+    need[1] |= nblk > 0;
+    need[2] |= count > 0 && d.dst_space == 0;
+    need[3] |= (count > 0 && d.dst_space == 1) || hist > 0;
+    decode_tiles += (d.src_frames + tile - 1) / tile;
+    gcc_items += nblk * (d.channels - 1);
+    sum_tiles += (count + tile - 1) / tile;
+    if (decode_tiles > 0x7fffffff || gcc_items > 0x7fffffff || sum_tiles > 0x7fffffff) return bad("more than 2^31 - 1 tiles");
+    if (nblk > 0 && d.hop > max_hop) max_hop = d.hop;
+    int logW = 1;
+    while ((1 << logW) < 2 * d.hop) ++logW;
+    work[0] += (double)nbytes + 4.0 * (double)d.src_frames * d.channels;
+    work[1] += (double)nblk * 2.0 * (d.channels - 1) * 5.0 * 2.0 * d.hop * logW;
+    work[2] += (double)nblk * (d.channels - 1) * (16.0 * d.hop + 8.0);
+    work[3] += 2.0 * (double)(d.n1 - d.n0) * d.channels;
+    work[4] += 4.0 * (double)(d.n1 - d.n0) * (d.channels + 1) + 8.0 * (double)hist;
+  }
+  if ((need[0] && !d_planar) || (need[1] && (!d_twiddles || !d_planar || !d_lag || !d_peak || !d_state || !d_delay)) ||
+      (need[2] && (!d_pool || !d_delay || !d_planar)) || (need[3] && (!d_beam || !d_delay || !d_planar)))
+    return refuse("null pointer");
+  if (decode_tiles == 0 && gcc_items == 0 && sum_tiles == 0) return DZN_OK;
+  DeviceGuard dg(device);
+  if (!dg.ok) return DZN_E_HIP;
+  return launch_beamform_many(d_stage, d_desc, num_desc, decode_tiles, gcc_items, sum_tiles, max_hop, work, d_twiddles,
+                              d_planar, d_lag, d_peak, d_state, d_delay, d_pool, d_beam, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
 int dzn_gather_windows(int32_t device, const float* d_pool, int64_t pool_floats, const int64_t* h_offsets,
                        const int64_t* d_offsets, int32_t B, int32_t window, float* d_dst, void* hip_stream) {
   auto refuse = [](const std::string& why) {
@@ -2460,6 +2588,7 @@ int dzn_checked_collect_ingest(unsigned int*, int);
 int dzn_checked_collect_gallery(unsigned int*, int);
 int dzn_checked_collect_beamform(unsigned int*, int);
 int dzn_checked_collect_beamform_live(unsigned int*, int);
+int dzn_checked_collect_beamform_many(unsigned int*, int);
 }
 #endif
 int dzn_checked_status(uint32_t* out4, int32_t reset) {
@@ -2470,7 +2599,8 @@ int dzn_checked_status(uint32_t* out4, int32_t reset) {
                             dzn_checked_collect_attention_split, dzn_checked_collect_attention_planes,
                             dzn_checked_collect_frontend_fused, dzn_checked_collect_post,
                             dzn_checked_collect_resample, dzn_checked_collect_ingest, dzn_checked_collect_gallery,
-                            dzn_checked_collect_beamform, dzn_checked_collect_beamform_live};
+                            dzn_checked_collect_beamform, dzn_checked_collect_beamform_live,
+                            dzn_checked_collect_beamform_many};
   unsigned int tot[4] = {0u, 0u, 0u, 0u};
   for (collect_fn f : fns) {
     unsigned int w[4] = {0u, 0u, 0u, 0u};

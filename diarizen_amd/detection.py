@@ -211,14 +211,17 @@ class _Detection:
         feeds are the source's own bytes, G.711 or PCM frames at its rate, decoded and resampled on the device)."""
         return DetectionStream(self, uri=uri, tasks=tasks, scores=scores, **kw)
 
-    def open_hub(self, max_sessions: int = 64, max_seconds: float = 600.0, slot_bytes: int = 1 << 20, slots: int = 4):
+    def open_hub(self, max_sessions: int = 64, max_seconds: float = 600.0, slot_bytes: int = 1 << 20, slots: int = 4,
+                 array_channels: int = 0, array_rate: Optional[int] = None):
         """many concurrent detection streams, one batched forward per tick: a hub.LiveHub whose `open(uri, ...)` takes the
         keywords of open_stream but the ingest's and returns a DetectionStream; `feed()` is then host work only and
         `hub.tick()` does the device work of every session at once.  max_sessions x max_seconds size ONE pooled device
-        buffer (max_sessions x (max_seconds x rate + window) x 4 B), so max_seconds is far below a solo stream's 4 h."""
+        buffer (max_sessions x (max_seconds x rate + window) x 4 B), so max_seconds is far below a solo stream's 4 h.
+        array_channels / array_rate: the most microphones and the highest feed rate of an array session (0: none are taken),
+        as DiariZenPipeline.open_hub."""
         from .hub import LiveHub
         return LiveHub(self, lambda uri, hub, **kw: DetectionStream(self, uri=uri, hub=hub, **kw), max_sessions, max_seconds,
-                       slot_bytes, slots)
+                       slot_bytes, slots, array_channels, array_rate)
 
     def stream(self, chunks: Iterable, uri: Optional[str] = None, **kw) -> Iterator[Tuple[float, float, Any]]:
         """generator form: chunks of float32 samples at the pipeline's rate (feed_format=: of the source's own bytes) -> (seconds received, committed seconds,

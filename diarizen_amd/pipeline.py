@@ -465,17 +465,21 @@ class DiariZenPipeline:
         return LiveDiarization(self, sess_name, delta_new=delta_new, max_speakers=max_speakers, max_seconds=max_seconds,
                                slot_seconds=slot_seconds, slots=slots, feed_format=feed_format)
 
-    def open_hub(self, max_sessions: int = 64, max_seconds: float = 600.0, slot_bytes: int = 1 << 20, slots: int = 4):
+    def open_hub(self, max_sessions: int = 64, max_seconds: float = 600.0, slot_bytes: int = 1 << 20, slots: int = 4,
+                 array_channels: int = 0, array_rate: Optional[int] = None):
         """many concurrent live sessions, one batched forward per tick: a hub.LiveHub whose `open(name, ...)` takes the
         keywords of open_live but the ingest's and returns a live.LiveDiarization; `feed()` is then host work only and
         `hub.tick()` does the device work of every session at once — one staging upload, one ingest launch, ceil(ready
         windows / batch_size) forwards — with the bits each session would have alone.  max_sessions x max_seconds size ONE
         pooled device buffer (max_sessions x (max_seconds x rate + window) x 4 B: 2.5 GB at the defaults), so max_seconds is
-        deliberately far below a solo session's 4 h."""
+        deliberately far below a solo session's 4 h.  array_channels: the most microphones of an array session
+        (`feed_format=FeedFormat(..., channels=C, channel=Beamform(causal=True))`), an integer in [2, 64]; with the default 0
+        the hub refuses array feeds and allocates nothing for them.  array_rate: the highest feed rate of an array session
+        (default: the model's rate).  All array calls of a tick then share one upload and one dzn_beamform_many."""
         from .hub import LiveHub
         from .live import LiveDiarization
         return LiveHub(self, lambda name, hub, **kw: LiveDiarization(self, name, hub=hub, **kw), max_sessions, max_seconds,
-                       slot_bytes, slots)
+                       slot_bytes, slots, array_channels, array_rate)
 
     def stream_live(self, chunks, sess_name: Optional[str] = None, **kw):
         """generator form of open_live: yields (seconds received, committed seconds, Annotation) for every feed that has an

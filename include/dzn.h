@@ -650,6 +650,104 @@ int dzn_ingest_many(int32_t device, const void* d_stage, int64_t stage_bytes, co
 int dzn_gather_windows(int32_t device, const float* d_pool, int64_t pool_floats, const int64_t* h_offsets,
                        const int64_t* d_offsets, int32_t B, int32_t window, float* d_dst, void* hip_stream);
 
+/* Live hub, array feeds (diarizen_amd/hub.py, csrc/beamform_many.hip): the beamforming of MANY array sessions
+ * in one fixed set of four launches.  A descriptor is what ONE dzn_beamform_feed call takes; its stored frames lie in one
+ * staging buffer, its twiddle table in one buffer of tables, its planar decode and lag / peak temporaries in scratch shared by
+ * the table, its tracker state and delay table in one buffer each (a region per session), and its output in the pooled session
+ * buffer or in a pool of beamformed staging buffers.  Fixed-width fields, 208 bytes, no padding:
+ *   src_offset        byte offset of the stored frames inside d_stage (aligned to the sample size, as dzn_ingest_desc)
+ *   src_first,        the frames at src_offset are frames src_first .. + src_frames of a feed of T frames so far (the true
+ *   src_frames, T     length at the end of the stream): dzn_beamform_feed's arguments
+ *   twiddle_offset    float offset of the table f32 [hop][2] of this hop inside d_twiddles (audio.beamform_twiddle)
+ *   planar_offset,    the planar decode f32 [channels][ch_stride] lies at float planar_offset of d_planar; ch_stride >=
+ *   ch_stride         src_frames.  Regions of different descriptors must not overlap (they are written in one launch)
+ *   lag_offset,       lag i32 / peak f32 [channels][b1 - b0] lie at element lag_offset of d_lag / d_peak, in a region of
+ *   blk_cap           channels * blk_cap elements (b1 - b0 <= blk_cap); regions must not overlap
+ *   b0, b1            the blocks [b0, b1) the call completes
+ *   seen              the HOST's count of blocks tracked on the state at state_offset: b0 must equal it.  The caller advances
+ *                     its count to b1 after a successful call; device memory is never read back
+ *   state_offset      int offset of the tracker state i32 [channels][DZN_BEAMFORM_STATE_INTS] inside d_state.  Two
+ *                     descriptors of one table never name the same state: the second would read what the first writes
+ *   delay_offset,     int offset of the delay table i32 [channels][table_blocks] inside d_delay; columns [b0, b1) are
+ *   table_blocks      written, and the columns the samples use are read
+ *   n0, n1            the beamformed samples [n0, n1) the call makes, at the feed's rate
+ *   s_first           s_first <= n0: the first sample the destination holds.  [s_first, n0) is COPIED from carry_offset
+ *                     (the history a resampler still reads, made by the call before), [n0, n1) is delay-and-sum
+ *   dst_offset        float offset of sample s_first inside the destination: [dst_offset, dst_offset + n1 - s_first)
+ *   carry_offset      float offset inside d_beam where sample s_first lies, or -1 (then s_first = n0).  The carried range
+ *                     and the destination range must not overlap: a call never reads the buffer it writes
+ *   src_format,       DZN_SRC_* / 2 .. 64 interleaved channels / the reference channel / the hop, a power of two in
+ *   channels, ref,    [256, 4096] / the search range, 1 .. hop / 2, which also bounds the tracked delays / the peak below
+ *   hop, max_lag,     which a block's lag is not trusted (float32)
+ *   min_peak
+ *   dst_space         0: d_pool (a feed at the model's rate: straight into the session's row), 1: d_beam
+ *   decode_tile0,     the three tile prefixes (the caller writes them, the call verifies them): tiles owned by the
+ *   gcc_item0,        descriptors before this one, where a descriptor owns ceil(src_frames / dzn_beamform_tile()) decode
+ *   sum_tile0         tiles, (b1 - b0) * (channels - 1) GCC-PHAT work items and ceil((n1 - s_first) / dzn_beamform_tile())
+ *                     sum tiles
+ *   reserved          0 */
+typedef struct dzn_beamform_desc {
+  int64_t src_offset;
+  int64_t src_first;
+  int64_t src_frames;
+  int64_t T;
+  int64_t twiddle_offset;
+  int64_t planar_offset;
+  int64_t ch_stride;
+  int64_t lag_offset;
+  int64_t blk_cap;
+  int64_t b0;
+  int64_t b1;
+  int64_t seen;
+  int64_t state_offset;
+  int64_t delay_offset;
+  int64_t table_blocks;
+  int64_t n0;
+  int64_t n1;
+  int64_t s_first;
+  int64_t dst_offset;
+  int64_t carry_offset;
+  int32_t src_format;
+  int32_t channels;
+  int32_t ref;
+  int32_t hop;
+  int32_t max_lag;
+  float min_peak;
+  int32_t dst_space;
+  int32_t decode_tile0;
+  int32_t gcc_item0;
+  int32_t sum_tile0;
+  int32_t reserved[2];
+} dzn_beamform_desc;
+
+/* FOUR launches, enqueue-only, on `hip_stream` of `device` (< 0 = current): no synchronisation, no allocation, no read-back.
+ * Every launch is table-driven; a workgroup finds its descriptor by a wave-uniform binary search over the prefix of its launch.
+ *   1. the planar decode: one tile of dzn_beamform_tile() frames of one descriptor (dzn_decode_planar's conversions)
+ *   2. GCC-PHAT: one workgroup per (descriptor, block, non-reference channel).  Each transforms the reference frame itself and
+ *      then its channel's, with the arithmetic of dzn_beamform_delays operation for operation: lag and peak have its bits.
+ *      The workgroup of the lowest non-reference channel also writes the reference row's 0 / 0.  Block size and dynamic LDS
+ *      are those of the largest hop in the table
+ *   3. the tracker: one wavefront per descriptor, a lane per channel (dzn_beamform_track's rule, lags clamped to max_lag)
+ *   4. the alignment pass: one tile of dzn_beamform_tile() samples of [s_first, n1) of one descriptor: copied below n0,
+ *      dzn_beamform_sum's arithmetic from n0 on
+ * so every lag, peak, state, delay and output sample has the bits of dzn_beamform_feed on the same arguments.
+ *   d_stage, stage_bytes       the staging buffer on the device and its size
+ *   h_desc, d_desc             the table of num_desc descriptors: the host's image (validated here) and the device copy
+ *   d_twiddles, twiddle_floats the buffer of twiddle tables and its size in floats
+ *   d_planar, planar_floats    the planar scratch
+ *   d_lag, d_peak, temp_elems  the lag / peak scratch and its size in elements
+ *   d_state, state_ints        the tracker states; d_delay, delay_ints: the delay tables
+ *   d_pool, pool_floats        the pooled session buffer; d_beam, beam_floats: the beamformed staging buffers
+ * num_desc = 0 launches nothing and returns DZN_OK.  Anything dzn_beamform_feed would refuse for a descriptor's arguments —
+ * and b0 != seen, a range that leaves its buffer, a misaligned source, overlapping scratch regions, a tile prefix that is not
+ * the prefix, a carried range that overlaps the destination, two descriptors with the same state_offset — makes the WHOLE call
+ * return DZN_E_INVALID with a dzn_last_error(NULL) message that names the descriptor index, and launches nothing. */
+int dzn_beamform_many(int32_t device, const void* d_stage, int64_t stage_bytes, const dzn_beamform_desc* h_desc,
+                      const dzn_beamform_desc* d_desc, int32_t num_desc, const float* d_twiddles, int64_t twiddle_floats,
+                      float* d_planar, int64_t planar_floats, int32_t* d_lag, float* d_peak, int64_t temp_elems,
+                      int32_t* d_state, int64_t state_ints, int32_t* d_delay, int64_t delay_ints, float* d_pool,
+                      int64_t pool_floats, float* d_beam, int64_t beam_floats, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
