@@ -424,7 +424,9 @@ int launch_gemm_mx(const dzn_gemm_desc& d, hipStream_t s) {
   // tiles for K <= 512 and for widths that 64-wide tiles pad less — do NOT carry over: measured at M = 223 839 (first GPU run of
   // the round, profiles/r5_gemm_mx_first_bench.txt) the wide tile wins on all of them (N 1024 K 256: 186 vs 166 TFLOP/s, K 480:
   // 243 vs 214, N 320 K 1024: 256 vs 244): a 32 x 64 wavefront tile has half the MFMAs per converted A value.
-  const bool narrow = d.N <= 64 || (int64_t)((d.M + 127) / 128) * (cols128 / 128) * (d.nz > 0 ? d.nz : 1) < 448;
+  // (not for a launch that leaves LayerNorm partials: its tile width must not follow M, gemm_split.hip)
+  const bool narrow = d.N <= 64 ||
+                      (!d.stat_partial && (int64_t)((d.M + 127) / 128) * (cols128 / 128) * (d.nz > 0 ? d.nz : 1) < 448);
   const char* force = g_gemm_mx_cfg.get();   // tuning knob: force one tile shape
   if (force && !strcmp(force, "128x64")) return launch_mx_cfg<128, 64, 4, 1, 2, 3>(d, s);
   if (force && !strcmp(force, "128x128")) return launch_mx_cfg<128, 128, 4, 1, 2, 2>(d, s);

@@ -413,7 +413,12 @@ int launch_gemm_split_np(const dzn_gemm_desc& d, hipStream_t s) {
   const int cols128 = (d.N + 127) / 128 * 128, cols64 = (d.N + 63) / 64 * 64;
   // small launches (BASELINE configs[1]: 32 windows of 5 s = 7968 rows): 128 x 128 tiles would leave most of the 512
   // workgroup slots (256 CUs x 2) empty — halve the tile so that twice as many workgroups exist
-  if ((int64_t)((d.M + 127) / 128) * (cols128 / 128) * (d.nz > 0 ? d.nz : 1) < 448)
+  // A launch that leaves LayerNorm partials (stat_partial) is exempt: a partial is the sum over ONE wavefront tile's columns, so
+  // the tile width decides how a row's statistics are added up, and with this rule it would follow M — the float outputs of a
+  // window (log-probabilities, soft scores) would depend on how many windows share its batch (17 or fewer windows of 8 s took
+  // the narrow tile, 18 or more the wide one).  The u8 decisions never showed it; the live scores compare
+  // floats of windows run one by one with those of a whole recording.
+  if (!d.stat_partial && (int64_t)((d.M + 127) / 128) * (cols128 / 128) * (d.nz > 0 ? d.nz : 1) < 448)
     return launch_split_cfg<128, 64, 4, 1, 2, NP, OCC64>(d, s);
   if (d.N % 80 == 0 && d.N < cols64 && d.N * 9 < cols128 * 8) return launch_split_cfg<128, 80, 4, 1, 2, NP, 2>(d, s);
   if (cols64 * 9 < cols128 * 8) return launch_split_cfg<128, 64, 4, 1, 2, NP, OCC64>(d, s);

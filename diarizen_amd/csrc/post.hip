@@ -304,11 +304,21 @@ __global__ __launch_bounds__(256) void speaker_scores_kernel(const float* __rest
 //     rank = #{j : act_j > act_k or (act_j == act_k and j < k)},
 // which is k's position in np.argsort(-act, kind="stable"); it is active when rank < min(count, K).  KP is a power of two
 // <= 32, so a frame never straddles a wave64 and the lanes of a frame read one LDS address (a broadcast).
+//
+// SCORES (dzn_diarize_range_scores): lane (f, k) is also the thread speaker_scores_kernel would run for (t, k) — the same windows
+// in the same ascending order, hard[c, :] already at hand — so the score walk joins the loop with that kernel's arithmetic, term
+// for term: the float32 max over the local speakers of label k (a NaN or no speaker: a missing entry that adds two zeros),
+// ((score * mask) * hamming[l]) * warm_up[l] in __dmul_rn / __dadd_rn into float32 accumulators, one __fdiv_rn at the end.  The
+// accumulators are registers of the lane: no LDS beyond the ranking's, nothing atomic, and the u8 / int32 outputs are computed
+// by the very statements of the plain form.
+template <bool SCORES>
 __global__ __launch_bounds__(256) void diarize_range_kernel(const uint8_t* __restrict__ seg, const int8_t* __restrict__ hard,
-                                                            int C, int L, int S, const int32_t* __restrict__ start, int t0,
-                                                            int t1, int K, int kp_log2, int max_count,
-                                                            uint8_t* __restrict__ count, uint8_t* __restrict__ active,
-                                                            int32_t* __restrict__ act_out) {
+                                                            const float* __restrict__ soft, int C, int L, int S,
+                                                            const int32_t* __restrict__ start, const double* __restrict__ ham,
+                                                            const double* __restrict__ wu, int t0, int t1, int K, int kp_log2,
+                                                            int max_count, uint8_t* __restrict__ count,
+                                                            uint8_t* __restrict__ active, int32_t* __restrict__ act_out,
+                                                            float* __restrict__ scores) {
   __shared__ int32_t sa[256];
   const int tid = threadIdx.x;
   const int f = tid >> kp_log2, k = tid & ((1 << kp_log2) - 1);
@@ -316,6 +326,8 @@ __global__ __launch_bounds__(256) void diarize_range_kernel(const uint8_t* __res
   const bool live = row < (int64_t)(t1 - t0) && k < K;
   const int t = t0 + (int)(live ? row : 0);
   int a = 0, tot = 0, cover = 0;
+  float acc = 0.f, wsum = 0.f;
+  bool seen = false;
   if (live) {
     // covering windows: start[c] <= t < start[c] + L  ->  c in [c0, c1)
     int lo = 0, hi = C;
@@ -345,6 +357,25 @@ __global__ __launch_bounds__(256) void diarize_range_kernel(const uint8_t* __res
       }
       a += v;
       ++cover;
+      if (SCORES) {
+        DZN_CHECK((int64_t)c * L + l < (int64_t)C * L, 0x833, c);
+        const float* fr = soft + ((int64_t)c * L + l) * S;
+        bool has = false, isnan_ = false;
+        float fv = 0.f;
+        for (int s = 0; s < S; ++s) {
+          if (hc[s] != k) continue;
+          const float x = fr[s];
+          isnan_ |= x != x;                       // np.max propagates a NaN: the entry is then missing like an absent label
+          fv = (!has || x > fv) ? x : fv;
+          has = true;
+        }
+        const bool valid = has && !isnan_;
+        const double sc = valid ? (double)fv : 0.0, m = valid ? 1.0 : 0.0;
+        const double hl = ham[l], wl = wu[l];
+        acc = (float)__dadd_rn((double)acc, __dmul_rn(__dmul_rn(__dmul_rn(sc, m), hl), wl));
+        wsum = (float)__dadd_rn((double)wsum, __dmul_rn(__dmul_rn(m, hl), wl));
+        seen |= valid;
+      }
     }
   }
   sa[tid] = a;
@@ -363,13 +394,17 @@ __global__ __launch_bounds__(256) void diarize_range_kernel(const uint8_t* __res
   if (k == 0) count[row] = (uint8_t)cnt;
   active[row * K + k] = rank < min(cnt, K) ? 1 : 0;
   if (act_out) act_out[row * K + k] = a;
+  if (SCORES) {
+    DZN_CHECK(row * K + k < (int64_t)(t1 - t0) * K, 0x834, (int)row);
+    // average = acc / max(weight sum, epsilon) in float32; `missing` = 0 where no non-NaN entry landed
+    scores[row * K + k] = seen ? __fdiv_rn(acc, fmaxf(wsum, 1e-12f)) : 0.f;
+  }
 }
 
-}  // namespace
-
-extern "C" int dzn_diarize_range(const uint8_t* d_seg, const int8_t* d_hard, int32_t C, int32_t L, int32_t S,
-                                 const int32_t* d_start_frame, int32_t t0, int32_t t1, int32_t K, int32_t max_count,
-                                 uint8_t* d_count, uint8_t* d_active, int32_t* d_act, void* stream) {
+// the one launch behind dzn_diarize_range (d_scores == nullptr: the plain form) and dzn_diarize_range_scores
+int launch_diarize_range(const uint8_t* d_seg, const int8_t* d_hard, const float* d_soft, int C, int L, int S,
+                         const int32_t* d_start_frame, const double* d_hamming, const double* d_warm_up, int t0, int t1, int K,
+                         int max_count, uint8_t* d_count, uint8_t* d_active, int32_t* d_act, float* d_scores, void* stream) {
   if (!d_seg || !d_hard || !d_start_frame || !d_count || !d_active || C < 0 || L < 1 || S < 1 || S > 8 || t0 < 0 || t1 < t0 ||
       K < 1 || K > 32 || max_count < 0)
     return DZN_E_INVALID;
@@ -379,9 +414,29 @@ extern "C" int dzn_diarize_range(const uint8_t* d_seg, const int8_t* d_hard, int
   while ((1 << kp_log2) < K) ++kp_log2;         // lanes per frame: the power of two >= K (<= 32)
   const int per_block = 256 >> kp_log2;
   const int n = t1 - t0;
-  hipLaunchKernelGGL(diarize_range_kernel, dim3((unsigned)cdiv64(n, per_block)), dim3(256), 0, st, d_seg, d_hard, C, L, S,
-                     d_start_frame, t0, t1, K, kp_log2, max_count, d_count, d_active, d_act);
+  hipLaunchKernelGGL(d_scores ? diarize_range_kernel<true> : diarize_range_kernel<false>, dim3((unsigned)cdiv64(n, per_block)),
+                     dim3(256), 0, st, d_seg, d_hard, d_soft, C, L, S, d_start_frame, d_hamming, d_warm_up, t0, t1, K, kp_log2,
+                     max_count, d_count, d_active, d_act, d_scores);
   return hipGetLastError() == hipSuccess ? DZN_OK : DZN_E_HIP;
+}
+
+}  // namespace
+
+extern "C" int dzn_diarize_range(const uint8_t* d_seg, const int8_t* d_hard, int32_t C, int32_t L, int32_t S,
+                                 const int32_t* d_start_frame, int32_t t0, int32_t t1, int32_t K, int32_t max_count,
+                                 uint8_t* d_count, uint8_t* d_active, int32_t* d_act, void* stream) {
+  return launch_diarize_range(d_seg, d_hard, nullptr, C, L, S, d_start_frame, nullptr, nullptr, t0, t1, K, max_count, d_count,
+                              d_active, d_act, nullptr, stream);
+}
+
+// the same launch with the per-speaker activity scores of the same frames (dzn_speaker_scores' bits) as a fourth output
+extern "C" int dzn_diarize_range_scores(const uint8_t* d_seg, const int8_t* d_hard, const float* d_soft, int32_t C, int32_t L,
+                                        int32_t S, const int32_t* d_start_frame, const double* d_hamming,
+                                        const double* d_warm_up, int32_t t0, int32_t t1, int32_t K, int32_t max_count,
+                                        uint8_t* d_count, uint8_t* d_active, int32_t* d_act, float* d_scores, void* stream) {
+  if (!d_soft || !d_hamming || !d_warm_up || !d_scores) return DZN_E_INVALID;
+  return launch_diarize_range(d_seg, d_hard, d_soft, C, L, S, d_start_frame, d_hamming, d_warm_up, t0, t1, K, max_count,
+                              d_count, d_active, d_act, d_scores, stream);
 }
 
 extern "C" int dzn_speaker_count(const uint8_t* d_seg, int32_t C, int32_t L, int32_t S, const int32_t* d_start_frame,

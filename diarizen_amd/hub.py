@@ -32,6 +32,9 @@ What one tick() does:
      window order, the host labelling and the session's own range call (dzn_diarize_range / dzn_detect_range) — the sessions
      are ordinary LiveDiarization / DetectionStream objects whose "take results" and "advance" steps the hub calls
      (streaming.WindowStream).  The range calls stay per session; `stats` counts them;
+     A session opened with `scores=True` (live.LiveDiarization) makes the tick's forwards write the classifier's soft output as
+     well — only in a tick where such a session has new windows — into a device tensor that never goes to the host; the
+     session copies its rows device to device and its range call is dzn_diarize_range_scores, still one launch;
   e. `stats`: {"ticks", "tick": the last tick's counters, "total": their sums} with uploads, ingest_launches, forwards,
      windows, range_calls and sessions_advanced.
 
@@ -494,11 +497,12 @@ class HubBook:
 
 
 class _TickResult:
-    """what a session takes from a tick's forwards: its new windows' rows of the device results, and of the host copy"""
-    __slots__ = ("segmentations", "embeddings", "host")
+    """what a session takes from a tick's forwards: its new windows' rows of the device results, and of the host copy;
+    `scores`: their rows of the tick's soft scores (device; None in a tick where no ready session asked for them)"""
+    __slots__ = ("segmentations", "embeddings", "host", "scores")
 
-    def __init__(self, segmentations, embeddings, host):
-        self.segmentations, self.embeddings, self.host = segmentations, embeddings, host
+    def __init__(self, segmentations, embeddings, host, scores=None):
+        self.segmentations, self.embeddings, self.host, self.scores = segmentations, embeddings, host, scores
 
 
 # ----------------------------------------------------------------------------- the hub
@@ -674,10 +678,12 @@ class LiveHub:
             ready = [max(u - s.done, 0) for s, u in zip(sessions, upto)]
             batches = plan_batches(ready, self.runner.batch_size)
             total = sum(ready)
-            host = seg_all = emb_all = None
+            host = seg_all = emb_all = soft_all = None
             if total:
                 want_emb = any(s.EMBEDDINGS for s in sessions)
-                seg_all, emb_all, buf = self._forward(sessions, batches, total, want_emb, t)
+                # the classifier's soft output only in a tick where a session WITH new windows keeps scores; it stays on the device
+                want_soft = any(s.SCORES and c for s, c in zip(sessions, ready))
+                seg_all, emb_all, buf, soft_all = self._forward(sessions, batches, total, want_emb, t, want_soft)
                 if want_emb:                                                # d: ONE D2H of the tick's embeddings and decisions
                     h = buf.cpu().numpy()
                     ne = emb_all.numel() * 4
@@ -688,7 +694,8 @@ class LiveHub:
                 calls0 = s.stats["range_calls"]
                 if c:
                     s._take(_TickResult(seg_all[a:a + c], None if emb_all is None else emb_all[a:a + c],
-                                        None if host is None else (host[0][a:a + c].copy(), host[1][a:a + c].copy())), u)
+                                        None if host is None else (host[0][a:a + c].copy(), host[1][a:a + c].copy()),
+                                        soft_all[a:a + c] if s.SCORES else None), u)
                     a += c
                 if s.finished:
                     if s.n == 0:
@@ -786,9 +793,10 @@ class LiveHub:
         self.ingest_event = ev
         self.next_slot = (i + 1) % len(self.ring)
 
-    def _forward(self, sessions, batches, total: int, want_emb: bool, t: dict):
+    def _forward(self, sessions, batches, total: int, want_emb: bool, t: dict, want_soft: bool = False):
         """the tick's forwards on the current stream, behind the ingest event -> (decisions u8 [total, L, S], embeddings f32
-        [total, S, dim] or None, the one buffer that holds both)"""
+        [total, S, dim] or None, the one buffer that holds both, the soft scores f32 [total, L, S] — a device tensor of their
+        own, not part of the buffer that goes to the host — or None)"""
         import torch
         r, eng = self.runner, self.runner.engine
         L, S = r.num_frames, eng.seg.max_speakers_per_chunk
@@ -799,6 +807,7 @@ class LiveHub:
         buf = torch.empty(ne + total * L * S, device=self.device, dtype=torch.uint8)
         seg_all = buf[ne:].view(total, L, S)
         emb_all = buf[:ne].view(torch.float32).view(total, S, dim) if want_emb else None
+        soft_all = torch.empty((total, L, S), device=self.device, dtype=torch.float32) if want_soft else None
         offs = np.array([sessions[i].ingest.row * self.book.row_floats + (sessions[i].done + k) * self.book.step
                          for batch in batches for i, k in batch], dtype=np.int64)
         d_off = torch.from_numpy(offs).pin_memory().to(self.device, non_blocking=True)
@@ -811,7 +820,10 @@ class LiveHub:
                                               C.c_void_p(offs[b0:].ctypes.data), C.c_void_p(d_off.data_ptr() + 8 * b0), B,
                                               r.window, C.c_void_p(chunk.data_ptr()), C.c_void_p(cur.cuda_stream)),
                        None, "dzn_gather_windows")
-            _, ml = eng.segment(chunk, want_logp=False)
+            if want_soft:
+                _, ml, soft_all[b0:b0 + B] = eng.segment(chunk, want_logp=False, want_soft=True)
+            else:
+                _, ml = eng.segment(chunk, want_logp=False)
             filt, masks = eng.prepare_masks(ml, r.median_size, r.exclude_overlap,
                                             r.min_num_frames if r.exclude_overlap else -1, want_masks=want_emb)
             seg_all[b0:b0 + B] = filt
@@ -821,7 +833,7 @@ class LiveHub:
             t["forwards"] += 1
         self._gathered = torch.cuda.Event()
         self._gathered.record(cur)
-        return seg_all, emb_all, buf
+        return seg_all, emb_all, buf, soft_all
 
     def _release(self, sess) -> None:
         """a session has ended: its row is free; whoever takes it next zeroes [0, n + window) behind the last gather"""

@@ -448,22 +448,27 @@ class DiariZenPipeline:
         Annotation) at every refresh and finally (total seconds, final Annotation == __call__ on the whole file).
         See streaming.StreamingSession for the push form (feed / finish).  feed_format=audio.FeedFormat(8000, "ulaw",
         channels=2): the chunks are the source's own bytes (G.711 / PCM frames at 8 .. 48 kHz, any chunk length), decoded,
-        channel-selected and resampled on the device; the result is that of the file at that rate with resample="device"."""
+        channel-selected and resampled on the device; the result is that of the file at that rate with resample="device".
+        return_scores=True: (seconds, Annotation, scores) each time — the windows' soft scores stay on the device across feeds
+        and the final pair is `__call__(file, return_scores=True)` bit for bit, crop included."""
         from .streaming import stream as _stream
         return _stream(self, chunks, sess_name, **kw)
 
     def open_live(self, sess_name: Optional[str] = None, delta_new: Optional[float] = None,
                   max_speakers: Optional[int] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
-                  slots: int = 4, feed_format=None):
+                  slots: int = 4, feed_format=None, scores: bool = False):
         """live diarization with stable labels and a committed prefix: a live.LiveDiarization to `feed(samples)` /
         `finish()`.  delta_new: the centroid distance beyond which a clean local speaker opens a new label (default: the
         config's ahc_threshold); max_speakers: the cap on labels (default: the config's, at most 32); the other keywords size
         the ingest ring (streaming.WaveIngest); feed_format: an audio.FeedFormat when the feeds are the source's own bytes
-        (refused here when it cannot be served).  `stream` / StreamingSession stay what they are: provisional re-clusterings
+        (refused here when it cannot be served); scores=True: the session also gives the per-speaker activity scores of
+        `__call__(return_scores=True)` live (`committed_scores`, `scores`, `final_scores`) from a device buffer of its windows'
+        soft scores, windows x L x S x 4 bytes — about 115 MB at the default max_seconds of 4 h.
+        `stream` / StreamingSession stay what they are: provisional re-clusterings
         whose last annotation is the offline result."""
         from .live import LiveDiarization
         return LiveDiarization(self, sess_name, delta_new=delta_new, max_speakers=max_speakers, max_seconds=max_seconds,
-                               slot_seconds=slot_seconds, slots=slots, feed_format=feed_format)
+                               slot_seconds=slot_seconds, slots=slots, feed_format=feed_format, scores=scores)
 
     def open_hub(self, max_sessions: int = 64, max_seconds: float = 600.0, slot_bytes: int = 1 << 20, slots: int = 4,
                  array_channels: int = 0, array_rate: Optional[int] = None):
@@ -483,12 +488,13 @@ class DiariZenPipeline:
 
     def stream_live(self, chunks, sess_name: Optional[str] = None, **kw):
         """generator form of open_live: yields (seconds received, committed seconds, Annotation) for every feed that has an
-        annotation, then the final triple.  Keywords as open_live, and recluster (live.LiveDiarization.finish)."""
+        annotation, then the final triple.  Keywords as open_live, and recluster (live.LiveDiarization.finish).  scores=True:
+        (seconds, committed seconds, Annotation, scores), scores a SlidingWindowFeature [frames so far, K]."""
         from .live import stream_live as _stream_live
         return _stream_live(self, chunks, sess_name, **kw)
 
     # ------------------------------------------------------------------ many recordings
-    def diarize_many(self, recordings, sess_names=None, overlap: bool = True):
+    def diarize_many(self, recordings, sess_names=None, overlap: bool = True, return_scores: bool = False):
         """The loop the reference's entry points run over a corpus (diarizen/pipelines/inference.py:365-368: `for audio_file in
         audio_f: diarizen_pipeline(audio_file, sess_name=...)`; recipes/diar_ssl/infer_avg.py:334-338), as a generator of
         (sess_name, Annotation) in input order, with the SAME result per recording as `__call__`.
@@ -498,7 +504,9 @@ class DiariZenPipeline:
         postprocess.DevicePost), so neither side queues behind the other; on the 30-min workload the host stage is 70 ms
         against 1.04 s of device stage, i.e. the corpus rate becomes the device rate.  At most one finished device stage
         waits for the worker (its seg / emb arrays: a few MB per hour of audio).  With torch.distributed initialised every
-        rank calls this with the same list; only rank 0 yields Annotations (the others yield None), as in `__call__`."""
+        rank calls this with the same list; only rank 0 yields Annotations (the others yield None), as in `__call__`.
+        return_scores=True (one device only): (sess_name, Annotation, scores) with the scores of `__call__(return_scores=True)`;
+        the soft scores of a recording stay on the device and travel with its pending host stage."""
         import time
         from concurrent.futures import ThreadPoolExecutor
         from . import dist as dz_dist
@@ -508,19 +516,31 @@ class DiariZenPipeline:
         sess_names = list(sess_names)
         if len(sess_names) != len(recordings):
             raise ValueError("diarize_many: one session name per recording")
+        if return_scores and dz_dist.world_size() > 1:
+            raise RuntimeError(self._ONE_DEVICE % ("diarize_many(return_scores=True)", dz_dist.world_size()))
         if not overlap:
             for rec, name in zip(recordings, sess_names):
-                yield name, self(rec, sess_name=name)
+                yield (name, *self(rec, sess_name=name, return_scores=True)) if return_scores else (name, self(rec, sess_name=name))
             return
         rank0 = dz_dist.rank() == 0
 
-        def host(seg, emb, name):
+        def host(seg, emb, name, soft=None, n=0):
             t = time.perf_counter()
-            res = self.host_stage(seg, emb, name)
+            if soft is None:
+                res = ann = self.host_stage(seg, emb, name)
+            else:                                        # the crop rule of __call__
+                r = self._runner
+                grid, _, T = _frame_grid(seg.shape[0], seg.shape[1], self.chunks_window(),
+                                         receptive_field(self.segmentation_model.sample_rate))
+                if window_plan(n, r.window, r.step)[1]:
+                    T = crop_end(T, grid, n / self.segmentation_model.sample_rate)
+                with torch.cuda.device(self.device):
+                    res = self.host_stage(seg, emb, name, soft=soft, num_frames=T)
+                ann = res[0]
             if self.rttm_out_dir is not None:
                 assert name is not None
                 with open(os.path.join(self.rttm_out_dir, name + ".rttm"), "w") as f:
-                    f.write(res.to_rttm())
+                    f.write(ann.to_rttm())
             return res, time.perf_counter() - t
 
         def load(rec):
@@ -539,12 +559,16 @@ class DiariZenPipeline:
                 nxt = loader.submit(load, recordings[i + 1]) if i + 1 < len(recordings) else None
                 n = int(waveform.num_samples) if hasattr(waveform, "num_samples") else len(waveform)
                 t1 = time.perf_counter()
-                seg, emb = self.device_stage(waveform)
+                if return_scores:
+                    seg, emb, soft = self.device_stage(waveform, with_scores=True)
+                else:
+                    (seg, emb), soft = self.device_stage(waveform), None
                 t2 = time.perf_counter()
                 del waveform
                 if pending is not None:                  # recording i-1's host stage ran beside this device stage
                     yield self._collect(pending)
-                fut = pool.submit(host, seg, emb, name) if rank0 else None
+                fut = pool.submit(host, seg, emb, name, soft, n) if rank0 else None
+                del soft
                 pending = (fut, name, load_s, t2 - t1, n / self.segmentation_model.sample_rate)
             if pending is not None:
                 yield self._collect(pending)
@@ -557,7 +581,7 @@ class DiariZenPipeline:
         res, host_s = fut.result() if fut is not None else (None, 0.0)
         self.timings = {"load_s": load_s, "device_s": device_s, "host_s": host_s, "audio_s": audio_s}
         self.corpus_timings.append(dict(self.timings, sess_name=name))
-        return name, res
+        return (name, *res) if isinstance(res, tuple) else (name, res)
 
     def _open(self, in_wav):
         """decode (or, in a sharded run, lazily open) one recording: the first lines of `__call__`"""

@@ -168,6 +168,44 @@ def speaker_scores(soft: np.ndarray, chunks: SlidingWindow, frames: SlidingWindo
     return SlidingWindowFeature(avg, grid)
 
 
+def speaker_scores_range(soft: np.ndarray, hard_clusters: np.ndarray, starts: np.ndarray, t0: int, t1: int, K: int,
+                         duration: float, warm_up=(0.0, 0.0), epsilon: float = 1e-12) -> np.ndarray:
+    """speaker_scores for a FIXED number of columns K and the frames [t0, t1) only — the numpy restatement of the scores of
+    dzn_diarize_range_scores (needs no device; the kernel is checked against it bit for bit): soft f32 [C, L, S], hard_clusters
+    [C, S] (labels < 0 or >= K match no column), starts int [C] the windows' start frames, duration the windows' length in
+    seconds (the warm-up table's unit) -> f32 [t1 - t0, K], row t - t0.  A frame's score sees the windows that cover it in
+    ascending order with speaker_scores' arithmetic, so the concatenation over a partition of [0, T) is the [0, T) result, and
+    columns [0, max(hard) + 1) of a call with a larger K are those of speaker_scores; a column no window holds is zeros."""
+    soft = np.asarray(soft, dtype=np.float32)
+    hard_clusters = np.asarray(hard_clusters)
+    C, L, S = soft.shape
+    t0, t1, K = int(t0), int(t1), int(K)
+    n = max(t1 - t0, 0)
+    ham, wu = (w.reshape(-1, 1) for w in aggregation_windows(L, duration, warm_up, epsilon))
+    out = np.zeros((n, K), dtype=np.float32)
+    cnt = np.zeros((n, K), dtype=np.float32)
+    seen = np.zeros((n, K), dtype=np.float32)
+    for c in range(C):
+        s0 = int(starts[c])
+        a, b = max(s0, t0), min(s0 + L, t1)                         # the frames of window c inside the range
+        if a >= b:
+            continue
+        clustered = np.full((b - a, K), np.nan, dtype=np.float64)   # float64 holding float32 values, as in the reference
+        for k in range(K):
+            sel = hard_clusters[c] == k
+            if sel.any():
+                clustered[:, k] = soft[c, a - s0:b - s0][:, sel].max(axis=1)      # float32 max; a NaN propagates
+        mask = 1 - np.isnan(clustered)
+        data = np.nan_to_num(clustered, copy=True, nan=0.0)
+        h, w = ham[a - s0:b - s0], wu[a - s0:b - s0]
+        out[a - t0:b - t0] += data * mask * h * w
+        cnt[a - t0:b - t0] += mask * h * w
+        np.maximum(seen[a - t0:b - t0], mask, out=seen[a - t0:b - t0])
+    avg = out / np.maximum(cnt, np.float32(epsilon))
+    avg[seen == 0.0] = 0.0
+    return avg
+
+
 # ----------------------------------------------------------------------------- device versions (row f2)
 def _aggregate_grid(chunks: SlidingWindow, frames: SlidingWindow) -> SlidingWindow:
     """the frame grid of aggregate(): the receptive field's duration and step from the chunks' start"""
@@ -410,6 +448,31 @@ def diarize_range_launch(seg_t, hard_t, num_windows: int, d_start, t0: int, t1: 
     _call("dzn_diarize_range", seg_t, hard_t, int(num_windows), L, S, d_start, int(t0), int(t1), int(K), int(max_count),
           count, active, act)
     return count, active, act
+
+
+def diarize_range_scores_launch(seg_t, hard_t, soft_t, num_windows: int, d_start, d_ham, d_wu, t0: int, t1: int, K: int,
+                                max_count: int, want_activations: bool = False):
+    """one dzn_diarize_range_scores call on the current stream over device operands: those of diarize_range_launch, soft_t
+    f32 [>= num_windows, L, S] and the two float64 [L] tables of aggregation_windows -> (count u8 [t1 - t0], active u8
+    [t1 - t0, K], activations int32 [t1 - t0, K] or None, scores f32 [t1 - t0, K]), device tensors.  Enqueue only."""
+    import torch
+    dev = seg_t.device
+    _, L, S = seg_t.shape
+    assert seg_t.is_cuda and seg_t.dtype == torch.uint8 and seg_t.is_contiguous()
+    assert hard_t.is_cuda and hard_t.dtype == torch.int8 and hard_t.is_contiguous() and hard_t.shape[1] == S
+    assert soft_t.is_cuda and soft_t.dtype == torch.float32 and soft_t.is_contiguous() and tuple(soft_t.shape[1:]) == (L, S)
+    assert d_start.dtype == torch.int32 and min(len(seg_t), len(hard_t), len(soft_t), len(d_start)) >= int(num_windows)
+    assert d_ham.dtype == torch.float64 and d_wu.dtype == torch.float64 and len(d_ham) == L and len(d_wu) == L
+    n = max(int(t1) - int(t0), 0)
+    count = torch.empty((n,), device=dev, dtype=torch.uint8)
+    active = torch.empty((n, int(K)), device=dev, dtype=torch.uint8)
+    act = torch.empty((n, int(K)), device=dev, dtype=torch.int32) if want_activations else None
+    scores = torch.empty((n, int(K)), device=dev, dtype=torch.float32)
+    if n == 0:
+        return count, active, act, scores       # nothing to compute (an empty tensor has no address to hand over)
+    _call("dzn_diarize_range_scores", seg_t, hard_t, soft_t, int(num_windows), L, S, d_start, d_ham, d_wu, int(t0), int(t1),
+          int(K), int(max_count), count, active, act, scores)
+    return count, active, act, scores
 
 
 def diarize_range_host(seg: np.ndarray, hard: np.ndarray, starts: np.ndarray, t0: int, t1: int, K: int, max_count: int):

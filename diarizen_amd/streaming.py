@@ -302,6 +302,7 @@ class WindowStream:
     the three steps "stage" (`_append` / `_flush`: host only), "take results" (`_take`) and "advance" (`_step`) are what
     feed() / finish() of a solo session run back to back."""
     EMBEDDINGS = True                                                   # run_views(with_embeddings=...)
+    SCORES = False                                                      # run_views(with_scores=True): the classifier's soft output too
 
     def __init__(self, pipeline, name: Optional[str] = None, max_seconds: float = 4 * 3600.0, slot_seconds: float = 10.0,
                  slots: int = 4, feed_format=None, hub=None):
@@ -355,7 +356,8 @@ class WindowStream:
         if upto <= self.done:
             return
         self.ingest.wait()
-        self._take(self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=self.EMBEDDINGS), upto)
+        kw = {"with_scores": True} if self.SCORES else {}
+        self._take(self.runner.run_views(self.ingest.views, self.done, upto, with_embeddings=self.EMBEDDINGS, **kw), upto)
 
     def _take(self, res, upto: int) -> None:
         """take the results of windows done .. upto - 1 from the forward that ran them (here, or a hub's batch over many
@@ -388,17 +390,27 @@ class WindowStream:
 
 class StreamingSession(WindowStream):
     def __init__(self, pipeline, sess_name: Optional[str] = None, max_seconds: float = 4 * 3600.0, refresh_s: Optional[float] = 8.0,
-                 slot_seconds: float = 10.0, slots: int = 4, feed_format=None):
+                 slot_seconds: float = 10.0, slots: int = 4, feed_format=None, return_scores: bool = False):
+        """return_scores=True: feed() / finish() give (Annotation, scores) — the per-speaker activity scores of
+        `pipeline(file, return_scores=True)`; the windows' soft scores stay on the device across feeds (one device only)"""
+        if not isinstance(return_scores, (bool, np.bool_)):
+            raise ValueError(f"return_scores is True or False, not {return_scores!r}")
+        if return_scores and dz_dist.world_size() > 1:
+            raise RuntimeError(pipeline._ONE_DEVICE % ("stream(return_scores=True)", dz_dist.world_size()))
+        self.SCORES = bool(return_scores)
         super().__init__(pipeline, sess_name, max_seconds, slot_seconds, slots, feed_format)
         self.refresh_s = refresh_s
         self.seg = []                                                   # per batch: u8 [c, L, S] host arrays
         self.emb = []
+        self.soft = []                                                  # per batch: f32 [c, L, S] DEVICE tensors (return_scores)
         self.last_refresh_n = 0
         self.stats["refreshes"] = 0
 
     def _windows(self, res, lo: int, hi: int) -> None:
         self.seg.append(res.segmentations.cpu().numpy())               # 5.7 KB per window
         self.emb.append(res.embeddings.cpu().numpy())
+        if self.SCORES:
+            self.soft.append(res.scores)
 
     def feed(self, samples) -> Optional[Annotation]:
         """append float32 samples (16 kHz mono, the pipeline's rate) — or, in a session with a feed_format, bytes / arrays of
@@ -413,9 +425,19 @@ class StreamingSession(WindowStream):
             return self._annotate()
         return None
 
-    def _annotate(self) -> Annotation:
+    def _annotate(self):
         seg, emb = np.concatenate(self.seg), np.concatenate(self.emb)
-        return self.pipe.host_stage(seg, emb, self.name)
+        if not self.SCORES:
+            return self.pipe.host_stage(seg, emb, self.name)
+        from .postprocess import crop_end
+        chunks = self.pipe.chunks_window()
+        grid, _, T = _frame_grid(seg.shape[0], seg.shape[1], chunks, receptive_field(self.sr))
+        if self.finished and self._final_windows()[1]:                  # the crop of __call__: the last window was zero-padded
+            T = crop_end(T, grid, self.n / self.sr)
+        with torch.cuda.device(self.device):
+            if len(self.soft) > 1:
+                self.soft = [torch.cat(self.soft)]
+            return self.pipe.host_stage(seg, emb, self.name, soft=self.soft[0], num_frames=T)
 
     def finish(self) -> Annotation:
         """end of stream: the zero-padded tail window (if the reference would run one), then the final host stage"""
@@ -425,22 +447,28 @@ class StreamingSession(WindowStream):
             self._compute(self._final_windows()[0])
         self.finished = True
         if self.done == 0:
-            return Annotation(uri=self.name)
-        ann = self._annotate()
-        self._write_rttm(ann)
-        return ann
+            ann = Annotation(uri=self.name)
+            if self.SCORES:
+                from .core import SlidingWindowFeature
+                grid = _frame_grid(0, self.runner.num_frames, self.pipe.chunks_window(), receptive_field(self.sr))[0]
+                return ann, SlidingWindowFeature(np.zeros((0, 0), dtype=np.float32), grid)
+            return ann
+        out = self._annotate()
+        self._write_rttm(out[0] if self.SCORES else out)
+        return out
 
 
 def stream(pipeline, chunks: Iterable, sess_name: Optional[str] = None, **kw) -> Iterator[Tuple[float, Annotation]]:
     """generator form: yields (seconds of audio received, provisional Annotation) at every refresh and finally
-    (total seconds, final Annotation).  feed_format=audio.FeedFormat(...): the chunks are the source's own bytes"""
+    (total seconds, final Annotation).  feed_format=audio.FeedFormat(...): the chunks are the source's own bytes.
+    return_scores=True: (seconds, Annotation, scores) each time; the final pair is `pipeline(file, return_scores=True)`"""
     sess = StreamingSession(pipeline, sess_name, **kw)
+    one = (lambda out: (sess.seconds,) + tuple(out)) if sess.SCORES else (lambda out: (sess.seconds, out))
     for c in chunks:
         ann = sess.feed(c)
         if ann is not None:
-            yield sess.seconds, ann
-    ann = sess.finish()                                                 # (a stored feed: finish() makes the last samples final)
-    yield sess.seconds, ann
+            yield one(ann)
+    yield one(sess.finish())                                            # (a stored feed: finish() makes the last samples final)
 
 
 # ----------------------------------------------------------------------------- sessions with a committed prefix

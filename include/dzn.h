@@ -304,6 +304,24 @@ int dzn_diarize_range(const uint8_t* d_seg, const int8_t* d_hard, int32_t C, int
                       uint8_t* d_count, uint8_t* d_active, int32_t* d_act, void* hip_stream);
 
 /*
+ * dzn_diarize_range with the per-speaker activity scores of the same frames, still ONE launch (diarizen_amd/live.py,
+ * LiveDiarization(scores=True)).  d_count / d_active / d_act are byte for byte what dzn_diarize_range writes for the same
+ * arguments.  d_scores f32 [t1-t0, K]: row t - t0, column k holds the value dzn_speaker_scores (below) gives for frame t and
+ * column k of a K-column call over the same C windows — the float32 max over the local speakers s with hard[c,s] == k of
+ * d_soft[c, t-start_c, s] (NaN or no such speaker: a missing entry), accumulated over the covering windows in ascending c as
+ * ((score * mask) * hamming[l]) * warm_up[l] with the two float64 [L] tables kept apart, divided as acc / max(cnt, 1e-12) in
+ * float32, 0 where no valid entry landed (a column no window holds is all zeros).  d_soft f32 [C,L,S].  Lane (t, k) of
+ * dzn_diarize_range's layout does the score walk inside its own loop over the covering windows: no atomics, no second pass.
+ * As final as the other three outputs: a range call is the same bits as the same rows of the whole.  DZN_E_INVALID for
+ * whatever dzn_diarize_range refuses and for a NULL d_soft, d_hamming, d_warm_up or d_scores; t1 == t0 returns DZN_OK
+ * without a launch.  Enqueue only.
+ */
+int dzn_diarize_range_scores(const uint8_t* d_seg, const int8_t* d_hard, const float* d_soft, int32_t C, int32_t L, int32_t S,
+                             const int32_t* d_start_frame, const double* d_hamming, const double* d_warm_up, int32_t t0,
+                             int32_t t1, int32_t K, int32_t max_count, uint8_t* d_count, uint8_t* d_active, int32_t* d_act,
+                             float* d_scores, void* hip_stream);
+
+/*
  * Per-speaker activity scores (stateless, no handle): the soft scores of every window, mapped to the global clusters and
  * overlap-added.
  *   clustered[c, :, k] = max_{s : hard[c,s] == k} soft[c, :, s], NaN when window c has no local speaker in cluster k

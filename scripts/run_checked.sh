@@ -31,5 +31,7 @@ python -m pytest tests/test_beamform_live_gpu.py -m gpu -q -x 2>&1 | tail -3
 # array feeds in the hub (beamform_many.hip, ids 0x87x: tiles and work items of their descriptors, the carried samples; the
 # 0x85x / 0x86x checks of beamform_tile.h against the wave's scratch and the rows' tables): likewise
 python -m pytest tests/test_beamform_many_gpu.py tests/test_hub_array_gpu.py -m gpu -q -x 2>&1 | tail -3
+# live per-speaker scores (post.hip, ids 0x833 / 0x834: the soft row read and the score write of the fused range kernel): likewise
+python -m pytest tests/test_live_scores_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
