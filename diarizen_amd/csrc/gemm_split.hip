@@ -342,11 +342,11 @@ __global__ __launch_bounds__(WGM * WGN * 64, OCC) void gemm_split_kernel(const d
 // tile above and lost 4 % on the step; it was removed (profiles/r4_gemm_m32_probe.txt).
 
 template <int BM, int BN, int WGM, int WGN, int S, int NP, int OCC = 1>
-int launch_split_cfg(const dzn_gemm_desc& d, hipStream_t s) {
+int launch_split_cfg(const dzn_gemm_desc& d, hipStream_t s, const char* tag = nullptr) {
   size_t lds = (size_t)S * (BM * 128 + NP * BN * 64);
   if (d.A2 && a2_tab_in_lds((int)lds, BM, OCC)) lds += BM * 4;   // + the second segment's row table
-  return launch_contraction<gemm_split_kernel<BM, BN, WGM, WGN, S, NP, OCC>>(d, s, WGM * WGN * 64, lds, BM, BN, WGN,
-                                                                             NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16", NP * 2);
+  if (!tag) tag = NP == 3 ? "f32s" : NP == 2 ? "f32h" : "f16";
+  return launch_contraction<gemm_split_kernel<BM, BN, WGM, WGN, S, NP, OCC>>(d, s, WGM * WGN * 64, lds, BM, BN, WGN, tag, NP * 2);
 }
 
 // W [rows][K] fp32 (row stride ldw)  ->  W3 [rows][K/32][3][32] bf16, k permuted inside each block
@@ -385,6 +385,8 @@ int launch_gemm_split_np(const dzn_gemm_desc& d, hipStream_t s) {
     } else {
       if (!strcmp(force, "128x128w4")) return launch_split_cfg<128, 128, 4, 1, 2, NP, 2>(d, s);
     }
+    // (short-K probes at NP = 2, measured behind 128x128w4 at every K = 128 .. 512 and removed: 128 x 256 tiles of 4 x 2 wavefronts and
+    //  256 x 128 tiles of 8 x 1, one 512-thread workgroup per CU, 96 KB of LDS — profiles/short_k_wide_probe.txt)
     if constexpr (NP == 1) {
       if (!strcmp(force, "256x128w8s3")) return launch_split_cfg<256, 128, 8, 1, 3, NP, 2>(d, s);
     }
@@ -399,18 +401,30 @@ int launch_gemm_split_np(const dzn_gemm_desc& d, hipStream_t s) {
   // room to trade occupancy for more loads in flight; 128x64 tiles want 3 workgroups per CU, 128x128 two)
   constexpr int OCC64 = NP <= 2 ? 3 : 2;
   if (d.N <= 32) return launch_split_cfg<128, 32, 4, 1, 2, NP>(d, s);
+  const int cols128 = (d.N + 127) / 128 * 128, cols64 = (d.N + 63) / 64 * 64;
+  // Short K on wide outputs (NP = 2, N >= 512, 128 <= K <= 512: the out-projections and the narrow FFN-down launches of the
+  // pruned encoder, 44 launches per forward of the large model): the 128 x 128 tile of 4 x 1 wavefronts — the SAME kernel as the
+  // K > 512 class below — under a profiler class of its own, gemm_f32h_sk_128x128, so that gemm_f32h_128x128 stays the
+  // homogeneous long-K class of the roofline line.  Isolated sweep at 223839 x 1024 (profiles/short_k_wide_probe.txt): 7-15 %
+  // below the 128 x 64 tile at every K from 128 (514 vs 607 us) to 512 (967 vs 1054 us), no crossover; 128 x 256 and
+  // 256 x 128 tiles (one 512-thread workgroup per CU) lie between the two and were removed.  A/B on the step:
+  // profiles/short_k_wide_ab.txt.  (r3 had measured 4-7 % in isolation with the step unmoved inside a +-1 % noise,
+  // profiles/r3_tile_choice_short_k.txt.)
+  // The rule reads N, K and NP only — never M, nz or stat_partial: a LayerNorm partial is the sum over ONE wavefront tile's
+  // columns, so a tile that followed M would make a window's float outputs depend on its batch (see the 448-workgroup rule
+  // below).  At N = 1024 these launches now leave 8 partials per row instead of 16.  Widths whose last 128-wide tile would be
+  // mostly padding stay narrow, by the same 1/8 test as for long K.  K < 128 (the heavily pruned layers, ~6 ms of the step)
+  // and N < 512 stay on the narrow tile: they were not measured.
+  if constexpr (NP == 2)
+    if (d.N >= 512 && d.K >= 128 && d.K <= 512 && cols64 * 9 >= cols128 * 8)
+      return launch_split_cfg<128, 128, 4, 1, 2, NP, 2>(d, s, "f32h_sk");
   // 128x64 tiles run 4 wavefronts as 4x1 (32 rows x 64 columns each): the in-register operand
   // split is per A row, so wide-and-short wavefront tiles halve the VALU work per MFMA
-  // (r3 probe, profiles/r3_tile_choice_short_k.txt: in isolation the 128x128 tile is 4-7 % faster on the K = 256 .. 512
-  // shapes now that the epilogue is pipelined — 424 vs 444 us at 149226 x 1024 x 256; in the pipeline the step time did
-  // not move (1139 vs 1124-1142 ms), so the short-K launches stay on the narrow tile and the 128x128 symbol stays a
-  // homogeneous K >= 768 class for the roofline line)
   // (r5) requesting the residual of short-K launches at kernel start cost the third workgroup per CU (class 168 -> 134 TFLOP/s) and
   // was removed: DESIGN.md §4.9, profiles/r5_rpf_probe.txt
   if (d.N <= 64 || d.K <= 512) return launch_split_cfg<128, 64, 4, 1, 2, NP, OCC64>(d, s);
   // 128-wide column tiles unless 64-wide ones save more than ~1/8 of the (padded) columns; widths that
   // are multiples of 80 but not of 64 (conv1 of the extractor: 153 -> 160) get exact 80-wide tiles
-  const int cols128 = (d.N + 127) / 128 * 128, cols64 = (d.N + 63) / 64 * 64;
   // small launches (BASELINE configs[1]: 32 windows of 5 s = 7968 rows): 128 x 128 tiles would leave most of the 512
   // workgroup slots (256 CUs x 2) empty — halve the tile so that twice as many workgroups exist
   // A launch that leaves LayerNorm partials (stat_partial) is exempt: a partial is the sum over ONE wavefront tile's columns, so
