@@ -191,6 +191,7 @@ def load() -> C.CDLL:
     sig("dzn_diarize_range", i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp])
     sig("dzn_diarize_range_scores", i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp])
     sig("dzn_speaker_scores", i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp])
+    sig("dzn_match_counts", i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp])
     sig("dzn_debug_fetch", i32, [vp, C.c_char_p, vp, i64, C.POINTER(i64)])
     sig("dzn_embed_skip_stats", i32, [vp, C.POINTER(i64), C.POINTER(i64)])
     sig("dzn_num_ignored", i32, [vp])
@@ -292,7 +293,7 @@ def load() -> C.CDLL:
 
 EXPORTED = [
     "dzn_create", "dzn_load_tensor", "dzn_finalize_weights", "dzn_num_frames",
-    "dzn_segment_forward", "dzn_segment_forward_soft", "dzn_embed_forward", "dzn_embed_forward_strided", "dzn_prepare_masks", "dzn_speaker_count", "dzn_cluster_activations", "dzn_detect", "dzn_detect_range", "dzn_diarize_range", "dzn_diarize_range_scores", "dzn_speaker_scores", "dzn_debug_fetch", "dzn_embed_skip_stats", "dzn_num_ignored",
+    "dzn_segment_forward", "dzn_segment_forward_soft", "dzn_embed_forward", "dzn_embed_forward_strided", "dzn_prepare_masks", "dzn_speaker_count", "dzn_cluster_activations", "dzn_detect", "dzn_detect_range", "dzn_diarize_range", "dzn_diarize_range_scores", "dzn_speaker_scores", "dzn_match_counts", "dzn_debug_fetch", "dzn_embed_skip_stats", "dzn_num_ignored",
     "dzn_workspace_bytes", "dzn_last_error", "dzn_destroy", "dzn_version", "dzn_linkage_centroid", "dzn_cdist_cosine", "dzn_host_workspace_release",
     "dzn_host_workspace_bytes",
     "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_beamform_delays", "dzn_beamform_sum", "dzn_beamform_tile", "dzn_decode_planar", "dzn_beamform_track", "dzn_beamform_feed", "dzn_ingest_many", "dzn_beamform_many", "dzn_gather_windows", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",

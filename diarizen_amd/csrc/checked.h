@@ -48,4 +48,6 @@
 //            0x86x beamform_live (0x860 planar frame read / write, 0x862 tracker column),
 //            0x87x beamform_many (0x870 decode tile of its descriptor, 0x871 format, 0x872 GCC work item and LDS image,
 //                                 0x873 channel of the item, 0x874 tracker descriptor, 0x875 sum tile, 0x876 carried sample);
-//            the 0x85x / 0x86x checks of beamform_tile.h count in the translation unit that includes it
+//            the 0x85x / 0x86x checks of beamform_tile.h count in the translation unit that includes it;
+//            0x88x reseg (0x880 decision read, 0x881 reference read, 0x882 LDS word, 0x883 count write) — its collector
+//            dzn_checked_collect_reseg is read by tests/test_resegmentation_gpu.py, dzn_checked_status does not sum it

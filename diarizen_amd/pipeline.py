@@ -660,6 +660,17 @@ class DiariZenPipeline:
             return (result, scores, embeddings) if return_scores else (result, embeddings)
         return (result, scores) if return_scores else result
 
+    def resegment(self, file, diarization=None, hook=None, **params):
+        """refine a given diarization of `file` with this pipeline's segmentation model: resegmentation.Resegmentation over
+        this pipeline's engine (no second copy of the weights), instantiated with **params (warm_up, min_duration_on,
+        min_duration_off).  -> (Annotation with integer labels, the hypothesis's labels sorted: column k is labels[k])"""
+        from .resegmentation import Resegmentation
+        reseg = Resegmentation(self, rttm_out_dir=self.rttm_out_dir).instantiate(params)
+        try:
+            return reseg(file, diarization=diarization, hook=hook), reseg.labels
+        finally:
+            reseg.close()               # the borrowed engine stays open
+
     def voiceprint(self, in_wav, sess_name: Optional[str] = None) -> np.ndarray:
         """the enrolment call: float32 [256], the centroid of the label with the largest total duration in the recording (ties:
         the smaller label).  ValueError when the recording has no speech."""

@@ -282,6 +282,26 @@ class DevicePost:
             self.seg = torch.from_numpy(seg).to(self.device)
             self.starts = torch.from_numpy(starts).to(self.device)
 
+    @classmethod
+    def from_device(cls, seg_t, chunks: SlidingWindow, frames: SlidingWindow) -> "DevicePost":
+        """the same object over decisions u8 [C, L, S] that are already on the device (no download, no second upload): the
+        host stage's stream first waits for the current stream, where they were produced"""
+        import torch
+        _lib.load()
+        assert seg_t.is_cuda and seg_t.dtype == torch.uint8 and seg_t.is_contiguous() and seg_t.dim() == 3
+        self = cls.__new__(cls)
+        self.torch, self.device = torch, seg_t.device
+        self.C, self.L, self.S = (int(d) for d in seg_t.shape)
+        self.chunks, self.frames = chunks, frames
+        self.grid, starts, self.T = _frame_grid(self.C, self.L, chunks, frames)
+        self.stream = _host_stream(self.device)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            seg_t.record_stream(self.stream)
+            self.seg = seg_t
+            self.starts = torch.from_numpy(starts).to(self.device)
+        return self
+
     def speaker_count(self) -> SlidingWindowFeature:
         torch = self.torch
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
@@ -290,9 +310,13 @@ class DevicePost:
             _call("dzn_speaker_count", self.seg, self.C, self.L, self.S, self.starts, self.T, work, out)
             return SlidingWindowFeature(out.cpu().numpy().reshape(-1, 1), self.grid)
 
-    def reconstruct(self, hard_clusters: np.ndarray, count: SlidingWindowFeature):
+    def reconstruct(self, hard_clusters: np.ndarray, count: SlidingWindowFeature, num_clusters: Optional[int] = None):
+        """num_clusters: the number of activation columns when the caller fixes it (resegmentation: one column per speaker of
+        the padded matching, also those no window was assigned to); default max(hard_clusters) + 1"""
         torch = self.torch
         K = int(np.max(hard_clusters)) + 1 if hard_clusters.size else 0
+        if num_clusters is not None:
+            K = max(K, int(num_clusters))
         if K < 1 or K > 32:
             return None                                     # caller falls back to the numpy path
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
@@ -615,3 +639,192 @@ def _hysteresis(y: np.ndarray, onset: float, offset: float) -> np.ndarray:
             state = True
         act[i] = state
     return act
+
+
+# ----------------------------------------------------------------------------- resegmentation: matching to a given diarization
+MATCH_MAX_N = 32            # dzn_match_counts' widest padded side (include/dzn.h)
+
+
+def trim_frames(L: int, warm_up: float) -> Tuple[int, int]:
+    """(l0, L'): frames [l0, l0 + L') of every window survive Inference.trim(warm_up=(w, w)) (PA/core/inference.py:696-705)"""
+    l0 = round(L * warm_up)
+    return int(l0), int(L - 2 * l0)
+
+
+def trimmed_chunks(chunks: SlidingWindow, warm_up: float) -> SlidingWindow:
+    """the chunks of the trimmed windows (PA/core/inference.py:707-711): window c becomes [c step + w D, c step + (1 - w) D)"""
+    return SlidingWindow(start=chunks.start + warm_up * chunks.duration, step=chunks.step,
+                         duration=(1 - warm_up - warm_up) * chunks.duration)
+
+
+def reference_extent(num_samples: int, sample_rate: int, chunks: SlidingWindow, frames: SlidingWindow) -> Tuple[int, int]:
+    """(f0, Tr) of the discretised hypothesis: support Segment(0, duration + step) on the model's frames
+    (PA/pipelines/resegmentation.py:203-208), f0 = closest_frame(0), Tr = closest_frame(duration + step) - f0"""
+    f0 = int(frames.closest_frame(0.0))
+    return f0, max(int(frames.closest_frame(num_samples / sample_rate + chunks.step)) - f0, 0)
+
+
+def reference_rows(C: int, chunks: SlidingWindow, frames: SlidingWindow) -> np.ndarray:
+    """int32 [C]: the first reference row of every (trimmed) window — the first frame of SlidingWindowFeature.crop(chunk),
+    mode "loose" (PA/pipelines/resegmentation.py:234): max(0, ceil((chunk.start - frames.duration - frames.start) / step))"""
+    starts = chunks.start + np.arange(C, dtype=np.float64) * chunks.step
+    r = np.ceil((starts - frames.duration - frames.start) / frames.step)
+    return np.maximum(r, 0).astype(np.int32)
+
+
+def annotation_turns(annotation) -> list:
+    """[(start, end, label)] of an Annotation (or of a list of such triples, der.parse_rttm's form), in its own order"""
+    if hasattr(annotation, "itertracks"):
+        return [(float(s.start), float(s.end), label) for s, _, label in annotation.itertracks(yield_label=True)]
+    return [(float(a), float(b), label) for a, b, label in annotation]
+
+
+def discretize_turns(annotation, frames: SlidingWindow, Tr: int):
+    """-> (ref u8 [Tr, K], labels): the hypothesis on the frame grid, as Annotation.discretize(support=Segment(0, end),
+    resolution=frames) of pyannote.core 5.0.0 does it (restated: that package is not a dependency, the boundary is unpinned).
+    labels = the input's labels sorted by str(), column k = labels[k].  A turn [a, b) sets rows max(0, closest_frame(a) - f0)
+    .. min(closest_frame(b) - f0, Tr - 1), f0 = closest_frame(0) (SlidingWindow.crop(mode="center")); turns that end at or
+    before 0 are outside the support."""
+    turns = annotation_turns(annotation)
+    labels = sorted({label for _, _, label in turns}, key=str)
+    col = {label: k for k, label in enumerate(labels)}
+    Tr = max(int(Tr), 0)
+    ref = np.zeros((Tr, len(labels)), dtype=np.uint8)
+    f0 = int(frames.closest_frame(0.0))
+    for a, b, label in turns:
+        if b <= 0.0 or b <= a:
+            continue
+        lo = max(0, int(frames.closest_frame(a)) - f0)
+        hi = min(int(frames.closest_frame(b)) - f0, Tr - 1)
+        if hi >= lo:
+            ref[lo:hi + 1, col[label]] = 1
+    return ref, labels
+
+
+def match_counts_host(seg: np.ndarray, ref: np.ndarray, rows: np.ndarray, l0: int, Lt: int, K: int) -> np.ndarray:
+    """numpy twin of dzn_match_counts (needs no device; the kernel is checked against it): seg u8 [C, L, S], ref u8 [Tr, K],
+    rows int [C] -> int32 [C, n, n], n = max(K, S): count[c, i, j] = #{l < Lt : refpad[rows[c] + l, i] != segpad[c, l0 + l, j]},
+    both sides widened to n columns with zeros, reference rows at or beyond Tr zero"""
+    seg = np.asarray(seg)
+    C, L, S = seg.shape
+    K, l0, Lt = int(K), int(l0), int(Lt)
+    n = max(K, S)
+    if Lt < 1 or l0 < 0 or l0 + Lt > L:
+        raise ValueError(f"frames [{l0}, {l0 + Lt}) are not inside a window of {L}")
+    ref = np.asarray(ref) != 0
+    assert ref.ndim == 2 and ref.shape[1] == K
+    Tr = len(ref)
+    out = np.zeros((C, n, n), dtype=np.int32)
+    sp = np.zeros((Lt, n), dtype=bool)
+    for c in range(C):
+        rp = np.zeros((Lt, n), dtype=bool)
+        r = int(rows[c])
+        a, b = min(max(r, 0), Tr), min(max(r + Lt, 0), Tr)
+        if b > a:
+            rp[a - r:b - r, :K] = ref[a:b]
+        sp[:, :S] = seg[c, l0:l0 + Lt] != 0
+        out[c] = np.count_nonzero(rp[:, :, None] != sp[:, None, :], axis=0)
+    return out
+
+
+def match_counts_device(seg_t, ref, rows: np.ndarray, l0: int, Lt: int, K: int) -> np.ndarray:
+    """dzn_match_counts on the current stream: seg_t u8 [C, L, S] on the device, ref u8 [Tr, K] (host array or device tensor),
+    rows int [C] -> int32 [C, n, n] on the host.  Only the counts come back."""
+    import torch
+    assert seg_t.is_cuda and seg_t.dtype == torch.uint8 and seg_t.is_contiguous()
+    dev = seg_t.device
+    C, L, S = (int(d) for d in seg_t.shape)
+    K = int(K)
+    n = max(K, S)
+    with torch.cuda.device(dev):
+        if not isinstance(ref, torch.Tensor):
+            ref = torch.from_numpy(np.ascontiguousarray(ref, dtype=np.uint8)).to(dev)
+        assert ref.dtype == torch.uint8 and ref.is_contiguous() and ref.dim() == 2 and ref.shape[1] == K
+        Tr = int(ref.shape[0])
+        d_row = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
+        assert len(d_row) == C
+        out = torch.empty((C, n, n), device=dev, dtype=torch.int32)
+        _call("dzn_match_counts", seg_t, ref if ref.numel() else None, C, L, S, Tr, K, d_row, int(l0), int(Lt), out)
+        return out.cpu().numpy()
+
+
+def assign_windows(counts: np.ndarray, Lt: int, S: int) -> np.ndarray:
+    """int32 counts [C, n, n] -> hard int8 [C, S]: hard[c, j] = i, the speaker of the hypothesis that local speaker j of
+    window c is matched to.  cost = float32(count) / float32(Lt) (mae_cost_func's torch.mean, PA/utils/permutation.py:83-95),
+    then scipy.optimize.linear_sum_assignment per window (permutation.py:152-156)."""
+    from scipy.optimize import linear_sum_assignment
+    cost = (counts.astype(np.float32) / np.float32(Lt)).astype(np.float64)
+    hard = np.zeros((len(counts), int(S)), dtype=np.int8)
+    for c in range(len(counts)):
+        i, j = linear_sum_assignment(cost[c])
+        keep = j < S
+        hard[c, j[keep]] = i[keep]
+    return hard
+
+
+def permutated_decisions(trimmed: np.ndarray, hard: np.ndarray, n: int) -> np.ndarray:
+    """the permutated segmentations of PA/pipelines/resegmentation.py:231-243 as float32 [C, L', n]: column hard[c, j] of
+    window c is local speaker j, the other columns (matched to padded local speakers) are zero"""
+    C, Lt, S = trimmed.shape
+    out = np.zeros((C, Lt, int(n)), dtype=np.float32)
+    cc = np.arange(C)
+    for j in range(S):
+        out[cc, :, hard[:, j].astype(np.int64)] = trimmed[:, :, j]
+    return out
+
+
+def resegment_host(seg: np.ndarray, ref: np.ndarray, chunks: SlidingWindow, frames: SlidingWindow, warm_up: float = 0.0):
+    """the host composition of PA/pipelines/resegmentation.py:184-246 on hard decisions seg u8 [C, L, S] and a discretised
+    hypothesis ref u8 [Tr, K] -> (speaker count [T, 1], counts int32 [C, n, n], hard int8 [C, S], discrete diarization [T, n']).
+    Needs no device; the device path of resegmentation.Resegmentation is checked against it."""
+    seg = np.ascontiguousarray(seg, dtype=np.uint8)
+    C, L, S = seg.shape
+    ref = np.asarray(ref, dtype=np.uint8)
+    K = int(ref.shape[1])
+    n = max(K, S)
+    l0, Lt = trim_frames(L, warm_up)
+    tc = trimmed_chunks(chunks, warm_up) if warm_up else chunks
+    trimmed = seg[:, l0:l0 + Lt]
+    count = speaker_count(trimmed.astype(np.float32), tc, frames)
+    counts = match_counts_host(seg, ref, reference_rows(C, tc, frames), l0, Lt, K)
+    hard = assign_windows(counts, Lt, S)
+    discrete, _ = to_diarization(permutated_decisions(trimmed, hard, n), tc, count)
+    return count, counts, hard, discrete
+
+
+def resegment_device(seg_t, ref: np.ndarray, chunks: SlidingWindow, frames: SlidingWindow, warm_up: float = 0.0, step=None):
+    """resegment_host over decisions u8 [C, L, S] that are on the device, same return value, same bits.  The matching counts
+    are dzn_match_counts'; with warm_up == 0 the speaker count and the aggregation of the matched decisions are DevicePost's
+    (dzn_speaker_count, dzn_cluster_activations), with warm_up > 0 they are the numpy functions on the trimmed download.  More
+    than MATCH_MAX_N speakers on the wider side: resegment_host on the download (the K > 32 rule of DevicePost.reconstruct).
+    step(name, artifact): called with "speaker_counting" and "permutated" as they become available."""
+    step = step or (lambda *a: None)
+    C, L, S = (int(d) for d in seg_t.shape)
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    K = int(ref.shape[1])
+    n = max(K, S)
+    if n > MATCH_MAX_N:
+        count, counts, hard, discrete = resegment_host(seg_t.cpu().numpy(), ref, chunks, frames, warm_up)
+        step("speaker_counting", count)
+        step("permutated", hard)
+        return count, counts, hard, discrete
+    l0, Lt = trim_frames(L, warm_up)
+    tc = trimmed_chunks(chunks, warm_up) if warm_up else chunks
+    rows = reference_rows(C, tc, frames)
+    if warm_up:
+        trimmed = seg_t.cpu().numpy()[:, l0:l0 + Lt]
+        count = speaker_count(trimmed.astype(np.float32), tc, frames)
+        step("speaker_counting", count)
+        counts = match_counts_device(seg_t, ref, rows, l0, Lt, K)
+        hard = assign_windows(counts, Lt, S)
+        step("permutated", hard)
+        discrete, _ = to_diarization(permutated_decisions(trimmed, hard, n), tc, count)
+        return count, counts, hard, discrete
+    post = DevicePost.from_device(seg_t, chunks, frames)
+    count = post.speaker_count()
+    step("speaker_counting", count)
+    counts = match_counts_device(seg_t, ref, rows, 0, L, K)
+    hard = assign_windows(counts, L, S)
+    step("permutated", hard)
+    discrete, _ = post.reconstruct(hard, count, num_clusters=n)
+    return count, counts, hard, discrete

@@ -340,6 +340,25 @@ int dzn_speaker_scores(const float* d_soft, const int8_t* d_hard, int32_t C, int
                        const int32_t* d_start_frame, const double* d_hamming, const double* d_warm_up,
                        int32_t T, int32_t K, float* d_scores, void* hip_stream);
 
+/*
+ * The matching step of the Resegmentation pipeline (stateless, no handle; csrc/reseg.hip): per window, the disagreement
+ * counts between the speakers of a given diarization and the model's local speakers — the cost matrices of the reference's
+ * per-window loop, as exact integers.
+ *   n = max(K, S): the narrower side is widened with zero columns      PA/pipelines/resegmentation.py:217-228
+ *   count[c, i, j] = #{ l < Lt : refpad[d_row[c] + l, i] != segpad[c, l0 + l, j] }
+ *                    <- the loop over windows, resegmentation.py:230-243; permutate's cost matrix, PA/utils/permutation.py:
+ *                       131-157, with mae_cost_func = torch.mean(|Y - y|) (permutation.py:83-95): the caller's
+ *                       float32(count) / float32(Lt) is that mean on {0,1} data
+ *   frames [l0, l0 + Lt) of every window are those Inference.trim keeps      PA/core/inference.py:669-713
+ * d_seg u8 [C,L,S] hard decisions; d_ref u8 [Tr,K] the given diarization on the frame grid (may be NULL when K == 0 or
+ * Tr == 0), rows at or beyond Tr read as inactive; d_row int32 [C] the first reference row of every window (the loose crop of
+ * resegmentation.py:234, computed by the caller in float64); d_count int32 [C,n,n].  One workgroup per window, no atomics.
+ * Enqueue-only.  DZN_E_INVALID, nothing launched: n > 32, S < 1, Lt < 1, l0 < 0, l0 + Lt > L, C < 0, K < 0, Tr < 0 or a null
+ * pointer; C == 0 returns DZN_OK without a launch.  The assignment (scipy.optimize.linear_sum_assignment) is the caller's.
+ */
+int dzn_match_counts(const uint8_t* d_seg, const uint8_t* d_ref, int32_t C, int32_t L, int32_t S, int32_t Tr, int32_t K,
+                     const int32_t* d_row, int32_t l0, int32_t Lt, int32_t* d_count /* [C, n, n] */, void* hip_stream);
+
 /* Copy a named intermediate activation of the LAST forward to host (debug / parity
  * tests).  *n_elems receives the element count; host_out may be NULL to query. */
 int dzn_debug_fetch(dzn_handle* h, const char* name, float* host_out, int64_t cap,
