@@ -205,6 +205,8 @@ def load() -> C.CDLL:
     sig("dzn_op_relpos_bucket", i32, [i32, i32, i32])
     sig("dzn_linkage_centroid", i32, [vp, i32, i32, vp, i32])
     sig("dzn_cdist_cosine", i32, [vp, i32, i32, vp, i32, vp, i32])
+    sig("dzn_link_speakers", i32, [vp, vp, i32, i32, C.c_double, vp, C.POINTER(i32), i32])
+    sig("dzn_link_speakers_last", i32, [C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32)])
     sig("dzn_host_workspace_release", i32, [i32])
     sig("dzn_host_workspace_bytes", i64, [i32])
     sig("dzn_vbx_create", i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_void_p)])
@@ -295,7 +297,7 @@ EXPORTED = [
     "dzn_create", "dzn_load_tensor", "dzn_finalize_weights", "dzn_num_frames",
     "dzn_segment_forward", "dzn_segment_forward_soft", "dzn_embed_forward", "dzn_embed_forward_strided", "dzn_prepare_masks", "dzn_speaker_count", "dzn_cluster_activations", "dzn_detect", "dzn_detect_range", "dzn_diarize_range", "dzn_diarize_range_scores", "dzn_speaker_scores", "dzn_match_counts", "dzn_debug_fetch", "dzn_embed_skip_stats", "dzn_num_ignored",
     "dzn_workspace_bytes", "dzn_last_error", "dzn_destroy", "dzn_version", "dzn_linkage_centroid", "dzn_cdist_cosine", "dzn_host_workspace_release",
-    "dzn_host_workspace_bytes",
+    "dzn_host_workspace_bytes", "dzn_link_speakers", "dzn_link_speakers_last",
     "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_beamform_delays", "dzn_beamform_sum", "dzn_beamform_tile", "dzn_decode_planar", "dzn_beamform_track", "dzn_beamform_feed", "dzn_ingest_many", "dzn_beamform_many", "dzn_gather_windows", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",
     "dzn_gallery_create", "dzn_gallery_put", "dzn_gallery_drop", "dzn_gallery_search", "dzn_gallery_geometry", "dzn_gallery_rows",
     "dzn_gallery_last_launch_ms", "dzn_gallery_destroy",

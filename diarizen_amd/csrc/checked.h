@@ -50,4 +50,6 @@
 //                                 0x873 channel of the item, 0x874 tracker descriptor, 0x875 sum tile, 0x876 carried sample);
 //            the 0x85x / 0x86x checks of beamform_tile.h count in the translation unit that includes it;
 //            0x88x reseg (0x880 decision read, 0x881 reference read, 0x882 LDS word, 0x883 count write) — its collector
-//            dzn_checked_collect_reseg is read by tests/test_resegmentation_gpu.py, dzn_checked_status does not sum it
+//            dzn_checked_collect_reseg is read by tests/test_resegmentation_gpu.py, dzn_checked_status does not sum it;
+//            0x89x linkage, pdist_cosine_group_kernel (0x890 LDS stage index, 0x891 embedding read, 0x892 norm / group read,
+//            0x893 matrix write) — its collector dzn_checked_collect_linkage is read by tests/test_linking_gpu.py the same way

@@ -29,6 +29,10 @@
 // it — equals scipy's (tests/test_ops_gpu.py compares Z and fcluster output, also at edge sizes and with
 // duplicated embeddings).
 //
+// The same loop under a second update rule links speakers ACROSS recordings (dzn_link_speakers): masked
+// cosine distances (pdist_cosine_group_kernel: two rows of one recording are 4.0 apart), the complete-linkage update
+// v = max(d_xi, d_yi) and a stop at the first closest pair above the threshold — step2_kernel<RULE_COMPLETE>.
+//
 // Retired forms: a two-kernel loop (single-workgroup selection + wide update per merge), the step loop with one
 // remembered neighbour, and a single persistent launch whose workgroups exchanged records through polled slots.
 // All three measured slower; their records are profiles/r3_linkage_step_vs_two_kernel.txt, profiles/r6_linkage_top2.txt
@@ -40,7 +44,10 @@
 #include <mutex>
 #include <vector>
 
+#include "checked.h"
 #include "common.h"
+
+DZN_CHECKED_TU(linkage)
 
 namespace {
 
@@ -90,6 +97,100 @@ __global__ __launch_bounds__(256) void pdist_kernel(const float* __restrict__ E,
       const int i = bi * 64 + ty * 4 + a, j = bj * 64 + tx * 4 + b;
       if (i < n && j < n) {
         const double d = i == j ? DINF : sqrt(acc[a][b]);
+        D[(int64_t)i * n + j] = d;
+        D[(int64_t)j * n + i] = d;
+      }
+    }
+}
+
+// row norms in float64, in-order sum (dzn_cdist_cosine and dzn_link_speakers)
+__global__ __launch_bounds__(256) void row_norm_f32_kernel(const float* __restrict__ E, int n, int dim,
+                                                           double* __restrict__ nrm) {
+#pragma clang fp contract(off)
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const float* e = E + (int64_t)r * dim;
+  double s = 0.0;
+  for (int i = 0; i < dim; ++i) {
+    const double c = (double)e[i];
+    const double p = c * c;
+    s = s + p;
+  }
+  nrm[r] = sqrt(s);
+}
+
+// ---- pairwise cosine distances with a cannot-link mask (dzn_link_speakers): the tile and LDS staging of pdist_kernel ----
+//     D[i][j] = group[i] == group[j] ? LINK_BIG : 1 - clip(dot(u_i, u_j) / (|u_i| |u_j|)),   D[i][i] = +inf
+// scipy's pdist(E, "cosine") formula in float64: in-order sum over k, product and sum rounded separately (a float32 x float32
+// product is exact in float64, so the sum is the same with or without contraction; it is switched off anyway).  LINK_BIG is
+// FINITE on purpose: cosine distances end at 2, so 4 sorts above every real distance, and a finite value keeps the loop's
+// "no finite distance left" test (STEP_FAIL) for NaN / inf input alone.  Complete linkage takes the max over member pairs,
+// so a forbidden pair poisons every union that holds it: the mask is all the constraint needs.
+constexpr double LINK_BIG = 4.0;
+
+__global__ __launch_bounds__(256) void pdist_cosine_group_kernel(const float* __restrict__ E, const double* __restrict__ nrm,
+                                                                 const int* __restrict__ group, int n, int dim,
+                                                                 double* __restrict__ D) {
+#pragma clang fp contract(off)
+  __shared__ float sa[64][17], sb[64][17];
+  const int bi = blockIdx.y, bj = blockIdx.x;
+  if (bj < bi) return;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;  // thread -> rows ty*4.., cols tx*4..
+  double acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+  for (int k0 = 0; k0 < dim; k0 += 16) {
+    for (int idx = threadIdx.x; idx < 64 * 16; idx += 256) {
+      const int r = idx >> 4, c = idx & 15;
+      const int gi = bi * 64 + r, gj = bj * 64 + r, gk = k0 + c;
+      DZN_CHECK(r < 64 && c < 16, 0x890, idx);
+      DZN_CHECK(!(gi < n && gk < dim) || (int64_t)gi * dim + gk < (int64_t)n * dim, 0x891, gi);
+      DZN_CHECK(!(gj < n && gk < dim) || (int64_t)gj * dim + gk < (int64_t)n * dim, 0x891, gj);
+      sa[r][c] = (gi < n && gk < dim) ? E[(int64_t)gi * dim + gk] : 0.f;
+      sb[r][c] = (gj < n && gk < dim) ? E[(int64_t)gj * dim + gk] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      double av[4], bv[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) av[a] = (double)sa[ty * 4 + a][c];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) bv[b] = (double)sb[tx * 4 + b][c];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const double p = av[a] * bv[b];
+          acc[a][b] = acc[a][b] + p;
+        }
+    }
+    __syncthreads();
+  }
+  double ni[4], nj[4];
+  int gi[4], gj[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int i = bi * 64 + ty * 4 + a, j = bj * 64 + tx * 4 + a;
+    DZN_CHECK(i >= 0 && j >= 0 && ty * 4 + a < 64 && tx * 4 + a < 64, 0x892, i);
+    ni[a] = i < n ? nrm[i] : 1.0;
+    gi[a] = i < n ? group[i] : 0;
+    nj[a] = j < n ? nrm[j] : 1.0;
+    gj[a] = j < n ? group[j] : 0;
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int i = bi * 64 + ty * 4 + a, j = bj * 64 + tx * 4 + b;
+      if (i < n && j < n) {
+        const double den = ni[a] * nj[b];
+        double cosine = acc[a][b] / den;
+        if (fabs(cosine) > 1.0) cosine = copysign(1.0, cosine);      // scipy clips the rounding error
+        const double d = i == j ? DINF : gi[a] == gj[b] ? LINK_BIG : 1.0 - cosine;
+        DZN_CHECK((int64_t)i * n + j < (int64_t)n * n && (int64_t)j * n + i < (int64_t)n * n, 0x893, i);
         D[(int64_t)i * n + j] = d;
         D[(int64_t)j * n + i] = d;
       }
@@ -153,7 +254,15 @@ __device__ __forceinline__ void block_min_pair(double v, int id, double& val, in
 // the next scan of the row refills both.  A numpy model of the rules is checked against scipy on the CPU
 // (tests/test_design_math.py::test_linkage_top2_model_equals_scipy); on the 4 h recording's 20 888 embeddings the loop needs
 // 1.1-1.3 launches per merge (profiles/r6_linkage_top2.txt).  The partial results of a row scan are top-2 pairs.
+//
+// The loop is indifferent to the update rule in every line but one: I1 / I2 / e1 / e2 are statements about bounds and hold for
+// any new distance v of the union.  RULE picks that line at compile time:
+//   RULE_CENTROID  scipy's Lance-Williams centroid update (dzn_linkage_centroid);
+//   RULE_COMPLETE  v = max(d_xi, d_yi), and the loop STOPS at the first closest pair above `threshold` (dzn_link_speakers):
+//                  the winner's bound is a lower bound of every distance left, so a bound above the threshold - exact or
+//                  stale - means no merge at or below it remains.  The stop is STEP_DONE with k = the merges made.
 enum { STEP_NONE = 0, STEP_MERGE = 1, STEP_RESCAN = 2, STEP_DONE = 3, STEP_FAIL = 4 };
+enum { RULE_CENTROID = 0, RULE_COMPLETE = 1 };
 struct StepState {
   int kind, lo, hi, nlo, nhi, k, x, pad;
   double dist;
@@ -290,11 +399,13 @@ __global__ __launch_bounds__(LB_BLK) void init_rec2_kernel(int n, const double* 
   }
 }
 
+template <int RULE>
 __global__ __launch_bounds__(LB_BLK) void step2_kernel(double* __restrict__ D, int n, double* __restrict__ l1a,
                                                        double* __restrict__ l2a, int* __restrict__ n1a, int* __restrict__ n2a,
                                                        int* __restrict__ fla, int* __restrict__ size, int* __restrict__ cid,
                                                        double* __restrict__ Z, StepState* __restrict__ st2,
-                                                       StepRec* __restrict__ rec2, StepPart2* __restrict__ part2, int parity) {
+                                                       StepRec* __restrict__ rec2, StepPart2* __restrict__ part2, int parity,
+                                                       double threshold) {
   __shared__ double sval[12];
   __shared__ int sidx[12];
   __shared__ int sy[2];
@@ -364,6 +475,10 @@ __global__ __launch_bounds__(LB_BLK) void step2_kernel(double* __restrict__ D, i
     if (w == 0 && t == 0) { StepState s = prev; s.kind = STEP_FAIL; *st_out = s; }
     return;
   }
+  if (RULE == RULE_COMPLETE && d > threshold) {   // every distance left is >= d: the merges at or below the threshold are made
+    if (w == 0 && t == 0) { StepState s = prev; s.kind = STEP_DONE; *st_out = s; }
+    return;
+  }
   double pv = DINF;       // this thread's element of the row whose two smallest the step publishes
   int excl = -1;          // row left out of this step's records
   if (!exact) {
@@ -401,8 +516,10 @@ __global__ __launch_bounds__(LB_BLK) void step2_kernel(double* __restrict__ D, i
         my_l1 = my_l2 = DINF; my_fl = 0; dirty = true;                       // retired
       } else if (my_sz != 0) {
         const double dxi = D[(int64_t)lo * n + z], dyi = D[(int64_t)hi * n + z];
-        // scipy _hierarchy_distance_update.pxi, _centroid(d_xi, d_yi, d_xy, size_x, size_y, size_i), same order
-        const double v = sqrt((((nlo * dxi * dxi) + (nhi * dyi * dyi)) - (nlo * nhi * d * d) / (nlo + nhi)) / (nlo + nhi));
+        // scipy _hierarchy_distance_update.pxi, _centroid(d_xi, d_yi, d_xy, size_x, size_y, size_i), same order; _complete
+        const double v = RULE == RULE_COMPLETE
+                             ? fmax(dxi, dyi)
+                             : sqrt((((nlo * dxi * dxi) + (nhi * dyi * dyi)) - (nlo * nhi * d * d) / (nlo + nhi)) / (nlo + nhi));
         D[(int64_t)hi * n + z] = v;
         D[(int64_t)z * n + hi] = v;              // column lo is NOT blanked: readers of a row mask by size[]
         pv = v;
@@ -475,6 +592,7 @@ struct HostCtx {
   char* sbase = nullptr;      // second arena: a STATE that lives across calls (vbx.hip), leased to one state at a time
   size_t scap = 0;
   bool sleased = false;
+  hipEvent_t ev[2] = {nullptr, nullptr};      // created by the first dzn_link_speakers call on the device, kept with the stream
 };
 constexpr int MAX_DEV = 64;
 std::mutex g_host_mu;
@@ -610,8 +728,21 @@ extern "C" int64_t dzn_host_workspace_bytes(int32_t device) {
   return device >= 0 && device < MAX_DEV ? (int64_t)(g_host[device].cap + g_host[device].scap) : 0;
 }
 
-extern "C" int dzn_linkage_centroid(const float* h_emb, int32_t n, int32_t dim, double* h_Z, int32_t device) {
-  if (!h_emb || !h_Z || n < 2 || dim < 1) return DZN_E_INVALID;
+namespace {
+
+struct LinkStats {      // the last dzn_link_speakers call of the process (g_host_mu held while written and read)
+  int64_t launches = 0;     // step launches queued, surplus ones included
+  int32_t merges = 0, rescans = 0;
+  float pdist_ms = 0.f;     // the distance kernel alone, by HIP events
+};
+LinkStats g_link_stats;
+
+// Both clustering entry points: upload, distance matrix, step loop under RULE, download.  RULE_CENTROID: euclidean distances,
+// all n - 1 merges.  RULE_COMPLETE: masked cosine distances (h_group), the merges of height <= threshold, their number in
+// *h_merges.
+template <int RULE>
+int run_linkage(const float* h_emb, const int32_t* h_group, int32_t n, int32_t dim, double threshold, double* h_Z,
+                int32_t* h_merges, int32_t device) {
   int rc = DZN_OK;
   const int nblk = (n + LB_BLK - 1) / LB_BLK;
   std::vector<int> ones(n, 1), ids(n);
@@ -621,8 +752,8 @@ extern "C" int dzn_linkage_centroid(const float* h_emb, int32_t n, int32_t dim, 
   std::lock_guard<std::mutex> lk(g_host_mu);
   // the buffers of one call, carved from the arena (first pass: sizes only)
   float* E = nullptr;
-  double *D = nullptr, *Z = nullptr, *l1a = nullptr, *l2a = nullptr;
-  int *n1a = nullptr, *n2a = nullptr, *fla = nullptr, *size = nullptr, *cid = nullptr;
+  double *D = nullptr, *Z = nullptr, *l1a = nullptr, *l2a = nullptr, *nrm = nullptr;
+  int *n1a = nullptr, *n2a = nullptr, *fla = nullptr, *size = nullptr, *cid = nullptr, *group = nullptr;
   StepState* st2 = nullptr;
   StepRec* rec2 = nullptr;
   StepPart2* part2 = nullptr;
@@ -641,6 +772,10 @@ extern "C" int dzn_linkage_centroid(const float* h_emb, int32_t n, int32_t dim, 
     part2 = c.take<StepPart2>((size_t)2 * nblk);
     l2a = c.take<double>(n);
     n2a = c.take<int>(n);
+    if (RULE == RULE_COMPLETE) {
+      nrm = c.take<double>(n);
+      group = c.take<int>(n);
+    }
     return c.off;
   };
   HostCtx* ctx = nullptr;
@@ -648,13 +783,25 @@ extern "C" int dzn_linkage_centroid(const float* h_emb, int32_t n, int32_t dim, 
   if (rc != DZN_OK) return rc;
   carve(ctx->base);
   hipStream_t s = ctx->stream;
+  int merges = 0;
+  hipEvent_t* ev = ctx->ev;      // around the distance kernel of RULE_COMPLETE (dzn_link_speakers_last)
+  const bool timed = RULE == RULE_COMPLETE && ((ev[0] && ev[1]) || (hipEventCreate(&ev[0]) == hipSuccess &&
+                                                                    hipEventCreate(&ev[1]) == hipSuccess));
   LCHK(hipMemcpyAsync(E, h_emb, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice, s));
+  if (RULE == RULE_COMPLETE) LCHK(hipMemcpyAsync(group, h_group, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
   LCHK(hipMemcpyAsync(size, ones.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
   LCHK(hipMemcpyAsync(cid, ids.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
   LCHK(hipMemsetAsync(st2, 0, 2 * sizeof(StepState), s));
   {
     const int tiles = (n + 63) / 64;
-    hipLaunchKernelGGL(pdist_kernel, dim3(tiles, tiles), dim3(256), 0, s, E, n, dim, D);
+    if (RULE == RULE_COMPLETE) {
+      hipLaunchKernelGGL(row_norm_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, s, E, n, dim, nrm);
+      if (timed) LCHK(hipEventRecord(ev[0], s));
+      hipLaunchKernelGGL(pdist_cosine_group_kernel, dim3(tiles, tiles), dim3(256), 0, s, E, nrm, group, n, dim, D);
+      if (timed) LCHK(hipEventRecord(ev[1], s));
+    } else {
+      hipLaunchKernelGGL(pdist_kernel, dim3(tiles, tiles), dim3(256), 0, s, E, n, dim, D);
+    }
     hipLaunchKernelGGL(init_rows2_kernel, dim3(n), dim3(256), 0, s, D, n, l1a, l2a, n1a, n2a, fla);
     hipLaunchKernelGGL(init_rec2_kernel, dim3(nblk), dim3(LB_BLK), 0, s, n, l1a, n1a, rec2);
     // one launch per step (merge or rescan); the number of rescans is data dependent, so launches are queued in
@@ -664,32 +811,77 @@ extern "C" int dzn_linkage_centroid(const float* h_emb, int32_t n, int32_t dim, 
     int remaining = n - 1;
     const auto t_loop = std::chrono::steady_clock::now();
     for (int round = 0; remaining > 0; ++round) {
-      if (round > 64 + n) { rc = DZN_E_INVALID; goto done; }   // cannot happen: every batch completes >= 1 merge
+      if (round > 64 + n) { rc = DZN_E_INVALID; goto done; }   // cannot happen: every batch completes >= 1 merge or stops
       // surplus launches return at once but still cost a kernel boundary each: size the batch for the expected rescans
       // (1.1-1.3 launches per merge) and let the next round finish the rest
       const int batch = remaining + remaining / 8 + 32;
       for (int i = 0; i < batch; ++i, ++launched)
-        hipLaunchKernelGGL(step2_kernel, dim3(nblk), dim3(LB_BLK), 0, s, D, n, l1a, l2a, n1a, n2a, fla, size, cid, Z, st2, rec2,
-                           part2, (int)(launched & 1));
+        hipLaunchKernelGGL(step2_kernel<RULE>, dim3(nblk), dim3(LB_BLK), 0, s, D, n, l1a, l2a, n1a, n2a, fla, size, cid, Z, st2,
+                           rec2, part2, (int)(launched & 1), threshold);
       LCHK(hipGetLastError());
       StepState hs;
       LCHK(hipMemcpyAsync(&hs, st2 + (launched & 1), sizeof(StepState), hipMemcpyDeviceToHost, s));
       LCHK(hipStreamSynchronize(s));
       if (hs.kind == STEP_FAIL) { rc = DZN_E_INVALID; goto done; }   // non-finite distances
-      remaining = hs.kind == STEP_DONE ? 0 : n - 1 - hs.k;
+      remaining = hs.kind == STEP_DONE ? 0 : n - 1 - hs.k;           // (RULE_COMPLETE: also the stop at the threshold)
+      merges = hs.k;
+      if (remaining == 0 && RULE == RULE_COMPLETE) {
+        g_link_stats.launches = launched;
+        g_link_stats.merges = hs.k;
+        g_link_stats.rescans = hs.pad;
+      }
       if (remaining == 0 && getenv("DZN_LINKAGE_DEBUG"))
-        fprintf(stderr, "linkage[two neighbours]: n %d, %lld launches in %d batches, %d rescans, loop %.1f ms\n", n,
-                (long long)launched, round + 1, hs.pad,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count());
+        fprintf(stderr, "linkage[two neighbours%s]: n %d, %lld launches in %d batches, %d rescans, loop %.1f ms, %d merges\n",
+                RULE == RULE_COMPLETE ? ", complete" : "", n, (long long)launched, round + 1, hs.pad,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count(), hs.k);
     }
   }
   LCHK(hipGetLastError());
-  LCHK(hipMemcpyAsync(h_Z, Z, (size_t)(n - 1) * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (RULE == RULE_CENTROID) merges = n - 1;
+  if (merges > 0) LCHK(hipMemcpyAsync(h_Z, Z, (size_t)merges * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (h_merges) *h_merges = merges;
 done:
   // the host vectors above (ones, ids) are sources of queued copies; an asynchronous fault of a step kernel or of the final
   // copy surfaces HERE, and h_Z is garbage then: it must not return DZN_OK
   if (hipStreamSynchronize(s) != hipSuccess && rc == DZN_OK) rc = DZN_E_HIP;
+  if (RULE == RULE_COMPLETE) {
+    g_link_stats.pdist_ms = 0.f;
+    if (rc == DZN_OK && timed && hipEventElapsedTime(&g_link_stats.pdist_ms, ev[0], ev[1]) != hipSuccess)
+      g_link_stats.pdist_ms = 0.f;
+  }
   return rc;
+}
+
+}  // namespace
+
+extern "C" int dzn_linkage_centroid(const float* h_emb, int32_t n, int32_t dim, double* h_Z, int32_t device) {
+  if (!h_emb || !h_Z || n < 2 || dim < 1) return DZN_E_INVALID;
+  return run_linkage<RULE_CENTROID>(h_emb, nullptr, n, dim, 0.0, h_Z, nullptr, device);
+}
+
+extern "C" int dzn_link_speakers(const float* h_emb, const int32_t* h_group, int32_t n, int32_t dim, double threshold,
+                                 double* h_Z, int32_t* h_merges, int32_t device) {
+  if (!h_emb || !h_group || !h_Z || !h_merges || n < 2 || dim < 1) return DZN_E_INVALID;
+  if (!(threshold > 0.0 && threshold <= 2.0)) return DZN_E_INVALID;      // (NaN compares false)
+  for (int64_t r = 0; r < n; ++r) {      // a row that is all zero or not finite has no direction: refused before any upload
+    const float* e = h_emb + r * dim;
+    bool any = false;
+    for (int c = 0; c < dim; ++c) {
+      if (!isfinite(e[c])) return DZN_E_INVALID;
+      any |= e[c] != 0.f;
+    }
+    if (!any) return DZN_E_INVALID;
+  }
+  return run_linkage<RULE_COMPLETE>(h_emb, h_group, n, dim, threshold, h_Z, h_merges, device);
+}
+
+extern "C" int dzn_link_speakers_last(int64_t* launches, int32_t* merges, int32_t* rescans, float* pdist_ms) {
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  if (launches) *launches = g_link_stats.launches;
+  if (merges) *merges = g_link_stats.merges;
+  if (rescans) *rescans = g_link_stats.rescans;
+  if (pdist_ms) *pdist_ms = g_link_stats.pdist_ms;
+  return DZN_OK;
 }
 
 // ---- cosine distances of every embedding to the cluster centroids (row f1: `cdist` of the assignment step) -------
@@ -703,21 +895,6 @@ done:
 // embeddings x 13 centroids at 4 h of audio is 0.24 G flop in float64 — the point is the 0.3-0.7 s scipy spends
 // converting and scanning 147 MB on one host core.
 namespace {
-
-__global__ __launch_bounds__(256) void row_norm_f32_kernel(const float* __restrict__ E, int n, int dim,
-                                                           double* __restrict__ nrm) {
-#pragma clang fp contract(off)
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= n) return;
-  const float* e = E + (int64_t)r * dim;
-  double s = 0.0;
-  for (int i = 0; i < dim; ++i) {
-    const double c = (double)e[i];
-    const double p = c * c;
-    s = s + p;
-  }
-  nrm[r] = sqrt(s);
-}
 
 __global__ __launch_bounds__(256) void row_norm_f64_kernel(const double* __restrict__ X, int n, int dim,
                                                            double* __restrict__ nrm) {

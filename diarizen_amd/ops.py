@@ -331,6 +331,37 @@ def linkage_centroid(emb, device: int = -1):
     return Z
 
 
+def link_speakers(emb, group, threshold: float, device: int = -1):
+    """Complete linkage of cosine distances under a cannot-link constraint, cut at `threshold`, on the device (csrc/linkage.hip,
+    dzn_link_speakers): emb = host float32 [n, dim], group = int32 [n] (rows of one group never merge), threshold a cosine
+    distance in (0, 2].  Returns (Z_prefix float64 [m, 4], m): exactly the merges of height <= threshold of
+        y = pdist(emb.astype(float64), "cosine"); y[same group] = 4.0; linkage(y, "complete")
+    in scipy's order.  Bad shapes or arguments raise DznError (the library's DZN_E_INVALID), a matrix that does not fit raises
+    MemoryError."""
+    import numpy as np
+    lib = _lib.load()
+    e = np.ascontiguousarray(emb, dtype=np.float32)
+    g = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+    if e.ndim != 2 or g.shape[0] != e.shape[0]:
+        raise ValueError(f"link_speakers: emb is [n, dim] and group [n], not {e.shape} and {g.shape}")
+    n, dim = e.shape
+    Z = np.empty((max(n - 1, 1), 4), dtype=np.float64)
+    m = C.c_int32(0)
+    check(lib.dzn_link_speakers(e.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), n, dim, float(threshold),
+                                Z.ctypes.data_as(C.c_void_p), C.byref(m), device), what="dzn_link_speakers")
+    return Z[:m.value].copy(), int(m.value)
+
+
+def link_speakers_last():
+    """diagnostics of the last link_speakers call of the process: {launches, merges, rescans, pdist_ms} (the step launches
+    queued, surplus ones included; the distance kernel alone by HIP events)"""
+    lib = _lib.load()
+    launches, merges, rescans, ms = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_float(0.0)
+    check(lib.dzn_link_speakers_last(C.byref(launches), C.byref(merges), C.byref(rescans), C.byref(ms)),
+          what="dzn_link_speakers_last")
+    return {"launches": launches.value, "merges": merges.value, "rescans": rescans.value, "pdist_ms": ms.value}
+
+
 def cdist_cosine(emb, centroids, device: int = -1):
     """scipy.spatial.distance.cdist(emb, centroids, "cosine") on the device in scipy's float64 operation order
     (csrc/linkage.hip): emb = host float32 [n, dim], centroids [k, dim] -> float64 [n, k]."""

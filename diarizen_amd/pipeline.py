@@ -494,7 +494,8 @@ class DiariZenPipeline:
         return _stream_live(self, chunks, sess_name, **kw)
 
     # ------------------------------------------------------------------ many recordings
-    def diarize_many(self, recordings, sess_names=None, overlap: bool = True, return_scores: bool = False):
+    def diarize_many(self, recordings, sess_names=None, overlap: bool = True, return_scores: bool = False,
+                     return_embeddings: bool = False):
         """The loop the reference's entry points run over a corpus (diarizen/pipelines/inference.py:365-368: `for audio_file in
         audio_f: diarizen_pipeline(audio_file, sess_name=...)`; recipes/diar_ssl/infer_avg.py:334-338), as a generator of
         (sess_name, Annotation) in input order, with the SAME result per recording as `__call__`.
@@ -506,7 +507,9 @@ class DiariZenPipeline:
         waits for the worker (its seg / emb arrays: a few MB per hour of audio).  With torch.distributed initialised every
         rank calls this with the same list; only rank 0 yields Annotations (the others yield None), as in `__call__`.
         return_scores=True (one device only): (sess_name, Annotation, scores) with the scores of `__call__(return_scores=True)`;
-        the soft scores of a recording stay on the device and travel with its pending host stage."""
+        the soft scores of a recording stay on the device and travel with its pending host stage.
+        return_embeddings=True: the cluster centroids f32 [K, 256] of `__call__(return_embeddings=True)` are appended to every
+        tuple, after the scores when both are asked for (ranks other than 0: None, as the Annotation)."""
         import time
         from concurrent.futures import ThreadPoolExecutor
         from . import dist as dz_dist
@@ -520,14 +523,20 @@ class DiariZenPipeline:
             raise RuntimeError(self._ONE_DEVICE % ("diarize_many(return_scores=True)", dz_dist.world_size()))
         if not overlap:
             for rec, name in zip(recordings, sess_names):
-                yield (name, *self(rec, sess_name=name, return_scores=True)) if return_scores else (name, self(rec, sess_name=name))
+                if return_scores or return_embeddings:
+                    yield (name, *self(rec, sess_name=name, return_scores=return_scores, return_embeddings=return_embeddings))
+                else:
+                    yield (name, self(rec, sess_name=name))
             return
         rank0 = dz_dist.rank() == 0
+
+        want = {"return_embeddings": True} if return_embeddings else {}      # (a call without the flag is the parent's call)
 
         def host(seg, emb, name, soft=None, n=0):
             t = time.perf_counter()
             if soft is None:
-                res = ann = self.host_stage(seg, emb, name)
+                res = self.host_stage(seg, emb, name, **want)
+                ann = res[0] if return_embeddings else res
             else:                                        # the crop rule of __call__
                 r = self._runner
                 grid, _, T = _frame_grid(seg.shape[0], seg.shape[1], self.chunks_window(),
@@ -535,7 +544,7 @@ class DiariZenPipeline:
                 if window_plan(n, r.window, r.step)[1]:
                     T = crop_end(T, grid, n / self.segmentation_model.sample_rate)
                 with torch.cuda.device(self.device):
-                    res = self.host_stage(seg, emb, name, soft=soft, num_frames=T)
+                    res = self.host_stage(seg, emb, name, soft=soft, num_frames=T, **want)
                 ann = res[0]
             if self.rttm_out_dir is not None:
                 assert name is not None
@@ -551,7 +560,8 @@ class DiariZenPipeline:
         self.corpus_timings = []
         pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dzn-host-stage")
         loader = ThreadPoolExecutor(max_workers=1, thread_name_prefix="dzn-decode")      # recording i+1 is decoded beside device stage i
-        pending = None                                   # (future, name, load_s, device_s, audio_s)
+        pending = None                                   # (future, name, load_s, device_s, audio_s, what a rank without one yields)
+        blank = (None,) * (1 + int(return_scores) + int(return_embeddings)) if return_embeddings else None
         try:
             nxt = loader.submit(load, recordings[0]) if recordings else None
             for i, name in enumerate(sess_names):
@@ -569,7 +579,7 @@ class DiariZenPipeline:
                     yield self._collect(pending)
                 fut = pool.submit(host, seg, emb, name, soft, n) if rank0 else None
                 del soft
-                pending = (fut, name, load_s, t2 - t1, n / self.segmentation_model.sample_rate)
+                pending = (fut, name, load_s, t2 - t1, n / self.segmentation_model.sample_rate, blank)
             if pending is not None:
                 yield self._collect(pending)
         finally:
@@ -577,11 +587,45 @@ class DiariZenPipeline:
             pool.shutdown(wait=True)
 
     def _collect(self, pending):
-        fut, name, load_s, device_s, audio_s = pending
-        res, host_s = fut.result() if fut is not None else (None, 0.0)
+        fut, name, load_s, device_s, audio_s, blank = pending
+        res, host_s = fut.result() if fut is not None else (blank, 0.0)
         self.timings = {"load_s": load_s, "device_s": device_s, "host_s": host_s, "audio_s": audio_s}
         self.corpus_timings.append(dict(self.timings, sess_name=name))
         return (name, *res) if isinstance(res, tuple) else (name, res)
+
+    def link_many(self, recordings, threshold: float, sess_names=None, fmt: str = "spk{:04d}", backend: str = "auto"):
+        """Diarize a corpus and link its speakers across recordings (linking.SpeakerLinker; no reference counterpart):
+        `diarize_many(return_embeddings=True)`, every recording's centroids into ONE linker, one complete-linkage clustering
+        under the rule that two labels of one recording are different people, cut at `threshold` — a cosine distance in (0, 2],
+        required, no default (nothing here can calibrate one).  -> ({sess_name: Annotation whose labels are the corpus-wide
+        names fmt.format(identity)}, linking.SpeakerLinks).  Session names must be distinct.  With rttm_out_dir set the
+        per-recording RTTM files are rewritten with the global names after linking.  In a sharded run rank 0 has the result;
+        other ranks run the device stages and return ({}, None)."""
+        from . import dist as dz_dist
+        from .linking import SpeakerLinker
+        SpeakerLinker(threshold, backend=backend)            # a bad threshold or backend is refused before any device work
+        annotations, voiceprints = {}, {}
+        for name, annotation, centroids in self.diarize_many(recordings, sess_names=sess_names, return_embeddings=True):
+            if annotation is None:                           # a rank other than 0
+                continue
+            if name is None:
+                raise ValueError("link_many: every recording needs a session name")
+            if name in annotations:
+                raise ValueError(f"link_many: session name {name!r} twice")
+            annotations[name], voiceprints[name] = annotation, np.asarray(centroids, dtype=np.float32)
+        if dz_dist.rank() != 0:
+            return {}, None
+        dims = [v.shape[1] for v in voiceprints.values() if v.ndim == 2 and v.shape[0]]
+        linker = SpeakerLinker(threshold, dim=dims[0] if dims else 256, device=self.device, backend=backend)
+        for name, v in voiceprints.items():
+            linker.add(name, v)
+        links = linker.link()
+        out = {name: links.relabel(name, ann, fmt) for name, ann in annotations.items()}
+        if self.rttm_out_dir is not None:
+            for name, ann in out.items():
+                with open(os.path.join(self.rttm_out_dir, name + ".rttm"), "w") as f:
+                    f.write(ann.to_rttm())
+        return out, links
 
     def _open(self, in_wav):
         """decode (or, in a sharded run, lazily open) one recording: the first lines of `__call__`"""

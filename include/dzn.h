@@ -452,6 +452,28 @@ int dzn_gallery_rows(const void* g, int64_t* rows);
 int dzn_gallery_last_launch_ms(const void* g, float* ms, float* merge_ms);
 int dzn_gallery_destroy(void* g);
 
+/* Linking speakers across recordings (csrc/linkage.hip): complete-linkage agglomerative clustering of the
+ * voiceprints of a whole corpus under a cannot-link constraint, cut at a distance threshold.  No reference counterpart: the
+ * reference's labels restart at 0 in every recording.  The entry does what scipy does with
+ *     y = pdist(E.astype(float64), "cosine");  y[pairs with h_group[i] == h_group[j]] = 4.0;  Z = linkage(y, "complete")
+ * stopped early: the first *h_merges rows of h_Z are exactly the merges of height <= threshold, in scipy's order and with
+ * scipy's ids and sizes (no exact ties among the allowed distances assumed); rows past *h_merges are unspecified.
+ *   distances  float64 from the float32 rows: row norms as dzn_cdist_cosine, 1 - clip(dot / (|u||v|)), in-order sums;
+ *              |d - true| <= 2 (dim + 8) 2^-53.  Two rows of one group are set to 4.0: finite, above every cosine distance
+ *              (<= 2), so the pair can never merge at a threshold in (0, 2] — and with complete linkage neither can any two
+ *              clusters that hold such a pair.
+ *   loop       the step loop of dzn_linkage_centroid with the update v = max(d_xi, d_yi); it ends at the first closest pair
+ *              above the threshold.  The n x n float64 matrix lives in the host stage's arena (8 n^2 bytes -> DZN_E_NOMEM when
+ *              it does not fit); same stream, mutex and blocking behaviour as dzn_linkage_centroid.
+ * HOST pointers: h_emb f32 [n, dim], h_group i32 [n] (any integers; equal = same recording), h_Z f64 [n - 1, 4].
+ * DZN_E_INVALID, nothing written: null pointers, n < 2, dim < 1, threshold not in (0, 2], a row that is all zero or not finite
+ * (checked on the host before any upload).
+ *   dzn_link_speakers_last  diagnostics of the last call of the process (any pointer may be NULL): step launches queued
+ *                           (surplus ones included), merges, row rescans, HIP-event time of the distance kernel alone */
+int dzn_link_speakers(const float* h_emb, const int32_t* h_group, int32_t n, int32_t dim, double threshold, double* h_Z,
+                      int32_t* h_merges, int32_t device);
+int dzn_link_speakers_last(int64_t* launches, int32_t* merges, int32_t* rescans, float* pdist_ms);
+
 /* Row f3, audio ingest: native FLAC decoder (csrc/flac.cpp, host code; the reference reads whatever torchaudio.load does,
  * diarizen/pipelines/inference.py:127 — WAV is parsed in diarizen_amd/audio.py, FLAC here).  Frame-header CRC-8 and frame
  * CRC-16 are verified while decoding; the caller checks the STREAMINFO MD5 (audio.load_flac does).
