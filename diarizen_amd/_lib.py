@@ -222,6 +222,12 @@ def load() -> C.CDLL:
     sig("dzn_gallery_rows", i32, [vp, C.POINTER(i64)])
     sig("dzn_gallery_last_launch_ms", i32, [vp, C.POINTER(f32), C.POINTER(f32)])
     sig("dzn_gallery_destroy", i32, [vp])
+    sig("dzn_registry_create", i32, [i32, i32, i64, C.POINTER(C.c_void_p)])
+    sig("dzn_registry_append", i32, [vp, vp, i64, vp])
+    sig("dzn_registry_match", i32, [vp, vp, i32, C.c_double, i32, vp, vp, vp, C.POINTER(i32), vp])
+    sig("dzn_registry_rows", i32, [vp, C.POINTER(i64), C.POINTER(i64)])
+    sig("dzn_registry_last_launch_ms", i32, [vp, C.POINTER(f32)])
+    sig("dzn_registry_destroy", i32, [vp])
     sig("dzn_op_gemm", i32, [C.POINTER(DznGemmDesc), vp])
     sig("dzn_op_split_weights", i32, [vp, i64, i32, i64, vp, vp])
     sig("dzn_op_split_weights_h2", i32, [vp, i64, i32, i64, vp, vp, vp])
@@ -301,6 +307,8 @@ EXPORTED = [
     "dzn_flac_info", "dzn_flac_decode", "dzn_resample", "dzn_resample_tile", "dzn_decode", "dzn_beamform_delays", "dzn_beamform_sum", "dzn_beamform_tile", "dzn_decode_planar", "dzn_beamform_track", "dzn_beamform_feed", "dzn_ingest_many", "dzn_beamform_many", "dzn_gather_windows", "dzn_vbx_create", "dzn_vbx_stats", "dzn_vbx_estep", "dzn_vbx_gamma", "dzn_vbx_destroy",
     "dzn_gallery_create", "dzn_gallery_put", "dzn_gallery_drop", "dzn_gallery_search", "dzn_gallery_geometry", "dzn_gallery_rows",
     "dzn_gallery_last_launch_ms", "dzn_gallery_destroy",
+    "dzn_registry_create", "dzn_registry_append", "dzn_registry_match", "dzn_registry_rows", "dzn_registry_last_launch_ms",
+    "dzn_registry_destroy",
     "dzn_op_gemm", "dzn_op_split_weights", "dzn_op_split_weights_h2", "dzn_op_split_weights_mx", "dzn_op_set_gemm_mx_cfg", "dzn_checked_status", "dzn_op_set_gemm_cfg", "dzn_op_amax", "dzn_op_conv3x3_c32", "dzn_op_conv3x3_c32_h2", "dzn_op_resblock32_fused", "dzn_op_resblock_ws", "dzn_op_set_resblock_np", "dzn_op_conv3x3_c32_ex", "dzn_op_resblock32_fused_ex", "dzn_op_resblock_ws_ex", "dzn_op_set_attention_noskip", "dzn_op_split_rows", "dzn_op_layernorm", "dzn_op_row_stats", "dzn_op_gate", "dzn_op_gate_stats", "dzn_op_gate_heads", "dzn_op_stats_finalize", "dzn_op_attention", "dzn_op_attention_h2", "dzn_op_attention_planes", "dzn_op_set_attention_qb", "dzn_op_set_attention_prefetch",
     "dzn_profile_enable", "dzn_profile_collect", "dzn_profile_reserve", "dzn_op_relpos_bucket",
     "dzn_op_glu_dwconv", "dzn_op_classify", "dzn_op_groupnorm_gelu", "dzn_op_gn_stats_floats", "dzn_op_pad_rows", "dzn_op_ws_accum",

@@ -52,4 +52,7 @@
 //            0x88x reseg (0x880 decision read, 0x881 reference read, 0x882 LDS word, 0x883 count write) — its collector
 //            dzn_checked_collect_reseg is read by tests/test_resegmentation_gpu.py, dzn_checked_status does not sum it;
 //            0x89x linkage, pdist_cosine_group_kernel (0x890 LDS stage index, 0x891 embedding read, 0x892 norm / group read,
-//            0x893 matrix write) — its collector dzn_checked_collect_linkage is read by tests/test_linking_gpu.py the same way
+//            0x893 matrix write) — its collector dzn_checked_collect_linkage is read by tests/test_linking_gpu.py the same way;
+//            0x8ax registry (0x8a0 chunk of the member index, 0x8a1 stored row number, 0x8a2 segment id, 0x8a3 row read,
+//            0x8a4 LDS tile word, 0x8a5 segment-maximum write, 0x8a6 segment range of a column, 0x8a7 table write,
+//            0x8a8 triple slot) — its collector dzn_checked_collect_registry is read by tests/test_registry_gpu.py the same way

@@ -488,6 +488,83 @@ class GalleryState:
             pass
 
 
+class Registry:
+    """a device-resident, growing set of speaker identities and the match of a recording's voiceprints against it
+    (csrc/registry.hip): host arrays in, host arrays out; see diarizen_amd/registry.py:SpeakerRegistry for the rule that
+    drives it."""
+
+    def __init__(self, dim: int, capacity: int, device: int = -1):
+        import numpy as np
+        self.np, self.lib = np, _lib.load()
+        self.dim, self.capacity = int(dim), int(capacity)
+        self.state = C.c_void_p()
+        check(self.lib.dzn_registry_create(device, self.dim, self.capacity, C.byref(self.state)), what="dzn_registry_create")
+
+    def _counts(self):
+        n, i = C.c_int64(0), C.c_int64(0)
+        check(self.lib.dzn_registry_rows(self.state, C.byref(n), C.byref(i)), what="dzn_registry_rows")
+        return n.value, i.value
+
+    @property
+    def rows(self) -> int:
+        return self._counts()[0]
+
+    @property
+    def identities(self) -> int:
+        """the highest identity number appended + 1: the width of the dense table"""
+        return self._counts()[1]
+
+    def append(self, vecs, identity) -> None:
+        np = self.np
+        v = np.ascontiguousarray(vecs, dtype=np.float32).reshape(-1, self.dim)
+        i = np.ascontiguousarray(identity, dtype=np.int32).reshape(-1)
+        if len(i) != len(v):
+            raise ValueError(f"Registry.append: one identity per row ({len(v)} rows, {len(i)} identities)")
+        check(self.lib.dzn_registry_append(self.state, v.ctypes.data_as(C.c_void_p), len(v), i.ctypes.data_as(C.c_void_p)),
+              what="dzn_registry_append")
+
+    def match(self, queries, threshold: float, dense: bool = False, max_out: int = 0):
+        """queries f32 [Q, dim] -> (k i32 [m], identity i32 [m], d f64 [m]): the entries <= threshold of the table
+        D[k, i] = max over the rows of identity i of the cosine distance to query k, sorted by (k, i)  (+ the table itself,
+        f64 [Q, identities], with dense=True)"""
+        np = self.np
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        Q = q.shape[0]
+        width = self.identities
+        table = np.empty((Q, width), dtype=np.float64) if dense else None
+        # room for every entry of the table up to 2^16 triples (1 MB): a second sweep only beyond that, or under a small max_out
+        room = int(max_out) if max_out > 0 else max(1, min(Q * width, 1 << 16))
+        while True:
+            k, i, d = np.empty(room, dtype=np.int32), np.empty(room, dtype=np.int32), np.empty(room, dtype=np.float64)
+            m = C.c_int32(0)
+            check(self.lib.dzn_registry_match(self.state, q.ctypes.data_as(C.c_void_p), Q, float(threshold), room,
+                                              k.ctypes.data_as(C.c_void_p), i.ctypes.data_as(C.c_void_p),
+                                              d.ctypes.data_as(C.c_void_p), C.byref(m),
+                                              table.ctypes.data_as(C.c_void_p) if dense else None), what="dzn_registry_match")
+            if m.value <= room:
+                break
+            room = m.value              # more entries than room: once more with room for all
+        out = (k[:m.value].copy(), i[:m.value].copy(), d[:m.value].copy())
+        return out + (table,) if dense else out
+
+    def last_launch_ms(self) -> float:
+        """HIP-event time of the last match's launches, in ms"""
+        ms = C.c_float(0.0)
+        check(self.lib.dzn_registry_last_launch_ms(self.state, C.byref(ms)), what="dzn_registry_last_launch_ms")
+        return ms.value
+
+    def close(self):
+        if self.state:
+            self.lib.dzn_registry_destroy(self.state)
+            self.state = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # pragma: no cover
+            pass
+
+
 def layernorm(x, gamma, beta, C_true=None, eps=1e-5, gelu=False, out=None):
     lib = _lib.load()
     rows, ld = x.shape[0], x.stride(0)

@@ -627,6 +627,35 @@ class DiariZenPipeline:
                     f.write(ann.to_rttm())
         return out, links
 
+    def link_into(self, registry, recordings, sess_names=None, fmt: str = "spk{:04d}"):
+        """Diarize a corpus and link every recording into a growing registry AS IT FINISHES (registry.SpeakerRegistry; no
+        reference counterpart): a generator over `diarize_many(return_embeddings=True)` of (sess_name, Annotation whose labels
+        are the corpus-wide names fmt.format(identity), {label: identity}).  Unlike `link_many` nothing waits for the end of the
+        corpus, and the registry may already hold earlier corpora: identity numbers never change.  Session names must be given
+        and new to the registry.  With rttm_out_dir set each recording's RTTM file is rewritten with the global names.  In a
+        sharded run rank 0 yields; other ranks run the device stages and yield nothing."""
+        from .identification import relabel
+        if sess_names is not None:                           # refused before any device work
+            sess_names = list(sess_names)
+            if any(name is None for name in sess_names):
+                raise ValueError("link_into: every recording needs a session name")
+            if len(set(sess_names)) != len(sess_names):
+                raise ValueError("link_into: a session name twice")
+            known = [name for name in sess_names if name in registry]
+            if known:
+                raise ValueError(f"link_into: the registry already holds {known!r}")
+        for name, annotation, centroids in self.diarize_many(recordings, sess_names=sess_names, return_embeddings=True):
+            if annotation is None:                           # a rank other than 0
+                continue
+            if name is None:
+                raise ValueError("link_into: every recording needs a session name")
+            ids = registry.add(name, np.asarray(centroids, dtype=np.float32))
+            out = relabel(annotation, {label: fmt.format(i) for label, i in ids.items()})
+            if self.rttm_out_dir is not None:
+                with open(os.path.join(self.rttm_out_dir, name + ".rttm"), "w") as f:
+                    f.write(out.to_rttm())
+            yield name, out, ids
+
     def _open(self, in_wav):
         """decode (or, in a sharded run, lazily open) one recording: the first lines of `__call__`"""
         from . import dist as dz_dist

@@ -474,6 +474,41 @@ int dzn_link_speakers(const float* h_emb, const int32_t* h_group, int32_t n, int
                       int32_t* h_merges, int32_t device);
 int dzn_link_speakers_last(int64_t* launches, int32_t* merges, int32_t* rescans, float* pdist_ms);
 
+/* A speaker registry (csrc/registry.hip): the incremental counterpart of dzn_link_speakers.  The voiceprints
+ * linked so far stay on the device, every stored row under an identity number that the caller chose; the Q voiceprints of a new
+ * recording are matched against all of them in one sweep:
+ *     D[k][i] = max over the stored rows r with identity i of cosdist(q_k, E_r)
+ * — the complete-linkage distance of query k to identity i — and of that table the entries <= threshold come back as
+ * (k, i, d) triples.  The assignment rule that continues complete linkage from them is the caller's (diarizen_amd/registry.py).
+ *   storage    fp32 [capacity, dim] as given (dim a multiple of 4, 4 .. 1024) and the float64 row norms: the registry's own
+ *              allocation, made at create and freed at destroy; dzn_host_workspace_release leaves it alone.  Identity numbers
+ *              are any int32 in [0, 2^31 - 2]; numbers without a stored row are allowed (I = the highest number + 1).
+ *   distances  float64 from the float32 rows, exactly dzn_cdist_cosine's expression: row norms with in-order sums,
+ *              1 - clip(dot / (|q||e|)), one in-order sum over dim per (query, row); |d - true| <= 2 (dim + 8) 2^-53.  The result
+ *              does not depend on the launch geometry, on Q or on the order of earlier calls (max is order-free; no float atomics).
+ *   append     count rows with their identity numbers.  DZN_E_NOMEM when they do not fit the capacity, DZN_E_INVALID for a
+ *              negative number or a row that is all zero or not finite; a refused call stores nothing.  count = 0 is a no-op.
+ *   match      h_queries f32 [Q, dim] -> *h_count = the number of entries <= threshold, and the first min(*h_count, max_out) of
+ *              them in h_k / h_i (int32) / h_d (float64), sorted by (k, i).  *h_count > max_out: call again with room for all
+ *              (which of them were returned is unspecified then).  h_dense (optional) receives the whole table, float64 [Q, I],
+ *              +inf in the column of a number that holds no row.  Q = 0 or an empty registry: *h_count = 0, nothing launched.
+ *              DZN_E_INVALID, nothing written: null pointers, Q < 0, max_out < 0, threshold not in (0, 2], a query that is all
+ *              zero or not finite.
+ * HOST pointers, blocking calls on the host stage's stream and arena (as dzn_cdist_cosine: callable from a second thread beside
+ * the engine).
+ * One append / match / rows / last_launch_ms of a handle runs at a time (they may be called from several threads); destroy waits
+ * for a call in flight, and no call on the handle may begin once destroy has.  capacity: at most 2 114 445 312 rows (the
+ * segment ids of the member index are int32).
+ *   dzn_registry_rows            stored rows; identities (optional): I
+ *   dzn_registry_last_launch_ms  HIP-event time of the last match's launches (sweeps + reduce, without copies and index upload) */
+int dzn_registry_create(int32_t device, int32_t dim, int64_t capacity, void** out);
+int dzn_registry_append(void* r, const float* h_vecs, int64_t count, const int32_t* h_identity);
+int dzn_registry_match(void* r, const float* h_queries, int32_t Q, double threshold, int32_t max_out, int32_t* h_k, int32_t* h_i,
+                       double* h_d, int32_t* h_count, double* h_dense);
+int dzn_registry_rows(const void* r, int64_t* rows, int64_t* identities);
+int dzn_registry_last_launch_ms(const void* r, float* ms);
+int dzn_registry_destroy(void* r);
+
 /* Row f3, audio ingest: native FLAC decoder (csrc/flac.cpp, host code; the reference reads whatever torchaudio.load does,
  * diarizen/pipelines/inference.py:127 — WAV is parsed in diarizen_amd/audio.py, FLAC here).  Frame-header CRC-8 and frame
  * CRC-16 are verified while decoding; the caller checks the STREAMINFO MD5 (audio.load_flac does).

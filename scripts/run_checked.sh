@@ -36,5 +36,8 @@ python -m pytest tests/test_live_scores_gpu.py -m gpu -q -x 2>&1 | tail -3
 # the resegmentation matching (reseg.hip, ids 0x88x: decision / reference reads, LDS words, the count write); its word is read by
 # the test itself (dzn_checked_collect_reseg), not by dzn_checked_status
 python -m pytest tests/test_resegmentation_gpu.py -m gpu -q -x 2>&1 | tail -3
+# the speaker registry (registry.hip, ids 0x8ax: member index, row reads, LDS tile, segment and table writes); its word is read
+# by the test itself (dzn_checked_collect_registry)
+python -m pytest tests/test_registry_gpu.py -m gpu -q -x 2>&1 | tail -3
 cat gpurun_out/checked_build_status.txt >> gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
 tail -6 gpurun_out/${DZN_CHECKED_LOG:-r6_checked_build.log}
