@@ -295,6 +295,11 @@ def load() -> C.CDLL:
     sig("dzn_op_stats_pool", i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp])
     sig("dzn_op_window_active", i32, [vp, i32, i32, vp, vp])
     sig("dzn_op_compact_active", i32, [vp, i32, vp, vp, vp, vp])
+    # entry points younger than the libraries an A/B run selects through DZN_HIP_LIB: declared where the library has them
+    if hasattr(lib, "dzn_op_posconv_resident"):
+        sig("dzn_op_pad_rows_split2", i32, [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp])
+        sig("dzn_op_posconv_resident", i32, [C.POINTER(DznGemmDesc), i32, i32, i32, vp])
+        sig("dzn_op_posconv_resident_fits", i32, [i32, i32, i32])
     _LIB = lib
     return lib
 
@@ -314,7 +319,7 @@ EXPORTED = [
     "dzn_op_glu_dwconv", "dzn_op_classify", "dzn_op_groupnorm_gelu", "dzn_op_gn_stats_floats", "dzn_op_pad_rows", "dzn_op_ws_accum",
     "dzn_op_ws_sum", "dzn_op_col_scale", "dzn_op_layernorm_t", "dzn_op_wave_stats", "dzn_op_frame_prep", "dzn_op_power",
     "dzn_op_log_cmn", "dzn_op_log_cmn_gather", "dzn_op_stem_conv", "dzn_op_stats_pool", "dzn_op_window_active",
-    "dzn_op_compact_active",
+    "dzn_op_compact_active", "dzn_op_pad_rows_split2", "dzn_op_posconv_resident", "dzn_op_posconv_resident_fits",
     "dzn_op_conv0_lnq", "dzn_op_conv0", "dzn_op_split_weights_h2_frag", "dzn_op_conv01_fused",
 ]
 

@@ -109,6 +109,10 @@ int launch_gemm(const dzn_gemm_desc& d, hipStream_t s);
 int gemm_stat_partials_last();   // partials per row left by this thread's last launch_gemm with stat_partial set (gemm_launch.h)
 int launch_gemm_split(const dzn_gemm_desc& d, hipStream_t s); // gemm_split.hip: fp32 via 3-way bf16 split
 int launch_gemm_split_pre(const dzn_gemm_desc& d, hipStream_t s);  // gemm_split_pre.hip: A pre-split planes
+// posconv_resident.hip: the positional conv on resident plane rows (d as for launch_gemm_split_pre with two fp16 planes, 64 plane
+// channels per group, B windows of L rows, Kc taps); _fits: whether the rows a tile's taps touch fit LDS for that shape
+bool posconv_resident_fits(int B, int L, int Kc);
+int launch_posconv_resident(const dzn_gemm_desc& d, int B, int L, int Kc, hipStream_t s);
 int launch_pad_rows_split3(const float* x, void* planes, int64_t plane_stride, int B, int L, int Lp, int pad, int D,
                            hipStream_t st, int cg = 0, int cgp = 0);   // D = plane row width (groups padded from cg to cgp channels)
 int launch_pad_rows_split2(const float* x, void* planes, int64_t plane_stride, int B, int L, int Lp, int pad, int D,

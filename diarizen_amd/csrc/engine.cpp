@@ -152,6 +152,7 @@ struct Switches {
   bool emb_skip = true;
   bool fuse_resblock = true;    // (r4) stride-1 BasicBlocks in the two-term fp16 modes: both convolutions in one kernel
   bool fuse_shortcut = true;    // off: the shortcut of a down-sampling block stays its own launch
+  bool posconv_resident = true; // off: the positional conv stays on the generic pre-split contraction
   int resblock_ws = 2;          // bit mask: 1 = 32-plane blocks, 2 = 64-plane blocks on the producer / consumer form
   // DZN_PREC_F16 (reduced precision): which contraction classes keep two fp16 terms (F16Class bit mask; bit 14 = the
   // ResNet stages 2-4), and whether LayerNorm-folded single-term contractions subtract the row mean BEFORE rounding
@@ -188,6 +189,7 @@ Switches read_switches() {
   s.emb_skip = !getenv("DZN_EMB_NO_SKIP");                  // =1: windows without an active speaker go through the trunk too
   s.fuse_resblock = !getenv("DZN_NO_RESBLOCK_FUSION");      // =1: the per-conv kernels for the stride-1 BasicBlocks
   s.fuse_shortcut = !getenv("DZN_NO_SHORTCUT_FUSION");      // =1: the 1x1 shortcut of a down-sampling block as its own launch
+  s.posconv_resident = !getenv("DZN_NO_POSCONV_RESIDENT");  // =1: the positional conv stays on the generic pre-split contraction (f32h)
   if (const char* e = getenv("DZN_RESBLOCK_WS")) s.resblock_ws = atoi(e);                      // which fused blocks take the producer / consumer form
   if (const char* e = getenv("DZN_F16_KEEP2")) s.f16_keep2 = (unsigned)strtoul(e, nullptr, 0); // reduced mode: classes with two fp16 terms
   if (const char* e = getenv("DZN_F16_MX")) s.f16_mx = (unsigned)strtoul(e, nullptr, 0);       // reduced mode: classes with fp8 cross terms
@@ -228,6 +230,7 @@ struct dzn_handle {
   Lin posconv;
   int pos_rowD = 0;               // row width the row-offset table of the positional conv was built for
   int pos_cgp = 0;                // channels per positional-conv group in the pre-split planes (cg rounded up to 32)
+  bool posconv_resident = false;  // the positional conv takes posconv_resident.hip where a call's span fits LDS (fixed at create)
   std::vector<EncLayer> layers;
   std::vector<float> rel_embed;  // [num_buckets, H] host
   std::vector<float> wsum_w;
@@ -571,6 +574,7 @@ void finalize_seg(H* h) {
     // runs on the fp16 / bf16 planes instead of the fp32 MFMA fallback (r2: 15 % of BASELINE configs[1])
     const int cgp = prec_is_split(c.precision) ? round_up(cg, 32) : cg;
     h->pos_cgp = cgp;
+    h->posconv_resident = h->sw.posconv_resident && c.precision == DZN_PREC_F32_H2 && cgp == 64;
     std::vector<float> wp((size_t)D * K * cgp, 0.f);
     for (int o = 0; o < D; ++o)
       for (int ii = 0; ii < cg; ++ii)
@@ -1317,7 +1321,14 @@ void seg_project(const SegCall& s, float* feat) {
     if (pre2) d.a_amax = s.am(dzn_handle::AM_XPAD);
   }
   d.c_amax = s.am(dzn_handle::AM_X);
-  s.gemm(d, CLS_POSCONV);
+  // f32h planes of 64 channels per group: the Toeplitz-resident kernel (posconv_resident.hip) when the rows a tile's taps touch
+  // fit LDS at this (B, L) — a shape rule like the contraction families' tile rules; everything else keeps the generic kernel
+  if (h->posconv_resident && pre2 && tabled && posconv_resident_fits(B, L, Kc)) {
+    d.amax_unit = L;
+    chk(launch_posconv_resident(d, B, L, Kc, st), "posconv_resident");
+  } else {
+    s.gemm(d, CLS_POSCONV);
+  }
   if (!c.layer_norm_first) ln_t(h->x, D, h->x, D, h->enc_ln, ML, D, 0, st, nullptr, s.am(dzn_handle::AM_X), L);
 }
 

@@ -759,6 +759,56 @@ def pad_rows(x, xpad, *, B, L, Lp, pad, D):
     return xpad
 
 
+def pad_rows_split2(x, amax, *, B, L, taps, G, cg, cgp=64):
+    """x fp32 [B * L, G * cg], amax f32 [B] (>= the windows' |max|) -> (planes int16 [2, B * (L + taps), G * cgp], snapshot f32 [B]):
+    the fp16 two-term planes of the zero-padded copy the positional conv reads (dzn_op_pad_rows_split2)"""
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == B * L * G * cg
+    Lp = L + taps
+    planes = torch.empty((2, B * Lp, G * cgp), device=x.device, dtype=torch.int16)
+    snap = torch.empty((B,), device=x.device, dtype=torch.float32)
+    check(lib.dzn_op_pad_rows_split2(_p(x), _p(planes), planes.stride(0), int(B), int(L), int(Lp), int(taps // 2), int(G * cgp),
+                                     _p(amax), _p(snap), int(cg), int(cgp), _stream()), what="dzn_op_pad_rows_split2")
+    return planes, snap
+
+
+def posconv_resident_fits(B, L, taps) -> bool:
+    return bool(_lib.load().dzn_op_posconv_resident_fits(int(B), int(L), int(taps)))
+
+
+def posconv(planes, snap, W, h2_weights, *, B, L, taps, G, cg, bias=None, R=None, out=None, act=0, c_amax=None, resident=True):
+    """The positional conv over the planes of pad_rows_split2 (64 plane channels per group): out[b L + t, g cg + n] =
+    epilogue(sum_j sum_c planes[b, t + j, g 64 + c] W[g cg + n, j 64 + c]), W fp32 [G * cg, taps * 64] and h2_weights =
+    split_weights_h2(W).  resident=True: csrc/posconv_resident.hip (dzn_op_posconv_resident); False: the generic pre-split
+    contraction with its row-offset table (dzn_op_gemm) on the same descriptor."""
+    lib = _lib.load()
+    W2h, wsc = h2_weights
+    D, Dp, Lp, K = G * cg, planes.shape[2], L + taps, taps * 64
+    assert planes.dtype == torch.int16 and planes.shape == (2, B * Lp, G * 64) and W.shape == (D, K) and W.is_contiguous()
+    if out is None:
+        out = torch.empty((B * L, D), device=planes.device, dtype=torch.float32)
+    rowoff = ((torch.arange(B, device=planes.device, dtype=torch.int64)[:, None] * Lp
+               + torch.arange(L, device=planes.device, dtype=torch.int64)[None, :]) * Dp).to(torch.int32).reshape(-1).contiguous()
+    d = DznGemmDesc()
+    d.A, d.W, d.C, d.bias, d.R = _p(planes), _p(W), _p(out), _p(bias), _p(R)
+    d.M, d.N, d.K = B * L, cg, K
+    d.lda, d.kc, d.ldk, d.ldw, d.ldc = Dp, 64, Dp, K, D
+    d.act, d.alpha = act, 1.0
+    d.nz, d.zdiv = G, G
+    d.a_z1, d.w_z1, d.c_z1, d.b_z1 = 64, cg * K, cg, cg
+    d.a_rowoff = _p(rowoff)
+    d.precision = _lib.DZN_PREC_F32_H2
+    d.a_split3, d.a_plane = 2, planes.stride(0)
+    d.W2h, d.col_scale, d.a_amax, d.c_amax = _p(W2h), _p(wsc), _p(snap), _p(c_amax)
+    d.amax_unit = L
+    d.amax_count = B
+    if resident:
+        check(lib.dzn_op_posconv_resident(C.byref(d), int(B), int(L), int(taps), _stream()), what="dzn_op_posconv_resident")
+    else:
+        check(lib.dzn_op_gemm(C.byref(d), _stream()), what="dzn_op_gemm")
+    return out
+
+
 def ws_accum(x, ws, w, init, n):
     lib = _lib.load()
     check(lib.dzn_op_ws_accum(_p(x), _p(ws), float(w), int(bool(init)), int(n), _stream()), what="dzn_op_ws_accum")

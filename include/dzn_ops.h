@@ -203,6 +203,22 @@ int dzn_op_amax(const float* x, int64_t n, float* amax, void* stream);
  * every 32-block in fragment order: the pre-split A operand (dzn_gemm_desc.a_split3) */
 int dzn_op_split_rows(const float* x, void* planes, int64_t plane_stride, int64_t rows, int32_t D, void* stream);
 
+/* x fp32 [B, L, G * cg] -> the two fp16 planes (DZN_PREC_F32_H2) of its zero-padded copy [B, Lp, D = G * cgp], rows shifted
+ * by `pad`, plane_stride elements apart, channels cg .. cgp - 1 of a group zero (cgp % 32 == 0), every 32-block in fragment order.
+ * Window b is scaled by the power of two of amax[b] (>= max |x[b]|), which is copied to snapshot[b] for the consumer's a_amax. */
+int dzn_op_pad_rows_split2(const float* x, void* planes, int64_t plane_stride, int32_t B, int32_t L, int32_t Lp, int32_t pad,
+                           int32_t D, const float* amax, float* snapshot, int32_t cg, int32_t cgp, void* stream);
+
+/* The positional convolution on RESIDENT plane rows (csrc/posconv_resident.hip): C[b L + t, g cg + n] = epilogue(sum over taps j
+ * and the group's 64 plane channels of planes[b, t + j, g 64 + c] * W[g cg + n, j 64 + c]).  d is the descriptor the generic
+ * pre-split contraction (dzn_op_gemm, a_split3 == 2) takes for the same conv: A = the planes of dzn_op_pad_rows_split2 with
+ * Lp = L + taps and cgp == 64, a_plane, ldk = D, a_z1 = kc = 64, M = B * L, N = cg <= 64, K = ldw = taps * 64, nz = zdiv = G, w_z1,
+ * c_z1, b_z1, W2h / col_scale, a_amax = the snapshot, amax_unit = L, precision = DZN_PREC_F32_H2; a_rowoff is not read.  C is
+ * bit-identical to dzn_op_gemm's.  DZN_E_INVALID for any other descriptor and for a shape whose rows do not fit LDS
+ * (dzn_op_posconv_resident_fits == 0: B windows of L rows, `taps` taps). */
+int dzn_op_posconv_resident(const dzn_gemm_desc* d, int32_t B, int32_t L, int32_t taps, void* stream);
+int dzn_op_posconv_resident_fits(int32_t B, int32_t L, int32_t taps);
+
 /* 3x3 stride-1 convolution 32 -> 32 channels over zero-bordered fp32 NHWC images [B][Hs+2][Ws+2][32]
  * (first ResNet34 stage, wespeaker/resnet.py:139-144 with BatchNorm folded into W / bias) in the fp32-split
  * arithmetic: W3 = dzn_op_split_weights of W [32][(dh*3+dw)*32 + ci]; out = post_relu?max(0,·):(·) of
